@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of the car.fhd VoxelNet forward (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU.  Started under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE set) it runs as one rank of the
 job; started plainly (``python bench.py --gpus 8``) it launches its own N ranks through torch.distributed.run on 127.0.0.1 and
@@ -15,9 +15,11 @@ Default launch mode: hipGraph replays with four steps in flight (--inflight 4: f
 four streams; every step is still a full pass over its batch).  A step is three graphs -- sparse front end / RPN / predict -- and the
 lanes pass a token from RPN segment to RPN segment (--serialize-rpn 1), so that one lane at a time is in its MFMA-bound segment while
 the others' latency-bound segments run beside it; --serialize-rpn 0 replays one graph per step on uncoordinated lanes.
-`config.single_step_latency_ms` is one step alone as ONE graph, start to finish; `--inflight 1` runs strictly one step at a time.
+`config.single_step_latency_ms` (--full) is one step alone as ONE graph, start to finish; `--inflight 1` runs strictly one step at a time.
 
-Prints ONE JSON line on rank 0 with, besides the contract fields,
+A plain run sets up, warms up, times exactly K steps in one window and prints ONE JSON line on rank 0 (`value`, `ms_per_step` = that
+window / K, ...); `--dump-outputs DIR` writes what the last timed step returned (detections; loss terms for training) to DIR/*.npy.
+`--full` also measures, and adds to the line,
   roofline      -- the SubMConv3d 64->64 gather-GEMM kernel (the kernel BASELINE.json's metric names): algorithmic bytes
                    per launch / mean launch duration (HIP events around 100 re-issues of the very launch the timed graph
                    runs, right after the timed region), against the 8 TB/s HBM peak; `traffic` = HBM bytes per launch from
@@ -435,17 +437,21 @@ def train_bench(args, rank, local_rank, world, device):
         except Exception as e:  # noqa: BLE001
             print(f"[bench] whole-step capture failed ({e!r}); eager steps", file=sys.stderr)
             tr.static = False
-    elapsed, timing, out6 = measure(step_fn, barrier, args.steps, args.warmup, world, device)
+    elapsed, timing, out6 = measure(step_fn, barrier, args.steps, args.warmup, world, device, repeat=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss_terms": tr.last["out6"]})
     if tr.static:
         tr.check_overflow()
-    # the gradient all-reduce alone (the only collective of the step): 20 back-to-back reductions of the live bucket
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        tr.bucket.allreduce(average=True)
-    e1.record()
-    torch.cuda.synchronize()
-    ar_us = e0.elapsed_time(e1) * 1e3 / 20     # world 1: no collective runs, this is the bucket's pack / unpack cost only
+    ar_us = None
+    if args.full:
+        # the gradient all-reduce alone (the only collective of the step): 20 back-to-back reductions of the live bucket
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            tr.bucket.allreduce(average=True)
+        e1.record()
+        torch.cuda.synchronize()
+        ar_us = round(e0.elapsed_time(e1) * 1e3 / 20, 1)     # world 1: no collective runs, this is the bucket's pack / unpack cost only
     if rank == 0:
         losses = tr.loss_dict()
         res = {"metric": WL["metric"], "value": round(bs * args.steps * world / elapsed, 2), "unit": "samples/s", "n_gpus": world,
@@ -455,7 +461,7 @@ def train_bench(args, rank, local_rank, world, device):
                "config": {"workload": WL["desc"], "samples_per_step_per_gpu": bs, "parallelism": f"ddp{world}",
                           "points_per_frame": int(pts.shape[0]) // bs, "launch_mode": launch,
                           "gradient_bucket_bytes": tr.bucket.numel * 4,
-                          "allreduce_us": round(ar_us, 1) if world > 1 else None, "bucket_pack_unpack_us": round(ar_us, 1) if world == 1 else None,
+                          "allreduce_us": ar_us if world > 1 else None, "bucket_pack_unpack_us": ar_us if world == 1 else None,
                           "skipped_steps_loss_scale": tr.skipped_steps if (tr.loss_scale is not None or tr.loss_scale_dev is not None) else None,
                           "optimizer": "AdamW (adam + fixed weight decay 0.01, car.fhd.config:180-188)",
                           "target_assignment": "per anchor range" if tr.class_ranges else "single class"},
@@ -541,16 +547,17 @@ def build_detector(device, dtype, calib_cloud=None, exact=False):
 # ------------------------------------------------------------------------------------------ timing harness
 SELF_WARM_MIN_S = 1.0      # keep replaying after the --warmup steps until the clocks have ramped ...
 SELF_WARM_MAX_S = 4.0      # ... two consecutive 50-step windows agree within 2 %, or this much time has passed
-TIMED_MIN_S = 0.5          # repeat windows of exactly --steps steps until this much time is covered (at least 5 windows)
+TIMED_MIN_S = 0.5          # repeat=True: windows of exactly --steps steps until this much time is covered (at least 5 windows)
 
 
-def measure(step, barrier, steps, warmup, world=1, device=None):
+def measure(step, barrier, steps, warmup, world=1, device=None, repeat=False):
     """The timed region of every workload.  `warmup` untimed steps as the contract asks, then the harness warms ITSELF -- 50-step
     windows until >= SELF_WARM_MIN_S have passed and two consecutive windows agree within 2 % (a fresh box ramps its clocks over
-    the first second; `--warmup 5` alone is 3 ms of work) -- and then times WINDOWS of exactly `steps` steps, each bracketed by
-    barrier + torch.cuda.synchronize() on both sides, until they cover >= TIMED_MIN_S (5 ... 200 windows).  Per window the time
-    is the MAX over ranks; the reported figure is the MEDIAN window, the spread is reported beside it.  Every rank runs the same
-    number of windows (the continue / stop decisions are all-reduced)."""
+    the first second; `--warmup 5` alone is 3 ms of work) -- and then times ONE window of exactly `steps` steps, bracketed by
+    barrier + torch.cuda.synchronize() on both sides: the returned time (MAX over ranks) and output are that window's.
+    ``repeat`` (--full): before that window, further windows of exactly `steps` steps until they cover >= TIMED_MIN_S (5 ... 200
+    windows); their median and spread are reported in the info dict (`ms_per_step_median`, `spread_pct`), never as the returned
+    time.  Every rank runs the same number of windows (the continue / stop decisions are all-reduced)."""
     import torch.distributed as dist
 
     def agree(x, op=None):       # the same decision on every rank
@@ -580,23 +587,55 @@ def measure(step, barrier, steps, warmup, world=1, device=None):
         if (spent >= SELF_WARM_MIN_S and prev is not None and abs(t - prev) <= 0.02 * prev) or spent >= SELF_WARM_MAX_S:
             break
         prev = t
-    times = []
-    t, r = window(steps)
-    times.append(t)
-    n = int(min(200, max(5, -(-TIMED_MIN_S // max(t, 1e-6))))) if TIMED_MIN_S > 0 else 1
-    for _ in range(n - 1):
-        t, r = window(steps)
+    info = {"self_warm_windows_of_50": warm_windows}
+    if repeat and TIMED_MIN_S > 0:
+        times = []
+        t, _ = window(steps)
         times.append(t)
-    while TIMED_MIN_S > 0 and float(np.sum(times)) < TIMED_MIN_S and len(times) < 400:    # the first window was a slow one: keep going
-        t, r = window(steps)
-        times.append(t)
-    med = float(np.median(times))
-    info = {"windows": len(times), "steps_per_window": steps, "timed_s": round(float(np.sum(times)), 4),
-            "ms_per_step_median": round(med / steps * 1e3, 4), "ms_per_step_min": round(min(times) / steps * 1e3, 4),
-            "ms_per_step_max": round(max(times) / steps * 1e3, 4), "spread_pct": round((max(times) - min(times)) / med * 100, 2),
-            "self_warm_windows_of_50": warm_windows,
-            "what": "value = work of one window / MEDIAN window time; every window is exactly --steps steps between barrier + synchronize"}
-    return med, info, r
+        n = int(min(200, max(5, -(-TIMED_MIN_S // max(t, 1e-6)))))
+        for _ in range(n - 1):
+            t, _ = window(steps)
+            times.append(t)
+        while float(np.sum(times)) < TIMED_MIN_S and len(times) < 400:    # the first window was a slow one: keep going
+            t, _ = window(steps)
+            times.append(t)
+        med = float(np.median(times))
+        info.update({"windows": len(times), "steps_per_window": steps, "windows_s": round(float(np.sum(times)), 4),
+                     "ms_per_step_median": round(med / steps * 1e3, 4), "ms_per_step_min": round(min(times) / steps * 1e3, 4),
+                     "ms_per_step_max": round(max(times) / steps * 1e3, 4), "spread_pct": round((max(times) - min(times)) / med * 100, 2)})
+    elapsed, r = window(steps)
+    info.update({"timed_steps": steps, "timed_s": round(elapsed, 6),
+                 "what": "value = work of ONE window of exactly --steps steps between barrier + synchronize / its time"
+                         + ("; windows / ms_per_step_* / spread_pct: the windows of --steps steps run before it" if "windows" in info else "")})
+    return elapsed, info, r
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the tensors the timed path handed its caller in the last timed step, one ``<name>.npy`` each -- float32, or
+    float64 for integer and float64 tensors (exact).  Detection slots at or past a frame's count are undefined in the padded outputs
+    (models.SecondDetector.predict_device) and are written as zeros, so that two builds compare element for element."""
+    if isinstance(out, tuple):                     # InFlightRunner.step: (outputs, stream)
+        out = out[0]
+    if isinstance(out, list):                      # --branches > 1: one dict per frame group
+        out = {k: torch.cat([o[k] for o in out]) for k in out[0]}
+    torch.cuda.synchronize()
+    valid = out.get("valid")
+    arrays = {}
+    for name, t in out.items():
+        t = t.detach()
+        if valid is not None and name != "valid" and tuple(t.shape[:valid.dim()]) == tuple(valid.shape):
+            t = torch.where(valid.reshape(valid.shape + (1,) * (t.dim() - valid.dim())), t, torch.zeros_like(t))
+        dt = torch.float32 if (t.dtype in (torch.float32, torch.float16, torch.bfloat16, torch.bool)) else torch.float64
+        arrays[name] = t.to(dt).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -716,6 +755,14 @@ def dry_run(args, rank, local_rank, world, affinity=None):
                           "workload": args.workload}), flush=True)
 
 
+def median_rate(d):
+    """A --full child line -> (value, ms_per_step) of the median of its repeated windows (`timing`), the figure the side legs quote."""
+    cfg = d["config"]
+    per_step = (cfg.get("frames_per_step_per_gpu") or cfg.get("samples_per_step_per_gpu")) * d["n_gpus"]
+    ms = d["timing"]["ms_per_step_median"]
+    return round(per_step / (ms * 1e-3), 2), ms
+
+
 def other_configs(budget_s=270.0):
     """BASELINE.json configs 3 / 4 / 5 at their stated sizes, measured by THIS command (each in a child process: same file, --workload,
     a short run) so that the driver's record carries them; never part of `value`.  Best effort: a failure is reported, not raised."""
@@ -735,14 +782,15 @@ def other_configs(budget_s=270.0):
         if time.time() - t0 > budget_s:
             out[key] = {"skipped": "time budget"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "30", "--warmup", "5", "--no-kernel-table",
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "30", "--warmup", "5", "--full", "--no-kernel-table",
                "--no-cpu-baseline", "--no-extra-lines", "--no-other-configs", *extra]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             d = json.loads(line[-1])
             cfg = d.get("config", {})
-            out[key] = {"what": what, "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "dtype": d["dtype"],
+            value, ms = median_rate(d)
+            out[key] = {"what": what, "value": value, "unit": d["unit"], "ms_per_step": ms, "dtype": d["dtype"],
                        "per_step_per_gpu": cfg.get("frames_per_step_per_gpu") or cfg.get("samples_per_step_per_gpu"),
                        "points_per_frame": cfg.get("points_per_frame"), "rows_per_frame": cfg.get("rows_per_frame"),
                        "steps_in_flight": cfg.get("steps_in_flight"), "loss_last_step": d.get("loss_last_step"), "steps": d["steps"]}
@@ -761,7 +809,9 @@ def time_e2e(det, points, offsets, inflight, steps, warmup, serialize_rpn=False,
     hp, ho = points.cpu().pin_memory(), offsets.cpu().pin_memory()
     for _ in range(max(3, warmup)):
         runner.step(hp, ho, fetch=True)
-    dt, timing, _ = measure(lambda: runner.step(hp, ho, fetch=True), torch.cuda.synchronize, steps, 0)
+    dt, timing, _ = measure(lambda: runner.step(hp, ho, fetch=True), torch.cuda.synchronize, steps, 0, repeat=True)
+    if "windows" in timing:
+        dt = timing["ms_per_step_median"] * 1e-3 * steps      # the median window
     runner.synchronize()
     lat = []
     for _ in range(20):
@@ -774,7 +824,7 @@ def time_e2e(det, points, offsets, inflight, steps, warmup, serialize_rpn=False,
             "single_step_latency_ms": round(float(np.median(lat)) * 1e3, 4),
             "h2d_bytes_per_step": int(hp.numel() * 4 + ho.numel() * 4),
             "d2h_bytes_per_step": int(sum(v.numel() * v.element_size() for v in runner.host_outputs[0].values())),
-            "timing": {k: timing[k] for k in ("windows", "steps_per_window", "spread_pct")},
+            "timing": {k: timing.get(k) for k in ("windows", "steps_per_window", "spread_pct")},
             "what": "pinned host clouds -> HBM -> detections -> pinned host, copies inside the timed loop"}
 
 
@@ -1026,7 +1076,7 @@ def time_scene_density(args, main_value, budget_s=200.0):
     THIS command in a fresh child process (same harness, lanes and flags; `--scene` / `--background-skip`), so that no figure
     depends on what the parent process ran before; never `value`."""
     import subprocess
-    res = {"sparse_scene": {"frames_per_s": main_value, "what": "the timed region of this line (SURVEY 8d clouds)"}}
+    res = {"sparse_scene": {"frames_per_s": main_value, "what": "the median window of this line's timing (SURVEY 8d clouds)"}}
     t0 = time.time()
     for key, extra in (("dense_scene", ["--scene", "dense"]), ("dense_scene_skip_off", ["--scene", "dense", "--background-skip", "0"]),
                        ("sparse_scene_skip_off", ["--background-skip", "0"]), ("sparse_scene_scan_order", ["--point-order", "scan"])):
@@ -1034,21 +1084,22 @@ def time_scene_density(args, main_value, budget_s=200.0):
             res[key] = {"skipped": "time budget"}
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--inflight", str(args.inflight),
-               "--serialize-rpn", str(args.serialize_rpn), "--rpn-tokens", str(args.rpn_tokens), "--dtype", args.dtype, "--no-kernel-table", "--no-cpu-baseline",
-               "--no-extra-lines", "--no-other-configs", *extra]
+               "--serialize-rpn", str(args.serialize_rpn), "--rpn-tokens", str(args.rpn_tokens), "--dtype", args.dtype, "--full", "--no-kernel-table",
+               "--no-cpu-baseline", "--no-extra-lines", "--no-other-configs", *extra]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
             d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
             bt = d["config"].get("rpn_background_tiles") or {}
-            res[key] = {"frames_per_s": d["value"], "ms_per_step": d["ms_per_step"], "spread_pct": d["timing"]["spread_pct"],
+            value, ms = median_rate(d)
+            res[key] = {"frames_per_s": value, "ms_per_step": ms, "spread_pct": d["timing"]["spread_pct"],
                         "single_step_latency_ms": d["config"].get("single_step_latency_ms"), "rows_per_frame": d["config"].get("rows_per_frame"),
                         "bev_cells_occupied": bt.get("bev_cells_occupied"), "live_tiles_per_conv": bt.get("live_tiles_per_conv_last_step")}
         except Exception as e:  # noqa: BLE001
             res[key] = {"error": repr(e)[:300]}
     res["skip_off"] = {"sparse_scene": res["sparse_scene_skip_off"].get("frames_per_s"), "dense_scene": res["dense_scene_skip_off"].get("frames_per_s")}
-    res["what"] = ("frames/s of the default path on the bench's clouds (sparse_scene = `value`) and on a dense seeded scene, of "
+    res["what"] = ("frames/s of the default path on the bench's clouds (sparse_scene: this line's median window) and on a dense seeded scene, of "
                    "--background-skip 0 on both, and of the bench's clouds in lidar firing order instead of shuffled (--point-order scan: real "
-                   ".bin files are un-shuffled; the shuffle of SURVEY 8d is the worst case for every gather); fresh child processes of this command")
+                   ".bin files are un-shuffled; the shuffle of SURVEY 8d is the worst case for every gather); fresh child processes of this command, median windows")
     return res
 
 
@@ -1104,7 +1155,17 @@ def main():
                          "14-20 %% of the BEV cells occupied at the same points / voxels per frame (a robustness side measurement)")
     ap.add_argument("--dry-run", action="store_true", help="launcher plumbing only: ranks report themselves (gloo), no GPU work")
     ap.add_argument("--dropin-leg", default="", help="(internal) run ONE variant of config.dropin_fused in this process and print it")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check of the record: timing windows beside the timed one, single-step latency, "
+                         "roofline / roofline_mfma / per-launch kernel table, RPN background-tile figures, rows per frame, CPU baseline with the "
+                         "device-vs-CPU detection checks, pinned-host end-to-end, batch-1, drop-in legs, scene density, other BASELINE configs, "
+                         "the training all-reduce time (the --no-* options still drop parts of it).  Without it the run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_table = args.no_extra_lines = args.no_other_configs = True
     global WL, SELF_WARM_MIN_S, SELF_WARM_MAX_S, TIMED_MIN_S
     if args.profile_run:
         SELF_WARM_MIN_S = SELF_WARM_MAX_S = TIMED_MIN_S = 0.0
@@ -1164,7 +1225,8 @@ def main():
     # first subm2 layer (64->64 SubM on the 11x400x352 grid): the largest 64->64 3x3x3 launch of the forward
     timer = ConvCapture(lambda m: m["cin"] == 64 and m["cout"] == 64 and m["kvol"] == 27 and m["n_in"] == m["n_out"]
                         and m["n_out"] > 20000 * WL["batch"] // 8)
-    ops.set_conv_profiler(timer)
+    if args.full:
+        ops.set_conv_profiler(timer)
 
     def barrier():
         if world > 1:
@@ -1189,9 +1251,11 @@ def main():
             step = lambda: det.forward_points(points, offsets, static=True)
         else:
             step = lambda: det.forward_points(points, offsets)
-        elapsed, timing, r = measure(step, barrier, args.steps, args.warmup, world, device)
+        elapsed, timing, r = measure(step, barrier, args.steps, args.warmup, world, device, repeat=args.full)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, r)
         latency_ms = None
-        if args.mode == "graph":   # one step alone, start to finish, as ONE graph (what --inflight 1 would run back to back)
+        if args.full and args.mode == "graph":   # one step alone, start to finish, as ONE graph (what --inflight 1 would run back to back)
             one = det.make_graphed(points, offsets)[0] if isinstance(replays[0], tuple) else replays[0]
             for _ in range(3):
                 one()
@@ -1212,15 +1276,16 @@ def main():
         # the launch stream (events cannot be timed inside a captured graph; a single event pair around one
         # ~20 us launch would add ~10 us of launch gap).  profiles/ holds the rocprofv3 cross-check.
         # capture exactly the launch the timed region runs: with a branched graph that is the static forward of one branch
-        timer.enabled = True
-        if args.mode == "graph" and args.branches > 1:
-            det.forward_points(*graph_parts[0], static=True)
-            frames_in_launch = graph_parts[0][1].numel() - 1
-        else:
-            det.forward_points(points, offsets, static=args.mode != "eager")
-            frames_in_launch = WL["batch"]
-        torch.cuda.synchronize()
-        timer.enabled = False
+        if args.full:
+            timer.enabled = True
+            if args.mode == "graph" and args.branches > 1:
+                det.forward_points(*graph_parts[0], static=True)
+                frames_in_launch = graph_parts[0][1].numel() - 1
+            else:
+                det.forward_points(points, offsets, static=args.mode != "eager")
+                frames_in_launch = WL["batch"]
+            torch.cuda.synchronize()
+            timer.enabled = False
         t_kernel, kernel_sig = time_kernel(timer.call) if timer.call is not None else (None, "")
         # auxiliary: the same layer as ONE full-batch launch (what a single-chain graph, --branches 1, runs)
         aux = None
@@ -1242,7 +1307,7 @@ def main():
                 aux = {"frames": WL["batch"], "rows": rows8, "pairs": pairs8, "launch_us": round(t8 * 1e6, 2),
                        "frac": round(b8 / t8 / 1e9 / HBM_PEAK_GBS, 4)}
         ops.set_conv_profiler(None)
-        roof_mfma = time_rpn_conv(det, WL["batch"]) if args.dtype == "bf16" else None
+        roof_mfma = time_rpn_conv(det, WL["batch"]) if args.full and args.dtype == "bf16" else None
         dtype_note = {"bf16x3": "fp32 storage; every product = three bf16 MFMA passes on (hi, lo) operand pairs: 16 significant bits per operand "
                                 "and per stored activation plane pair, fp32 accumulation -- narrower than fp32 (see --dtype fp32_exact)",
                       "fp32": "IEEE fp32 products and accumulation (v_mfma_f32_32x32x2_f32 / VALU sparse convs, torch fp32 RPN)"}.get(det.arithmetic())
@@ -1273,7 +1338,8 @@ def main():
         if (rank == 0 and world == 1 and args.mode == "graph" and args.branches == 1 and args.workload == "car.fhd" and not args.no_extra_lines
                 and getattr(det.rpn, "background_convs", 0) and det.rpn.skip_background):
             try:
-                scenes = time_scene_density(args, round(WL["batch"] * args.steps * world / elapsed, 1))
+                med_s = timing["ms_per_step_median"] * 1e-3 * args.steps if "windows" in timing else elapsed
+                scenes = time_scene_density(args, round(WL["batch"] * args.steps * world / med_s, 1))
             except Exception as e:  # noqa: BLE001
                 scenes = {"error": repr(e)[:300]}
 
@@ -1320,7 +1386,7 @@ def main():
         stage_times(det, points, offsets)
 
     bg_tiles = None
-    if rank == 0 and getattr(det.rpn, "background_convs", 0):
+    if rank == 0 and args.full and getattr(det.rpn, "background_convs", 0):
         if det.rpn.skip_background:
             lt = [k for k in (ktable or []) if k["op"] in ("conv2d_nhwc_tiles", "conv2d_nhwc_gather", "conv2d_nhwc_tiles_tail")]
             bg_tiles = {"enabled": True, "lazy": bool(getattr(det.rpn, "lazy_background", False)), "live_tiles_per_conv": [k.get("live_tiles") for k in lt] or None, "tiles": lt[0].get("tiles") if lt else None,
@@ -1344,7 +1410,7 @@ def main():
         if scenes is not None:
             bg_tiles["frames_per_s"] = scenes
     rows_per_frame = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():   # live voxel / pillar count of this input (what BASELINE quotes the configs on)
             v_ = det.voxel_generator.generate_device(points, offsets)
         rows_per_frame = int(v_["voxel_num"]) // WL["batch"]

@@ -29,16 +29,16 @@ def _bench(*extra, timeout=900):
 
 @needs2
 def test_bench_two_ranks_inference_is_weak_scaling_without_a_collective():
-    d = _bench("--gpus", "2", "--steps", "5", "--warmup", "2", "--no-kernel-table", "--no-extra-lines", "--no-other-configs")
+    d = _bench("--gpus", "2", "--steps", "200", "--warmup", "2", "--no-kernel-table", "--no-extra-lines", "--no-other-configs")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["parallelism"] == "frame-dp2"
-    one = _bench("--gpus", "1", "--steps", "5", "--warmup", "2", "--no-kernel-table", "--no-extra-lines", "--no-other-configs",
+    one = _bench("--gpus", "1", "--steps", "200", "--warmup", "2", "--no-kernel-table", "--no-extra-lines", "--no-other-configs",
                  "--no-cpu-baseline")
     assert d["value"] > 1.2 * one["value"], (d["value"], one["value"])      # two ranks do more than one (no claim about how much)
 
 
 @needs2
 def test_bench_two_ranks_training_all_reduces_one_bucket_over_rccl():
-    d = _bench("--gpus", "2", "--workload", "car.fhd.train", "--dtype", "bf16", "--steps", "5", "--warmup", "2")
+    d = _bench("--gpus", "2", "--workload", "car.fhd.train", "--dtype", "bf16", "--steps", "5", "--warmup", "2", "--full")
     c = d["config"]
     assert d["n_gpus"] == 2 and c["parallelism"] == "ddp2" and c["allreduce_us"] is not None and c["allreduce_us"] > 0
     assert c["gradient_bucket_bytes"] > 5_000_000

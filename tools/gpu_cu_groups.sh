@@ -4,7 +4,7 @@
 export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/${1:-r06_cug}; mkdir -p $O
 run() {   # groups inflight serialize tokens [workload]
-  SEC_LANE_CU_GROUPS=$1 timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs \
+  SEC_LANE_CU_GROUPS=$1 timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs \
       --inflight $2 --serialize-rpn $3 --rpn-tokens $4 --workload ${5:-car.fhd} > $O/b.json 2> $O/b.err
   python - <<PY
 import json

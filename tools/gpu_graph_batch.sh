@@ -6,7 +6,7 @@ R=$PWD; O=$R/gpurun_out/${1:-r03_s}; mkdir -p $O
 for B in default 8 64 128 256; do
   if [ $B == default ]; then unset DEBUG_HIP_GRAPH_BATCH_SIZE; else export DEBUG_HIP_GRAPH_BATCH_SIZE=$B; fi
   echo "== DEBUG_HIP_GRAPH_BATCH_SIZE=$B"
-  timeout 300 python bench.py --steps 200 --warmup 20 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs 2>$O/b$B.err | python -c "
+  timeout 300 python bench.py --full --steps 200 --warmup 20 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs 2>$O/b$B.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']
 print(d['value'], d['ms_per_step'], 'single', c.get('single_step_latency_ms'), 'one-at-a-time', c.get('frames_per_s_one_step_at_a_time'))"

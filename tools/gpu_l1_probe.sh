@@ -12,11 +12,11 @@ export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 timeout 270 rocprofv3 --pmc $SET --kernel-trace --output-format csv -d $O/$NAME -- \
-  python $R/bench.py --mode static --profile-run --steps 4 --warmup 2 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs > $O/$NAME.log 2>&1
+  python $R/bench.py --full --mode static --profile-run --steps 4 --warmup 2 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs > $O/$NAME.log 2>&1
 echo "pmc rc=$?"; tail -3 $O/$NAME.log | cut -c1-300
 cd $R
 python tools/pmc_l1_summary.py $O/$NAME 2 > $O/${TAG}_$NAME.txt 2>&1; grep -E "^#|^kernel|sec::" -A 6 $O/${TAG}_$NAME.txt | grep -E "^#|^kernel|sec::|^    " | head -150 | cut -c1-60,97-210
 find $O/$NAME -name "*.csv" -size +20M -delete
 if [ "$4" != "nobench" ]; then
-  timeout 240 python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json
+  timeout 240 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-other-configs > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json
 fi

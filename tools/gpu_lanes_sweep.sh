@@ -3,7 +3,7 @@
 export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/${1:-r06_lanes2}; mkdir -p $O
 run() {
-  timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs --inflight $1 --serialize-rpn $2 --rpn-tokens $3 > $O/b.json 2> $O/b.err
+  timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs --inflight $1 --serialize-rpn $2 --rpn-tokens $3 > $O/b.json 2> $O/b.err
   python - <<PY
 import json
 try:

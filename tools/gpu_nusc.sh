@@ -2,7 +2,7 @@
 export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/${1:-r03_aj}; mkdir -p $O
 for WL in nusc.fhd nusc.pp; do
-timeout 300 python bench.py --workload $WL --steps 50 --warmup 10 --no-cpu-baseline --no-extra-lines --no-other-configs 2>$O/$WL.err > $O/$WL.json
+timeout 300 python bench.py --full --workload $WL --steps 50 --warmup 10 --no-cpu-baseline --no-extra-lines --no-other-configs 2>$O/$WL.err > $O/$WL.json
 python - <<PY
 import json
 d=json.load(open("$O/$WL.json")); c=d['config']

@@ -3,7 +3,7 @@ TAG=${1:-r06_i}
 export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 for ORD in shuffle sorted scan; do
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --point-order $ORD --no-cpu-baseline --no-extra-lines --no-other-configs > $O/bench_$ORD.json 2> $O/bench_$ORD.err; echo "bench $ORD rc=$?"
+  timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --point-order $ORD --no-cpu-baseline --no-extra-lines --no-other-configs > $O/bench_$ORD.json 2> $O/bench_$ORD.err; echo "bench $ORD rc=$?"
 done
 python - <<PY
 import json

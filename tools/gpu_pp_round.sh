@@ -4,7 +4,7 @@ TAG=${1:-pp_round}
 export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 timeout 900 python -m pytest tests -q -x -m gpu -k "conv2d_nhwc or pointpillars or pillar or pfn" > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -5 $O/pytest.log
-timeout 600 python bench.py --workload nusc.pp --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-extra-lines > $O/bench_pp.json 2> $O/bench_pp.err; echo "pp rc=$?"; cut -c1-300 $O/bench_pp.json
+timeout 600 python bench.py --full --workload nusc.pp --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-extra-lines > $O/bench_pp.json 2> $O/bench_pp.err; echo "pp rc=$?"; cut -c1-300 $O/bench_pp.json
 python - <<PY
 import json
 d=json.load(open("$O/bench_pp.json"))

@@ -10,7 +10,7 @@ if [ "$2" != "skip-tests" ]; then
   timeout 900 python -m pytest tests -m gpu -q -x -s > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee $O/pytest.rc
   tail -3 $O/pytest.log
 fi
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"     # the driver's own command line
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"     # the headline command line with every side measurement
 cut -c1-400 $O/bench.json
 timeout 600 python tools/bf16_error_trace.py > $O/bf16_error_trace.txt 2>&1; echo "trace rc=$?"; tail -32 $O/bf16_error_trace.txt
 if [ "$3" == "yardstick" ]; then

@@ -6,7 +6,7 @@ R=$PWD; O=$R/gpurun_out/${1:-r06_tail}; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_rpn_tiles.py tests/test_capi_symbols.py -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -15 $O/pytest.log
 for rep in 1 2; do
 for mode in 1 0; do
-  SEC_RPN_FUSED_TAIL=$mode timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-lines --no-other-configs $2 > $O/b_$mode.json 2> $O/b_$mode.err
+  SEC_RPN_FUSED_TAIL=$mode timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-lines --no-other-configs $2 > $O/b_$mode.json 2> $O/b_$mode.err
   python - <<PY
 import json
 try:

@@ -4,7 +4,7 @@ export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/${1:-r06_tok2}; mkdir -p $O
 for rep in 1 2; do for t in 0 1 2; do
 for wl in "--workload car.fhd" "--scene dense" "--workload nusc.fhd"; do
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs --rpn-tokens $t $wl > $O/b.json 2> $O/b.err
+  timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-kernel-table --no-cpu-baseline --no-extra-lines --no-other-configs --rpn-tokens $t $wl > $O/b.json 2> $O/b.err
   python - <<PY
 import json
 try:

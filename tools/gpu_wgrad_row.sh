@@ -27,7 +27,7 @@ PY
   cat $O/probe_$X.txt | grep -v amdgpu.ids
 done
 for X in 0 1 0 1; do
-  SEC_WGRAD_ROW=$X timeout 600 python bench.py --workload car.fhd.train --dtype bf16 --gpus 1 --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_train_$X.json 2> $O/bench_train_$X.err; echo "car.fhd.train row=$X rc=$?"
+  SEC_WGRAD_ROW=$X timeout 600 python bench.py --full --workload car.fhd.train --dtype bf16 --gpus 1 --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs > $O/bench_train_$X.json 2> $O/bench_train_$X.err; echo "car.fhd.train row=$X rc=$?"
   python -c "
 import json
 d=json.loads([l for l in open('$O/bench_train_$X.json').read().splitlines() if l.startswith('{')][-1]); print('   ', d['value'], d['unit'], d['ms_per_step'])"

@@ -5,7 +5,7 @@ export PYTHONUNBUFFERED=1
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_conv_rows.py tests/test_gpu_parity.py -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log
 for X in 0 1; do
-  SEC_CONV_ROWS_XCD=$X timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-lines --no-other-configs > $O/bench_xcd$X.json 2> $O/bench_xcd$X.err; echo "bench xcd=$X rc=$?"
+  SEC_CONV_ROWS_XCD=$X timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-lines --no-other-configs > $O/bench_xcd$X.json 2> $O/bench_xcd$X.err; echo "bench xcd=$X rc=$?"
   cut -c1-200 $O/bench_xcd$X.json
 done
 cd /tmp; export TMPDIR=/tmp
