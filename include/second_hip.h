@@ -495,6 +495,33 @@ int sec_conv2d_nhwc_x3_tiles(const void *x_hi, const void *x_lo, int batch, int 
                              const void *background_hi, const void *background_lo, const unsigned short *nbr_masks,
                              const void *background_in_hi, const void *background_in_lo, void *y_hi, void *y_lo, void *stream);
 
+/* The same layers in IEEE fp32 on the matrix pipe's fp32 instruction (v_mfma_f32_32x32x2_f32): fp32 channels-last images, fp32
+ * weights, fp32 accumulation, bias + ReLU in fp32 -- every output element is one fma chain over (tap, input channel) in an order that
+ * does not depend on the call form, so a tile of the list forms is bit-identical to the same tile of the full form.  No 16-bit
+ * operand anywhere: this is the arithmetic of SEC_FP32_EXACT for the RPN.
+ *   sec_conv2d_f32_packed_weight_bytes : bytes of the packed image; 0 = shape not supported (cin 128; ksize 3 with cout a multiple of
+ *                                        128, or ksize 1 with cout a multiple of 64);
+ *   sec_conv2d_f32_pack_weight         : torch-layout [Cout][128][k][k] fp32 -> the order the kernels stream;
+ *   sec_conv2d_nhwc_f32                : 3x3 / stride 1 / pad 1 on every tile; relu_flags bit 0 = ReLU, bit 1 = all-zero input
+ *                                        tiles write act(bias) without the MFMA loop (bit-identical);
+ *   sec_conv2d_nhwc_f32_tiles          : tile_order / live_counts = one layer of sec_rpn_tile_live(_masks); background = this layer's
+ *                                        output for an EMPTY frame [h][w][cout], copied into the tiles that are not live (NULL: they are
+ *                                        left unwritten, for a lazy consumer); nbr_masks (may be NULL: x holds every tile) +
+ *                                        background_in = the PRODUCING layer's empty-frame output [h][w][128], read for halo pixels
+ *                                        of tiles the producer did not write;
+ *   sec_conv1x1_chain_f32              : y = W2 * act(W1 * x + bias1) + bias2 over [pixels][128], 128 intermediate channels, cout2 in
+ *                                        {64, 128}, weights packed with ksize 1, bias2 may be NULL.
+ * Images are limited to h * w * 512 < 2^31 bytes per frame (SEC_E_UNSUPPORTED beyond). */
+size_t sec_conv2d_f32_packed_weight_bytes(int cout, int cin, int ksize);
+int sec_conv2d_f32_pack_weight(const float *weight, int cout, int cin, int ksize, void *packed, void *stream);
+int sec_conv2d_nhwc_f32(const float *x, int batch, int h, int w, const void *packed, const float *bias, int cout, int relu_flags,
+                        float *y, void *stream);
+int sec_conv2d_nhwc_f32_tiles(const float *x, int batch, int h, int w, const void *packed, const float *bias, int cout, int relu,
+                              const unsigned short *tile_order, const int *live_counts, const float *background,
+                              const unsigned short *nbr_masks, const float *background_in, float *y, void *stream);
+int sec_conv1x1_chain_f32(const float *x, long long pixels, const void *packed_w1, const float *bias1, int relu1,
+                          const void *packed_w2, const float *bias2, int cout2, float *y, void *stream);
+
 /* Fused tail of the RPN at inference: y = W2 * act(W1 * x + bias1) + bias2 over `pixels` channels-last pixels with
  * 128 input and 128 intermediate channels -- the 1x1/stride-1 ConvTranspose2d deblock with folded BatchNorm + ReLU
  * (second/pytorch/models/rpn.py:275-285) followed by the merged conv_box / conv_cls / conv_dir_cls 1x1 heads

@@ -21,7 +21,8 @@ strided layer, three modules per layer, the dense [B, 128, 200, 176] image and p
   * precision follows the caller: ``net.half()`` (train.py:470) runs the fp16 pipeline, ``dtype=torch.bfloat16`` may be forced; fp32
     networks run the fp32-storage pipeline whose products are, by default, three bf16 MFMA passes on split operands ("bf16x3": 16
     significant bits per operand, fp32 accumulation -- inside the 1e-4 of the parity rule, NOT the reference's fp32 arithmetic);
-    ``fp32_exact=True`` computes IEEE fp32 products (sparse convs on the fp32 MFMA, RPN on torch's fp32 convolutions);
+    ``fp32_exact=True`` computes IEEE fp32 products (sparse convs on the fp32 MFMA, RPN on torch's fp32 convolutions or, with
+    SEC_FP32_RPN=hip, on the fp32-MFMA kernels);
   * training mode: opt-in (``train_dtype``), served by :mod:`second_amd.dropin_train`; otherwise the original forward;
   * DataParallel-padded examples (``num_points`` 2-D, voxelnet.py:346), ``anchors_mask`` and per-frame anchor
     sets keep the original forward.

@@ -549,6 +549,18 @@ def fold_conv_bn_(seq):
     return nn.Sequential(*out)
 
 
+EXACT_RPN_BACKENDS = ("torch", "hip")
+
+
+def exact_rpn_default():
+    """Process default of ``prepare_inference(exact=True, exact_rpn=None)``: the environment variable SEC_FP32_RPN, "torch" (the
+    default: torch's fp32 convolutions) or "hip" (the fp32-MFMA kernels).  Any other value is an error, raised here."""
+    v = os.environ.get("SEC_FP32_RPN", "torch")
+    if v not in EXACT_RPN_BACKENDS:
+        raise ValueError(f"SEC_FP32_RPN={v!r}: allowed values are 'torch' and 'hip'")
+    return v
+
+
 class RPNInference(nn.Module):
     """Inference form of a single-block RPNV2: BatchNorm2d folded into the conv weights (scale) and a float32
     bias, ZeroPad2d merged into the conv padding, the stride-1 1x1 ConvTranspose2d rewritten as a 1x1 conv, the three
@@ -670,6 +682,23 @@ class RPNInference(nn.Module):
                         hw64 = torch.cat([hw, torch.zeros(pad, *hw.shape[1:], device=hw.device)], 0).contiguous()
                         hb64 = torch.cat([hb, torch.zeros(pad, device=hb.device)]).contiguous()
                         self.chain_x3 = [ops.conv2d_pack_weight_x3(wl_), ops.conv2d_pack_weight_x3(hw64), hb64]
+        # backend "hip_f32" (the exact mode's RPN, prepare_inference(exact_rpn="hip")): the same layers with IEEE fp32 products on the
+        # fp32 MFMA (sec_conv2d_nhwc_f32 / _tiles, sec_conv1x1_chain_f32); shapes the kernels do not take keep the torch path
+        self.packed_f32, self.chain_f32, self._f32_convs = None, None, 0
+        if backend == "hip_f32":
+            assert dtype == torch.float32, "RPNInference(backend='hip_f32') is the fp32 form"
+            convs = [i for kind, i in self.plan if kind == "c"]
+            if (single and next(rpn.parameters()).is_cuda
+                    and all(tuple(self.ws[i].shape[1:]) == (128, 3, 3) and self.ws[i].shape[0] % 128 == 0 and self.cfgs[i] == ([1, 1], [1, 1])
+                            and self.ups[i] == 1 for i in convs)):
+                self.packed_f32 = {i: ops.conv2d_pack_weight_f32(self.ws[i]) for i in convs}
+                self._f32_convs = len(convs) if (convs == list(range(len(convs))) and 2 <= len(convs) <= 8
+                                                 and all(self.ws[i].shape[0] == 128 for i in convs)) else 0
+                wl_ = self.ws[-1]
+                if (self.plan[-1][0] == "u" and tuple(wl_.shape) == (128, 128, 1, 1) and self.cfgs[-1] == ([1, 1], [0, 0])
+                        and self.ups[-1] == 1 and hw.shape[0] <= 64):
+                    hw64, hb64 = self._heads64()
+                    self.chain_f32 = [ops.conv2d_pack_weight_f32(wl_), ops.conv2d_pack_weight_f32(hw64), hb64]
         # deblock (1x1, stride 1, 128 -> 128) + heads (<= 128 padded channels) run as ONE kernel (sec_conv1x1_chain_nhwc)
         wl = self.ws[-1]
         self.concat_in_place = True      # multi-block RPNs: the deblocks write into the concatenated map (False: torch.cat of their outputs)
@@ -713,6 +742,16 @@ class RPNInference(nn.Module):
             and all(tuple(self.ws[i].shape) == (128, 128, 3, 3) and self.cfgs[i] == ([1, 1], [1, 1]) and self.ups[i] == 1 for i in convs)) else 0
         if self.packed_x3 is not None:          # fp32: the same live-tile machinery on the split-operand convs (always the lazy form)
             self.background_convs = getattr(self, "_x3_convs", 0)
+        if self.packed_f32 is not None:         # ... and on the fp32-MFMA convs
+            self.background_convs = self._f32_convs
+
+    def _heads64(self):
+        """Merged head weights / biases in fp32, zero-padded to 64 output channels (the second GEMM of sec_conv1x1_chain_f32)."""
+        pad = 64 - self.head_w.shape[0]
+        hw = self.head_w.detach().float()
+        hw64 = torch.cat([hw, torch.zeros(pad, *hw.shape[1:], device=hw.device)], 0).contiguous()
+        hb64 = torch.cat([self.head_b.detach().float(), torch.zeros(pad, device=hw.device)]).contiguous()
+        return hw64, hb64
 
     # The packed weight images (MFMA slab order, the gather permutation, the hi | lo pairs of the fp32 form) are derived from the
     # folded parameters at construction: keep them in step with the parameters.  In place, so that captured graphs stay valid.
@@ -737,6 +776,14 @@ class RPNInference(nn.Module):
                     self.chain_x3[0].copy_(ops.conv2d_pack_weight_x3(self.ws[-1]))
                     self.chain_x3[1].copy_(ops.conv2d_pack_weight_x3(hw64.contiguous()))
                     self.chain_x3[2][:self.head_b.numel()].copy_(self.head_b)
+            if self.packed_f32 is not None:
+                for i, pk in self.packed_f32.items():
+                    pk.copy_(ops.conv2d_pack_weight_f32(self.ws[i]))
+                if self.chain_f32 is not None:
+                    hw64, hb64 = self._heads64()
+                    self.chain_f32[0].copy_(ops.conv2d_pack_weight_f32(self.ws[-1]))
+                    self.chain_f32[1].copy_(ops.conv2d_pack_weight_f32(hw64))
+                    self.chain_f32[2].copy_(hb64)
         self._empty_maps.clear()
 
     def _apply(self, fn, *a, **k):
@@ -750,6 +797,10 @@ class RPNInference(nn.Module):
             self.packed_x3 = {i: move(t) for i, t in self.packed_x3.items()}
             if getattr(self, "chain_x3", None) is not None:
                 self.chain_x3 = [move(t) for t in self.chain_x3]
+        if getattr(self, "packed_f32", None) is not None:
+            self.packed_f32 = {i: move(t) for i, t in self.packed_f32.items()}
+            if self.chain_f32 is not None:
+                self.chain_f32 = [move(t) for t in self.chain_f32]
         self._empty_maps.clear()
         return self
 
@@ -866,6 +917,63 @@ class RPNInference(nn.Module):
             y = ops.bias_act_(F.conv2d(f, self.head_w, None), self.head_b, relu=False)
         return self._split_heads(y)
 
+    def empty_frame_maps_f32(self, h, w):
+        """Output of every 3x3 conv for a frame WITHOUT sites, fp32 channels_last [1, 128, h, w] each, from the fp32-MFMA kernel itself
+        (a copied or lazily read tile is then bit-identical to a computed one).  Cached per map size and weight version; not inside
+        a capture."""
+        src = [self.ws[i] for i in self.packed_f32] + [self.bs[i] for i in self.packed_f32]
+        key = ("f32", int(h), int(w), str(self.ws[0].device), tuple((t.data_ptr(), t._version) for t in src))
+        if key not in self._empty_maps:
+            assert not torch.cuda.is_current_stream_capturing(), "RPNInference.empty_frame_maps_f32: run one eager forward before capturing"
+            self._empty_maps = {k: v for k, v in self._empty_maps.items() if k[0] != "f32"}
+            with torch.no_grad():
+                x = torch.zeros((1, 128, h, w), dtype=torch.float32, device=self.ws[0].device).contiguous(memory_format=torch.channels_last)
+                maps = []
+                for kind, i in self.plan:
+                    if kind == "c":
+                        x = ops.conv2d_nhwc_f32(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], relu=True)
+                        maps.append(x)
+            self._empty_maps[key] = maps
+        return self._empty_maps[key]
+
+    def _forward_f32(self, x):
+        """The block in IEEE fp32 on the fp32 MFMA, structured like :meth:`_forward_x3`: given the sparse middle's rows (a SparseBEV)
+        conv j computes the tiles within j + 1 steps of a site and reads halo pixels of unwritten tiles from the empty frame's map;
+        the last conv materialises its background, because the 1x1 tail (one launch: deblock + heads) reads the whole map."""
+        lists = None
+        if isinstance(x, SparseBEV):
+            convs = [i for kind, i in self.plan if kind == "c"]
+            if self.background_convs and self.skip_background and convs == list(range(len(convs))):
+                sm = x.site_map()
+                empty = self.empty_frame_maps_f32(sm.shape[2], sm.shape[3])
+                live, self.last_live_counts, nbr = x.tile_lists(self.background_convs, masks=True)
+                lists = (live, nbr, empty)
+            x = x.dense()
+        x = x.float().contiguous(memory_format=torch.channels_last)
+        first, ups = self.sparse_input, []
+        for kind, i in self.plan:
+            if kind == "c" and lists is not None:
+                live, nbr, empty = lists
+                last = i == self.background_convs - 1
+                x = ops.conv2d_nhwc_f32_tiles(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], live[i], self.last_live_counts[i],
+                                              background=empty[i] if last else None, relu=True,
+                                              nbr_masks=nbr[i] if (i > 0 and nbr is not None) else None,
+                                              background_in=empty[i - 1] if (i > 0 and nbr is not None) else None)
+            elif kind == "c":
+                x = ops.conv2d_nhwc_f32(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], relu=True, sparse_input=first)
+                first = False
+            elif self.chain_f32 is not None:
+                w1, w2, b2 = self.chain_f32
+                return self._split_heads(ops.conv1x1_chain_f32(x, w1, self.bs[i], w2, b2, 64, relu1=True))
+            else:
+                ups.append(self._conv(x, i))
+        f = ups[0] if len(ups) == 1 else torch.cat(ups, dim=1)
+        if f.is_cuda and f.is_contiguous(memory_format=torch.channels_last):
+            y = self._conv1x1_gemm(f, self.head_w, self.head_b, relu=False)
+        else:
+            y = ops.bias_act_(F.conv2d(f, self.head_w, None), self.head_b, relu=False)
+        return self._split_heads(y)
+
     def _split_heads(self, y):
         n, _, h, wd = y.shape
         ret, c0 = {}, 0
@@ -879,6 +987,8 @@ class RPNInference(nn.Module):
     def forward(self, x):
         if self.packed_x3 is not None:
             return self._forward_x3(x.dense() if isinstance(x, PillarBEV) else x)
+        if self.packed_f32 is not None:
+            return self._forward_f32(x.dense() if isinstance(x, PillarBEV) else x)
         ups = []
         first = self.sparse_input     # x is the scattered sparse-middle output: mostly empty tiles
         gather = None
@@ -1052,18 +1162,22 @@ class SecondDetector(nn.Module):
                                                             **(dict(bf, block_filtering=True) if bf else {}))
 
     # -- inference preparation: bf16 channels-last RPN with folded BN; sparse stack in bf16 (BN folded at run time)
-    def prepare_inference(self, dtype=torch.bfloat16, rpn_backend="hip", gather_first=True, exact=False):
+    def prepare_inference(self, dtype=torch.bfloat16, rpn_backend="hip", gather_first=True, exact=False, exact_rpn=None):
         """``dtype=torch.float32`` selects the fp32-STORAGE pipeline, whose products by default run as three bf16 MFMA passes on split
         operands (16 significant bits per operand, fp32 accumulation; reported as ``ops.FP32_SPLIT_LABEL`` = "bf16x3").  ``exact=True``:
         true fp32 arithmetic, the reference's default precision (train.py:232-235) -- sparse convs on v_mfma_f32_32x32x2_f32 / VALU
-        (``ops.fp32_mode("exact")`` around every forward), the RPN on torch's fp32 convolutions: several times slower, for parity work."""
+        (``ops.fp32_mode("exact")`` around every forward), the RPN on torch's fp32 convolutions: several times slower, for parity work.
+        ``exact_rpn`` picks the exact mode's RPN: "torch" (those convolutions) or "hip" (``RPNInference(backend="hip_f32")``: the
+        fp32-MFMA convs on live tiles, no vendor convolution); None = the process default, :func:`exact_rpn_default` (SEC_FP32_RPN)."""
         # NOTE: MIOpen's fused conv+bias+ReLU plan (torch.miopen_convolution_relu) was measured at ~160 ms per
         # 3x3 conv for bf16 NHWC on gfx950 (naive fallback kernel) vs 0.14 ms unfused -- not an option; the
         # fused dense path is the hand-written MFMA conv (SURVEY 8f item 1).
         self.eval()
         self.fp32_exact = bool(exact) and dtype == torch.float32
+        if exact_rpn is not None and exact_rpn not in EXACT_RPN_BACKENDS:
+            raise ValueError(f"exact_rpn={exact_rpn!r}: allowed values are 'torch' and 'hip'")
         if self.fp32_exact:
-            rpn_backend = "miopen"
+            rpn_backend = "hip_f32" if (exact_rpn or exact_rpn_default()) == "hip" else "miopen"
         if isinstance(self.rpn, RPNV2) and RPNInference.supports(self.rpn) and next(self.parameters()).is_cuda:
             self.rpn = RPNInference(self.rpn, dtype, backend=rpn_backend, gather_first=gather_first)
         else:
@@ -1113,9 +1227,10 @@ class SecondDetector(nn.Module):
 
     def _rpn_takes_rows(self):
         """The RPN consumes the sparse middle's rows + site map (SparseBEV) instead of the dense image: the 16-bit gathered first conv, or
-        the fp32 split-operand convs on live tiles."""
+        the fp32 split-operand / fp32-MFMA convs on live tiles."""
         return getattr(self.rpn, "gather_packed", None) is not None or (
-            getattr(self.rpn, "packed_x3", None) is not None and getattr(self.rpn, "background_convs", 0) > 0)
+            (getattr(self.rpn, "packed_x3", None) is not None or getattr(self.rpn, "packed_f32", None) is not None)
+            and getattr(self.rpn, "background_convs", 0) > 0)
 
     def forward(self, example):
         voxels, num_points, coors = example["voxels"], example["num_points"], example["coordinates"]

@@ -995,6 +995,80 @@ def conv2d_nhwc_x3_tiles(x_hi, x_lo, packed_hi_lo, bias, cout, tile_order, live_
     return y_hi, y_lo
 
 
+def conv2d_pack_weight_f32(weight):
+    """fp32 [Cout, 128, 3, 3] / [Cout, 128, 1, 1] -> the packed fp32 image of :func:`conv2d_nhwc_f32` / :func:`conv1x1_chain_f32`
+    (lane order of v_mfma_f32_32x32x2_f32's weight operand); None when the kernels do not take the shape."""
+    rt.require_gpu(weight)
+    assert weight.dim() == 4 and weight.shape[2] == weight.shape[3]
+    w = weight.detach().float().contiguous()
+    cout, cin, ks = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    nbytes = rt.lib().sec_conv2d_f32_packed_weight_bytes(cout, cin, ks)
+    if nbytes == 0:
+        return None
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+    rt.check(rt.lib().sec_conv2d_f32_pack_weight(rt.ptr(w), cout, cin, ks, rt.ptr(packed), rt.stream()), "sec_conv2d_f32_pack_weight")
+    return packed
+
+
+def _check_f32_image(x):
+    assert x.dim() == 4 and x.shape[1] == 128 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)
+
+
+@_traced("conv2d_nhwc_f32")
+def conv2d_nhwc_f32(x, packed, bias, cout, relu=True, sparse_input=False):
+    """3x3 / stride 1 / pad 1 conv on 128 input channels in IEEE fp32 on the matrix pipe (sec_conv2d_nhwc_f32): x [B,128,H,W]
+    channels_last fp32 -> [B,cout,H,W] channels_last fp32.  ``sparse_input``: all-zero input tiles write act(bias) (bit-identical)."""
+    rt.require_gpu(x, packed)
+    _check_f32_image(x)
+    b, _, h, w = x.shape
+    y = torch.empty((b, int(cout), h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    rc = rt.lib().sec_conv2d_nhwc_f32(rt.ptr(x), b, h, w, rt.ptr(packed), rt.ptr(bias), int(cout), int(bool(relu)) | (2 if sparse_input else 0),
+                                      rt.ptr(y), rt.stream())
+    rt.check(rc, "sec_conv2d_nhwc_f32")
+    return y
+
+
+@_traced("conv2d_nhwc_f32_tiles")
+def conv2d_nhwc_f32_tiles(x, packed, bias, cout, tile_order, live_counts, background=None, relu=True, nbr_masks=None, background_in=None):
+    """:func:`conv2d_nhwc_f32` on the live tiles of one layer of :func:`rpn_tile_live` only (sec_conv2d_nhwc_f32_tiles).  ``background`` =
+    this layer's output for an EMPTY frame, copied into the other tiles (None: they stay unwritten, for a lazy consumer); ``nbr_masks``
+    + ``background_in`` = the producing layer's empty-frame output: halo pixels of tiles the producer did not write are read from it."""
+    rt.require_gpu(x, packed, tile_order, live_counts)
+    _check_f32_image(x)
+    b, _, h, w = x.shape
+    tiles = ((h + 7) // 8) * ((w + 15) // 16)
+    assert tile_order.dtype == torch.int16 and tile_order.is_contiguous() and tuple(tile_order.shape) == (b, tiles)
+    assert live_counts.dtype == torch.int32 and live_counts.is_contiguous() and live_counts.numel() == b
+    for t, ch in ((background, int(cout)), (background_in, 128)):
+        if t is not None:
+            rt.require_gpu(t)
+            assert t.dtype == torch.float32 and t.numel() == h * w * ch and t.is_contiguous(memory_format=torch.channels_last)
+    if nbr_masks is not None:
+        assert background_in is not None and nbr_masks.dtype == torch.int16 and nbr_masks.is_contiguous() and tuple(nbr_masks.shape) == (2, b, tiles)
+    y = torch.empty((b, int(cout), h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    if POISON_LAZY_OUTPUTS and background is None:
+        y.fill_(float("nan"))
+    rc = rt.lib().sec_conv2d_nhwc_f32_tiles(rt.ptr(x), b, h, w, rt.ptr(packed), rt.ptr(bias), int(cout), int(bool(relu)), rt.ptr(tile_order),
+                                            rt.ptr(live_counts), rt.ptr(background), rt.ptr(nbr_masks) if nbr_masks is not None else None,
+                                            rt.ptr(background_in), rt.ptr(y), rt.stream())
+    rt.check(rc, "sec_conv2d_nhwc_f32_tiles")
+    return y
+
+
+@_traced("conv1x1_chain_f32")
+def conv1x1_chain_f32(x, packed_w1, bias1, packed_w2, bias2, cout2, relu1=True):
+    """y = W2 * act(W1 * x + bias1) + bias2 in IEEE fp32 (sec_conv1x1_chain_f32): x [B,128,H,W] channels_last fp32 -> fp32
+    [B, cout2, H, W] channels_last.  Weights: :func:`conv2d_pack_weight_f32` of the [C,128,1,1] tensors (cout2 padded to 64 / 128)."""
+    rt.require_gpu(x, packed_w1, packed_w2)
+    _check_f32_image(x)
+    b, _, h, w = x.shape
+    y = torch.empty((b, int(cout2), h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    rc = rt.lib().sec_conv1x1_chain_f32(rt.ptr(x), b * h * w, rt.ptr(packed_w1), rt.ptr(bias1), int(bool(relu1)), rt.ptr(packed_w2),
+                                        rt.ptr(bias2), int(cout2), rt.ptr(y), rt.stream())
+    rt.check(rc, "sec_conv1x1_chain_f32")
+    return y
+
+
 @_traced("sparse_site_map")
 def sparse_site_map(indices, batch_size, spatial_shape, num_dev=None):
     """[B, D, H, W] int32 map of a sparse tensor's sites: row + 1, 0 = no active site (input of :func:`conv2d_nhwc_gather`)."""

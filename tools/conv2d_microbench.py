@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of sec_conv2d_nhwc on the car.fhd RPN layer (3x3, 128->128, 8 x 200 x 176) vs MIOpen."""
+"""Micro-benchmark of sec_conv2d_nhwc on the car.fhd RPN layer (3x3, 128->128, 8 x 200 x 176) vs MIOpen.
+FP32=1 adds the fp32 rows: sec_conv2d_nhwc_f32 on every tile, sec_conv2d_nhwc_f32_tiles on LIVE_SHARE (default 0.33, the bench
+clouds' 26-39 %) of the tiles -- lazy form and background-copying form -- and F.conv2d fp32 channels-last; fraction of the 157.3 TF
+fp32 matrix peak beside each."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "second.pytorch_amd"))
@@ -31,3 +34,24 @@ if os.environ.get("WITH_MIOPEN"):
     wcl = w.contiguous(memory_format=torch.channels_last)
     t = bench(lambda: ops.bias_act_(torch.nn.functional.conv2d(x, wcl, None, 1, 1), b, True))
     print(f"miopen conv + fused bias/relu: {t:.1f} us  {flop / t / 1e6:.0f} TFLOP/s")
+if os.environ.get("FP32"):
+    PEAK = 157.3
+    xf = x.float().contiguous(memory_format=torch.channels_last)
+    wf = w.float()
+    pkf = ops.conv2d_pack_weight_f32(wf)
+    t = bench(lambda: ops.conv2d_nhwc_f32(xf, pkf, b, 128, relu=True, sparse_input=ZSKIP))
+    print(f"fp32 hip, every tile: {t:.1f} us  {flop / t / 1e6:.1f} TFLOP/s  {flop / t / 1e6 / PEAK:.2f} of the fp32 matrix peak")
+    share = float(os.environ.get("LIVE_SHARE", "0.33"))
+    tiles = 25 * 11
+    n_live = int(round(share * tiles))
+    order = torch.stack([torch.randperm(tiles) for _ in range(8)]).to(torch.int16).cuda()
+    counts = torch.full((8,), n_live, dtype=torch.int32, device="cuda")
+    bg = ops.conv2d_nhwc_f32(torch.zeros_like(xf[:1]), pkf, b, 128, relu=True)
+    lflop = flop * n_live / tiles
+    t = bench(lambda: ops.conv2d_nhwc_f32_tiles(xf, pkf, b, 128, order, counts, relu=True))
+    print(f"fp32 hip, {8 * n_live} live tiles of {8 * tiles}, lazy: {t:.1f} us  {lflop / t / 1e6:.1f} TFLOP/s on its tiles  {lflop / t / 1e6 / PEAK:.2f} of peak")
+    t = bench(lambda: ops.conv2d_nhwc_f32_tiles(xf, pkf, b, 128, order, counts, background=bg, relu=True))
+    print(f"fp32 hip, {8 * n_live} live tiles of {8 * tiles}, background copied: {t:.1f} us  {lflop / t / 1e6:.1f} TFLOP/s on its tiles")
+    wfcl = wf.contiguous(memory_format=torch.channels_last)
+    t = bench(lambda: ops.bias_act_(torch.nn.functional.conv2d(xf, wfcl, None, 1, 1), b, True))
+    print(f"fp32 F.conv2d channels-last + fused bias/relu: {t:.1f} us  {flop / t / 1e6:.1f} TFLOP/s  {flop / t / 1e6 / PEAK:.2f} of peak")

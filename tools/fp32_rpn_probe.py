@@ -1,4 +1,5 @@
-"""Probe: where the fp32 drop-in call spends its time, and how fast torch/MIOpen runs the fp32 RPN block in three forms.
+"""Probe: where the fp32 drop-in call spends its time, and how fast torch/MIOpen runs the fp32 RPN block in three forms,
+beside the fp32-MFMA backend (RPNInference(backend="hip_f32"), dense input: every tile convolved).
     python tools/fp32_rpn_probe.py            (prints JSON lines)"""
 import json
 import os
@@ -37,6 +38,8 @@ def main():
         xcl = x.contiguous(memory_format=torch.channels_last)
         inf = RPNInference(rpn, torch.float32, backend="miopen").to(dev)
         b = timeit(lambda: inf(xcl))
+        inf32 = RPNInference(rpn, torch.float32, backend="hip_f32").to(dev)
+        h32 = timeit(lambda: inf32(xcl))
         import copy
         r2 = copy.deepcopy(rpn)
         r2.blocks = torch.nn.ModuleList([fold_conv_bn_(blk) for blk in r2.blocks])
@@ -48,7 +51,7 @@ def main():
         e = timeit(lambda: F.conv2d(xcl, wcl, None, 1, 1))
         xb, wb = x.bfloat16(), w.bfloat16()
         f = timeit(lambda: F.conv2d(xb, wb, None, 1, 1))
-    print(json.dumps({"rpn_ms": {"modules_nchw_unfolded": round(a, 3), "folded_channels_last": round(b, 3), "folded_nchw": round(c, 3)},
+    print(json.dumps({"rpn_ms": {"modules_nchw_unfolded": round(a, 3), "folded_channels_last": round(b, 3), "hip_f32_every_tile": round(h32, 3), "folded_nchw": round(c, 3)},
                       "one_conv3x3_128_ms": {"fp32_nchw": round(d, 3), "fp32_nhwc": round(e, 3), "bf16_nchw": round(f, 3)}}), flush=True)
 
 
