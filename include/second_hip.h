@@ -82,6 +82,23 @@ size_t sec_voxelize_workspace_bytes(int num_points, int batch, int max_voxels, i
 int sec_simple_voxel_f32(const float *voxels, const int *num_points, int n, const int *num_dev, int max_points, int num_features,
                          int mean_features, void *mean, int mean_dtype, void *stream);
 int sec_rows_differ_f32(const float *a, long long rows, const float *b, long long n, int *flag, void *stream);
+/* SimpleVoxelRadius (voxel_encoder.py:246-255) next to SimpleVoxel: with m = the SimpleVoxel means of the first four point
+ * features, the row is [sqrt(m.x^2 + m.y^2), m.z, m.w, 0] -- computed in fp32 from the same fp32 sums (products, sum and root each
+ * rounded once), rounded once to the storage type, stored with a pitch of FOUR channels (channel 3 = 0) so that the first sparse
+ * conv, its weight zero-padded 3 -> 4 input channels, runs on the 4-channel kernels with aligned row loads.
+ *   sec_voxelize_encode_f32 = sec_voxelize_f32 plus `encoder` (0 = SimpleVoxel, 1 = SimpleVoxelRadius) and `out_pitch` (channels per
+ *   row of `mean`: mean_features for encoder 0, 4 for encoder 1).  encoder outside {0, 1}, a wrong pitch, a radius call without
+ *   `mean` or with rows that are not 16-byte (fp32) / 8-byte (16-bit) aligned: SEC_E_INVALID; radius mode with mean_features != 4:
+ *   SEC_E_UNSUPPORTED; all decided before anything is enqueued.  sec_voxelize_f32 is the encoder-0 form of the same code.
+ *   sec_simple_voxel_radius_f32 = the encoder alone on a voxel tensor the caller holds (cf. sec_simple_voxel_f32), bit identical to
+ *   the fused epilogue; rows at or past *num_dev are zeros. */
+int sec_voxelize_encode_f32(const float *points, const int *point_offsets, int num_points, int num_features,
+                            int batch, const float *h_range6, const float *h_voxel_size3, int max_points,
+                            int max_voxels, int cap_mode, float *voxels, int *coors,
+                            int *num_points_per_voxel, int *voxel_offsets, void *mean, int mean_features,
+                            int mean_dtype, int encoder, int out_pitch, void *workspace, size_t workspace_bytes, void *stream);
+int sec_simple_voxel_radius_f32(const float *voxels, const int *num_points, int n, const int *num_dev, int max_points, int num_features,
+                                int mean_features, void *out, int out_pitch, int out_dtype, void *stream);
 int sec_voxelize_f32(const float *points, const int *point_offsets, int num_points, int num_features,
                      int batch, const float *h_range6, const float *h_voxel_size3, int max_points,
                      int max_voxels, int cap_mode, float *voxels, int *coors,

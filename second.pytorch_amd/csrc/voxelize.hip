@@ -641,10 +641,65 @@ __global__ __launch_bounds__(kBlock) void k_vox_fill(const float *__restrict__ p
     }
 }
 
+// SimpleVoxelRadius.forward (second/pytorch/models/voxel_encoder.py:246-255): [sqrt(mx^2 + my^2), mz, mw] of the SimpleVoxel means,
+// in fp32 (products, sum and root each rounded once: the build keeps them unfused), rounded ONCE to the storage type.  Rows have a
+// pitch of FOUR channels with channel 3 = 0 (8 bytes in 16-bit): the first sparse conv reads them with the aligned row loads of
+// the 4-channel kernels, its weight padded 3 -> 4 input channels with a zero row.
+template <typename OT>
+__device__ __forceinline__ void store_radius_row4(OT *__restrict__ out, size_t row, float mx, float my, float mz, float mw) {
+    const float r = __fsqrt_rn(__fadd_rn(__fmul_rn(mx, mx), __fmul_rn(my, my)));
+    if constexpr (std::is_same<OT, float>::value) {
+        *reinterpret_cast<float4 *>(out + row * 4) = make_float4(r, mz, mw, 0.0f);
+    } else {
+        union { OT h[4]; uint2 u; } v;
+        if constexpr (std::is_same<OT, __half>::value) {
+            v.h[0] = __float2half_rn(r); v.h[1] = __float2half_rn(mz); v.h[2] = __float2half_rn(mw); v.h[3] = __float2half_rn(0.0f);
+        } else {
+            v.h[0] = __float2bfloat16(r); v.h[1] = __float2bfloat16(mz); v.h[2] = __float2bfloat16(mw); v.h[3] = __float2bfloat16(0.0f);
+        }
+        *reinterpret_cast<uint2 *>(out + row * 4) = v.u;
+    }
+}
+
+// SimpleVoxelRadius on a voxel tensor [n, T, F >= 4]: one thread per voxel, the four sums in the slot order of k_vox_fill_mean4 /
+// k_vox_mean (padded slots hold +0.0f), so the row equals the fused epilogue's bit for bit.  Rows at or past the live count are zeros.
+template <typename OT>
+__global__ __launch_bounds__(kBlock) void k_simple_voxel_radius(const float *__restrict__ voxels, const int *__restrict__ num_points, int n,
+                                                               const int *__restrict__ num_dev, int T, int F, OT *__restrict__ out) {
+    const int vid = blockIdx.x * kBlock + threadIdx.x;
+    if (vid >= n) return;
+    const int live = num_dev ? (*num_dev < n ? *num_dev : n) : n;
+    float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (vid < live) {
+        const float *src = voxels + (size_t)vid * T * F;
+        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) s[f] = __fadd_rn(s[f], src[(size_t)t * F + f]);
+        const float cnt = (float)num_points[vid];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) m[f] = __fdiv_rn(s[f], cnt);
+    }
+    store_radius_row4(out, (size_t)vid, m[0], m[1], m[2], m[3]);
+}
+
+template <typename OT>
+static void launch_simple_voxel_radius(const float *voxels, const int *num_points, int n, const int *num_dev, int T, int F, void *out,
+                                       hipStream_t st) {
+    hipLaunchKernelGGL(k_simple_voxel_radius<OT>, dim3(div_up(n, kBlock)), dim3(kBlock), 0, st, voxels, num_points, n, num_dev, T, F, (OT *)out);
+}
+static void simple_voxel_radius_any(const float *voxels, const int *num_points, int n, const int *num_dev, int T, int F, void *out,
+                                    int dtype, hipStream_t st) {
+    if (dtype == SEC_F32) launch_simple_voxel_radius<float>(voxels, num_points, n, num_dev, T, F, out, st);
+    else if (dtype == SEC_F16) launch_simple_voxel_radius<__half>(voxels, num_points, n, num_dev, T, F, out, st);
+    else launch_simple_voxel_radius<__hip_bfloat16>(voxels, num_points, n, num_dev, T, F, out, st);
+}
+
 // k_vox_fill + k_vox_mean in one launch for the common shape (4 point features, a handful of points per voxel): one thread per
 // voxel copies its points and accumulates the SimpleVoxel sums in the same slot order k_vox_mean uses (padded slots add +0.0f,
 // exactly as there), so the results are bit-identical to the two-kernel path; one launch less on the latency chain.
-template <typename OT>
+// RADIUS: the SimpleVoxelRadius row (store_radius_row4) from the same sums instead of the mean row.
+template <typename OT, bool RADIUS = false>
 __global__ __launch_bounds__(kBlock) void k_vox_fill_mean4(const float *__restrict__ points, const int *__restrict__ voxel_offsets,
                                                           const int *__restrict__ count, const int *__restrict__ slot_idx,
                                                           VoxParams p, int mean_features, float *__restrict__ voxels,
@@ -672,6 +727,7 @@ __global__ __launch_bounds__(kBlock) void k_vox_fill_mean4(const float *__restri
     }
     const float inv = (float)n;
     const float m[4] = {__fdiv_rn(s.x, inv), __fdiv_rn(s.y, inv), __fdiv_rn(s.z, inv), __fdiv_rn(s.w, inv)};
+    if constexpr (RADIUS) { store_radius_row4(mean, vid, m[0], m[1], m[2], m[3]); return; }
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
         if (f >= mean_features) break;
@@ -794,12 +850,14 @@ SEC_API size_t sec_voxelize_workspace_bytes(int num_points, int batch, int max_v
     return carve_vox(nullptr, 0, num_points, batch, max_voxels, max_points).bytes;
 }
 
-SEC_API int sec_voxelize_f32(const float *points, const int *point_offsets, int num_points,
-                             int num_features, int batch, const float *h_range6,
-                             const float *h_voxel_size3, int max_points, int max_voxels, int cap_mode,
-                             float *voxels, int *coors, int *num_points_per_voxel, int *voxel_offsets,
-                             void *mean, int mean_features, int mean_dtype, void *workspace, size_t workspace_bytes,
-                             void *stream) {
+// sec_voxelize_f32 / sec_voxelize_encode_f32.  encoder 0 = SimpleVoxel (mean rows of mean_features channels), 1 = SimpleVoxelRadius
+// (rows [r, z, w, 0]); the callers have validated the encoder arguments.
+static int voxelize_impl(const float *points, const int *point_offsets, int num_points,
+                         int num_features, int batch, const float *h_range6,
+                         const float *h_voxel_size3, int max_points, int max_voxels, int cap_mode,
+                         float *voxels, int *coors, int *num_points_per_voxel, int *voxel_offsets,
+                         void *mean, int mean_features, int mean_dtype, int encoder, void *workspace, size_t workspace_bytes,
+                         void *stream) {
     if (num_points < 0 || num_features < 3 || batch <= 0 || max_points <= 0 || max_voxels <= 0 ||
         !h_range6 || !h_voxel_size3 || (!voxels && mean) || !coors || !num_points_per_voxel || !voxel_offsets ||
         (mean && (mean_features <= 0 || mean_features > num_features || mean_dtype < SEC_F32 || mean_dtype > SEC_BF16)))
@@ -907,7 +965,15 @@ SEC_API int sec_voxelize_f32(const float *points, const int *point_offsets, int 
     } else if (bound > 0 && mean && num_features == 4 && max_points <= kCascadeMaxPoints &&
         (reinterpret_cast<uintptr_t>(points) & 15) == 0 && (reinterpret_cast<uintptr_t>(voxels) & 15) == 0) {
         const dim3 gf(div_up(bound, kBlock));
-        if (mean_dtype == SEC_F32)
+        if (encoder == 1) {
+            if (mean_dtype == SEC_F32)
+                hipLaunchKernelGGL((k_vox_fill_mean4<float, true>), gf, dim3(kBlock), 0, st, points, voxel_offsets, w.count, w.slot_idx, p, mean_features, voxels, num_points_per_voxel, (float *)mean);
+            else if (mean_dtype == SEC_F16)
+                hipLaunchKernelGGL((k_vox_fill_mean4<__half, true>), gf, dim3(kBlock), 0, st, points, voxel_offsets, w.count, w.slot_idx, p, mean_features, voxels, num_points_per_voxel, (__half *)mean);
+            else
+                hipLaunchKernelGGL((k_vox_fill_mean4<__hip_bfloat16, true>), gf, dim3(kBlock), 0, st, points, voxel_offsets, w.count, w.slot_idx, p, mean_features, voxels, num_points_per_voxel,
+                                   (__hip_bfloat16 *)mean);
+        } else if (mean_dtype == SEC_F32)
             hipLaunchKernelGGL(k_vox_fill_mean4<float>, gf, dim3(kBlock), 0, st, points, voxel_offsets, w.count, w.slot_idx, p, mean_features, voxels, num_points_per_voxel, (float *)mean);
         else if (mean_dtype == SEC_F16)
             hipLaunchKernelGGL(k_vox_fill_mean4<__half>, gf, dim3(kBlock), 0, st, points, voxel_offsets, w.count, w.slot_idx, p, mean_features, voxels, num_points_per_voxel, (__half *)mean);
@@ -917,7 +983,10 @@ SEC_API int sec_voxelize_f32(const float *points, const int *point_offsets, int 
     } else if (bound > 0) {
         hipLaunchKernelGGL(k_vox_fill, dim3(div_up(bound * max_points, kBlock)), dim3(kBlock), 0, st, points,
                            voxel_offsets, w.count, w.slot_idx, p, voxels, num_points_per_voxel);
-        if (mean) {
+        if (mean && encoder == 1) {
+            // the shapes k_vox_fill_mean4 does not take: the stand-alone kernel on the tensor k_vox_fill just wrote, live rows only
+            simple_voxel_radius_any(voxels, num_points_per_voxel, (int)bound, voxel_offsets + batch, max_points, num_features, mean, mean_dtype, st);
+        } else if (mean) {
             const dim3 gm(div_up(bound * mean_features, kBlock));
             if (mean_dtype == SEC_F32)
                 hipLaunchKernelGGL(k_vox_mean<float>, gm, dim3(kBlock), 0, st, voxels, voxel_offsets, num_points_per_voxel, p, mean_features, (float *)mean);
@@ -929,6 +998,44 @@ SEC_API int sec_voxelize_f32(const float *points, const int *point_offsets, int 
         }
     }
     return check_launch();
+}
+
+SEC_API int sec_voxelize_f32(const float *points, const int *point_offsets, int num_points,
+                             int num_features, int batch, const float *h_range6,
+                             const float *h_voxel_size3, int max_points, int max_voxels, int cap_mode,
+                             float *voxels, int *coors, int *num_points_per_voxel, int *voxel_offsets,
+                             void *mean, int mean_features, int mean_dtype, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+    return voxelize_impl(points, point_offsets, num_points, num_features, batch, h_range6, h_voxel_size3, max_points, max_voxels, cap_mode,
+                         voxels, coors, num_points_per_voxel, voxel_offsets, mean, mean_features, mean_dtype, 0, workspace, workspace_bytes,
+                         stream);
+}
+
+// radius rows are stored whole (16 bytes in fp32, 8 in 16-bit)
+static bool radius_row_aligned(const void *out, int dtype) {
+    return (reinterpret_cast<uintptr_t>(out) & (dtype == SEC_F32 ? 15 : 7)) == 0;
+}
+
+SEC_API int sec_voxelize_encode_f32(const float *points, const int *point_offsets, int num_points,
+                                    int num_features, int batch, const float *h_range6,
+                                    const float *h_voxel_size3, int max_points, int max_voxels, int cap_mode,
+                                    float *voxels, int *coors, int *num_points_per_voxel, int *voxel_offsets,
+                                    void *mean, int mean_features, int mean_dtype, int encoder, int out_pitch,
+                                    void *workspace, size_t workspace_bytes, void *stream) {
+    if (encoder < 0 || encoder > 1) return SEC_E_INVALID;
+    if (mean && mean_features > 0 && mean_dtype >= SEC_F32 && mean_dtype <= SEC_BF16) {
+        if (encoder == 1) {
+            if (mean_features != 4) return SEC_E_UNSUPPORTED;      // x, y, z and one more feature in, [r, z, w, 0] out
+            if (out_pitch != 4 || !radius_row_aligned(mean, mean_dtype)) return SEC_E_INVALID;
+        } else if (out_pitch != mean_features) {
+            return SEC_E_INVALID;
+        }
+    } else if (encoder == 1 && !mean) {
+        return SEC_E_INVALID;                                       // nothing to encode into
+    }
+    return voxelize_impl(points, point_offsets, num_points, num_features, batch, h_range6, h_voxel_size3, max_points, max_voxels, cap_mode,
+                         voxels, coors, num_points_per_voxel, voxel_offsets, mean, mean_features, mean_dtype, encoder, workspace,
+                         workspace_bytes, stream);
 }
 
 namespace sec {
@@ -992,6 +1099,18 @@ SEC_API int sec_simple_voxel_f32(const float *voxels, const int *num_points, int
     else
         hipLaunchKernelGGL(k_simple_voxel<__hip_bfloat16>, grid, dim3(kBlock), 0, st, voxels, num_points, n, num_dev, max_points, num_features, mean_features,
                            (__hip_bfloat16 *)mean);
+    return check_launch();
+}
+
+SEC_API int sec_simple_voxel_radius_f32(const float *voxels, const int *num_points, int n, const int *num_dev, int max_points,
+                                        int num_features, int mean_features, void *out, int out_pitch, int out_dtype, void *stream) {
+    if (n < 0 || max_points <= 0 || num_features <= 0 || mean_features <= 0 || mean_features > num_features || !out ||
+        (n > 0 && (!voxels || !num_points)))
+        return SEC_E_INVALID;
+    if (out_dtype < SEC_F32 || out_dtype > SEC_BF16 || mean_features != 4) return SEC_E_UNSUPPORTED;
+    if (out_pitch != 4 || !radius_row_aligned(out, out_dtype)) return SEC_E_INVALID;
+    if (n == 0) return SEC_OK;
+    simple_voxel_radius_any(voxels, num_points, n, num_dev, max_points, num_features, out, out_dtype, (hipStream_t)stream);
     return check_launch();
 }
 

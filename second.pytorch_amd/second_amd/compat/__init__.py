@@ -140,6 +140,10 @@ def load_protos(reference_root):
         add(name)
     import second  # the reference package (namespace for second.protos)
     pkg = importlib.import_module("second.protos")
+    if getattr(pkg, "_second_amd_loaded_from", None) == proto_dir:
+        # a second install() must not replace the message classes: modules imported since (voxel_builder.py:20 ...) hold the first
+        # set and check their arguments with isinstance
+        return sorted(m for _, m in files.values())
     for name, (fdp, modname) in files.items():
         mod = types.ModuleType(f"second.protos.{modname}")
         fd = pool.FindFileByName(name)
@@ -152,6 +156,7 @@ def load_protos(reference_root):
                 setattr(mod, v.name, v.number)
         sys.modules[mod.__name__] = mod
         setattr(pkg, modname, mod)
+    pkg._second_amd_loaded_from = proto_dir
     return sorted(m for _, m in files.values())
 
 

@@ -14,7 +14,7 @@ strided layer, three modules per layer, the dense [B, 128, 200, 176] image and p
   * the parameters move by state-dict key into :class:`second_amd.models.SecondDetector` (same keys as the reference), the
     BatchNorms are folded, the RPN is repacked for the hand-written MFMA convs; adoption is redone whenever a parameter of the
     network changes (``load_state_dict`` after acceleration, ``net.half()``, ``.to(device)``);
-  * one call = copy the example into static-capacity buffers, ONE hipGraph replay (SimpleVoxel mean | PillarFeatureNet ->
+  * one call = copy the example into static-capacity buffers, ONE hipGraph replay (SimpleVoxel mean | SimpleVoxelRadius | PillarFeatureNet ->
     fused rulebook chain -> 14 sparse convs -> RPN on live tiles -> select / decode / NMS / finalize), ONE device -> host copy of
     the padded detections, and the reference's return value (voxelnet.py:616-643: a list of
     ``{box3d_lidar [k, 7] float32, scores [k] float32, label_preds [k] int64, metadata}`` on the input's device);
@@ -41,6 +41,10 @@ class NotAccelerable(NotImplementedError):
     """The network is outside what the fused pipeline reproduces exactly; the message says which property."""
 
 
+# (y, x) stride of the sparse middles the fused pipeline mirrors (second_amd.models.MIDDLES; middle.py:111-210, 213-300, 418-483)
+SPARSE_MIDDLE_STRIDE = {"SpMiddleFHD": 8, "SpMiddleFHDLite": 8, "SpMiddleFHDPeople": 4}
+
+
 def _seq(v):
     return [float(x) for x in np.asarray(v).reshape(-1)]
 
@@ -51,10 +55,12 @@ def model_config(net):
     why = []
     vfe, mid, rpn = net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn
     vfe_t, mid_t, rpn_t = type(vfe).__name__, type(mid).__name__, type(rpn).__name__
-    if vfe_t not in ("SimpleVoxel", "PillarFeatureNet"):
+    if vfe_t not in ("SimpleVoxel", "SimpleVoxelRadius", "PillarFeatureNet"):
         why.append(f"voxel feature extractor {vfe_t}")
-    if mid_t not in ("SpMiddleFHD", "PointPillarsScatter"):
+    if mid_t not in SPARSE_MIDDLE_STRIDE and mid_t != "PointPillarsScatter":
         why.append(f"middle feature extractor {mid_t}")
+    if vfe_t == "SimpleVoxelRadius" and int(getattr(net, "_num_input_features", 4)) != 4:
+        why.append(f"SimpleVoxelRadius on {int(net._num_input_features)} point features (x, y, z and one more only)")
     if (vfe_t == "PillarFeatureNet") != (mid_t == "PointPillarsScatter"):
         why.append(f"{vfe_t} with {mid_t}")
     if rpn_t != "RPNV2" or getattr(rpn, "_use_groupnorm", False) or not getattr(rpn, "_use_norm", True):
@@ -71,7 +77,14 @@ def model_config(net):
     vg = net.voxel_generator
     pillars = vfe_t == "PillarFeatureNet"
     ups = [float(u) for u in rpn._upsample_strides]
-    factor = (1 if pillars else 8) * float(np.prod([float(s) for s in rpn._layer_strides[:rpn._upsample_start_idx + 1]])) / ups[0]
+    mid_stride = 1 if pillars else SPARSE_MIDDLE_STRIDE[mid_t]
+    # input channels of the sparse middle: what its first conv takes (SimpleVoxelRadius feeds 3 of the 4 point features' means)
+    first = next((m for m in mid.modules() if hasattr(m, "in_channels") and hasattr(m, "indice_key")), None)
+    mid_in = 64 if pillars else int(first.in_channels if first is not None else net._num_input_features)
+    want_in = int(net._num_input_features) - (1 if vfe_t == "SimpleVoxelRadius" else 0)
+    if not pillars and mid_in != want_in:
+        raise NotAccelerable(f"accelerate_model: {mid_t} takes {mid_in} input channels, {vfe_t} produces {want_in}")
+    factor = mid_stride * float(np.prod([float(s) for s in rpn._layer_strides[:rpn._upsample_start_idx + 1]])) / ups[0]
     if abs(factor - round(factor)) > 1e-6:
         raise NotAccelerable(f"accelerate_model: non-integer feature map factor {factor}")
     cfg = dict(
@@ -79,7 +92,7 @@ def model_config(net):
         point_cloud_range=_seq(vg.point_cloud_range), voxel_size=_seq(vg.voxel_size),
         max_points_per_voxel=int(vg.max_num_points_per_voxel), max_voxels=int(getattr(vg, "_max_voxels", 20000)),
         num_point_features=int(net._num_input_features),
-        middle=mid_t, middle_in=64 if pillars else int(net._num_input_features),
+        middle=mid_t, middle_in=mid_in,
         rpn=dict(layer_nums=[int(v) for v in rpn._layer_nums], layer_strides=[int(v) for v in rpn._layer_strides],
                  num_filters=[int(v) for v in rpn._num_filters], upsample_strides=ups,
                  num_upsample_filters=[int(v) for v in rpn._num_upsample_filters], num_input_features=int(rpn._num_input_features),
@@ -93,6 +106,8 @@ def model_config(net):
         use_rotate_nms=bool(net._use_rotate_nms),
         post_center_range=_seq(net._post_center_range) if len(net._post_center_range) else [-1e30] * 3 + [1e30] * 3,
     )
+    if vfe_t == "SimpleVoxelRadius":
+        cfg.update(vfe="SimpleVoxelRadius")
     if pillars:
         lin = vfe.pfn_layers[0].linear
         if len(vfe.pfn_layers) != 1 or lin.in_features != int(net._num_input_features) + 5:
@@ -267,18 +282,23 @@ class _Session:
         # gained nothing and three asynchronous lanes LOST a fifth of their throughput, 16.8 k -> 13.2 k frames/s -- a branched hipGraph
         # serialises against the other lanes' graphs.  Kept linear; the check itself became one launch instead.)
         stale = self.eng.weights_changed_flag()
+        pitch = None
         if det.pillars:
             feats = det.voxel_feature_extractor(self.voxels, self.num_points, self.coors, out_dtype=dt, num_dev=self.n_dev)
         else:
             nf = det.cfg["num_point_features"]      # SimpleVoxel (voxel_encoder.py:207-225), summed in fp32 whatever the storage type
-            if self.voxels.dtype == torch.float32 and self.voxels.is_cuda:
+            if det.encoder == "SimpleVoxelRadius":  # (:228-255) rows [r, z, w, 0] for the zero-padded first conv: one launch
+                vox32 = self.voxels if self.voxels.dtype == torch.float32 else self.voxels.float()
+                feats = det.voxel_feature_extractor.rows4(vox32, self.num_points, out_dtype=dt or torch.float32, num_dev=self.n_dev)
+                pitch = det.voxel_feature_extractor.ROW_PITCH
+            elif self.voxels.dtype == torch.float32 and self.voxels.is_cuda:
                 feats = ops.simple_voxel(self.voxels, self.num_points, nf, out_dtype=dt or torch.float32, num_dev=self.n_dev)   # one launch
             else:
                 feats = self.voxels[:, :, :nf].float().sum(1) / self.num_points.float().unsqueeze(1)
                 if dt is not None:
                     feats = feats.to(dt)
         with det.lazy_heads():          # the head tensor's background tiles stay unwritten: predict_device reads them from the empty frame's map
-            preds = det.network_forward(feats, self.coors, b, num_active_dev=self.n_dev)
+            preds = det.network_forward(feats, self.coors, b, num_active_dev=self.n_dev, in_pitch=pitch)
         out = det.predict_device(preds, b, self.anchors)
         checks = list(getattr(det.middle_feature_extractor, "last_overflow_checks", [])) if not det.pillars else []
         packed = torch.cat([out["boxes"].reshape(b, -1).float(), out["scores"].float(), out["labels"].float(),
@@ -495,8 +515,12 @@ class FusedVoxelNet:
         anchors = example["anchors"].reshape(batch, -1, 7).float()
         with torch.no_grad():
             voxels = example["voxels"]
-            feats = det.voxel_feature_extractor(voxels.float(), example["num_points"], example["coordinates"])
-            preds = det.network_forward(feats, example["coordinates"], batch)
+            pitch = None
+            if det.encoder == "SimpleVoxelRadius":
+                feats, pitch = det.voxel_feature_extractor.encode(voxels.float(), example["num_points"])
+            else:
+                feats = det.voxel_feature_extractor(voxels.float(), example["num_points"], example["coordinates"])
+            preds = det.network_forward(feats, example["coordinates"], batch, in_pitch=pitch)
             out = det.predict_device(preds, batch, anchors)
         self.stats["fused_calls"] += 1
         res = []
@@ -532,8 +556,12 @@ class FusedVoxelNet:
         try:
             with torch.no_grad():
                 nf = det.cfg["num_point_features"]
-                feats = example["voxels"][:, :, :nf].float().sum(1) / example["num_points"].float().unsqueeze(1)
-                det.network_forward(feats, example["coordinates"].int(), batch)
+                pitch = None
+                if det.encoder == "SimpleVoxelRadius":
+                    feats, pitch = det.voxel_feature_extractor.encode(example["voxels"].float(), example["num_points"].int())
+                else:
+                    feats = example["voxels"][:, :, :nf].float().sum(1) / example["num_points"].float().unsqueeze(1)
+                det.network_forward(feats, example["coordinates"].int(), batch, in_pitch=pitch)
         finally:
             ops.set_rulebook_numbering(prev)
         caps = []

@@ -270,6 +270,12 @@ class FusedTrainStep:
             raise NotTrainable("accelerate_model(training): 16-bit features only (train_dtype=torch.bfloat16 / torch.float16)")
         if cfg.get("vfe") == "PillarFeatureNet":
             raise NotTrainable("accelerate_model(training): PointPillars networks train through second_amd.training.DeviceTrainer")
+        # the captured step is built for SimpleVoxel + SpMiddleFHD; the other networks the inference path adopts are refused HERE,
+        # before any forward runs, so training-mode calls keep the reference's own forward from the first one on
+        if cfg.get("vfe", "SimpleVoxel") != "SimpleVoxel":
+            raise NotTrainable(f"accelerate_model(training): voxel feature extractor {cfg['vfe']} has no captured training step")
+        if cfg.get("middle", "SpMiddleFHD") != "SpMiddleFHD":
+            raise NotTrainable(f"accelerate_model(training): middle feature extractor {cfg['middle']} has no captured training step")
         self.net, self.cfg, self.dtype = net, cfg, dtype
         self.loss_cfg = train_config(net)
         self.margin, self.row_bucket = float(margin), int(row_bucket)

@@ -94,6 +94,58 @@ ALL_FHD_NUSC = dict(
 )  # second/configs/nuscenes/all.fhd.config
 
 
+CAR_LITE = dict(
+    name="car.lite",
+    point_cloud_range=[0, -32.0, -3, 52.8, 32.0, 1], voxel_size=[0.05, 0.05, 0.1], max_points_per_voxel=1,
+    max_voxels=30000, num_point_features=4,
+    vfe="SimpleVoxelRadius", middle="SpMiddleFHDLite", middle_in=3,
+    rpn=dict(layer_nums=[5], layer_strides=[1], num_filters=[128], upsample_strides=[1],
+             num_upsample_filters=[128], num_input_features=128),
+    downsample_factor=8,
+    anchor_sizes=[[1.6, 3.9, 1.56]], anchor_ranges=[[0, -32.0, -1.0, 52.8, 32.0, -1.0]], rotations=[0, 1.57],
+    matched_thresholds=[0.6], unmatched_thresholds=[0.45], assign_per_class=True,
+    num_class=1, num_direction_bins=2, direction_offset=0.0, direction_limit_offset=1.0,
+    nms_score_threshold=0.3, nms_pre_max_size=1000, nms_post_max_size=100, nms_iou_threshold=0.01,
+    use_rotate_nms=True, post_center_range=[0, -40, -2.2, 70.4, 40, 0.8],
+)  # second/configs/car.lite.config ("SECOND lite": 160 x 132 feature map)
+
+
+PEOPLE_FHD = dict(
+    name="people.fhd",
+    point_cloud_range=[0, -20, -2.5, 48, 20, 0.5], voxel_size=[0.05, 0.05, 0.15], max_points_per_voxel=5,
+    max_voxels=40000, num_point_features=4,
+    vfe="SimpleVoxel", middle="SpMiddleFHDPeople", middle_in=4,
+    rpn=dict(layer_nums=[5], layer_strides=[1], num_filters=[128], upsample_strides=[1],
+             num_upsample_filters=[128], num_input_features=128),
+    downsample_factor=4,
+    # Cyclist, Pedestrian
+    anchor_sizes=[[0.6, 1.76, 1.73], [0.6, 0.8, 1.73]],
+    anchor_ranges=[[0, -20, -0.6, 48, 20.0, -0.6], [0, -20, -0.6, 48, 20.0, -0.6]], rotations=[0, 1.57],
+    matched_thresholds=[0.5, 0.5], unmatched_thresholds=[0.35, 0.35], assign_per_class=True,
+    num_class=2, num_direction_bins=2, direction_offset=0.0, direction_limit_offset=1.0,
+    nms_score_threshold=0.4, nms_pre_max_size=1000, nms_post_max_size=100, nms_iou_threshold=0.2,
+    use_rotate_nms=True, post_center_range=[0, -20, -2.5, 48.4, 20, -0.5],
+)  # second/configs/people.fhd.config (200 x 240 feature map)
+
+
+ALL_FHD_KITTI = dict(
+    name="all.fhd",
+    point_cloud_range=[0, -32.0, -3, 52.8, 32.0, 1], voxel_size=[0.05, 0.05, 0.1], max_points_per_voxel=5,
+    max_voxels=60000, num_point_features=4,
+    vfe="SimpleVoxelRadius", middle="SpMiddleFHD", middle_in=3,
+    rpn=dict(layer_nums=[5, 5], layer_strides=[1, 2], num_filters=[64, 128], upsample_strides=[1, 2],
+             num_upsample_filters=[128, 128], num_input_features=128),
+    downsample_factor=8,
+    # Car, Cyclist, Pedestrian, Van
+    anchor_sizes=[[1.6, 3.9, 1.56], [0.6, 1.76, 1.73], [0.6, 0.8, 1.73], [1.87103749, 5.02808195, 2.20964255]],
+    anchor_ranges=[[0, -32.0, z, 52.8, 32.0, z] for z in (-1.0, -0.6, -0.6, -1.41)], rotations=[0, 1.57],
+    matched_thresholds=[0.6, 0.35, 0.35, 0.6], unmatched_thresholds=[0.45, 0.2, 0.2, 0.45], assign_per_class=True,
+    num_class=4, num_direction_bins=2, direction_offset=0.0, direction_limit_offset=1.0,
+    nms_score_threshold=0.3, nms_pre_max_size=1000, nms_post_max_size=100, nms_iou_threshold=0.1,
+    use_rotate_nms=True, post_center_range=[0, -40, -2.2, 70.4, 40, 0.8],
+)  # second/configs/all.fhd.config (KITTI, four classes, two-block RPN, 160 x 132 feature map)
+
+
 def anchors_per_location(cfg):
     """target_assigner.num_anchors_per_location (target_assigner.py:249-254): sum over generators of sizes x rotations."""
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
@@ -148,6 +200,42 @@ class SimpleVoxel(nn.Module):
     def forward(self, features, num_voxels, coors=None):
         s = features[:, :, :self.num_input_features].sum(dim=1)
         return (s / num_voxels.type_as(features).view(-1, 1)).contiguous()
+
+
+class SimpleVoxelRadius(nn.Module):
+    """voxel_encoder.py:228-255: the SimpleVoxel means with (x, y) replaced by their radius -- three channels, (r, z, w).
+    ``forward`` is the module's own interface and ALWAYS returns those three columns (torch formulation: CPU tests, training, the
+    module graph).  The device form is a method of its own, :meth:`rows4`: one launch (sec_simple_voxel_radius_f32) that writes rows
+    of FOUR channels ``[r, z, w, 0]`` in ``out_dtype``; whoever uses it hands them to the sparse middle with ``in_pitch=4``, whose
+    first conv then runs with its weight zero-padded 3 -> 4 input channels (SparseConvolution.pad_in_channels)."""
+
+    ROW_PITCH = 4
+
+    def __init__(self, num_input_features=4):
+        super().__init__()
+        self.num_input_features = num_input_features
+
+    def forward(self, features, num_voxels, coors=None):
+        nf = self.num_input_features
+        mean = features[:, :, :nf].sum(dim=1) / num_voxels.type_as(features).view(-1, 1)
+        radius = torch.linalg.vector_norm(mean[:, :2], ord=2, dim=1, keepdim=True)
+        return torch.cat([radius, mean[:, 2:nf]], dim=1)
+
+    def has_rows4(self, features):
+        """the device kernel takes fp32 voxel tensors of >= 4 point features on the GPU, inference only"""
+        return (features.is_cuda and features.dtype == torch.float32 and self.num_input_features == 4 and features.shape[2] >= 4
+                and not torch.is_grad_enabled())
+
+    def rows4(self, features, num_voxels, out_dtype=None, num_dev=None):
+        return ops.simple_voxel_radius(features.contiguous(), num_voxels.int().contiguous(), self.num_input_features,
+                                       out_dtype=out_dtype, num_dev=num_dev)
+
+    def encode(self, features, num_voxels, out_dtype=None, num_dev=None):
+        """-> (rows, in_pitch): the pitch-4 device rows where the kernel applies, else the three-column formulation (in_pitch None)."""
+        if self.has_rows4(features):
+            return self.rows4(features, num_voxels, out_dtype=out_dtype, num_dev=num_dev), self.ROW_PITCH
+        rows = self.forward(features.float(), num_voxels)
+        return (rows if out_dtype is None else rows.to(out_dtype)), None
 
 
 class PFNLayer(nn.Module):
@@ -276,12 +364,17 @@ class SpMiddleFHD(nn.Module):
         self.middle_conv = spconv.SparseSequential(*layers)
         self.fused_chain = True       # static inference: all eight rulebooks from one fused build (SparseSequential.plan_chain)
 
-    def forward(self, voxel_features, coors, batch_size, channels_last=False, num_active_dev=None, site_table=None, bev_sparse=False):
-        """``site_table``: the ``site_table`` entry of the ops.voxelize result these (unfiltered) coors come from -- the first
+    def forward(self, voxel_features, coors, batch_size, channels_last=False, num_active_dev=None, site_table=None, bev_sparse=False,
+                in_pitch=None):
+        """``in_pitch``: the caller declares that ``voxel_features`` are rows of that many channels padded with zeros behind the
+        layer's input channels (SimpleVoxelRadius.rows4: 4); the first conv must have been built for it (pad_in_channels).
+        ``site_table``: the ``site_table`` entry of the ops.voxelize result these (unfiltered) coors come from -- the first
         SubM rulebook then looks its sites up in the voxeliser's hash table instead of hashing them again.
         ``bev_sparse``: return a :class:`SparseBEV` (rows + indices) instead of the dense image when the output grid allows it."""
         x = spconv.SparseConvTensor(voxel_features, coors.int(), self.sparse_shape, batch_size,
                                     num_active_dev=num_active_dev)
+        if in_pitch is not None:
+            x.in_pitch = int(in_pitch)
         if site_table is not None and x.indices.data_ptr() == coors.data_ptr():
             x.site_table = ((x.indices.data_ptr(), x.indices.shape[0]), site_table)
         if num_active_dev is not None and self.fused_chain:
@@ -295,6 +388,53 @@ class SpMiddleFHD(nn.Module):
         d = x.dense()
         n, c, dd, h, w = d.shape
         return d.view(n, c * dd, h, w)
+
+
+# Layer plans of the reference's other sparse middles: ("subm", cout, indice_key) | ("down", cout, kernel, stride, padding).
+MIDDLE_PLANS = {
+    # middle.py:418-483: four strided convs, no SubM level; z 41 -> 21 -> 11 -> 5 -> 2, (y, x) / 8
+    "SpMiddleFHDLite": [("down", 16, 3, 2, 1), ("down", 32, 3, 2, 1), ("down", 64, 3, 2, [0, 1, 1]), ("down", 64, (3, 1, 1), (2, 1, 1), 0)],
+    # middle.py:213-300: SpMiddleFHD minus one stride-2 level; z 21 -> 11 -> 5 -> 2, (y, x) / 4
+    "SpMiddleFHDPeople": [("subm", 16, "subm0"), ("subm", 16, "subm0"), ("down", 32, 3, 2, 1),
+                          ("subm", 32, "subm1"), ("subm", 32, "subm1"), ("down", 64, 3, 2, [0, 1, 1]),
+                          ("subm", 64, "subm2"), ("subm", 64, "subm2"), ("subm", 64, "subm2"), ("down", 64, (3, 1, 1), (2, 1, 1), 0)],
+}
+
+
+class SpMiddlePlanned(SpMiddleFHD):
+    """A sparse middle built from a row of MIDDLE_PLANS: same state-dict keys (``middle_conv.<3 i>.weight``, BatchNorm1d at 3 i + 1),
+    forward, fused rulebook chain and SparseBEV output as :class:`SpMiddleFHD`.  A first layer with fewer than four input channels
+    (SimpleVoxelRadius' three) keeps the reference's weight shape and takes the encoder's pitch-4 rows (pad_in_channels)."""
+
+    plan_name = None
+
+    def __init__(self, output_shape, num_input_features=4):
+        nn.Module.__init__(self)
+        self.sparse_shape = [int(output_shape[1]) + 1, int(output_shape[2]), int(output_shape[3])]
+        layers, cin = [], int(num_input_features)
+        for spec in MIDDLE_PLANS[self.plan_name]:
+            if spec[0] == "subm":
+                conv = spconv.SubMConv3d(cin, spec[1], 3, bias=False, indice_key=spec[2])
+            else:
+                conv = spconv.SparseConv3d(cin, spec[1], spec[2], spec[3], padding=spec[4], bias=False)
+            cin = spec[1]
+            layers.extend([conv, _bn1d(cin), nn.ReLU()])
+        if num_input_features < 4:
+            layers[0].pad_in_channels = 4
+        self.middle_conv = spconv.SparseSequential(*layers)
+        self.fused_chain = True
+
+
+class SpMiddleFHDLite(SpMiddlePlanned):
+    plan_name = "SpMiddleFHDLite"
+
+
+class SpMiddleFHDPeople(SpMiddlePlanned):
+    plan_name = "SpMiddleFHDPeople"
+
+
+VFES = {"SimpleVoxel": SimpleVoxel, "SimpleVoxelRadius": SimpleVoxelRadius}
+MIDDLES = {"SpMiddleFHD": SpMiddleFHD, "SpMiddleFHDLite": SpMiddleFHDLite, "SpMiddleFHDPeople": SpMiddleFHDPeople}
 
 
 class SparseBEV:
@@ -1129,13 +1269,16 @@ class SecondDetector(nn.Module):
         self.grid_size = gs
         dense_shape = [1] + gs[::-1].tolist() + [64]
         self.pillars = cfg.get("vfe") == "PillarFeatureNet"
+        self.encoder = "SimpleVoxelRadius" if cfg.get("vfe") == "SimpleVoxelRadius" else "SimpleVoxel"
         if self.pillars:
             self.voxel_feature_extractor = PillarFeatureNet(cfg["num_point_features"], cfg["vfe_filters"], cfg["voxel_size"],
                                                            cfg["point_cloud_range"])
             self.middle_feature_extractor = PointPillarsScatter(dense_shape, cfg["middle_in"])
         else:
-            self.voxel_feature_extractor = SimpleVoxel(cfg["num_point_features"])
-            self.middle_feature_extractor = SpMiddleFHD(dense_shape, cfg["middle_in"])
+            self.voxel_feature_extractor = VFES[cfg.get("vfe", "SimpleVoxel")](cfg["num_point_features"])
+            self.middle_feature_extractor = MIDDLES[cfg.get("middle", "SpMiddleFHD")](dense_shape, cfg["middle_in"])
+            if cfg["middle_in"] < 4 and isinstance(self.middle_feature_extractor, SpMiddleFHD):
+                self.middle_feature_extractor.middle_conv[0].pad_in_channels = 4      # KITTI all.fhd: SubMConv3d(3, 16) on radius rows
         # a config adopted from a reference-built VoxelNet (second_amd.dropin) names the anchor count only: its anchors arrive
         # with every example (voxelnet.py:358), so no anchor table is generated here
         a_per_loc = int(cfg.get("num_anchor_per_loc") or anchors_per_location(cfg))
@@ -1191,9 +1334,10 @@ class SecondDetector(nn.Module):
         return self
 
     # -- stages ------------------------------------------------------------------------------------
-    def network_forward(self, voxel_features, coors, batch_size, num_active_dev=None, site_table=None):
+    def network_forward(self, voxel_features, coors, batch_size, num_active_dev=None, site_table=None, in_pitch=None):
+        """``in_pitch``: see the sparse middle's forward (pitch-4 rows of SimpleVoxelRadius.rows4 / the voxeliser's radius epilogue)."""
         with ops.fp32_mode("exact" if getattr(self, "fp32_exact", False) else None):
-            return self._network_forward(voxel_features, coors, batch_size, num_active_dev, site_table)
+            return self._network_forward(voxel_features, coors, batch_size, num_active_dev, site_table, in_pitch)
 
     def arithmetic(self):
         """What the prepared pipeline computes with, for records: "bf16" / "fp16" (16-bit features, fp32 accumulation), "fp32" (exact
@@ -1205,8 +1349,9 @@ class SecondDetector(nn.Module):
             return "fp32"
         return ops.FP32_SPLIT_LABEL if next(self.parameters()).is_cuda else "fp32"
 
-    def _network_forward(self, voxel_features, coors, batch_size, num_active_dev=None, site_table=None):
+    def _network_forward(self, voxel_features, coors, batch_size, num_active_dev=None, site_table=None, in_pitch=None):
         dt = self._infer_dtype
+        pitch = {} if in_pitch is None else {"in_pitch": in_pitch}
         if self.pillars:
             mfe = self.middle_feature_extractor
             if (dt in (torch.bfloat16, torch.float16) and isinstance(self.rpn, RPNInference) and self.rpn.use_hip and self.rpn.packed_x3 is None
@@ -1219,10 +1364,10 @@ class SecondDetector(nn.Module):
         if dt is not None:
             spatial = self.middle_feature_extractor(voxel_features.to(dt), coors, batch_size, channels_last=True,
                                                     num_active_dev=num_active_dev, site_table=site_table,
-                                                    bev_sparse=self._rpn_takes_rows())
+                                                    bev_sparse=self._rpn_takes_rows(), **pitch)
         else:
             spatial = self.middle_feature_extractor(voxel_features, coors, batch_size, num_active_dev=num_active_dev,
-                                                    site_table=site_table)
+                                                    site_table=site_table, **pitch)
         return self.rpn(spatial)
 
     def _rpn_takes_rows(self):
@@ -1235,9 +1380,13 @@ class SecondDetector(nn.Module):
     def forward(self, example):
         voxels, num_points, coors = example["voxels"], example["num_points"], example["coordinates"]
         batch_size = example["anchors"].shape[0]
-        with torch.no_grad():
-            feats = self.voxel_feature_extractor(voxels, num_points, coors)
-        preds = self.network_forward(feats, coors, batch_size)
+        pitch = None
+        if self.encoder == "SimpleVoxelRadius":      # (decided under the caller's grad mode: the pitch-4 rows are an inference form)
+            feats, pitch = self.voxel_feature_extractor.encode(voxels, num_points)
+        else:
+            with torch.no_grad():
+                feats = self.voxel_feature_extractor(voxels, num_points, coors)
+        preds = self.network_forward(feats, coors, batch_size, in_pitch=pitch)
         with torch.no_grad():
             return self.predict(preds, example["anchors"].view(batch_size, -1, 7))
 
@@ -1299,14 +1448,16 @@ class SecondDetector(nn.Module):
                                                      out_dtype=self._infer_dtype, num_dev=nd)
             preds = self.network_forward(feats, vox["coordinates"], batch_size, num_active_dev=nd)
             return self.predict_device(preds, batch_size)
+        # SimpleVoxelRadius: rows [r, z, w, 0] from the voxeliser's epilogue, declared to the middle as pitch-4 rows
+        enc, pitch = ({}, {}) if self.encoder == "SimpleVoxel" else ({"encoder": self.encoder}, {"in_pitch": SimpleVoxelRadius.ROW_PITCH})
         if not static:
-            vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, mean_dtype=self._infer_dtype)
-            preds = self.network_forward(vox["mean"], vox["coordinates"], batch_size, site_table=vox.get("site_table"))
+            vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, mean_dtype=self._infer_dtype, **enc)
+            preds = self.network_forward(vox["mean"], vox["coordinates"], batch_size, site_table=vox.get("site_table"), **pitch)
         else:
             # (the voxel means are stored in the sparse stack's dtype by the voxeliser itself: no cast launch inside the captured step)
-            vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, sync=False, mean_dtype=self._infer_dtype)
+            vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, sync=False, mean_dtype=self._infer_dtype, **enc)
             preds = self.network_forward(vox["mean"], vox["coordinates"], batch_size,
-                                         num_active_dev=vox["voxel_offsets"][batch_size:], site_table=vox.get("site_table"))
+                                         num_active_dev=vox["voxel_offsets"][batch_size:], site_table=vox.get("site_table"), **pitch)
         return self.predict_device(preds, batch_size)
 
     def calibrate(self, points, point_offsets, margin=1.25):
@@ -1415,11 +1566,13 @@ class SecondDetector(nn.Module):
             with torch.no_grad():
                 with ops.rt.capture_guard(), torch.cuda.graph(ga, pool=pool, capture_error_mode="thread_local"):
                     vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, sync=False,
-                                                               mean_dtype=self._infer_dtype)
+                                                               mean_dtype=self._infer_dtype,
+                                                               **({} if self.encoder == "SimpleVoxel" else {"encoder": self.encoder}))
+                    pitch = {} if self.encoder == "SimpleVoxel" else {"in_pitch": SimpleVoxelRadius.ROW_PITCH}
                     spatial = self.middle_feature_extractor(vox["mean"].to(self._infer_dtype), vox["coordinates"], batch_size,
                                                             channels_last=True, num_active_dev=vox["voxel_offsets"][batch_size:],
                                                             site_table=vox.get("site_table"),
-                                                            bev_sparse=self._rpn_takes_rows())
+                                                            bev_sparse=self._rpn_takes_rows(), **pitch)
                     self._branch_overflow = [list(getattr(self.middle_feature_extractor, "last_overflow_checks", []))]
                     if isinstance(spatial, SparseBEV) and getattr(self.rpn, "background_convs", 0) and self.rpn.skip_background:
                         lazy_ = self.rpn.lazy_background and self.rpn.background_convs >= 2

@@ -42,9 +42,12 @@ def _traced(name):
 
 
 # ----------------------------------------------------------------------------- voxelisation
+ENCODERS = {"SimpleVoxel": 0, "SimpleVoxelRadius": 1}      # `encoder` of sec_voxelize_encode_f32
+
+
 @_traced("voxelize")
 def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, max_voxels,
-             cap_mode="break", mean_features=0, sync=True, mean_dtype=None, fill=True):
+             cap_mode="break", mean_features=0, sync=True, mean_dtype=None, fill=True, encoder="SimpleVoxel"):
     """Batched points_to_voxel (spconv VoxelGeneratorV2.generate; second/data/preprocess.py:301-316).
 
     points [N,F] float32 cuda (clouds concatenated), point_offsets [B+1] int32 cuda.
@@ -53,8 +56,11 @@ def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, m
     with ``sync=False`` they keep capacity B*max_voxels and only rows < voxel_offsets[B] are defined.
     ``fill=False``: no ``voxels`` tensor (None in the result); the per-voxel point lists stay in the workspace behind
     ``site_table`` for :func:`pfn_forward_slots` (``points`` must stay alive and unchanged until then).
+    ``encoder="SimpleVoxelRadius"`` (voxel_encoder.py:246-255; ``mean_features`` must be 4): ``mean`` holds the rows
+    ``[sqrt(mx^2 + my^2), mz, mw, 0]`` -- pitch 4, channel 3 zero -- instead of the means (sec_voxelize_encode_f32).
     """
     rt.require_gpu(points, point_offsets)
+    enc = ENCODERS[encoder]
     assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous()
     assert point_offsets.dtype == torch.int32
     n, f = points.shape
@@ -74,11 +80,14 @@ def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, m
     l = rt.lib()
     ws_bytes = l.sec_voxelize_workspace_bytes(n, batch, max_voxels, max_points)
     ws = rt.workspace(ws_bytes, dev)
-    rc = l.sec_voxelize_f32(rt.ptr(points), rt.ptr(point_offsets), n, f, batch, rt.f_arr(point_cloud_range),
-                            rt.f_arr(voxel_size), int(max_points), int(max_voxels),
-                            {"break": 0, "continue": 1}[cap_mode], rt.ptr(voxels), rt.ptr(coors), rt.ptr(npv),
-                            rt.ptr(voff), rt.ptr(mean), int(mean_features), rt.dtype_code(mean_dtype), rt.ptr(ws), ws.numel(), rt.stream())
-    rt.check(rc, "sec_voxelize_f32")
+    head = (rt.ptr(points), rt.ptr(point_offsets), n, f, batch, rt.f_arr(point_cloud_range),
+            rt.f_arr(voxel_size), int(max_points), int(max_voxels),
+            {"break": 0, "continue": 1}[cap_mode], rt.ptr(voxels), rt.ptr(coors), rt.ptr(npv),
+            rt.ptr(voff), rt.ptr(mean), int(mean_features), rt.dtype_code(mean_dtype))
+    if enc:
+        rt.check(l.sec_voxelize_encode_f32(*head, enc, 4, rt.ptr(ws), ws.numel(), rt.stream()), "sec_voxelize_encode_f32")
+    else:
+        rt.check(l.sec_voxelize_f32(*head, rt.ptr(ws), ws.numel(), rt.stream()), "sec_voxelize_f32")
     out = {"voxels": voxels, "coordinates": coors, "num_points_per_voxel": npv, "voxel_offsets": voff}
     # the hash table this call leaves in its workspace (cell -> voxel row) is the site lookup of the first SubM rulebook
     r6, v3 = np.asarray(point_cloud_range, np.float32), np.asarray(voxel_size, np.float32)
@@ -364,6 +373,21 @@ def simple_voxel(voxels, num_points, mean_features, out_dtype=None, num_dev=None
     rt.check(rt.lib().sec_simple_voxel_f32(rt.ptr(voxels), rt.ptr(num_points), n, rt.ptr(num_dev), t, f, int(mean_features), rt.ptr(mean),
                                            rt.dtype_code(out_dtype), rt.stream()), "sec_simple_voxel_f32")
     return mean
+
+
+def simple_voxel_radius(voxels, num_points, mean_features=4, out_dtype=None, num_dev=None):
+    """SimpleVoxelRadius.forward (voxel_encoder.py:246-255) of a voxel tensor the caller already holds: -> [N, 4] rows
+    ``[sqrt(mx^2 + my^2), mz, mw, 0]`` in ``out_dtype`` (default fp32), one launch, bit identical to the voxeliser's fused
+    epilogue (sec_simple_voxel_radius_f32).  ``num_dev``: device int32[1], rows at or past it come out as zeros."""
+    rt.require_gpu(voxels, num_points)
+    assert voxels.dtype == torch.float32 and voxels.dim() == 3 and voxels.is_contiguous()
+    assert num_points.dtype == torch.int32 and num_points.is_contiguous() and num_points.numel() == voxels.shape[0]
+    n, t, f = voxels.shape
+    out_dtype = out_dtype or torch.float32
+    out = torch.empty((n, 4), dtype=out_dtype, device=voxels.device)
+    rt.check(rt.lib().sec_simple_voxel_radius_f32(rt.ptr(voxels), rt.ptr(num_points), n, rt.ptr(num_dev), t, f, int(mean_features),
+                                                  rt.ptr(out), 4, rt.dtype_code(out_dtype), rt.stream()), "sec_simple_voxel_radius_f32")
+    return out
 
 
 def tensors_checksum(tensors):

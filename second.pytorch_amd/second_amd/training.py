@@ -125,6 +125,11 @@ class DeviceTrainer:
         (the reference's default training precision); float16 adds dynamic loss scaling (``init_loss_scale``, see
         :meth:`_unscale_and_check`).  Thresholds default to the config's class_settings."""
         from . import models
+        if getattr(det, "encoder", "SimpleVoxel") != "SimpleVoxel":
+            # the training forward feeds the voxeliser's SimpleVoxel means straight to the middle; a network whose middle expects
+            # another encoder's rows (car.lite, KITTI all.fhd) must not be trained on them
+            raise NotImplementedError(f"DeviceTrainer: voxel feature extractor {det.encoder} has no device training step "
+                                      "(train such a network through its own module graph)")
         self.det = det.train()
         self.cfg = det.cfg
         self.max_grad_norm = float(max_grad_norm)

@@ -43,6 +43,14 @@ class SparseConvolution(SparseModule):
         self.static_growth = 2.0
         self.static_out_rows = None
         self.last_num_out = None
+        # A first layer whose input rows are WIDER than in_channels (set by a model, never by the generic API): the rows of
+        # SimpleVoxelRadius' device kernel have a pitch of 4 channels, channel 3 = 0.  The producer SAYS so on the tensor it hands in
+        # (SparseConvTensor.in_pitch, set by the sparse middle's ``in_pitch`` argument) -- nothing is inferred from the column count, so
+        # four columns of anything else fail the kernels' shape check as they always did -- and the [.., 3, Cout] weight is then
+        # zero-padded to `pad_in_channels` input channels when it is handed to the kernels (exact: a zero weight row times a zero
+        # channel), so the layer runs on the 4-channel kernels.  The parameter keeps the reference's shape and state-dict key.
+        self.pad_in_channels = None
+        self._padded = None
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -107,8 +115,39 @@ class SparseConvolution(SparseModule):
             return tbl[1]
         return None
 
-    def packed_weight(self):
+    def takes_padded_rows(self, x):
+        """True when ``x`` is declared to hold this layer's padded rows (see ``pad_in_channels``); a declared pitch the layer was not
+        built for is an error, not a guess."""
+        pitch = getattr(x, "in_pitch", None)
+        if pitch is None:
+            return False
+        if pitch != self.pad_in_channels or x.features.shape[1] != pitch or torch.is_grad_enabled():
+            raise ValueError(f"rows declared with a pitch of {pitch} channels ({x.features.shape[1]} columns, grad "
+                             f"{'on' if torch.is_grad_enabled() else 'off'}) into a layer with in_channels = {self.in_channels}, "
+                             f"pad_in_channels = {self.pad_in_channels}: the padded form is an inference path of layers built for it")
+        return True
+
+    def kernel_weight(self, padded=False):
+        """``weight`` as the kernels consume it: the parameter itself, or -- ``padded``: rows of ``pad_in_channels`` channels, inference
+        only -- its zero-padded image (cached until the parameter changes)."""
         w = self.weight
+        if not padded:
+            return w
+        pad = self.pad_in_channels
+        key = (w._version, w.dtype, w.device, w.data_ptr())
+        if self._padded is None or self._padded[0] != key:
+            self._padded = (key, torch.nn.functional.pad(w.detach(), (0, 0, 0, pad - self.in_channels)).contiguous())
+        return self._padded[1]
+
+    def packed_weight(self, padded=False):
+        w = self.kernel_weight(padded)
+        if padded:                     # the padded image: packed once per parameter version
+            w0 = self.weight
+            key = ("padded", w0._version, w.dtype, w.device, w0.data_ptr(), _ops.get_fp32_mode() if (w.is_cuda and w.dtype == torch.float32) else None)
+            if self._packed_key != key:
+                self._packed = _ops.pack_weight(w) if w.is_cuda else None
+                self._packed_key = key
+            return self._packed
         key = (w._version, w.dtype, w.device, w.data_ptr(), _ops.get_fp32_mode() if (w.is_cuda and w.dtype == torch.float32) else None)
         if self._packed_key != key:
             self._packed = _ops.pack_weight(w.detach().contiguous()) if w.is_cuda else None
@@ -141,11 +180,13 @@ class SparseConvolution(SparseModule):
             out.indice_dict = x.indice_dict
             return out
         rb = self._rulebook(x)
+        padded = self.takes_padded_rows(x)
+        w = self.kernel_weight(padded)
         if self.weight.dtype == x.features.dtype:
-            w, packed = self.weight, self.packed_weight()
+            packed = self.packed_weight(padded)
         else:
             # mixed precision (fp32 master weights, 16-bit features): IndiceConvFunction casts + packs and returns dW in fp32
-            w, packed = self.weight, None
+            packed = None
         feats = Fsp.indice_conv(x.features, w, rb, packed)
         if self.bias is not None:
             feats = feats + self.bias.to(feats.dtype)
@@ -154,8 +195,9 @@ class SparseConvolution(SparseModule):
     def forward_fused(self, x, scale, shift, relu):
         """Inference: conv + per-channel scale/shift (folded BatchNorm1d, bias) + ReLU in ONE launch."""
         rb = self._rulebook(x)
-        w = self.weight.detach()
-        packed = self.packed_weight()
+        padded = self.takes_padded_rows(x)
+        w = self.kernel_weight(padded).detach()
+        packed = self.packed_weight(padded)
         if w.dtype != x.features.dtype:
             w, packed = w.to(x.features.dtype), None
         feats = _ops.indice_conv(x.features.contiguous(), w.contiguous(), rb.nbr_out, rb.num_out, packed=packed,
