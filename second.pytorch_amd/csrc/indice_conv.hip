@@ -606,6 +606,24 @@ constexpr int kBalWgs = 256;                                 // one workgroup pe
 #else
 #define SEC_PACKED_F32_OK
 #endif
+// FL bit 13 (XSH): x-adjacent lanes share gathered rows.  The rows of the device path are numbered in sorted cell order, x fastest, so
+// when lanes r and r + 1 of a tile are x-adjacent cells, lane r's neighbour at (dz, dy, +1) IS lane r + 1's neighbour at (dz, dy, 0) and
+// lane r + 1's at (dz, dy, -1) is lane r's at (dz, dy, 0): the same 64-128 bytes were requested up to three times by adjacent lanes.
+// Per (dz, dy) line g (offsets 3g, 3g + 1, 3g + 2) a lane compares ROW INDICES only -- equal index = equal bytes, whatever the geometry:
+//   offset 3g     comes from the left  when tbl[r][3g]     == tbl[r - 1][3g + 1] >= 0,
+//   offset 3g + 2 comes from the right when tbl[r][3g + 2] == tbl[r + 1][3g + 1] >= 0     (both lanes live, same 32-lane half).
+// Such a lane gives the offset the out-of-range address (no request, zeros) and, at the MFMA, takes the CENTRE fragment of the lane
+// beside it through a DPP wave shift -- same operand, same position in the k = 0..26 sequence, so results are bit-identical.  The
+// centre slot of the register ring therefore lives until offset 3g + 2 is consumed: its refill is issued one offset later.
+template <int CTRL> __device__ __forceinline__ int rows_lane_shift(int v) {
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);   // (lanes 0 / 63 read nothing: zero -- the share rule never uses them)
+}
+constexpr int kDppWaveShl1 = 0x130, kDppWaveShr1 = 0x138;      // lane i reads lane i + 1 / lane i - 1 (all 64 lanes; gfx9 only)
+// t = this lane's table entry at 3g (LEFT) or 3g + 2, c = the entry at 3g + 1 that this lane really gathers (-1: none / lane not live)
+template <bool LEFT> __device__ __forceinline__ bool rows_xshare(int t, int c, int r) {
+    const int n = rows_lane_shift<LEFT ? kDppWaveShr1 : kDppWaveShl1>(c);
+    return t >= 0 && t == n && (LEFT ? r > 0 : r < 31);
+}
 template <typename T, int CIN, int COUT, int KVOL, int DIST, int WAVES, int MINW, int FL>
 SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_rows_buf(const T *__restrict__ feat, long long feat_bytes,
                                                                    const T *__restrict__ packed, const int *__restrict__ nbr,
@@ -640,6 +658,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     // launch's 24 us on that lock step).  W of window g + 1 is loaded when window g starts and stored into the other half of the ring
     // when it ends; every wave has left that half at the barrier that opened window g.
     constexpr bool WIN3 = (FL & 512) != 0;
+    constexpr bool XSH = (FL & 8192) != 0 && STAGE && KVOL == 27 && DIST >= 3 && (ALLW || (WIN3 && LAZY));
     static_assert(!WIN3 || (STAGE && !PIPE && !ALLW && KVOL % 3 == 0 && DIST <= 3), "window form: non-pipelined, 3 offsets per window");
     constexpr int LBUF = ALLW ? (KVOL * C::BSLOT > WAVES * TBL16 ? KVOL * C::BSLOT : WAVES * TBL16) : 1;
     __shared__ __attribute__((aligned(16))) uint4 lbuf[LBUF];
@@ -687,6 +706,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     const u32x4_t *wpv = reinterpret_cast<const u32x4_t *>(packed) + (size_t)piece0 * 64 + lane;
     // byte offset of this lane's first 16-byte chunk of every neighbour row; no neighbour -> beyond the buffer -> zeros
     unsigned off[KVOL];
+    unsigned shm = 0;                                    // XSH: bit 2g = offset 3g comes from lane r - 1, bit 2g + 1 = offset 3g + 2 from lane r + 1
     if constexpr (STAGE) {
         const long long tile_row0 = (long long)bid * (rw * WAVES) + w * rw;   // (32 rows are staged whatever rw is)
         const long long tbl_bytes = (long long)n_cap * KVOL * 4;
@@ -707,7 +727,13 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
         if constexpr (!LAZY) {
 #pragma unroll
             for (int k = 0; k < KVOL; ++k) {
-                const int t = valid ? mine[k] : -1;
+                int t = valid ? mine[k] : -1;
+                if constexpr (XSH) {
+                    if (k % 3 != 1) {
+                        const int c = valid ? mine[k - k % 3 + 1] : -1;
+                        if (k % 3 == 0 ? rows_xshare<true>(t, c, r) : rows_xshare<false>(t, c, r)) { shm |= 1u << (2 * (k / 3) + (k % 3) / 2); t = -1; }
+                    }
+                }
                 off[k] = t >= 0 ? (unsigned)t * ROWB + h * 16 : 0x80000000u;
             }
         }
@@ -740,6 +766,33 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
     u32x4_t areg[DIST][C::KS];
+    // A fragment of offset k, k-step s: the lane's own gather, or (XSH) the centre fragment of the lane beside it
+    auto afrag = [&](int k, int s) __attribute__((always_inline)) -> uint4 {
+        u32x4_t a = areg[k % DIST][s];
+        if constexpr (XSH) {
+            if (k % 3 != 1) {
+                const bool sh = ((shm >> (2 * (k / 3) + (k % 3) / 2)) & 1u) != 0;
+                const u32x4_t c = areg[(k - k % 3 + 1) % DIST][s];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int n = k % 3 == 0 ? rows_lane_shift<kDppWaveShr1>((int)c[i]) : rows_lane_shift<kDppWaveShl1>((int)c[i]);
+                    a[i] = sh ? (unsigned)n : a[i];
+                }
+            }
+        }
+        return __builtin_bit_cast(uint4, a);
+    };
+    // XSH ring discipline: the refill of a centre slot (k % 3 == 1) waits until offset k + 1 has been consumed
+#define SEC_XSH_REFILL(k, FETCH)                                                                                      \
+    if constexpr (XSH) {                                                                                              \
+        if ((k) % 3 == 0) { if ((k) + DIST < KVOL) FETCH((k) + DIST) }                                                \
+        else if ((k) % 3 == 2) {                                                                                      \
+            if ((k) - 1 + DIST < KVOL) FETCH((k) - 1 + DIST)                                                          \
+            if ((k) + DIST < KVOL) FETCH((k) + DIST)                                                                  \
+        }                                                                                                             \
+    } else {                                                                                                          \
+        if ((k) + DIST < KVOL) FETCH((k) + DIST)                                                                      \
+    }
     if constexpr (ALLW) {
 #define SEC_FETCH_A(k)                                                                                                \
     {                                                                                                                 \
@@ -768,12 +821,12 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s = 0; s < C::KS; ++s) {
-                const uint4 a = __builtin_bit_cast(uint4, areg[k % DIST][s]);
+                const uint4 a = afrag(k, s);
 #pragma unroll
                 for (int t = 0; t < C::NT; ++t) acc[t] = Mfma<T>::run(bf[k & 1][s * C::NT + t], a, acc[t]);   // D^T
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (k + DIST < KVOL) SEC_FETCH_A(k + DIST)
+            SEC_XSH_REFILL(k, SEC_FETCH_A)
         }
 #undef SEC_FETCH_A
         SEC_RTL(if (tl) tl2 = clock64();)
@@ -785,7 +838,13 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     const int *lazy_tbl = reinterpret_cast<const int *>(&stage[(STAGE && !ALLW) ? w : 0][0]) + r * KVOL;
     auto off_of = [&](int k) -> unsigned {
         if constexpr (LAZY) {
-            const int t = valid ? lazy_tbl[k] : -1;
+            int t = valid ? lazy_tbl[k] : -1;
+            if constexpr (XSH) {
+                if (k % 3 != 1) {
+                    const int c = valid ? lazy_tbl[k - k % 3 + 1] : -1;
+                    if (k % 3 == 0 ? rows_xshare<true>(t, c, r) : rows_xshare<false>(t, c, r)) { shm |= 1u << (2 * (k / 3) + (k % 3) / 2); t = -1; }
+                }
+            }
 #ifdef SEC_CONV_ABLATIONS
             if constexpr ((FL & 4) != 0) return 0x80000000u;                                  // no gather touches memory
             if constexpr ((FL & 16) != 0) return t >= 0 ? (unsigned)(h * 16) : 0x80000000u;   // all gathers hit one row
@@ -810,8 +869,10 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
         bslot[((k) % 3) * C::BSLOT] = wr0[(k) % DIST];                                                                \
         if (NBW > 1) bslot[((k) % 3) * C::BSLOT + 64] = wr1[(k) % DIST];                                              \
     }
+    if constexpr (!(WIN3 && XSH)) {                      // (the window form issues its own first gathers below)
 #pragma unroll
-    for (int k = 0; k < DIST && k < KVOL; ++k) SEC_FETCH(k)
+        for (int k = 0; k < DIST && k < KVOL; ++k) SEC_FETCH(k)
+    }
     SEC_RTL(long long ts_wait = 0, ts_comp = 0, ts_issue = 0;)
     if constexpr (WIN3) {
         u32x4_t ww0[3], ww1[3];
@@ -867,12 +928,12 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int s2 = 0; s2 < C::KS; ++s2) {
-                    const uint4 a = __builtin_bit_cast(uint4, areg[k % DIST][s2]);
+                    const uint4 a = afrag(k, s2);
 #pragma unroll
                     for (int t = 0; t < C::NT; ++t) acc[t] = Mfma<T>::run(bf[s2 * C::NT + t], a, acc[t]);   // D^T
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (k + DIST < KVOL) SEC_GFETCH(k + DIST)
+                SEC_XSH_REFILL(k, SEC_GFETCH)
             }
             if (g + 1 < KVOL / 3) {
                 SEC_WSTORE(g + 1)
@@ -940,6 +1001,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     }
 #undef SEC_FETCH
 #undef SEC_WPUT
+#undef SEC_XSH_REFILL
     SEC_RTL(if (tl) tl2 = clock64();)
     rows_store<T, COUT>(acc, out, row, valid, h, aff, scale != nullptr, shift != nullptr, relu);
 #ifdef SEC_CONV_TIMELINE
@@ -1056,6 +1118,8 @@ static int g_variant_override = -1;     // sec_indice_conv_set_variant (A/B runs
 // v_mfma_f32_32x32x2_f32 / VALU fma -- IEEE fp32 products and accumulation, the arithmetic of the reference's default precision.
 static int g_fp32_mode = 0;
 static int conv_variant() {
+    // 80 / 81 = the automatic choice, 82 / 83 = variant 22, with the x-share forms of k_conv_rows_buf off / on (xshare_mode below)
+    if (g_variant_override >= 80 && g_variant_override <= 83) return g_variant_override <= 81 ? 1 : 22;
     if (g_variant_override >= 0) return g_variant_override;
     return 1;  // 1 = automatic choice; 0 = one wave per 32-row tile; 8 / 9 / 10.. force one kernel family (sec_indice_conv_set_variant)
 }
@@ -1083,6 +1147,18 @@ static bool ks_auto() {                      // SEC_CONV_KS=1 (experiment builds
     if (v < 0) { const char *e = getenv("SEC_CONV_KS"); v = e ? atoi(e) != 0 : 0; }
     return v != 0;
 }
+// x-share forms of k_conv_rows_buf (FL bit 13): 0 = never, 1 = wherever one exists, -1 = the measured per-instantiation default.
+// Variants 80 / 82 and 81 / 83 (sec_indice_conv_set_variant) or SEC_CONV_XSHARE=0 / 1 force it for A/B runs and the bit-identity tests.
+static int xshare_mode() {
+    if (g_variant_override == 80 || g_variant_override == 82) return 0;
+    if (g_variant_override == 81 || g_variant_override == 83) return 1;
+    static int v = -2;
+    if (v == -2) { const char *e = getenv("SEC_CONV_XSHARE"); v = e ? (atoi(e) != 0) : -1; }
+    return v;
+}
+// Defaults from the A/B on one MI355X (DESIGN_APPENDIX.md, "x-share record"): the 32 -> 32 and the eight-wave 64 -> 64 forms gain per
+// launch and in the headline; the four-wave 64 -> 64 form (two waves per SIMD) is slower per launch and stays on the old path
+constexpr bool kXshare32 = true, kXshare64w8 = true, kXshare64w4 = false;
 static bool rows_balance() { return true; }   // rows per wave chosen on the device so that a launch fills every CU once (round 3: kept)
 static bool buf_shape(int cin, int cout, int kvol) {
     if (kvol == 3) return cin == 64 && cout == 64;
@@ -1217,7 +1293,13 @@ static void launch_mfma(const void *feat, long long n_feat, const void *packed, 
                 // FL + 2048 (BAL): rows per wave chosen on the device so that the launch fills every CU once (SEC_CONV_BAL=0: fixed 32)
                 const bool bal = rows_balance();
                 // 16- and 32-channel layers: the whole weight tensor lives in LDS, no per-offset barrier (-13 .. -24 % per layer)
-                if constexpr (CIN <= 32 && COUT <= 32) { if (bal) { SEC_BUF(6, 8, 3 + 64 + 2048, 27); } else { SEC_BUF(6, 8, 3 + 64, 27); } }
+                const int xsm = xshare_mode();
+                if constexpr (CIN <= 32 && COUT <= 32) {
+                    if constexpr (CIN == 32) {
+                        if (bal && (xsm < 0 ? kXshare32 : xsm != 0)) { SEC_BUF(6, 8, 3 + 64 + 2048 + 8192, 27); return; }
+                    }
+                    if (bal) { SEC_BUF(6, 8, 3 + 64 + 2048, 27); } else { SEC_BUF(6, 8, 3 + 64, 27); }
+                }
                 else if constexpr (CIN == 64 && COUT == 64) {
 #define SEC_BUFM(D, W, M, FLG) launch_rows_buf<T, CIN, COUT, D, W, M, FLG, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st)
                     // prefetch distance 3, B fragments not double-buffered, neighbour offsets re-read from the staged table (FL 1 + 128):
@@ -1230,10 +1312,12 @@ static void launch_mfma(const void *feat, long long n_feat, const void *packed, 
                         // (two waves per SIMD asked for, not three: 63 KB of LDS per four-wave workgroup allow two workgroups per CU whatever
                         // the registers do -- with MINW = 3 hipcc squeezed the kernel into 122 VGPRs + 32 AGPR spill slots for nothing and
                         // warned that it could not meet the occupancy)
+                        else if (bal && (xsm < 0 ? kXshare64w4 : xsm != 0)) { SEC_BUFM(3, 4, 2, 1 + 128 + 512 + 2048 + 8192); }
                         else if (bal) { SEC_BUFM(3, 4, 2, 1 + 128 + 512 + 2048); }
                         else { SEC_BUFM(3, 4, 2, 1 + 128 + 512); }
                     } else if (rows_footprint() == 1) { SEC_BUF(4, 8, 3, 27); }
                     else if (rows_footprint() == 3) { SEC_BUFM(3, 8, 3, 1 + 128); }
+                    else if (bal && (xsm < 0 ? kXshare64w8 : xsm != 0)) { SEC_BUFM(3, 8, 3, 1 + 128 + 512 + 2048 + 8192); }
                     else if (bal) { SEC_BUFM(3, 8, 3, 1 + 128 + 512 + 2048); }
                     else { SEC_BUFM(3, 8, 3, 1 + 128 + 512); }
 #undef SEC_BUFM
