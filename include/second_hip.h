@@ -237,10 +237,27 @@ int sec_indice_conv_fwd(const void *features, int n_in, int cin, const void *wei
 /* Which kernel sec_indice_conv_fwd dispatches for a shape (no launch): 0 generic VALU, 1 register-tiled VALU (fp32),
  * 2 Cin=4 first layer, 3 one MFMA wave per tile, 4 split-K MFMA, 5 split-K MFMA per 32-column slice, 6 row-split MFMA
  * with LDS-staged operands, 7-10 its A/B forms, 11 the buffer-load row-split kernel (the SubMConv3d 64->64 kernel of the
- * roofline figure), 12 the Cin=4 first layer on MFMA.  The parity tests
- * use it to prove which kernel an oracle comparison exercised.  sec_indice_conv_set_variant forces one kernel family
- * (same numbers as the SEC_CONV_VARIANT environment variable; < 0 restores the automatic choice): process-wide,
- * not thread-safe, meant for A/B measurements and tests. */
+ * roofline figure), 12 the Cin=4 first layer on MFMA; builds with -DSEC_CONV_EXPERIMENTS add 13 two row tiles per wave,
+ * 14 input planes staged in LDS windows, 15 the offsets of a row tile split over wave groups, and 99 an A/B kernel
+ * without an id of its own (6-10 exist in those builds only, too).  The parity tests use it to prove which kernel an
+ * oracle comparison exercised; the launch and this query ask the same decision function.
+ * sec_indice_conv_set_variant forces a kernel family: process-wide, not thread-safe, meant for A/B measurements and
+ * tests.  The numbers a shipped build honours:
+ *    < 0, 1   the automatic choice
+ *    0        one MFMA wave per 32-row tile
+ *    8        the sliced split-K kernel (plan 5) for every MFMA shape
+ *    22       the row-split kernel (plan 11) wherever it has a form, whatever the row count
+ *    29       the automatic choice without the row-split kernel and without the Cin=4 MFMA kernel
+ *    30       fp32 features: the register-tiled VALU kernel
+ *    31       fp32 features: the fp32-MFMA kernel
+ *    32       fp32 features: the split-operand kernel that ignores a packed (hi | lo) weight image
+ *    41       16-bit weight gradient: the compacting kernel
+ *    80, 81   the automatic choice with the x-share forms of the row-split kernel off / on
+ *    82, 83   22 with the x-share forms off / on
+ * Any other non-negative number selects split-K (plan 4) for every MFMA shape; on 16-bit features so do 30-32 and 41.
+ * That includes the numbers only experiment builds know (2-7, 9-21, 23-28, 36-46, 50, 60-67, 71-73, 91-96; listed in
+ * tools/kernel_experiments/indice_conv_dispatch.inc): 16-28, 36-40, 44, 45 and 60-67 used to alias 22 for some shapes
+ * in a shipped build and no longer do. */
 int sec_indice_conv_fwd_plan(int cin, int cout, int kvol, int n_out, int dtype, int out_dtype, int has_packed);
 int sec_indice_conv_set_variant(int variant);
 /* Arithmetic of the fp32 sparse convolutions, forward and data gradient (the reference computes fp32 products and sums:

@@ -241,7 +241,7 @@ __device__ long long *g_timeline = nullptr;
 #define SEC_TL_STAMP(x) do {} while (0)
 #endif
 
-static int conv_swizzle() { return 1; }      // XCD-aware tile order (round-1 A/B settled: on)
+constexpr int kReluXcdOrder = 0x10000;       // `relu` bit 16 of the split-K kernels: XCD-aware tile order (round-1 A/B settled: always on)
 static int rows_xcd_order() {                // the same for k_conv_rows_buf (round 6): SEC_CONV_ROWS_XCD=0 keeps the plain order (A/B)
     static int v = -1;
     if (v < 0) {
@@ -466,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_conv_c4(const T *__restrict__ feat, 
 
 
 // ------------------------------------------------------------------------------------------------------------------
-// Row-split kernels: shared configuration and epilogue.  (The first form, with LDS-staged operands -- SEC_CONV_VARIANT=9 -- now lives in
+// Row-split kernels: shared configuration and epilogue.  (The first form, with LDS-staged operands -- variant 9 of experiment builds -- lives in
 // tools/kernel_experiments/indice_conv_rows_ab.inc; its design notes follow because k_conv_rows_buf keeps the work split.)
 // The split-K kernel above moves 5x more weight bytes than feature bytes through the vector L1 (every 32-row tile
 // re-fetches all kvol weight blocks: 380 MB of B against 76 MB of gathered A for the 64->64 SubM layer) and gathers
@@ -574,12 +574,12 @@ __device__ __forceinline__ void rows_stage_affine(float *aff, const float *__res
 #define SEC_RTL(...)
 #endif
 
-#ifdef SEC_CONV_EXPERIMENTS   // the LDS-DMA and register-direct row-split forms (SEC_CONV_VARIANT 9-15): measured, superseded
+#ifdef SEC_CONV_EXPERIMENTS   // the LDS-DMA and register-direct row-split forms (variants 9-15): measured, superseded
 #include "../../tools/kernel_experiments/indice_conv_rows_ab.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
-// Row-split kernel, BUFFER-load form (SEC_CONV_VARIANT 16..19).  What the per-wave timeline of the forms above showed
+// Row-split kernel, BUFFER-load form (plan 11).  What the per-wave timeline of the forms above showed
 // (profiles/r02_a_timeline_conv_rows.txt): the waves hardly wait -- 7 % of the offset loop -- they are busy ISSUING: ~100
 // instructions per offset, a quarter of them v_cndmask that zero the fragments of rows without a neighbour, plus 64-bit
 // address arithmetic, and (LDS-DMA forms) an M0 hand-off per DMA.  Here the gathers are raw buffer loads over the feature
@@ -589,7 +589,15 @@ __device__ __forceinline__ void rows_stage_affine(float *aff, const float *__res
 // gathers because vmcnt retires in order), 8 ds_read_b128 and 8 MFMAs: ~35 instructions.  WAVES = 8 makes the workgroup 256
 // rows, so one copy of W[k] per CU and step instead of two.
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-constexpr int kBalWgs = 256;                                 // one workgroup per CU of an MI355X (FL bit 11, below)
+constexpr int kBalWgs = 256;                                 // one workgroup per CU of an MI355X (kFlBal, below)
+// The FL template argument of k_conv_rows_buf is a sum of these bits (each is explained where the kernel tests it; the decimal sums
+// are part of the kernel names the tests and the bench tables quote, so the values stay)
+enum : int {
+    kFlStage = 1, kFlPipe = 2, kFlSkew = 32, kFlAllW = 64, kFlLazy = 128, kFlWin3 = 512, kFlBal = 2048, kFlXsh = 8192,
+    // timing-only forms of ablation builds (wrong results): no gather touches memory, 8 instead of 32 cache lines per gather
+    // instruction, all gathers hit one line, the weight slices are not fetched
+    kFlAblNoGather = 4, kFlAblFewLines = 8, kFlAblOneLine = 16, kFlAblNoWeights = 4096,
+};
 // FL bit 0: the tile's 32 x KVOL neighbour table arrives as four coalesced 16-byte loads per lane staged through LDS (instead
 //           of KVOL strided dword loads per lane, each a 32-cache-line gather: 27 x 8 waves of them kept the CU's address
 //           pipe busy for ~5000 clocks before the first offset);
@@ -633,20 +641,20 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     using C = RowsCfg<T, CIN, COUT>;
     constexpr int NBW = (C::BPIECES + WAVES - 1) / WAVES;   // 1 KB weight pieces per wave and offset (narrow layers: duplicated)
     constexpr int ROWB = CIN * (int)sizeof(T);           // bytes per feature row
-    constexpr bool STAGE = (FL & 1) != 0, PIPE = (FL & 2) != 0;
+    constexpr bool STAGE = (FL & kFlStage) != 0, PIPE = (FL & kFlPipe) != 0;
     // FL bit 6 (ALLW, narrow layers): W[0..KVOL) of a 16- or 32-channel layer is 14-55 KB -- the whole tensor is copied into LDS
     // once per workgroup and the offset loop runs WITHOUT the per-offset workgroup barrier of the three-slot ring: the eight
     // waves drift apart and hide each other's gather latency.  The staged neighbour tables alias the same LDS (prologue only).
-    constexpr bool ALLW = (FL & 64) != 0;
+    constexpr bool ALLW = (FL & kFlAllW) != 0;
     // FL bit 7 (LAZY): the 27 neighbour offsets of a lane are not held in VGPRs for the whole kernel but re-read from the staged table in
     // LDS when the gather of that offset is issued (one ds_read_b32 + 3 VALU per offset): -25 VGPRs, which is what lets the 64 -> 64
     // kernel fit 168 registers -- three waves per SIMD, or one RPN-conv workgroup beside it on the CU while steps are in flight.
-    constexpr bool LAZY = (FL & 128) != 0 && STAGE && !ALLW;
+    constexpr bool LAZY = (FL & kFlLazy) != 0 && STAGE && !ALLW;
     // FL bit 5 (SKEW, 8-wave workgroups): every step ends in a workgroup barrier, so the two waves of a SIMD leave it together,
     // want the MFMA pipe together, and the loser's later instructions (its next gathers) sit behind its queued MFMAs.  Waves
     // 4..7 therefore issue their gathers BEFORE their MFMAs (one offset later than waves 0..3 would): while one wave of the
     // SIMD multiplies, the other one issues loads, and vice versa.
-    constexpr bool SKEW = (FL & 32) != 0 && WAVES == 8 && PIPE;
+    constexpr bool SKEW = (FL & kFlSkew) != 0 && WAVES == 8 && PIPE;
     const bool early = SKEW && __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) != 0;
     constexpr int TBL16 = 32 * KVOL / 4;                 // 16-byte pieces of one tile's neighbour table
     static_assert(NBW >= 1 && NBW <= 2, "one or two weight pieces per wave");
@@ -657,8 +665,8 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     // apart, so one's B reads run under the other's MFMAs instead of both leaving every barrier together (the ablations put 18 of the
     // launch's 24 us on that lock step).  W of window g + 1 is loaded when window g starts and stored into the other half of the ring
     // when it ends; every wave has left that half at the barrier that opened window g.
-    constexpr bool WIN3 = (FL & 512) != 0;
-    constexpr bool XSH = (FL & 8192) != 0 && STAGE && KVOL == 27 && DIST >= 3 && (ALLW || (WIN3 && LAZY));
+    constexpr bool WIN3 = (FL & kFlWin3) != 0;
+    constexpr bool XSH = (FL & kFlXsh) != 0 && STAGE && KVOL == 27 && DIST >= 3 && (ALLW || (WIN3 && LAZY));
     static_assert(!WIN3 || (STAGE && !PIPE && !ALLW && KVOL % 3 == 0 && DIST <= 3), "window form: non-pipelined, 3 offsets per window");
     constexpr int LBUF = ALLW ? (KVOL * C::BSLOT > WAVES * TBL16 ? KVOL * C::BSLOT : WAVES * TBL16) : 1;
     __shared__ __attribute__((aligned(16))) uint4 lbuf[LBUF];
@@ -677,7 +685,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
     // CU; the 23 k-row stage goes from 179 four-wave workgroups to 238 of 96 rows.  Lanes r >= rw of the 32-row MFMA tile gather
     // nothing (out-of-range offsets) and store nothing.  rw is a multiple of 4 (16-byte table pieces) computed from the DEVICE-side row
     // count; the host launches max(ceil(capacity / (32 * WAVES)), kBalWgs) workgroups, the surplus ones exit here.
-    constexpr bool BAL = (FL & 2048) != 0;
+    constexpr bool BAL = (FL & kFlBal) != 0;
     int rw = 32;
     if constexpr (BAL) {
         const int per_wg = (n_out + kBalWgs - 1) / kBalWgs;
@@ -746,15 +754,15 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
         }
     }
 #ifdef SEC_CONV_ABLATIONS   // timing-only forms (wrong results): where does the offset loop's time go?
-    if constexpr ((FL & 4) != 0) {          // no gather touches memory
+    if constexpr ((FL & kFlAblNoGather) != 0) {          // no gather touches memory
 #pragma unroll
         for (int k = 0; k < KVOL; ++k) off[k] = 0x80000000u;
     }
-    if constexpr ((FL & 8) != 0) {          // every gather instruction touches 8 cache lines instead of 32
+    if constexpr ((FL & kFlAblFewLines) != 0) {          // every gather instruction touches 8 cache lines instead of 32
 #pragma unroll
         for (int k = 0; k < KVOL; ++k) off[k] = (unsigned)__shfl((int)off[k], lane & ~3, 64);
     }
-    if constexpr ((FL & 16) != 0) {         // all gathers hit one line
+    if constexpr ((FL & kFlAblOneLine) != 0) {         // all gathers hit one line
 #pragma unroll
         for (int k = 0; k < KVOL; ++k) off[k] = h * 16;
     }
@@ -846,8 +854,8 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
                 }
             }
 #ifdef SEC_CONV_ABLATIONS
-            if constexpr ((FL & 4) != 0) return 0x80000000u;                                  // no gather touches memory
-            if constexpr ((FL & 16) != 0) return t >= 0 ? (unsigned)(h * 16) : 0x80000000u;   // all gathers hit one row
+            if constexpr ((FL & kFlAblNoGather) != 0) return 0x80000000u;                                  // no gather touches memory
+            if constexpr ((FL & kFlAblOneLine) != 0) return t >= 0 ? (unsigned)(h * 16) : 0x80000000u;   // all gathers hit one row
 #endif
             return t >= 0 ? (unsigned)t * ROWB + h * 16 : 0x80000000u;
         } else {
@@ -888,7 +896,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(WAVES * 64, MINW) void k_conv_row
 #define SEC_WLOAD(g)                                                                                                  \
     {                                                                                                                 \
         _Pragma("unroll") for (int j_ = 0; j_ < 3; ++j_) {                                                            \
-            if constexpr ((FL & 4096) != 0) { ww0[j_] = u32x4_t{(unsigned)lane, 0u, 0u, 0u}; if (NBW > 1) ww1[j_] = ww0[j_]; }  \
+            if constexpr ((FL & kFlAblNoWeights) != 0) { ww0[j_] = u32x4_t{(unsigned)lane, 0u, 0u, 0u}; if (NBW > 1) ww1[j_] = ww0[j_]; }  \
             else {                                                                                                    \
             ww0[j_] = wpv[(size_t)(3 * (g) + j_) * C::BSLOT];                                                         \
             if (NBW > 1) ww1[j_] = wpv[(size_t)(3 * (g) + j_) * C::BSLOT + 64];                                       \
@@ -1018,7 +1026,7 @@ static void launch_rows_buf(const void *feat, long long n_feat, const void *pack
                             const float *scale, const float *shift, int relu, void *out, hipStream_t st) {
     set_last_kernel("k_conv_rows_buf<%s, %d, %d, %d, %d, %d, %d, %d>", dtype_name<T>(), CIN, COUT, KVOL, DIST, WAVES, MINW, FL);
     int blocks = div_up(n_out, 32 * WAVES);
-    if ((FL & 2048) != 0 && blocks < kBalWgs) blocks = kBalWgs;      // BAL: the kernel spreads the rows over up to kBalWgs workgroups
+    if ((FL & kFlBal) != 0 && blocks < kBalWgs) blocks = kBalWgs;      // BAL: the kernel spreads the rows over up to kBalWgs workgroups
     const int xcd = rows_xcd_order();
     if (xcd) blocks = (blocks + 7) / 8 * 8 + 8;                      // the XCD-contiguous order needs ceil(live tiles / 8) workgroups per XCD
     hipLaunchKernelGGL((k_conv_rows_buf<T, CIN, COUT, KVOL, DIST, WAVES, MINW, FL>), dim3(blocks), dim3(WAVES * 64), 0, st,
@@ -1026,12 +1034,9 @@ static void launch_rows_buf(const void *feat, long long n_feat, const void *pack
                        (relu & 1) | (xcd << 16), (T *)out);
 }
 
-#ifdef SEC_CONV_EXPERIMENTS   // round-6 A/B form: the offsets of a row tile split over three wave groups (k_conv_rows_ks): measured slower
-#include "../../tools/kernel_experiments/indice_conv_rows_r06.inc"
-#endif
-
-#ifdef SEC_CONV_EXPERIMENTS   // round-3 A/B forms: two row tiles per wave (k_conv_rows_m2), input planes in LDS windows (k_conv_rows_lds)
-#include "../../tools/kernel_experiments/indice_conv_rows_r03.inc"
+#ifdef SEC_CONV_EXPERIMENTS
+#include "../../tools/kernel_experiments/indice_conv_rows_r06.inc"   // round 6: the offsets of a row tile split over three wave groups (k_conv_rows_ks): measured slower
+#include "../../tools/kernel_experiments/indice_conv_rows_r03.inc"   // round 3: two row tiles per wave (k_conv_rows_m2), input planes in LDS windows (k_conv_rows_lds)
 #endif
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1112,318 +1117,207 @@ __global__ __launch_bounds__(kBlock) void k_conv_c4_mfma(const T *__restrict__ f
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Host dispatch of the 16-bit forward (and of the data gradient, which runs the same kernels with Cin / Cout swapped).
+// Variant numbers of sec_indice_conv_set_variant that a shipped build honours (the table in include/second_hip.h); any other
+// non-negative number selects split-K k_conv_mfma_sk for every MFMA shape.
+enum ConvVariant : int {
+    kVarWave = 0,                // one wave per 32-row tile (k_conv_mfma)
+    kVarAuto = 1,                // the automatic choice (also every negative number)
+    kVarSks = 8,                 // the cout-sliced split-K kernel for every MFMA shape
+    kVarRows = 22,               // the row-split kernel wherever it has a form, whatever the row count
+    kVarAutoPlain = 29,          // the automatic choice without the row-split and the C4-MFMA kernels
+    kVarF32Valu = 30,            // fp32 features: the register-tiled VALU kernel
+    kVarF32Mfma = 31,            // fp32 features: the fp32-MFMA kernel
+    kVarF32SplitUnpacked = 32,   // fp32 features: the split-operand kernel that ignores the packed (hi | lo) image
+    kVarWgradCompact = 41,       // 16-bit weight gradient: the compacting kernel instead of k_conv_wgrad_tr
+    kVarXshOffAuto = 80, kVarXshOnAuto = 81,   // kVarAuto with the x-share forms of k_conv_rows_buf off / on
+    kVarXshOffRows = 82, kVarXshOnRows = 83,   // kVarRows with them off / on
+};
 static int g_variant_override = -1;     // sec_indice_conv_set_variant (A/B runs and the parity tests of every shipped kernel)
 // sec_set_fp32_mode: arithmetic of the fp32 sparse convolutions (forward and data gradient).  0 = SEC_FP32_SPLIT16: operands split
 // into bf16 (hi, lo) pairs on the bf16 matrix pipe, 16 significant bits per operand, fp32 accumulation (fast).  1 = SEC_FP32_EXACT:
 // v_mfma_f32_32x32x2_f32 / VALU fma -- IEEE fp32 products and accumulation, the arithmetic of the reference's default precision.
 static int g_fp32_mode = 0;
-static int conv_variant() {
-    // 80 / 81 = the automatic choice, 82 / 83 = variant 22, with the x-share forms of k_conv_rows_buf off / on (xshare_mode below)
-    if (g_variant_override >= 80 && g_variant_override <= 83) return g_variant_override <= 81 ? 1 : 22;
-    if (g_variant_override >= 0) return g_variant_override;
-    return 1;  // 1 = automatic choice; 0 = one wave per 32-row tile; 8 / 9 / 10.. force one kernel family (sec_indice_conv_set_variant)
-}
 
-// kernel ids reported by sec_indice_conv_fwd_plan
+// The variant in force and the x-share mode of k_conv_rows_buf (kFlXsh): 0 = never, 1 = wherever a sharing form exists, -1 = the
+// measured per-form default.  SEC_CONV_XSHARE=0 / 1 or the variants 80-83 force it for A/B runs and the bit-identity tests.
+struct ConvSetting { int variant, xshare; };
+static ConvSetting conv_setting() {
+    switch (g_variant_override) {
+    case kVarXshOffAuto: return {kVarAuto, 0};
+    case kVarXshOnAuto: return {kVarAuto, 1};
+    case kVarXshOffRows: return {kVarRows, 0};
+    case kVarXshOnRows: return {kVarRows, 1};
+    default: break;
+    }
+    static int env = -2;
+    if (env == -2) { const char *e = getenv("SEC_CONV_XSHARE"); env = e ? (atoi(e) != 0) : -1; }
+    return {g_variant_override < 0 ? kVarAuto : g_variant_override, env};
+}
+static int conv_variant() { return conv_setting().variant; }
+
+// kernel ids reported by sec_indice_conv_fwd_plan (6-10, 13-15 and 99: experiment builds only)
 enum { PLAN_GENERIC = 0, PLAN_TILED = 1, PLAN_C4 = 2, PLAN_MFMA_WAVE = 3, PLAN_MFMA_SK = 4, PLAN_MFMA_SKS = 5, PLAN_ROWS = 6,
        PLAN_ROWS_COMPACT = 7, PLAN_ROWS_TOUCH = 8, PLAN_ROWS_COMPACT_TOUCH = 9, PLAN_ROWS_REG = 10, PLAN_ROWS_BUF = 11, PLAN_C4_MFMA = 12, PLAN_ROWS_M2 = 13, PLAN_ROWS_LDS = 14, PLAN_ROWS_KS = 15, PLAN_EXPERIMENT = 99 };
 
-// Row count from which the buffer-load row-split kernel replaces split-K in the automatic choice (the
-// row-split chain of 27 offsets needs enough workgroups to fill the chip, split-K has a 4x shorter chain per wave)
-static int rows_min() {
-    return 40000;   // car.fhd batch 8: layers 1-8 (>= 56k rows) gain 25-30 %, the 23k-row layers lose
+// the (Cin, Cout) pairs with k_conv_mfma* instantiations: the forward shapes of the served networks and their data gradients
+#define SEC_MFMA_SHAPES(X) X(16, 16) X(16, 32) X(32, 32) X(32, 64) X(64, 64) X(64, 128) X(128, 128) X(16, 64) X(64, 32) X(32, 16) X(128, 64)
+static bool mfma_shape(int cin, int cout) {
+#define SEC_IS(CI, CO) if (cin == CI && cout == CO) return true;
+    SEC_MFMA_SHAPES(SEC_IS)
+#undef SEC_IS
+    return false;
 }
-constexpr int kRowsMinSmall = 8192;
-// A/B switch of the 64 -> 64 row-split kernel: 0 = default (small footprint + one barrier per three offsets, 142 VGPRs), 1 = the 194-VGPR
-// form (prefetch distance 4, double-buffered B fragments, a barrier per offset), 3 = small footprint with a barrier per offset (134 VGPRs),
-// 4 = the 128-row workgroups of the mid-size layers with a barrier per offset (198 VGPRs)
-static int rows_footprint() {
-    return 0;       // rounds 2-3 A/B settled: form 0 (numbers in DESIGN_APPENDIX.md)
+
+// Row counts from which the row-split kernel replaces split-K in the automatic choice (its chain of 27 offsets needs enough workgroups
+// to fill the chip, split-K has a 4x shorter chain per wave).  kRowsMin, every shape: car.fhd batch 8, layers 1-8 (>= 56 k rows) gain
+// 25-30 %, the 23 k-row layers lose.  kRowsMinSmall, 64 -> 64 with 27 offsets (the 23 k-row stage of car.fhd at batch 8): four-wave
+// workgroups (128 rows) fill the chip where the eight-wave form leaves CUs idle -- 13.2 us vs 14.9 us split-K.
+constexpr int kRowsMin = 40000, kRowsMinSmall = 8192;
+
+// The shapes k_conv_rows_buf is instantiated for, and its shipped forms.  Every 27-offset form carries kFlBal (rows per wave chosen on
+// the device so that a launch fills every CU once; round 3 A/B: kept).
+constexpr bool rows_shape_narrow(int cin, int cout) { return (cin == 16 && (cout == 16 || cout == 32)) || (cin == 32 && cout == 32); }
+constexpr bool rows_shape_wide(int cin, int cout) { return cin == 32 && cout == 64; }
+constexpr bool rows_shape_64(int cin, int cout) { return cin == 64 && cout == 64; }
+constexpr bool buf_shape(int cin, int cout, int kvol) {
+    if (kvol == 3) return rows_shape_64(cin, cout);
+    return kvol == 27 && (rows_shape_narrow(cin, cout) || rows_shape_wide(cin, cout) || rows_shape_64(cin, cout));
 }
-// 1: the automatic choice would take the two-tiles-per-wave kernel (k_conv_rows_m2, experiment builds) for the 64 -> 64 layers: measured slower
-static int m2_auto() { return 0; }
-static bool ks_auto() {                      // SEC_CONV_KS=1 (experiment builds): k_conv_rows_ks for the mid-size 64 -> 64 layers (A/B)
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("SEC_CONV_KS"); v = e ? atoi(e) != 0 : 0; }
-    return v != 0;
-}
-// x-share forms of k_conv_rows_buf (FL bit 13): 0 = never, 1 = wherever one exists, -1 = the measured per-instantiation default.
-// Variants 80 / 82 and 81 / 83 (sec_indice_conv_set_variant) or SEC_CONV_XSHARE=0 / 1 force it for A/B runs and the bit-identity tests.
-static int xshare_mode() {
-    if (g_variant_override == 80 || g_variant_override == 82) return 0;
-    if (g_variant_override == 81 || g_variant_override == 83) return 1;
-    static int v = -2;
-    if (v == -2) { const char *e = getenv("SEC_CONV_XSHARE"); v = e ? (atoi(e) != 0) : -1; }
-    return v;
-}
-// Defaults from the A/B on one MI355X (DESIGN_APPENDIX.md, "x-share record"): the 32 -> 32 and the eight-wave 64 -> 64 forms gain per
-// launch and in the headline; the four-wave 64 -> 64 form (two waves per SIMD) is slower per launch and stays on the old path
+// 16- and 32-channel layers, prefetch distance 6: the whole weight tensor lives in LDS, no per-offset barrier (-13 .. -24 % per layer)
+constexpr int kFlNarrow = kFlStage + kFlPipe + kFlAllW + kFlBal;
+// 32 -> 64, prefetch distance 4: three-slot weight ring, B fragments double-buffered, a barrier per offset
+constexpr int kFlWide = kFlStage + kFlPipe + kFlBal;
+// 64 -> 64, 27 offsets: prefetch distance 3, B fragments not double-buffered, neighbour offsets re-read from the staged table
+// (kFlStage + kFlLazy): 134 VGPRs instead of the 194 of the kFlWide form at distance 4, at the same stand-alone time (23.3 vs 23.6 us)
+// -- and +3.9 % frames/s with three steps in flight, where the kernel's footprint decides what else fits on the CU beside it; plus one
+// barrier per three offsets (kFlWin3, six-slot weight ring, 142 VGPRs): 23.5 -> 22.1 us stand-alone.  Rounds 2-3 A/B, numbers in
+// DESIGN_APPENDIX.md.  The same flags serve the four-wave (128-row) workgroups of the mid-size layers: 12.65 us against 13.3 us for
+// their barrier-per-offset form at distance 4 (198 VGPRs).  Those ask for two waves per SIMD, not three: 63 KB of LDS per four-wave
+// workgroup allow two workgroups per CU whatever the registers do -- with MINW = 3 hipcc squeezed the kernel into 122 VGPRs + 32 AGPR
+// spill slots for nothing and warned that it could not meet the occupancy.
+constexpr int kFl64 = kFlStage + kFlLazy + kFlWin3 + kFlBal;
+constexpr int kFl64K3 = kFlStage + kFlPipe;      // 64 -> 64, three offsets
+static_assert(kFlNarrow == 2115 && kFlNarrow + kFlXsh == 10307 && kFlWide == 2051 && kFl64 == 2689 && kFl64 + kFlXsh == 10881 && kFl64K3 == 3,
+              "the decimal FL values are part of the kernel names that tests and bench tables quote");
+// x-share defaults from the A/B on one MI355X (DESIGN_APPENDIX.md, "x-share record"): the 32 -> 32 and the eight-wave 64 -> 64 forms gain
+// per launch and in the headline; the four-wave 64 -> 64 form (two waves per SIMD) is slower per launch and stays on the old path
 constexpr bool kXshare32 = true, kXshare64w8 = true, kXshare64w4 = false;
-static bool rows_balance() { return true; }   // rows per wave chosen on the device so that a launch fills every CU once (round 3: kept)
-static bool buf_shape(int cin, int cout, int kvol) {
-    if (kvol == 3) return cin == 64 && cout == 64;
-    if (kvol != 27) return false;
-    return (cin == 16 && (cout == 16 || cout == 32)) || (cin == 32 && (cout == 32 || cout == 64)) || (cin == 64 && cout == 64);
+enum RowsForm : int { kRowsNone = 0, kRowsNarrow, kRowsNarrowXsh, kRowsWide, kRows64W8, kRows64W8Xsh, kRows64W4, kRows64W4Xsh, kRows64K3 };
+
+// the shipped form of a buf_shape(); `mid`: the mid-size layers of the automatic choice (128-row workgroups for 64 -> 64)
+static int rows_form(int cin, int cout, int kvol, bool mid, int xshare) {
+    auto xsh = [&](bool dflt) { return xshare < 0 ? dflt : xshare != 0; };
+    if (kvol == 3) return kRows64K3;
+    if (rows_shape_narrow(cin, cout)) return cin == 32 && xsh(kXshare32) ? kRowsNarrowXsh : kRowsNarrow;
+    if (rows_shape_wide(cin, cout)) return kRowsWide;
+    if (mid) return xsh(kXshare64w4) ? kRows64W4Xsh : kRows64W4;
+    return xsh(kXshare64w8) ? kRows64W8Xsh : kRows64W8;
 }
 
-// which row-split kernel (0 = none) the 16-bit MFMA path takes for this shape under the current variant setting
-static int rows_plan(int cin, int cout, int kvol, int n_out, bool same_dtype) {
-    if (!same_dtype) return 0;
-    const int v = conv_variant();
-    if (buf_shape(cin, cout, kvol)) {
-#ifdef SEC_CONV_EXPERIMENTS
-        if (cin == 64 && cout == 64 && kvol == 27 && v == 46) return PLAN_ROWS_LDS;          // input planes staged in LDS (round 3)
-        if (cin == 64 && cout == 64 && kvol == 27 && (v == 41 || v == 42 || v == 43 || (v == 1 && m2_auto() && n_out >= rows_min())))
-            return PLAN_ROWS_M2;                                                           // two row tiles per wave (round 3)
+struct ConvPlan { int id, form; };      // form: a RowsForm, for PLAN_ROWS_BUF
+#ifdef SEC_CONV_EXPERIMENTS             // the plan and launch hooks of A/B builds
+#include "../../tools/kernel_experiments/indice_conv_dispatch.inc"
 #endif
-        // offsets split over wave groups (k_conv_rows_ks, round 6, experiment builds): 50 forces it for any row count, SEC_CONV_KS=1 makes
-        // it the automatic choice of the mid-size 64 -> 64 layers (measured slower than the four-wave form of k_conv_rows_buf)
-#ifdef SEC_CONV_EXPERIMENTS
-        if (cin == 64 && cout == 64 && kvol == 27 && (v == 50 || (v >= 71 && v <= 73) || (v == 1 && n_out >= kRowsMinSmall && n_out < rows_min() && ks_auto()))) return PLAN_ROWS_KS;
-#endif
-        if (v == 22 || (((v >= 16 && v <= 28) || v == 44 || v == 45 || (v >= 60 && v <= 67)) && cin == 64 && cout == 64 && kvol == 27)) return PLAN_ROWS_BUF;
-        if (v >= 36 && v <= 40) return PLAN_ROWS_BUF;
-        if (v == 1 && n_out >= rows_min()) return PLAN_ROWS_BUF;
-        // 64 -> 64, 27 offsets, 8 k .. 40 k rows (the 23 k-row stage of car.fhd at batch 8): four-wave workgroups (128 rows) fill the
-        // chip where the eight-wave form leaves CUs idle: 13.2 us vs 14.9 us split-K
-        if (v == 1 && cin == 64 && cout == 64 && kvol == 27 && n_out >= kRowsMinSmall) return PLAN_ROWS_BUF;
+
+// THE decision of the 16-bit forward: which kernel serves a (Cin, Cout, kvol) layer of `rows` output rows.  sec_indice_conv_fwd, the
+// data gradient and sec_indice_conv_fwd_plan all ask here.  PLAN_GENERIC = none of the packed-weight kernels (the caller goes on to the
+// kernels that read the plain weight).  feat_bytes: size of the feature matrix, < 0 = unknown (the plan query: assumed to fit); the
+// kernels that gather through raw buffer resources need it below 2 GiB and silently give way to split-K / the VALU first layer otherwise.
+static ConvPlan conv_fwd_decide(int cin, int cout, int kvol, int rows, bool same_dtype, bool has_packed, bool has_feat, long long feat_bytes,
+                                int variant, int xshare) {
+    const bool fits = feat_bytes < 0x7fffffffll;
+    if (!has_packed) return {PLAN_GENERIC, kRowsNone};
+    if (cin == 4 && cout == 16 && kvol == 27)            // first layer of SpMiddleFHD on the matrix cores (k_conv_c4_mfma)
+        return {same_dtype && variant != kVarAutoPlain && fits ? PLAN_C4_MFMA : PLAN_GENERIC, kRowsNone};
+    if (!mfma_shape(cin, cout)) return {PLAN_GENERIC, kRowsNone};
+    // split-K; a single 32-column slice per wave (the leaner kernel) for the narrow outputs of the automatic choice
+    ConvPlan p = {PLAN_MFMA_SK, kRowsNone};
+    if (variant == kVarSks || ((variant == kVarAuto || variant == kVarAutoPlain) && cout <= 32)) p.id = PLAN_MFMA_SKS;
+    else if (variant == kVarWave) p.id = PLAN_MFMA_WAVE;
+    if (same_dtype && has_feat && fits && buf_shape(cin, cout, kvol)) {
+        const bool mid = rows_shape_64(cin, cout) && kvol == 27 && rows >= kRowsMinSmall && rows < kRowsMin;
+        if (variant == kVarRows || (variant == kVarAuto && (rows >= kRowsMin || mid)))
+            p = {PLAN_ROWS_BUF, rows_form(cin, cout, kvol, variant == kVarAuto && mid, xshare)};
     }
 #ifdef SEC_CONV_EXPERIMENTS
-    if (kvol != 27 || !(cin == 64 || cin == 32) || !(cout == 64 || cout == 32)) return 0;
-    if (cin == 64) {
-        if (v == 10) return PLAN_ROWS_COMPACT;
-        if (v == 11) return PLAN_ROWS_TOUCH;
-        if (v == 12) return PLAN_ROWS_COMPACT_TOUCH;
-        if (v >= 13 && v <= 15 && cout == 64) return PLAN_ROWS_REG;
+    experiment_plan(cin, cout, kvol, rows, same_dtype, has_feat, fits, variant, xshare, &p);
+#endif
+    return p;
+}
+static ConvPlan conv_fwd_plan_now(int cin, int cout, int kvol, int rows, bool same_dtype, bool has_packed, bool has_feat, long long feat_bytes) {
+    const ConvSetting cs = conv_setting();
+    return conv_fwd_decide(cin, cout, kvol, rows, same_dtype, has_packed, has_feat, feat_bytes, cs.variant, cs.xshare);
+}
+
+// PLAN_ROWS_BUF: one instantiation per (shape, form); a shape without forms compiles none
+template <typename T, int CIN, int COUT>
+static bool launch_rows_form(int form, const void *feat, long long n_feat, const void *packed, const int *nbr, int n_out, const int *num_out_dev,
+                             const float *scale, const float *shift, int relu, void *out, hipStream_t st) {
+#define SEC_FORM(FORM, SHAPE, KV, D, W, M, FLG)                                                                                  \
+    case FORM:                                                                                                                   \
+        if constexpr (SHAPE) {                                                                                                   \
+            launch_rows_buf<T, CIN, COUT, D, W, M, FLG, KV>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); \
+            return true;                                                                                                         \
+        }                                                                                                                        \
+        break;
+    switch (form) {     //                                               kvol, prefetch distance, waves, waves per SIMD asked for, FL
+    SEC_FORM(kRowsNarrow, rows_shape_narrow(CIN, COUT), 27, 6, 8, 2, kFlNarrow)
+    SEC_FORM(kRowsNarrowXsh, rows_shape_narrow(CIN, COUT) && CIN == 32, 27, 6, 8, 2, kFlNarrow + kFlXsh)
+    SEC_FORM(kRowsWide, rows_shape_wide(CIN, COUT), 27, 4, 8, 2, kFlWide)
+    SEC_FORM(kRows64W8, rows_shape_64(CIN, COUT), 27, 3, 8, 3, kFl64)
+    SEC_FORM(kRows64W8Xsh, rows_shape_64(CIN, COUT), 27, 3, 8, 3, kFl64 + kFlXsh)
+    SEC_FORM(kRows64W4, rows_shape_64(CIN, COUT), 27, 3, 4, 2, kFl64)
+    SEC_FORM(kRows64W4Xsh, rows_shape_64(CIN, COUT), 27, 3, 4, 2, kFl64 + kFlXsh)
+    SEC_FORM(kRows64K3, rows_shape_64(CIN, COUT), 3, 3, 8, 2, kFl64K3)
+    default: break;
     }
-    if (v == 9) return PLAN_ROWS;
-#endif
-    return 0;
+#undef SEC_FORM
+    return false;
 }
 
-#ifdef SEC_CONV_EXPERIMENTS
-template <typename T>
-static void launch_rows_lds(const void *feat, long long n_feat, const void *packed, const int *nbr, int n_out, const int *num_out_dev,
-                            const float *scale, const float *shift, int relu, void *out, hipStream_t st) {
-    set_last_kernel("k_conv_rows_lds<%s>", dtype_name<T>());
-    hipLaunchKernelGGL((k_conv_rows_lds<T>), dim3(div_up(n_out, 256)), dim3(256), 0, st, (const T *)feat,
-                       n_feat * 64 * (long long)sizeof(T), (const T *)packed, nbr, n_out, num_out_dev, scale, shift, relu, (T *)out);
-}
-
-#endif
 template <typename T, typename OT, int CIN, int COUT>
-static void launch_mfma(const void *feat, long long n_feat, const void *packed, const int *nbr, int n_out, const int *num_out_dev,
-                        int kvol, const float *scale, const float *shift, int relu, void *out, hipStream_t st) {
-    constexpr int MT = 1;
-    if constexpr (std::is_same<T, OT>::value && CIN <= 64 && COUT <= 64 && (COUT >= CIN) ) {
-        const int rp = feat ? rows_plan(CIN, COUT, kvol, n_out, true) : 0;
+static void launch_mfma(const ConvPlan &p, const void *feat, long long n_feat, const void *packed, const int *nbr, int n_out,
+                        const int *num_out_dev, int kvol, const float *scale, const float *shift, int relu, void *out, hipStream_t st) {
 #ifdef SEC_CONV_EXPERIMENTS
-        if constexpr (CIN == 64 && COUT == 64) {
-            if (rp == PLAN_ROWS_M2 && n_feat * CIN * (long long)sizeof(T) < 0x7fffffffll) {
-                launch_rows_m2<T>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                return;
-            }
-            if (rp == PLAN_ROWS_LDS && n_feat * CIN * (long long)sizeof(T) < 0x7fffffffll) {
-                launch_rows_lds<T>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                return;
-            }
-        }
+    if (experiment_launch<T, OT, CIN, COUT>(p, feat, n_feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st)) return;
 #endif
-#ifdef SEC_CONV_EXPERIMENTS
-        if constexpr (CIN == 64 && COUT == 64) {
-            if (rp == PLAN_ROWS_KS && n_feat * CIN * (long long)sizeof(T) < 0x7fffffffll) {
-#ifdef SEC_CONV_ABLATIONS
-                if (conv_variant() == 71) { launch_rows_ks<T, 4, 3, 2>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return; }
-                if (conv_variant() == 72) { launch_rows_ks<T, 4, 3, 1>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return; }
-                if (conv_variant() == 73) { launch_rows_ks<T, 4, 3, 3>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return; }
-#endif
-                launch_rows_ks<T, 4, 3>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                return;
-            }
-        }
-#endif
-        if (rp == PLAN_ROWS_BUF && n_feat * CIN * (long long)sizeof(T) < 0x7fffffffll) {
-#define SEC_BUF(D, W, FLG, KV) launch_rows_buf<T, CIN, COUT, D, W, 2, FLG, KV>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st)
-            if (kvol == 3) {
-                if constexpr (CIN == 64 && COUT == 64) { SEC_BUF(3, 8, 3, 3); return; }
-            } else {
-#ifdef SEC_CONV_EXPERIMENTS   // A/B forms of the buffer-load kernel: prefetch distance, 4- or 8-wave workgroups, staging / pipelining off, skew
-                if constexpr (CIN <= 32) {     // narrow layers: a gather is 1-2 registers per offset, deeper prefetch is nearly free
-                    switch (conv_variant()) {
-                    case 36: SEC_BUF(6, 8, 3, 27); return;
-                    case 37: SEC_BUF(8, 8, 3, 27); return;
-                    case 38: SEC_BUF(12, 8, 3, 27); return;
-                    case 39: if constexpr (COUT <= 32) { SEC_BUF(4, 8, 3 + 64, 27); return; } break;
-                    case 40: if constexpr (COUT <= 32) { SEC_BUF(6, 8, 3 + 64, 27); return; } break;
-                    default: break;
-                    }
-                }
-                if constexpr (CIN == 64 && COUT == 64) {
-                    switch (conv_variant()) {
-                    case 16: SEC_BUF(4, 4, 0, 27); return;
-                    case 17: SEC_BUF(4, 4, 1, 27); return;
-                    case 18: SEC_BUF(4, 4, 2, 27); return;
-                    case 19: SEC_BUF(4, 4, 3, 27); return;
-                    case 20: SEC_BUF(5, 4, 3, 27); return;
-                    case 21: SEC_BUF(5, 8, 3, 27); return;
-                    case 23: SEC_BUF(6, 4, 3, 27); return;
-                    case 27: SEC_BUF(5, 8, 3 + 32, 27); return;
-                    case 28: SEC_BUF(6, 8, 3 + 32, 27); return;
-#ifdef SEC_CONV_ABLATIONS
-                    case 24: SEC_BUF(4, 8, 3 + 4, 27); return;
-                    case 25: SEC_BUF(4, 8, 3 + 8, 27); return;
-                    case 26: SEC_BUF(4, 8, 3 + 16, 27); return;
-                    // 60-65 (round 6): the shipped four-wave (23 k rows) and eight-wave (56 k rows) forms without the W stream (FL 4096), without
-                    // gathers that touch memory (FL 4), without both
-                    case 60: launch_rows_buf<T, CIN, COUT, 3, 4, 2, 1 + 128 + 512 + 2048 + 4096, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 61: launch_rows_buf<T, CIN, COUT, 3, 4, 2, 1 + 128 + 512 + 2048 + 4, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 62: launch_rows_buf<T, CIN, COUT, 3, 4, 2, 1 + 128 + 512 + 2048 + 4096 + 4, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 63: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 2048 + 4096, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 64: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 2048 + 4, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 65: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 2048 + 4096 + 4, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 66: launch_rows_buf<T, CIN, COUT, 3, 4, 2, 1 + 128 + 512 + 2048, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;   // the plain four-wave form, any row count
-                    case 67: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 2048, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;   // the plain eight-wave form, any row count
-                    case 44: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 4, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-                    case 45: launch_rows_buf<T, CIN, COUT, 3, 8, 3, 1 + 128 + 512 + 16, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st); return;
-#endif
-                    default: break;
-                    }
-                }
-#endif
-                // FL + 2048 (BAL): rows per wave chosen on the device so that the launch fills every CU once (SEC_CONV_BAL=0: fixed 32)
-                const bool bal = rows_balance();
-                // 16- and 32-channel layers: the whole weight tensor lives in LDS, no per-offset barrier (-13 .. -24 % per layer)
-                const int xsm = xshare_mode();
-                if constexpr (CIN <= 32 && COUT <= 32) {
-                    if constexpr (CIN == 32) {
-                        if (bal && (xsm < 0 ? kXshare32 : xsm != 0)) { SEC_BUF(6, 8, 3 + 64 + 2048 + 8192, 27); return; }
-                    }
-                    if (bal) { SEC_BUF(6, 8, 3 + 64 + 2048, 27); } else { SEC_BUF(6, 8, 3 + 64, 27); }
-                }
-                else if constexpr (CIN == 64 && COUT == 64) {
-#define SEC_BUFM(D, W, M, FLG) launch_rows_buf<T, CIN, COUT, D, W, M, FLG, 27>(feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st)
-                    // prefetch distance 3, B fragments not double-buffered, neighbour offsets re-read from the staged table (FL 1 + 128):
-                    // 134 VGPRs instead of 194 at the same stand-alone time (23.3 vs 23.6 us) -- and +3.9 % frames/s with three steps in
-                    // flight, where the kernel's footprint decides what else fits on the CU beside it (SEC_CONV_FOOTPRINT=1: the old form)
-                    // (the same form for the 128-row workgroups of the mid-size layers: 13.4 vs 13.2 us stand-alone, no gain in flight)
-                    // + one barrier per three offsets (FL 512, six-slot weight ring): 23.5 -> 22.1 us stand-alone
-                    if (n_out < rows_min() && conv_variant() == 1) {      // mid-size layers: 128-row workgroups
-                        if (rows_footprint() == 4) { SEC_BUF(4, 4, 3, 27); }          // the form with a barrier per offset (13.3 vs 12.65 us)
-                        // (two waves per SIMD asked for, not three: 63 KB of LDS per four-wave workgroup allow two workgroups per CU whatever
-                        // the registers do -- with MINW = 3 hipcc squeezed the kernel into 122 VGPRs + 32 AGPR spill slots for nothing and
-                        // warned that it could not meet the occupancy)
-                        else if (bal && (xsm < 0 ? kXshare64w4 : xsm != 0)) { SEC_BUFM(3, 4, 2, 1 + 128 + 512 + 2048 + 8192); }
-                        else if (bal) { SEC_BUFM(3, 4, 2, 1 + 128 + 512 + 2048); }
-                        else { SEC_BUFM(3, 4, 2, 1 + 128 + 512); }
-                    } else if (rows_footprint() == 1) { SEC_BUF(4, 8, 3, 27); }
-                    else if (rows_footprint() == 3) { SEC_BUFM(3, 8, 3, 1 + 128); }
-                    else if (bal && (xsm < 0 ? kXshare64w8 : xsm != 0)) { SEC_BUFM(3, 8, 3, 1 + 128 + 512 + 2048 + 8192); }
-                    else if (bal) { SEC_BUFM(3, 8, 3, 1 + 128 + 512 + 2048); }
-                    else { SEC_BUFM(3, 8, 3, 1 + 128 + 512); }
-#undef SEC_BUFM
-                } else if (bal) { SEC_BUF(4, 8, 3 + 2048, 27); }
-                else { SEC_BUF(4, 8, 3, 27); }
-                return;
-            }
-#undef SEC_BUF
-        }
-    }
-#ifdef SEC_CONV_EXPERIMENTS
-    if constexpr (std::is_same<T, OT>::value && (CIN == 64 || CIN == 32) && (COUT == 64 || COUT == 32)) {
-        const int rp = feat ? rows_plan(CIN, COUT, kvol, n_out, true) : 0;
-        if constexpr (CIN == 64) {
-            if (rp == PLAN_ROWS_COMPACT) { launch_rows<T, CIN, COUT, 32>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); return; }
-            if (rp == PLAN_ROWS_TOUCH) { launch_rows<T, CIN, COUT, 64>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); return; }
-            if (rp == PLAN_ROWS_COMPACT_TOUCH) { launch_rows<T, CIN, COUT, 96>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); return; }
-            if constexpr (COUT == 64) {
-                if (rp == PLAN_ROWS_REG) {
-                    const int v = conv_variant();
-                    if (v == 13) launch_rows_reg<T, CIN, COUT, 4, 2>(feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                    else if (v == 14) launch_rows_reg<T, CIN, COUT, 2, 3>(feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                    else launch_rows_reg<T, CIN, COUT, 5, 2>(feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-                    return;
-                }
-            }
-        }
-        if (rp == PLAN_ROWS) {
-            launch_rows<T, CIN, COUT, 0>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st);
+    if constexpr (std::is_same<T, OT>::value && buf_shape(CIN, COUT, 27)) {
+        if (p.id == PLAN_ROWS_BUF && launch_rows_form<T, CIN, COUT>(p.form, feat, n_feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st))
             return;
-        }
-#ifdef SEC_CONV_ABLATIONS
-        if (conv_variant() >= 91 && conv_variant() <= 96 && kvol == 27 && feat && CIN == 64 && COUT == 64) {
-            switch (conv_variant()) {
-            case 91: launch_rows<T, CIN, COUT, 1>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            case 92: launch_rows<T, CIN, COUT, 2>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            case 93: launch_rows<T, CIN, COUT, 4>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            case 94: launch_rows<T, CIN, COUT, 8>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            case 95: launch_rows<T, CIN, COUT, 16>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            default: launch_rows<T, CIN, COUT, 3>(feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); break;
-            }
-            return;
-        }
-#endif
     }
-#endif
-#ifdef SEC_CONV_EXPERIMENTS   // measured dead ends, compiled only for A/B builds
-    if (conv_variant() == 2 && kvol == 27) {
-        hipLaunchKernelGGL((k_conv_mfma_lds<T, OT, CIN, COUT, 27>), dim3(div_up(n_out, 128)), dim3(kBlock), 0, st,
-                           (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, scale, shift, relu, (OT *)out);
-        return;
-    }
-    if (conv_variant() == 7 && kvol == 27 && CIN <= 64 && CIN >= 32) {
-        launch_wlds_fl<T, OT, CIN, COUT>(feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-        return;
-    }
-    if ((conv_variant() == 6 || conv_variant() == 7) && kvol == 27 && CIN <= 64) {
-        launch_wlds<T, OT, CIN, COUT>(feat, packed, nbr, n_out, num_out_dev, scale, shift, relu, out, st);
-        return;
-    }
-#endif
-    if (conv_variant() == 8 || ((conv_variant() == 1 || conv_variant() == 29) && COUT <= 32)) {   // single 32-column slice: leaner split-K kernel (29 = the automatic choice without the row-split kernels)
+    if (p.id == PLAN_MFMA_SKS) {
         hipLaunchKernelGGL((k_conv_mfma_sks<T, OT, CIN, COUT, 4>), dim3((div_up(n_out, 32) + 7) / 8 * 8, (COUT + 31) / 32),
                            dim3(256), 0, st, (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift,
                            relu, (OT *)out);
         return;
     }
-#ifdef SEC_CONV_EXPERIMENTS
-    if (conv_variant() == 3 && kvol == 27) {
-        hipLaunchKernelGGL((k_conv_mfma_lds2<T, OT, CIN, COUT, 27>), dim3(div_up(n_out, 128)), dim3(kBlock), 0, st,
-                           (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, scale, shift, relu, (OT *)out);
+    if (p.id == PLAN_MFMA_WAVE) {
+        constexpr int MT = 1;
+        int rows_per_block = (kBlock / 64) * 32 * MT;
+        hipLaunchKernelGGL((k_conv_mfma<T, OT, CIN, COUT, MT>), dim3(div_up(n_out, rows_per_block)), dim3(kBlock), 0, st,
+                           (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, (OT *)out);
         return;
     }
-    if (conv_variant() == 4 || conv_variant() == 5) {
-        if (conv_variant() == 4)
-            hipLaunchKernelGGL((k_conv_mfma_skm<T, OT, CIN, COUT, 2>), dim3(div_up(n_out, 64)), dim3(kBlock), 0, st,
-                               (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, (OT *)out);
-        else
-            hipLaunchKernelGGL((k_conv_mfma_skm<T, OT, CIN, COUT, 1>), dim3(div_up(n_out, 32)), dim3(kBlock), 0, st,
-                               (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, (OT *)out);
-        return;
-    }
-#endif
-    if (conv_variant() >= 1) {
-        constexpr int NW = 4;
-        hipLaunchKernelGGL((k_conv_mfma_sk<T, OT, CIN, COUT, NW>), dim3((div_up(n_out, 32) + 7) / 8 * 8), dim3(NW * 64), 0, st,
-                           (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift,
-                           relu | (conv_swizzle() << 16), (OT *)out);
-        return;
-    }
-    int rows_per_block = (kBlock / 64) * 32 * MT;
-    hipLaunchKernelGGL((k_conv_mfma<T, OT, CIN, COUT, MT>), dim3(div_up(n_out, rows_per_block)), dim3(kBlock), 0, st,
-                       (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, (OT *)out);
+    constexpr int NW = 4;       // PLAN_MFMA_SK
+    hipLaunchKernelGGL((k_conv_mfma_sk<T, OT, CIN, COUT, NW>), dim3((div_up(n_out, 32) + 7) / 8 * 8), dim3(NW * 64), 0, st,
+                       (const T *)feat, (const T *)packed, nbr, n_out, num_out_dev, kvol, scale, shift,
+                       relu | kReluXcdOrder, (OT *)out);
 }
 
+// false: `p` is not a plan of the k_conv_mfma* / k_conv_rows_buf family (nothing launched)
 template <typename T, typename OT>
-static bool dispatch_mfma(int cin, int cout, const void *feat, long long n_feat, const void *packed, const int *nbr, int n_out,
-                          const int *num_out_dev, int kvol, const float *scale, const float *shift, int relu, void *out,
+static bool dispatch_mfma(const ConvPlan &p, int cin, int cout, const void *feat, long long n_feat, const void *packed, const int *nbr,
+                          int n_out, const int *num_out_dev, int kvol, const float *scale, const float *shift, int relu, void *out,
                           hipStream_t st) {
+    if (p.id == PLAN_GENERIC || p.id == PLAN_C4_MFMA) return false;
 #define SEC_CASE(CI, CO)                                                                                         \
     if (cin == CI && cout == CO) {                                                                               \
-        launch_mfma<T, OT, CI, CO>(feat, n_feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); \
+        launch_mfma<T, OT, CI, CO>(p, feat, n_feat, packed, nbr, n_out, num_out_dev, kvol, scale, shift, relu, out, st); \
         return true;                                                                                             \
     }
-    SEC_CASE(16, 16) SEC_CASE(16, 32) SEC_CASE(32, 32) SEC_CASE(32, 64) SEC_CASE(64, 64) SEC_CASE(64, 128)
-    SEC_CASE(128, 128) SEC_CASE(16, 64) SEC_CASE(64, 32) SEC_CASE(32, 16) SEC_CASE(128, 64)
+    SEC_MFMA_SHAPES(SEC_CASE)
 #undef SEC_CASE
     return false;
 }
@@ -1933,10 +1827,10 @@ static bool launch_tiled(const void *feat, const void *w, const int *nbr, int n_
                          int kvol, int w_t, int mirror, const float *scale, const float *shift, int relu, void *out,
                          hipStream_t st) {
     if constexpr (std::is_same<T, float>::value && std::is_same<OT, float>::value) {
-        // fp32 on the matrix cores for the channel plans of SECOND's layers (and their data gradients); g_variant_override 30 keeps
+        // fp32 on the matrix cores for the channel plans of SECOND's layers (and their data gradients); kVarF32Valu keeps
         // the VALU form (parity tests compare the two)
-        // round 5: the split-operand form on the bf16 pipe (k_conv_rows_x3_f32); variant 31 keeps the fp32-MFMA form, 30 the VALU form
-        if (kvol <= 27 && conv_variant() != 30 && conv_variant() != 31 && g_fp32_mode == 0) {
+        // round 5: the split-operand form on the bf16 pipe (k_conv_rows_x3_f32); kVarF32Mfma keeps the fp32-MFMA form, kVarF32Valu the VALU form
+        if (kvol <= 27 && conv_variant() != kVarF32Valu && conv_variant() != kVarF32Mfma && g_fp32_mode == 0) {
 #define SEC_X3(CI, CO)                                                                                                       \
             if (cin == CI && cout == CO) {                                                                                   \
                 if (n_out >= 40000) {                                                                                        \
@@ -1953,7 +1847,7 @@ static bool launch_tiled(const void *feat, const void *w, const int *nbr, int n_
             SEC_X3(16, 32) SEC_X3(32, 32) SEC_X3(32, 64) SEC_X3(64, 32) SEC_X3(64, 64)
 #undef SEC_X3
         }
-        if (kvol <= 27 && conv_variant() != 30) {
+        if (kvol <= 27 && conv_variant() != kVarF32Valu) {
 #define SEC_MF(CI, CO)                                                                                                       \
             if (cin == CI && cout == CO) {                                                                                   \
                 set_last_kernel("void sec::k_conv_mfma_f32<%d, %d>", CI, CO);                                                \
@@ -2367,12 +2261,12 @@ static bool launch_wgrad_tiled(const void *feat, const void *dout, const int *nb
             return true;                                                                                                  \
         }
 #define SEC_WT(CI, CO)                                                                                                    \
-        if (cin == CI && cout == CO && conv_variant() != 41) {                                                            \
+        if (cin == CI && cout == CO && conv_variant() != kVarWgradCompact) {                                                     \
             hipLaunchKernelGGL((k_conv_wgrad_tr<T, CI, CO>), grid, dim3(kBlock), 0, st, (const T *)feat, (const T *)dout, nbr,   \
                                n_out, kvol, chunk, dw);                                                                   \
             return true;                                                                                                  \
         }
-        SEC_WT(32, 32) SEC_WT(32, 64) SEC_WT(64, 32) SEC_WT(64, 64)        // (SEC_CONV_VARIANT=41: the compacting kernel below, for A/B)
+        SEC_WT(32, 32) SEC_WT(32, 64) SEC_WT(64, 32) SEC_WT(64, 64)        // (kVarWgradCompact: the compacting kernel below, for A/B)
 #undef SEC_WT
         SEC_WM(4, 16) SEC_WM(16, 16) SEC_WM(16, 32) SEC_WM(32, 32) SEC_WM(32, 64) SEC_WM(64, 64)
 #undef SEC_WM
@@ -2436,26 +2330,15 @@ SEC_API int sec_set_fp32_mode(int mode) {
 SEC_API int sec_get_fp32_mode(void) { return g_fp32_mode; }
 
 SEC_API int sec_indice_conv_set_variant(int variant) {
-    g_variant_override = variant;      // < 0: back to SEC_CONV_VARIANT / the automatic choice
+    g_variant_override = variant;      // < 0: back to the automatic choice
     return SEC_OK;
 }
 
 SEC_API int sec_indice_conv_fwd_plan(int cin, int cout, int kvol, int n_out, int dtype, int out_dtype, int has_packed) {
-    static const int mfma_shapes[][2] = {{16, 16}, {16, 32}, {32, 32}, {32, 64}, {64, 64}, {64, 128}, {128, 128}, {16, 64},
-                                         {64, 32}, {32, 16}, {128, 64}};
-    bool mfma = false;
-    for (auto &sh : mfma_shapes) mfma |= sh[0] == cin && sh[1] == cout;
-    if (has_packed && dtype != SEC_F32 && mfma) {
-        const int rp = rows_plan(cin, cout, kvol, n_out, dtype == out_dtype);
-        if (rp) return rp;
-        const int v = conv_variant();
-#ifdef SEC_CONV_EXPERIMENTS
-        if (v >= 2 && v <= 7) return PLAN_EXPERIMENT;
-#endif
-        if (v == 8 || ((v == 1 || v == 29) && cout <= 32)) return PLAN_MFMA_SKS;
-        return v >= 1 ? PLAN_MFMA_SK : PLAN_MFMA_WAVE;
+    if (dtype != SEC_F32) {     // (no n_in here: the features are taken to be present and addressable)
+        const ConvPlan p = conv_fwd_plan_now(cin, cout, kvol, n_out, out_dtype == dtype, has_packed != 0, true, -1);
+        if (p.id != PLAN_GENERIC) return p.id;
     }
-    if (has_packed && dtype != SEC_F32 && cin == 4 && cout == 16 && kvol == 27 && out_dtype == dtype && conv_variant() != 29) return PLAN_C4_MFMA;
     if (cin == 4 && cout == 16 && (size_t)kvol * 4 * 16 * sizeof(float) <= 48 * 1024) return PLAN_C4;
     static const int tiled_shapes[][2] = {{16, 16}, {16, 32}, {32, 16}, {32, 32}, {32, 64}, {64, 32}, {64, 64}};
     for (auto &sh : tiled_shapes)
@@ -2477,8 +2360,10 @@ SEC_API int sec_indice_conv_fwd(const void *features, int n_in, int cin, const v
     if (!nbr_out || !out || (n_in > 0 && !features)) return SEC_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     bool done = false;
-    if (packed_weight && dtype != SEC_F32 && cin == 4 && cout == 16 && kvol == 27 && out_dtype == dtype && conv_variant() != 29 &&
-        (long long)n_in * 8 < 0x7fffffffll) {
+    ConvPlan p = {PLAN_GENERIC, kRowsNone};
+    if (dtype != SEC_F32)
+        p = conv_fwd_plan_now(cin, cout, kvol, n_out, out_dtype == dtype, packed_weight != nullptr, features != nullptr, (long long)n_in * cin * 2);
+    if (p.id == PLAN_C4_MFMA) {
         const long long fb = (long long)n_in * 8;
         const int c4_xcd = rows_xcd_order();
         const int c4_blocks = c4_xcd ? (div_up(n_out, 128) + 7) / 8 * 8 : div_up(n_out, 128);
@@ -2491,21 +2376,21 @@ SEC_API int sec_indice_conv_fwd(const void *features, int n_in, int cin, const v
                                (const __half *)packed_weight, nbr_out, n_out, num_out_dev, scale, shift, c4_relu, (__half *)out);
         return check_launch();
     }
-    if (packed_weight && dtype != SEC_F32 && cin % 16 == 0) {
+    if (p.id != PLAN_GENERIC) {
         if (dtype == SEC_BF16) {
             done = out_dtype == SEC_F32
-                       ? dispatch_mfma<__hip_bfloat16, float>(cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st)
-                       : dispatch_mfma<__hip_bfloat16, __hip_bfloat16>(cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st);
+                       ? dispatch_mfma<__hip_bfloat16, float>(p, cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st)
+                       : dispatch_mfma<__hip_bfloat16, __hip_bfloat16>(p, cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st);
         } else {
             done = out_dtype == SEC_F32
-                       ? dispatch_mfma<__half, float>(cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st)
-                       : dispatch_mfma<__half, __half>(cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st);
+                       ? dispatch_mfma<__half, float>(p, cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st)
+                       : dispatch_mfma<__half, __half>(p, cin, cout, features, n_in, packed_weight, nbr_out, n_out, num_out_dev, kvol, scale, shift, relu, out, st);
         }
     }
     // fp32 features with an x3-packed weight (ops.pack_weight of an fp32 weight: [k][hi | lo] bf16 B-fragment pieces): the pipelined
-    // split-operand kernel; variants 30 / 31 (VALU / fp32-MFMA forms) and 32 (the unpacked split form) ignore the packed image
-    if (!done && packed_weight && dtype == SEC_F32 && out_dtype == SEC_F32 && conv_variant() != 30 && conv_variant() != 31 && conv_variant() != 32 &&
-        g_fp32_mode == 0)
+    // split-operand kernel; kVarF32Valu / kVarF32Mfma (VALU / fp32-MFMA forms) and kVarF32SplitUnpacked ignore the packed image
+    if (!done && packed_weight && dtype == SEC_F32 && out_dtype == SEC_F32 && conv_variant() != kVarF32Valu && conv_variant() != kVarF32Mfma &&
+        conv_variant() != kVarF32SplitUnpacked && g_fp32_mode == 0)
         done = launch_x3p(features, n_in, packed_weight, nbr_out, n_out, num_out_dev, cin, cout, kvol, scale, shift, relu, out, st);
     if (!done) {
 #define SEC_GEN(T, OT) launch_generic<T, OT>(features, weight, nbr_out, n_out, num_out_dev, cin, cout, kvol, scale, shift, relu, out, st)
@@ -2596,13 +2481,14 @@ static int run_bwd(const void *features, int n_in, int cin, const void *weight, 
         if constexpr (!std::is_same<T, float>::value) {
             // MFMA path: forward kernels on (dout, Wt) with Cin <-> Cout swapped
             const size_t need = sec_packed_weight_bytes(kvol, cout, cin, dtype);
+            const ConvPlan p = conv_fwd_plan_now(cout, cin, kvol, n_in, true, true, dout != nullptr, (long long)n_out * cout * (long long)sizeof(T));
             if (need > 0 && packed_dgrad && n_out > 0) {   // the caller packed it already (sec_pack_conv_weight_train)
-                done = dispatch_mfma<T, T>(cout, cin, dout, n_out, packed_dgrad, tbl, n_in, nullptr, kvol, nullptr, nullptr, 0, dfeat, st);
+                done = dispatch_mfma<T, T>(p, cout, cin, dout, n_out, packed_dgrad, tbl, n_in, nullptr, kvol, nullptr, nullptr, 0, dfeat, st);
             } else if (need > 0 && workspace && workspace_bytes >= need && n_out > 0) {
                 long long total = (long long)kvol * cout * ((cin + 31) / 32) * 32;
                 hipLaunchKernelGGL(k_pack_weight_t<T>, dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const T *)weight, kvol, cin,
                                    cout, nbr_in ? 0 : 1, (T *)workspace);
-                done = dispatch_mfma<T, T>(cout, cin, dout, n_out, workspace, tbl, n_in, nullptr, kvol, nullptr, nullptr, 0, dfeat, st);
+                done = dispatch_mfma<T, T>(p, cout, cin, dout, n_out, workspace, tbl, n_in, nullptr, kvol, nullptr, nullptr, 0, dfeat, st);
             }
         }
         if (!done)   // register-tiled VALU forward on (dout, W^T): Cin <-> Cout swapped, weights read transposed in place

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmark of sec_indice_conv_fwd on the car.fhd subm2 layer (64->64, batch 8) for profiling
-(rocprofv3 --kernel-trace / --pmc).  SEC_CONV_VARIANT selects the kernel variant.
+(rocprofv3 --kernel-trace / --pmc).  sec_indice_conv_set_variant selects the kernel variant.
 
     python tools/conv_microbench.py [--iters 50] [--cin 64 --cout 64] [--layer subm2|subm0|subm1|subm3]
 """
@@ -88,7 +88,7 @@ def main():
     ap.add_argument("--sorted", action="store_true", help="spatially sorted clouds (rows in (z,y,x) order per frame)")
     ap.add_argument("--sorted-numbering", action="store_true", help="strided rulebooks in spconv's GPU numbering (ascending cell order): what the device fast path runs")
     ap.add_argument("--timeline", action="store_true", help="per-wave clock64 timeline of the row-split kernels (with --variants; needs a build with SEC_EXTRA_HIPCC_FLAGS=-DSEC_CONV_TIMELINE)")
-    ap.add_argument("--variants", default="", help="comma list of SEC_CONV_VARIANT numbers timed back to back in this process (each checked against split-K)")
+    ap.add_argument("--variants", default="", help="comma list of sec_indice_conv_set_variant numbers timed back to back in this process (each checked against split-K)")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--backward", action="store_true", help="also time sec_indice_conv_bwd (dgrad + wgrad), bf16 and fp32")
     ap.add_argument("--all-layers", action="store_true", help="every conv layer of SpMiddleFHD at batch 8, each --variants entry per layer")

@@ -1,5 +1,5 @@
 // Measured dead ends of the sparse convolution (DESIGN.md section 4), compiled only with -DSEC_CONV_EXPERIMENTS and selected
-// by SEC_CONV_VARIANT = 2 / 3 / 4 / 5 / 6 / 7 for A/B runs.  Included by indice_conv.hip inside namespace sec; not part of
+// by variants 2 / 3 / 4 / 5 / 6 / 7 of sec_indice_conv_set_variant for A/B runs.  Included by indice_conv.hip inside namespace sec; not part of
 // the shipped library.
 
 // Lock-step variant: the 4 waves of a workgroup own 4 x 32 consecutive rows and walk the offsets together,
@@ -464,5 +464,5 @@ static void launch_wlds(const void *feat, const void *packed, const int *nbr, in
         configured = true;
     }
     hipLaunchKernelGGL(fn, dim3((div_up(n_out, 512) + 7) / 8 * 8, (COUT + 31) / 32), dim3(1024), lds, st, (const T *)feat,
-                       (const T *)packed, nbr, n_out, num_out_dev, scale, shift, relu | (conv_swizzle() << 16), (OT *)out);
+                       (const T *)packed, nbr, n_out, num_out_dev, scale, shift, relu | kReluXcdOrder, (OT *)out);
 }

@@ -1,4 +1,4 @@
-// Earlier forms of the row-split sparse convolution, kept for A/B builds (-DSEC_CONV_EXPERIMENTS, SEC_CONV_VARIANT 9-15):
+// Earlier forms of the row-split sparse convolution, kept for A/B builds (-DSEC_CONV_EXPERIMENTS, variant 9-15):
 //   k_conv_rows      gathers by LDS-DMA in full 128-byte lines into a per-wave LDS ring (9), compacted gathers (10), L2 "touch"
 //                    prefetches eight offsets ahead (11), both (12)                                   -- round 1 / round 2
 //   k_conv_rows_reg  register-direct gathers at prefetch distance 4 / 2 / 5, W[k] through a 3-slot LDS ring (13 / 14 / 15)
@@ -9,7 +9,7 @@
 // swizzle key of a row's 16-byte chunks: makes the 16 lanes of every ds_read_b128 group hit 16 distinct bank slots
 template <int LPR> __device__ __forceinline__ int row_key(int r) { return (r / (16 / LPR)) & (LPR - 1); }
 
-// ABL (profiling builds of the same kernel, -DSEC_CONV_ABLATIONS + SEC_CONV_VARIANT 91..96): 1 no gather DMA, 2 no weight
+// ABL (profiling builds of the same kernel, -DSEC_CONV_ABLATIONS + variant 91..96): 1 no gather DMA, 2 no weight
 // DMA, 4 no MFMA, 8 no per-offset barrier, 16 gathers all read row 0.
 // The LDS pointers are __restrict__: after inlining they carry alias scopes, without which the compiler puts
 // s_waitcnt vmcnt(0) in front of every ds_read that follows an LDS-DMA.
@@ -38,7 +38,7 @@ __device__ __forceinline__ void rows_compute(const uint4 *__restrict__ a_cur, co
     }
 }
 
-// COMPACT form (ABL bit 32, SEC_CONV_VARIANT=10): the gathered rows of an offset sit in LDS in COMPACTED order -- row r of the
+// COMPACT form (ABL bit 32, variant 10): the gathered rows of an offset sit in LDS in COMPACTED order -- row r of the
 // tile reads slot `pos` = number of valid rows below it -- so only ceil(valid / 8) gather DMAs are issued per offset.
 template <typename T, int CIN, int COUT>
 __device__ __forceinline__ void rows_compute_compact(const uint4 *__restrict__ a_cur, const uint4 *__restrict__ b_cur, int idx_cur,
@@ -257,7 +257,7 @@ static void launch_rows(const void *feat, const void *packed, const int *nbr, in
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Row-split kernel with REGISTER-direct gathers (SEC_CONV_VARIANT 13/14/15).  Same work split as k_conv_rows (128 rows per
+// Row-split kernel with REGISTER-direct gathers (variant 13/14/15).  Same work split as k_conv_rows (128 rows per
 // workgroup, one 32-row tile per wave, W[k] shared through a 3-slot LDS ring), but the gathered rows never touch LDS: lane
 // (r, h) loads the 16-byte K-chunks of its row straight into the registers the MFMA reads (the transposed product takes the
 // features as its second operand, whose fragment IS 8 consecutive channels of one row).  LDS then only holds the weight ring

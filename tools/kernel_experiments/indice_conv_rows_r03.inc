@@ -1,4 +1,4 @@
-// Round-3 experiments on the 64 -> 64 row-split sparse conv (A/B builds only: -DSEC_CONV_EXPERIMENTS; SEC_CONV_VARIANT 41 / 46, and
+// Round-3 experiments on the 64 -> 64 row-split sparse conv (A/B builds only: -DSEC_CONV_EXPERIMENTS; variant 41 / 46, and
 // the timing-only ablations 42 / 43 with -DSEC_CONV_ABLATIONS).  Both are parity-green under tests/test_gpu_conv_rows.py and both are
 // SLOWER than the shipped form on the bench launch (profiles/r03_b_*, r03_l_*, r03_m_*): what bounds the launch is the bytes a CU pulls
 // through its L2 -> L1 path (590 KB per workgroup: 346 KB of gathered rows, 216 KB of weight slices, 28 KB of table, at ~13 B/clk/CU),
@@ -6,7 +6,7 @@
 // Included by indice_conv.hip inside namespace sec.
 
 // ------------------------------------------------------------------------------------------------------------------
-// Row-split kernel, TWO 32-row tiles per wave (SEC_CONV_VARIANT 41; round 3).  What round 2 left on the table for the 64 -> 64
+// Row-split kernel, TWO 32-row tiles per wave (variant 41; round 3).  What round 2 left on the table for the 64 -> 64
 // layers: at batch 8 the subm2 stage is 220 workgroups of 256 rows -- ONE workgroup per CU, every workgroup resident at once -- so a
 // launch is one workgroup life of 27 offset steps, and a step cost ~1350 clocks for 256 clocks of MFMA per wave: two waves per SIMD
 // that each read the full 8 KB W[k] from LDS, leave every barrier together and queue for the same matrix pipe.  Here a wave owns 64
@@ -148,7 +148,7 @@ SEC_PACKED_F32_OK __global__ __launch_bounds__(256, 1) void k_conv_rows_m2(const
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Row-split kernel with the INPUT rows of two of the three kernel planes staged in LDS (SEC_CONV_VARIANT 46 / the automatic choice
+// Row-split kernel with the INPUT rows of two of the three kernel planes staged in LDS (variant 46 / the automatic choice
 // for SubM 64 -> 64 layers whose rows are in ascending cell order; round 3).  The ablations of the forms above
 // (profiles/r03_l_ablations_subm2.txt) put 7-11 us of the 20-22 us launch on the gathers themselves -- every (output row, offset)
 // pair pulls its 128-byte input row through the texture path and the L2, 88 MB per launch for 7.2 MB of distinct rows -- and 11 us on

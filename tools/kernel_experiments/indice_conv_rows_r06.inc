@@ -1,4 +1,4 @@
-// Round-6 experiment on the mid-size 64 -> 64 sparse convs (A/B builds only: -DSEC_CONV_EXPERIMENTS; SEC_CONV_VARIANT 50, or the automatic
+// Round-6 experiment on the mid-size 64 -> 64 sparse convs (A/B builds only: -DSEC_CONV_EXPERIMENTS; variant 50, or the automatic
 // choice with SEC_CONV_KS=1).  Parity-green under tests/test_gpu_conv_rows.py and SLOWER than the shipped four-wave form on the four
 // 23 k-row launches of car.fhd at batch 8 (gpurun r06_u, same build, same box: 11.65 / 13.21 / 13.17 / 13.03 us against 11.94 / 12.25 /
 // 12.15 / 12.02 us): three times the waves per SIMD on the same bytes per workgroup buy nothing, i.e. the launch is NOT bound by
