@@ -767,6 +767,60 @@ int sec_flat_adamw_f32(float *param, const float *grad, float *exp_avg, float *e
 int sec_flat_adamw_dev_f32(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, long long n, const float *hyper6,
                            float *state4, float *loss_scale4, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training augmentation: the geometric stages of prep_pointcloud (second/data/preprocess.py:250-286) for a whole batch on the
+ * device -- what the reference runs per sample in DataLoader workers as numba loops (second/core/preprocess.py).  Frames are
+ * concatenated: frame b owns points [point_offsets[b], point_offsets[b+1]) (rows of `point_pitch` >= 3 floats, only x, y, z are
+ * read or written) and boxes [box_offsets[b], box_offsets[b+1]) (x, y, z centre, w, l, h, yaw about z; corner convention of
+ * center_to_corner_box3d with origin (0.5, 0.5, 0.5), second/core/box_np_ops.py:377-402).  n_points / n_boxes are the row
+ * CAPACITIES of the arrays; every per-frame count is read from the offsets on the device, so the calls capture into a hipGraph.
+ * `valid` [n_boxes] bytes (NULL = all valid) is the reference's gt_boxes_mask.  None of the four needs a workspace.
+ *
+ * sec_points_in_boxes_f32 -- box_np_ops.points_in_rbbox / points_count_rbbox (box_np_ops.py:728-739).  first_box [n_points]: the
+ *   global row of the lowest-numbered VALID box of the point's frame that strictly contains it, -1 if none (a point on a face is
+ *   outside, second/core/geometry.py:202-230 `sign >= 0`); rows outside every frame are not written.  box_counts [n_boxes] (may be
+ *   NULL): points inside each box, valid or not (integer atomics).  The test rotates the point into the box frame and compares with
+ *   the half extents; its fp32 error at |coordinate| <= 80 m is ~1.5e-5 m.
+ * sec_noise_per_box_f32 -- preprocess.noise_per_box + _select_transform (second/core/preprocess.py:244-273, 478-484), the form
+ *   without group ids and without the per-object global rotation.  loc_noises [n_boxes, num_try, 3], rot_noises [n_boxes, num_try]
+ *   are given.  Per frame, boxes in order: a valid box takes its first try whose BEV rectangle collides with no other box of the
+ *   frame at that box's CURRENT place (earlier boxes have moved, invalid boxes block but never move).  selected [n_boxes] = the try
+ *   taken, -1 if none; loc_transform [n_boxes, 3] / rot_transform [n_boxes] = its noise, zeros where selected is -1.  Collision =
+ *   box_collision_test (preprocess.py:803-883) with the meaning it has compiled by numba: overlapping standup boxes and either two
+ *   crossing edges or one rectangle wholly inside the other.  (Run as plain Python the reference's `ret[i, j] is False` is never
+ *   true and containment goes undetected; that is not reproduced.)  num_try <= 128 and max_boxes_per_frame <= 512, else
+ *   SEC_E_UNSUPPORTED; a frame that holds more than max_boxes_per_frame boxes -- known on the device only -- gets selected = -1
+ *   and zero transforms for all its boxes.  One workgroup per frame; deterministic.
+ * sec_augment_points_f32 -- in place, one read and one write per point: (1) if first_box[i] >= 0 and that box is valid,
+ *   p = (p - c) @ R(rot_transform) + c + loc_transform about the box's original centre c (points_transform_, preprocess.py:450-466);
+ *   then with frame_params [batch, 8] = (flip_x, flip_y, angle, scale, tx, ty, tz, 0): (2) y = -y if flip_y, (3) x = -x if flip_x
+ *   (random_flip, preprocess.py:749-769), (4) rotation about z (global_rotation_v2, preprocess.py:781-799 ->
+ *   rotation_points_single_angle, box_np_ops.py:322-341), (5) scaling of x, y, z (global_scaling_v2, preprocess.py:772-778),
+ *   (6) translation (global_translate_, preprocess.py:885-899).  first_box NULL: no per-object stage (boxes, valid and the
+ *   transforms are not read).
+ * sec_augment_boxes_f32 -- the same on the boxes: box3d_transform_ (preprocess.py:469-475; loc_transform / rot_transform both
+ *   NULL = none), flips (yaw -> -yaw + pi for y, -yaw for x), rotation of the centre with the angle added to the yaw, scaling of
+ *   columns 0-5, translation, limit_period(yaw, 0.5, 2 pi) (box_np_ops.py:503-504).  A box survives if it is valid and its centre
+ *   lies strictly inside h_bev_range4 = (xmin, ymin, xmax, ymax) (filter_gt_box_outside_range_by_center, preprocess.py:153-164, and
+ *   the _dict_select calls of second/data/preprocess.py:268,282).  Survivors are written in their original order to out_boxes
+ *   [n_boxes, 7], out_classes [n_boxes] (classes NULL = all 1) and out_importance [n_boxes] (importance NULL = all 1; either
+ *   output may be NULL), out_offsets [batch + 1] receives the new frame boundaries, rows behind out_offsets[batch] are zeroed.
+ *   One workgroup, a block scan per frame: no host read of any count.
+ * --------------------------------------------------------------------------------------------- */
+int sec_points_in_boxes_f32(const float *points, int point_pitch, const int *point_offsets, int n_points, const float *boxes,
+                            const int *box_offsets, int n_boxes, int batch, const unsigned char *valid, int *first_box,
+                            int *box_counts, void *stream);
+int sec_noise_per_box_f32(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
+                          const float *loc_noises, const float *rot_noises, int num_try, int max_boxes_per_frame, int *selected,
+                          float *loc_transform, float *rot_transform, void *stream);
+int sec_augment_points_f32(float *points, int point_pitch, const int *point_offsets, int n_points, int batch, const int *first_box,
+                           const float *boxes, const unsigned char *valid, const float *loc_transform, const float *rot_transform,
+                           const float *frame_params, void *stream);
+int sec_augment_boxes_f32(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
+                          const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
+                          const float *frame_params, const float *h_bev_range4, float *out_boxes, int *out_classes,
+                          float *out_importance, int *out_offsets, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1534,6 +1534,111 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     return labels, targets, importance
 
 
+# ----------------------------------------------------------------------------- training: augmentation (prep_pointcloud's geometric stages)
+AUG_MAX_TRY, AUG_MAX_BOXES_PER_FRAME = 128, 512      # limits of sec_noise_per_box_f32 (include/second_hip.h)
+
+
+def _aug_frames(points, point_offsets, boxes, box_offsets, valid):
+    """Argument checks the augmentation wrappers share; returns (valid as uint8 or None, batch)."""
+    rt.require_gpu(points, point_offsets, boxes, box_offsets, valid)
+    if points is not None:
+        assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous(), "points: contiguous fp32 [N, pitch]"
+        assert point_offsets.dtype == torch.int32 and point_offsets.numel() == box_offsets.numel()
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 7 and boxes.is_contiguous(), "boxes: contiguous fp32 [G, 7]"
+    assert box_offsets.dtype == torch.int32 and box_offsets.numel() >= 2
+    if valid is not None:
+        assert valid.numel() == boxes.shape[0] and valid.dtype in (torch.bool, torch.uint8), "valid: one bool per box"
+        valid = valid.contiguous().view(torch.uint8)
+    return valid, box_offsets.numel() - 1
+
+
+@_traced("points_in_boxes")
+def points_in_boxes(points, point_offsets, boxes, box_offsets, valid=None, want_counts=False):
+    """box_np_ops.points_in_rbbox for a batch (second/core/box_np_ops.py:728-733): -> first_box [N] int32, the global row of the
+    lowest-numbered (valid) box of the point's frame that strictly contains it, -1 for none; with ``want_counts`` also the
+    points inside every box, valid or not (points_count_rbbox, box_np_ops.py:735-739)."""
+    valid, b = _aug_frames(points, point_offsets, boxes, box_offsets, valid)
+    n, g = points.shape[0], boxes.shape[0]
+    first = torch.full((n,), -1, dtype=torch.int32, device=points.device)
+    counts = torch.empty((g,), dtype=torch.int32, device=points.device) if want_counts else None
+    rc = rt.lib().sec_points_in_boxes_f32(rt.ptr(points), points.shape[1], rt.ptr(point_offsets), n, rt.ptr(boxes), rt.ptr(box_offsets),
+                                          g, b, rt.ptr(valid), rt.ptr(first), rt.ptr(counts), rt.stream())
+    rt.check(rc, "sec_points_in_boxes_f32")
+    return (first, counts) if want_counts else first
+
+
+@_traced("noise_per_box")
+def noise_per_box(boxes, box_offsets, valid, loc_noises, rot_noises, max_boxes_per_frame=AUG_MAX_BOXES_PER_FRAME):
+    """preprocess.noise_per_box + _select_transform (second/core/preprocess.py:244-273, 478-484) for a batch, with the given noise
+    loc_noises [G, T, 3] / rot_noises [G, T].  -> selected [G] int32 (-1: no try succeeded or the box is invalid),
+    loc_transform [G, 3], rot_transform [G] (zeros where selected is -1).  Containment counts as a collision (header)."""
+    valid, b = _aug_frames(None, None, boxes, box_offsets, valid)
+    rt.require_gpu(loc_noises, rot_noises)
+    g = boxes.shape[0]
+    assert loc_noises.dtype == torch.float32 and loc_noises.dim() == 3 and loc_noises.shape[0] == g and loc_noises.shape[2] == 3
+    t = loc_noises.shape[1]
+    assert rot_noises.dtype == torch.float32 and tuple(rot_noises.shape) == (g, t)
+    loc_noises, rot_noises = loc_noises.contiguous(), rot_noises.contiguous()
+    dev = boxes.device
+    selected = torch.empty((g,), dtype=torch.int32, device=dev)
+    loc_t = torch.empty((g, 3), dtype=torch.float32, device=dev)
+    rot_t = torch.empty((g,), dtype=torch.float32, device=dev)
+    rc = rt.lib().sec_noise_per_box_f32(rt.ptr(boxes), rt.ptr(box_offsets), g, b, rt.ptr(valid), rt.ptr(loc_noises), rt.ptr(rot_noises),
+                                        t, int(max_boxes_per_frame), rt.ptr(selected), rt.ptr(loc_t), rt.ptr(rot_t), rt.stream())
+    rt.check(rc, "sec_noise_per_box_f32")
+    return selected, loc_t, rot_t
+
+
+@_traced("augment_points")
+def augment_points_(points, point_offsets, frame_params, first_box=None, boxes=None, valid=None, loc_transform=None, rot_transform=None):
+    """In place on x, y, z of ``points``: the transform of each point's first containing box (``first_box`` from
+    :func:`points_in_boxes`, transforms from :func:`noise_per_box`; None = no per-object stage), then the frame's flips, rotation,
+    scaling and translation, frame_params [B, 8] = (flip_x, flip_y, angle, scale, tx, ty, tz, 0)."""
+    rt.require_gpu(points, point_offsets, frame_params, first_box, boxes, valid, loc_transform, rot_transform)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous(), "points: contiguous fp32 [N, pitch]"
+    b = point_offsets.numel() - 1
+    assert point_offsets.dtype == torch.int32 and frame_params.dtype == torch.float32 and tuple(frame_params.shape) == (b, 8)
+    assert frame_params.is_contiguous()
+    if first_box is not None:
+        assert first_box.dtype == torch.int32 and first_box.numel() == points.shape[0]
+        assert loc_transform.is_contiguous() and rot_transform.is_contiguous() and boxes.is_contiguous()
+        if valid is not None:
+            valid = valid.contiguous().view(torch.uint8)
+    rc = rt.lib().sec_augment_points_f32(rt.ptr(points), points.shape[1], rt.ptr(point_offsets), points.shape[0], b, rt.ptr(first_box),
+                                         rt.ptr(boxes), rt.ptr(valid), rt.ptr(loc_transform), rt.ptr(rot_transform),
+                                         rt.ptr(frame_params), rt.stream())
+    rt.check(rc, "sec_augment_points_f32")
+    return points
+
+
+@_traced("augment_boxes")
+def augment_boxes(boxes, box_offsets, frame_params, bev_range, valid=None, classes=None, importance=None, loc_transform=None,
+                  rot_transform=None):
+    """The boxes' side of the same stages, the range filter of filter_gt_box_outside_range_by_center on (xmin, ymin, xmax, ymax) =
+    ``bev_range`` and the compaction: -> (out_boxes [G, 7], out_offsets [B+1] int32, out_classes [G] int32, out_importance [G]),
+    survivors first in their original order, zero rows behind out_offsets[-1]."""
+    valid, b = _aug_frames(None, None, boxes, box_offsets, valid)
+    rt.require_gpu(frame_params, classes, importance, loc_transform, rot_transform)
+    g, dev = boxes.shape[0], boxes.device
+    assert frame_params.dtype == torch.float32 and tuple(frame_params.shape) == (b, 8) and frame_params.is_contiguous()
+    if classes is not None:
+        assert classes.numel() == g
+        classes = classes.to(torch.int32).contiguous()
+    if importance is not None:
+        assert importance.numel() == g
+        importance = importance.to(torch.float32).contiguous()
+    out_boxes = torch.empty((g, 7), dtype=torch.float32, device=dev)
+    out_classes = torch.empty((g,), dtype=torch.int32, device=dev)
+    out_importance = torch.empty((g,), dtype=torch.float32, device=dev)
+    out_offsets = torch.empty((b + 1,), dtype=torch.int32, device=dev)
+    rc = rt.lib().sec_augment_boxes_f32(rt.ptr(boxes), rt.ptr(box_offsets), g, b, rt.ptr(valid), rt.ptr(classes), rt.ptr(importance),
+                                        rt.ptr(loc_transform), rt.ptr(rot_transform), rt.ptr(frame_params), rt.f_arr(bev_range),
+                                        rt.ptr(out_boxes), rt.ptr(out_classes), rt.ptr(out_importance), rt.ptr(out_offsets),
+                                        rt.stream())
+    rt.check(rc, "sec_augment_boxes_f32")
+    return out_boxes, out_offsets, out_classes, out_importance
+
+
 LOSS_DEFAULTS = dict(alpha=0.25, gamma=2.0, sigma=3.0, pos_cls_weight=1.0, neg_cls_weight=1.0, classification_weight=1.0,
                      localization_weight=2.0, direction_loss_weight=0.2, direction_offset=0.0, sin_error_factor=1.0,
                      code_weights=(1.0,) * 7)   # second/configs/car.fhd.config:35-68

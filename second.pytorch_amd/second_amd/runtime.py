@@ -36,6 +36,7 @@ SYMBOLS = [
     "sec_heads_loss_fwd", "sec_heads_loss_fwd_terms", "sec_heads_loss_bwd", "sec_set_fp32_mode", "sec_get_fp32_mode",
     "sec_conv2d_pack_weight_train", "sec_conv2d_pack_weight_train_multi", "sec_pack_conv_weight_train_multi", "sec_conv2d_wgrad_workspace_bytes", "sec_conv2d_wgrad_nhwc", "sec_bn_train_workspace_bytes", "sec_bn_relu_fwd_nhwc",
     "sec_bn_relu_bwd_nhwc", "sec_flat_adamw_workspace_bytes", "sec_flat_adamw_f32", "sec_flat_adamw_dev_f32",
+    "sec_points_in_boxes_f32", "sec_noise_per_box_f32", "sec_augment_points_f32", "sec_augment_boxes_f32",
 ]
 
 _lib = None
@@ -215,6 +216,10 @@ def lib():
         l.sec_flat_adamw_workspace_bytes.argtypes = []
         l.sec_flat_adamw_f32.argtypes = [vp, vp, vp, vp, ll, cf, cf, cf, cf, cf, cf, vp, vp, vp, sz, vp]
         l.sec_flat_adamw_dev_f32.argtypes = [vp, vp, vp, vp, ll, vp, vp, vp, vp, sz, vp]
+        l.sec_points_in_boxes_f32.argtypes = [vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+        l.sec_noise_per_box_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp]
+        l.sec_augment_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        l.sec_augment_boxes_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = l
     return _lib
 
