@@ -821,6 +821,52 @@ int sec_augment_boxes_f32(const float *boxes, const int *box_offsets, int n_boxe
                           const float *frame_params, const float *h_bev_range4, float *out_boxes, int *out_classes,
                           float *out_importance, int *out_offsets, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ground-truth database sampling: DataBaseSamplerV2.sample_all (second/core/sample_ops.py:95-216, 238-285) and the merge of
+ * second/data/preprocess.py:210-249, for a whole batch, for single-class sample groups without the sampler's rotation and without
+ * random_crop (every config under second/configs).  The database lives on the device: db_boxes [n_db, 7], the objects' points
+ * pool_points [P, point_pitch] relative to their box centre, pool_offsets [n_db + 1].  Frames, offsets and capacities as above;
+ * every count stays on the device.
+ *
+ * sec_db_sample_select_f32 -- acceptance and the merged boxes, two launches of one workgroup per frame.  gt_classes [n_gt] (NULL =
+ *   all 1): 1-based target class, 0 = other.  candidates [batch, num_groups, k]: database rows drawn for every frame and sample
+ *   group, -1 (or a row outside the database) = absent.  class_of_group [num_groups]: the target class of each group.  num_table
+ *   [num_groups, table_len]: num_table[c][n] = round(rate * (max_num[c] - n)), the number to draw with n gt boxes of class
+ *   class_of_group[c] in the frame -- filled by the host in float64, half to even, as sample_all computes it; n >= table_len or a
+ *   non-positive entry = none.  n counts every gt box of the frame, whatever gt_valid says.  Per group, in order: the first
+ *   min(num_table[c][n], candidates present) present candidates are tested against avoid = the frame's gt boxes + what earlier
+ *   groups accepted (BEV rectangles of center_to_corner_box2d; collision = box_collision_test with the compiled meaning described at
+ *   sec_noise_per_box_f32: containment collides).  The walk is sample_class_v2's: candidate i is accepted iff it collides with no
+ *   avoid box, no earlier ACCEPTED candidate of the group and NO LATER candidate of the group, accepted or not (a rejected
+ *   candidate's row and column are cleared only when the walk reaches it).  accepted [batch, num_groups * k]: the database rows in
+ *   acceptance order (group order, then candidate order), -1 behind; accepted_count [batch]; accepted_per_group [batch, num_groups].
+ *   Merged output, out_capacity >= n_gt + batch * num_groups * k rows (else SEC_E_INVALID): per frame its gt rows, unchanged and in
+ *   order, then its accepted boxes -- out_boxes [out_capacity, 7], out_classes, out_valid (gt_valid, NULL = 1; accepted: 1),
+ *   out_importance (gt_importance, NULL = 1; accepted: sample_importance), out_sampled (1 on accepted rows: the `valid` of the
+ *   sec_points_in_boxes_f32 call that marks the scene points to remove); any of the four may be NULL.  out_box_offsets [batch + 1]
+ *   starts at 0; rows behind the end are zeroed.  k <= 64 and num_groups <= 16, else SEC_E_UNSUPPORTED.  A frame whose gt boxes
+ *   plus candidates in use exceed 512 -- known on the device only -- accepts nothing and keeps its gt.  Deterministic.
+ * sec_db_sample_merge_points_f32 -- points = [points of the accepted objects, in order, x, y, z plus the box centre (one fp32 add
+ *   each, the other columns copied)] + [the scene points that survive, in order] per frame (preprocess.py:244-249), stable.  A scene
+ *   point is removed when first_box (NULL = keep all) is >= 0 for it.  slots = num_groups * k, the row length of `accepted`.
+ *   Three launches: keep counts per 256 rows, one workgroup scanning blocks, frames and accepted objects, the scatter.  Nothing is
+ *   written at or beyond out_capacity rows: if the batch needs more, its tail is cut, out_point_offsets [batch + 1] is clamped to
+ *   out_capacity and *overflow (device int, written by every call) is 1, else 0.  Rows between out_point_offsets[batch] and
+ *   out_capacity are not written.  workspace: sec_db_sample_merge_points_workspace_bytes(n_points, batch, slots).
+ * --------------------------------------------------------------------------------------------- */
+int sec_db_sample_select_f32(const float *gt_boxes, const int *gt_offsets, int n_gt, int batch, const int *gt_classes,
+                             const unsigned char *gt_valid, const float *gt_importance, const float *db_boxes, int n_db,
+                             const int *candidates, int num_groups, int k, const int *class_of_group, const int *num_table,
+                             int table_len, float sample_importance, int *accepted, int *accepted_count, int *accepted_per_group,
+                             float *out_boxes, int out_capacity, int *out_classes, unsigned char *out_valid, float *out_importance,
+                             unsigned char *out_sampled, int *out_box_offsets, void *stream);
+size_t sec_db_sample_merge_points_workspace_bytes(int n_points, int batch, int slots);
+int sec_db_sample_merge_points_f32(const float *points, int point_pitch, const int *point_offsets, int n_points, int batch,
+                                   const int *first_box, const float *pool_points, const int *pool_offsets, const float *db_boxes,
+                                   int n_db, const int *accepted, const int *accepted_count, int slots, float *out_points,
+                                   int out_capacity, int *out_point_offsets, int *overflow, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,10 @@
 //   sec_augment_points_f32   -- points_transform_, random_flip, global_rotation_v2, global_scaling_v2, global_translate_ on the points
 //   sec_augment_boxes_f32    -- box3d_transform_ and the same global stages on the boxes, filter_gt_box_outside_range_by_center,
 //                               _dict_select (compaction) and limit_period
-// Every count (points per frame, boxes per frame, boxes kept) is read from / written to device memory, so the four calls capture
-// into a hipGraph.  All arithmetic is plain fp32 (the library builds with -ffp-contract=off and without packed fp32).
+//   sec_db_sample_select_f32 / sec_db_sample_merge_points_f32 -- DataBaseSamplerV2.sample_all (second/core/sample_ops.py:95-216,
+//                               238-285) and the merge of second/data/preprocess.py:210-249, run in front of the stages above
+// Every count (points per frame, boxes per frame, boxes kept or accepted) is read from / written to device memory, so the calls
+// capture into a hipGraph.  All arithmetic is plain fp32 (the library builds with -ffp-contract=off and without packed fp32).
 #include "common.hpp"
 
 namespace sec {
@@ -316,6 +318,327 @@ static int point_blocks(int n_points, int batch) {
     return b < 1 ? 1 : (b > 256 ? 256 : b);
 }
 
+// ------------------------------------------------------------------------------------------------ database sampling: acceptance
+// DataBaseSamplerV2.sample_all / sample_class_v2 (second/core/sample_ops.py:95-160, 238-285) for single-class groups without the
+// sampler's rotation.  One workgroup per frame.  s_cur holds the BEV corners of `avoid`: the frame's gt boxes, then what earlier
+// groups accepted.  Per group the workgroup builds the corners of the candidates in use, tests every (candidate, avoid box) and
+// (candidate, candidate) pair in parallel -- s_hit[i]: candidate i meets an avoid box; s_cc[i]: a 64-bit row of the candidate x
+// candidate matrix -- and thread 0 walks the candidates as the reference walks its matrix: candidate i is rejected if its row still
+// has an entry, and only a rejected candidate's column is cleared, when the walk reaches it.  So later candidates block whether or
+// not they end up accepted; earlier ones only if they were accepted.
+constexpr int kDbMaxK = 64;            // candidates per frame and group
+constexpr int kDbMaxGroups = 16;
+
+__device__ __forceinline__ void bev_corners_of(const float *bx, float *c, float *s) {
+    float sn, cs;
+    sincosf(bx[6], &sn, &cs);
+    const float hw = 0.5f * bx[3], hl = 0.5f * bx[4];
+    const float lx[4] = {-hw, -hw, hw, hw}, ly[4] = {-hl, hl, hl, -hl};           // clockwise from the minimum corner
+    for (int k = 0; k < 4; ++k) {
+        float x, y;
+        rot_row(lx[k], ly[k], cs, sn, x, y);
+        c[2 * k] = x + bx[0]; c[2 * k + 1] = y + bx[1];
+    }
+    standup_of(c, s);
+}
+
+__global__ __launch_bounds__(kBlock) void k_db_select(const float *__restrict__ gt_boxes, const int *__restrict__ gt_offsets, int n_gt,
+                                                      const int *__restrict__ gt_classes, const float *__restrict__ db_boxes, int n_db,
+                                                      const int *__restrict__ candidates, int groups, int k,
+                                                      const int *__restrict__ class_of_group, const int *__restrict__ num_table,
+                                                      int table_len, int *__restrict__ accepted, int *__restrict__ accepted_count,
+                                                      int *__restrict__ accepted_per_group) {
+    __shared__ float s_cur[kAugMaxBoxes][8];
+    __shared__ float s_std[kAugMaxBoxes][4];
+    __shared__ float s_cand[kDbMaxK][8];
+    __shared__ float s_cstd[kDbMaxK][4];
+    __shared__ int s_row[kDbMaxK];
+    __shared__ int s_hit[kDbMaxK];
+    __shared__ unsigned s_cc[kDbMaxK][2];
+    __shared__ int s_take[kDbMaxK];
+    __shared__ int s_cnt[kDbMaxGroups];
+    __shared__ int s_m[kDbMaxGroups];
+    __shared__ int s_scan[8];
+    __shared__ int s_took;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int g0 = max(gt_offsets[b], 0), g1 = min(gt_offsets[b + 1], n_gt);
+    const int n = max(g1 - g0, 0);
+    int *acc = accepted + (size_t)b * groups * k;
+    for (int j = tid; j < groups * k; j += kBlock) acc[j] = -1;
+    if (tid < groups) { s_cnt[tid] = 0; accepted_per_group[b * groups + tid] = 0; }
+    __syncthreads();
+    for (int j = tid; j < n; j += kBlock) {                       // gt boxes per sample class: every box counts, masked or not
+        const int cls = gt_classes ? gt_classes[g0 + j] : 1;
+        for (int c = 0; c < groups; ++c)
+            if (cls > 0 && cls == class_of_group[c]) atomicAdd(&s_cnt[c], 1);
+    }
+    __syncthreads();
+    if (tid < groups) {                                           // candidates in use: min(sampled_num, candidates present)
+        int present = 0;
+        for (int q = 0; q < k; ++q) {
+            const int v = candidates[((size_t)b * groups + tid) * k + q];
+            present += v >= 0 && v < n_db;
+        }
+        const int want = s_cnt[tid] < table_len ? num_table[tid * table_len + s_cnt[tid]] : 0;
+        s_m[tid] = min(max(want, 0), present);
+    }
+    __syncthreads();
+    int total = n;
+    for (int c = 0; c < groups; ++c) total += s_m[c];
+    if (total > kAugMaxBoxes) {                                   // more than the LDS table holds: the frame keeps its gt (documented)
+        if (tid == 0) accepted_count[b] = 0;
+        return;
+    }
+    for (int j = tid; j < n; j += kBlock) bev_corners_of(gt_boxes + (size_t)(g0 + j) * 7, s_cur[j], s_std[j]);
+    int avoid = n, n_acc = 0;
+    for (int c = 0; c < groups; ++c) {
+        const int m = s_m[c];
+        if (m == 0) continue;                                     // (uniform over the workgroup)
+        const int v = tid < k ? candidates[((size_t)b * groups + c) * k + tid] : -1;
+        const int ok = v >= 0 && v < n_db;
+        int present;
+        const int pos = block_exclusive_scan(ok, s_scan, &present);
+        if (ok && pos < m) {
+            s_row[pos] = v;
+            bev_corners_of(db_boxes + (size_t)v * 7, s_cand[pos], s_cstd[pos]);
+            s_hit[pos] = 0; s_cc[pos][0] = 0u; s_cc[pos][1] = 0u;
+        }
+        __syncthreads();                                          // (also orders s_cur: the gt corners, the rows the last group added)
+        const int cols = avoid + m;
+        for (int p = tid; p < m * cols; p += kBlock) {
+            const int i = p / cols, j = p % cols, q = j - avoid;          // q >= 0: the other box is candidate q
+            if (q == i) continue;
+            const float *oc = q >= 0 ? s_cand[q] : s_cur[j], *os = q >= 0 ? s_cstd[q] : s_std[j];
+            if (!boxes_collide(s_cand[i], s_cstd[i], oc, os)) continue;
+            if (q >= 0) atomicOr(&s_cc[i][q >> 5], 1u << (q & 31));
+            else s_hit[i] = 1;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned rej0 = 0u, rej1 = 0u;
+            int took = 0;
+            for (int i = 0; i < m; ++i) {
+                if (s_hit[i] || (s_cc[i][0] & ~rej0) || (s_cc[i][1] & ~rej1)) {
+                    if (i < 32) rej0 |= 1u << i; else rej1 |= 1u << (i - 32);
+                    s_take[i] = -1;
+                } else {
+                    s_take[i] = took++;
+                }
+            }
+            s_took = took;
+            accepted_per_group[b * groups + c] = took;
+        }
+        __syncthreads();
+        if (tid < m && s_take[tid] >= 0) {
+            const int d = avoid + s_take[tid];
+            for (int e = 0; e < 8; ++e) s_cur[d][e] = s_cand[tid][e];
+            for (int e = 0; e < 4; ++e) s_std[d][e] = s_cstd[tid][e];
+            acc[n_acc + s_take[tid]] = s_row[tid];
+        }
+        const int took = s_took;
+        avoid += took; n_acc += took;
+        __syncthreads();
+    }
+    if (tid == 0) accepted_count[b] = n_acc;
+}
+
+// The merge of second/data/preprocess.py:229-237 on the boxes: per frame the gt rows, unchanged and in order, then the accepted
+// boxes.  A launch of its own: frame b's place depends on what the frames before it accepted.
+__global__ __launch_bounds__(kBlock) void k_db_merge_boxes(const float *__restrict__ gt_boxes, const int *__restrict__ gt_offsets, int n_gt,
+                                                           int batch, const int *__restrict__ gt_classes,
+                                                           const unsigned char *__restrict__ gt_valid,
+                                                           const float *__restrict__ gt_importance, const float *__restrict__ db_boxes,
+                                                           int n_db, int groups, int k, const int *__restrict__ class_of_group,
+                                                           float sample_importance, const int *__restrict__ accepted,
+                                                           const int *__restrict__ accepted_count,
+                                                           const int *__restrict__ accepted_per_group, float *__restrict__ out_boxes,
+                                                           int capacity, int *__restrict__ out_classes, unsigned char *__restrict__ out_valid,
+                                                           float *__restrict__ out_importance, unsigned char *__restrict__ out_sampled,
+                                                           int *__restrict__ out_offsets) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int first = max(gt_offsets[0], 0);
+    const int g0 = max(gt_offsets[b], 0), g1 = min(gt_offsets[b + 1], n_gt);
+    const int n = max(g1 - g0, 0);
+    int before = 0, all = 0;
+    for (int f = 0; f < batch; ++f) {
+        const int a = min(max(accepted_count[f], 0), groups * k);
+        if (f < b) before += a;
+        all += a;
+    }
+    const int cnt = min(max(accepted_count[b], 0), groups * k);
+    const int base = max(g0 - first, 0) + before;
+    const int end = max(min(gt_offsets[batch], n_gt) - first, 0) + all;
+    if (tid == 0) {
+        out_offsets[b] = min(base, capacity);
+        if (b == batch - 1) out_offsets[batch] = min(end, capacity);
+    }
+    for (int j = tid; j < n + cnt; j += kBlock) {
+        const int o = base + j;
+        if (o >= capacity) break;
+        const bool gt = j < n;
+        int row = gt ? g0 + j : accepted[(size_t)b * groups * k + (j - n)];
+        const float *src = gt ? gt_boxes : db_boxes;
+        if (!gt && (row < 0 || row >= n_db)) row = 0;                               // (k_db_select writes rows of the database only)
+        for (int e = 0; e < 7; ++e) out_boxes[(size_t)o * 7 + e] = src[(size_t)row * 7 + e];
+        int cls = 0;
+        if (gt) {
+            cls = gt_classes ? gt_classes[row] : 1;
+        } else {
+            int a = j - n;
+            for (int c = 0; c < groups; ++c) {
+                const int t = accepted_per_group[b * groups + c];
+                if (a < t) { cls = class_of_group[c]; break; }
+                a -= t;
+            }
+        }
+        if (out_classes) out_classes[o] = cls;
+        if (out_valid) out_valid[o] = gt ? (gt_valid ? gt_valid[row] : 1) : 1;
+        if (out_importance) out_importance[o] = gt ? (gt_importance ? gt_importance[row] : 1.0f) : sample_importance;
+        if (out_sampled) out_sampled[o] = gt ? 0 : 1;
+    }
+    for (int o = max(end, 0) + b * kBlock + tid; o < capacity; o += batch * kBlock) {
+        for (int e = 0; e < 7; ++e) out_boxes[(size_t)o * 7 + e] = 0.0f;
+        if (out_classes) out_classes[o] = 0;
+        if (out_valid) out_valid[o] = 0;
+        if (out_importance) out_importance[o] = 0.0f;
+        if (out_sampled) out_sampled[o] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ database sampling: the points
+// points = concatenate([sampled_points, points[~removed]]) per frame (second/data/preprocess.py:244-249), stable, in three launches:
+// keep counts per 256 rows of the flat point array; one workgroup that scans them, sizes every frame (accepted objects' points +
+// survivors) and places frames and objects; the scatter.  Workspace (ints): [blocks] keep prefix, [batch + 1] frame start,
+// [batch] keep prefix at the frame's first point, [batch] sampled points of the frame, [batch * slots] start of every accepted
+// object inside its frame.
+struct DbMergeWs {
+    int *blk, *start, *kp0, *sampled, *obj;
+};
+static size_t db_merge_ws_ints(int n_points, int batch, int slots) {
+    return (size_t)div_up(n_points > 0 ? n_points : 1, kBlock) + 3 * (size_t)batch + 1 + (size_t)batch * slots;
+}
+static DbMergeWs db_merge_ws(void *ws, int n_points, int batch, int slots) {
+    DbMergeWs w;
+    w.blk = (int *)ws;
+    w.start = w.blk + div_up(n_points > 0 ? n_points : 1, kBlock);
+    w.kp0 = w.start + batch + 1;
+    w.sampled = w.kp0 + batch;
+    w.obj = w.sampled + batch;
+    return w;
+}
+
+__device__ __forceinline__ int dbm_keep(int i, int lo, int hi, const int *__restrict__ first_box) {
+    return i >= lo && i < hi && !(first_box && first_box[i] >= 0);
+}
+
+__global__ __launch_bounds__(kBlock) void k_dbm_count(const int *__restrict__ point_offsets, int n_points, int batch,
+                                                      const int *__restrict__ first_box, int *__restrict__ blk) {
+    __shared__ int s_scan[8];
+    const int lo = max(point_offsets[0], 0), hi = min(point_offsets[batch], n_points);
+    int total;
+    block_exclusive_scan(dbm_keep(blockIdx.x * kBlock + threadIdx.x, lo, hi, first_box), s_scan, &total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void k_dbm_scan(const int *__restrict__ point_offsets, int n_points, int batch,
+                                                     const int *__restrict__ first_box, const int *__restrict__ pool_offsets, int n_db,
+                                                     const int *__restrict__ accepted, const int *__restrict__ accepted_count, int slots,
+                                                     int n_blocks, DbMergeWs w, int capacity, int *__restrict__ out_offsets,
+                                                     int *__restrict__ overflow) {
+    __shared__ int s_scan[8];
+    const int tid = threadIdx.x;
+    const int lo = max(point_offsets[0], 0), hi = min(point_offsets[batch], n_points);
+    int kept_all = 0;
+    for (int c0 = 0; c0 < n_blocks; c0 += kBlock) {
+        const int t = c0 + tid;
+        int total;
+        const int ex = block_exclusive_scan(t < n_blocks ? w.blk[t] : 0, s_scan, &total);
+        if (t < n_blocks) w.blk[t] = kept_all + ex;
+        kept_all += total;
+    }
+    __syncthreads();
+    int start = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int p0 = min(max(point_offsets[b], lo), hi), p1 = min(max(point_offsets[b + 1], p0), hi);
+        int kp[2];
+        for (int s = 0; s < 2; ++s) {                             // survivors in front of p0 / p1: whole blocks + the rows of a part block
+            const int p = s ? p1 : p0;
+            const int t = p / kBlock, r = p % kBlock;
+            int part;
+            block_exclusive_scan(tid < r ? dbm_keep(t * kBlock + tid, lo, hi, first_box) : 0, s_scan, &part);
+            kp[s] = (t < n_blocks ? w.blk[t] : kept_all) + part;
+        }
+        const int cnt = min(max(accepted_count[b], 0), slots);
+        int sampled = 0;
+        for (int a0 = 0; a0 < cnt; a0 += kBlock) {
+            const int a = a0 + tid;
+            int len = 0;
+            if (a < cnt) {
+                const int r = accepted[(size_t)b * slots + a];
+                if (r >= 0 && r < n_db) len = max(pool_offsets[r + 1] - pool_offsets[r], 0);
+            }
+            int total;
+            const int ex = block_exclusive_scan(len, s_scan, &total);
+            if (a < cnt) w.obj[(size_t)b * slots + a] = sampled + ex;
+            sampled += total;
+        }
+        if (tid == 0) {
+            w.start[b] = start; w.kp0[b] = kp[0]; w.sampled[b] = sampled;
+            out_offsets[b] = min(start, capacity);
+        }
+        start += sampled + (kp[1] - kp[0]);
+    }
+    if (tid == 0) {
+        w.start[batch] = start;
+        out_offsets[batch] = min(start, capacity);
+        *overflow = start > capacity ? 1 : 0;
+    }
+}
+
+// blocks [0, n_blocks): the survivors of 256 rows; blocks behind them: one accepted object each (frame, slot)
+__global__ __launch_bounds__(kBlock) void k_dbm_scatter(const float *__restrict__ points, int pitch, const int *__restrict__ point_offsets,
+                                                        int n_points, int batch, const int *__restrict__ first_box,
+                                                        const float *__restrict__ pool_points, const int *__restrict__ pool_offsets,
+                                                        const float *__restrict__ db_boxes, int n_db, const int *__restrict__ accepted,
+                                                        const int *__restrict__ accepted_count, int slots, int n_blocks, DbMergeWs w,
+                                                        float *__restrict__ out_points, int capacity) {
+    __shared__ int s_scan[8];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x < n_blocks) {
+        const int lo = max(point_offsets[0], 0), hi = min(point_offsets[batch], n_points);
+        const int i = blockIdx.x * kBlock + tid;
+        const int keep = dbm_keep(i, lo, hi, first_box);
+        int total;
+        const int ex = block_exclusive_scan(keep, s_scan, &total);
+        if (!keep) return;
+        int f0 = 0, f1 = batch - 1;                               // the frame that owns row i
+        while (f0 < f1) {
+            const int mid = (f0 + f1) >> 1;
+            if (point_offsets[mid + 1] <= i) f0 = mid + 1; else f1 = mid;
+        }
+        const int d = w.start[f0] + w.sampled[f0] + (w.blk[blockIdx.x] + ex - w.kp0[f0]);
+        if (d < 0 || d >= capacity) return;
+        for (int e = 0; e < pitch; ++e) out_points[(size_t)d * pitch + e] = points[(size_t)i * pitch + e];
+        return;
+    }
+    const int q = blockIdx.x - n_blocks;
+    const int b = q / slots, a = q % slots;
+    if (a >= min(accepted_count[b], slots)) return;
+    const int r = accepted[q];
+    if (r < 0 || r >= n_db) return;
+    const int s0 = pool_offsets[r], len = pool_offsets[r + 1] - s0;
+    const int d0 = w.start[b] + w.obj[q];
+    const float cx = db_boxes[(size_t)r * 7], cy = db_boxes[(size_t)r * 7 + 1], cz = db_boxes[(size_t)r * 7 + 2];
+    for (int j = tid; j < len; j += kBlock) {
+        const int d = d0 + j;
+        if (d < 0 || d >= capacity) break;
+        const float *src = pool_points + (size_t)(s0 + j) * pitch;
+        float *dst = out_points + (size_t)d * pitch;
+        dst[0] = src[0] + cx; dst[1] = src[1] + cy; dst[2] = src[2] + cz;     // s_points[:, :3] += box3d_lidar[:3]: one fp32 add
+        for (int e = 3; e < pitch; ++e) dst[e] = src[e];
+    }
+}
+
 }  // namespace sec
 
 using namespace sec;
@@ -371,5 +694,63 @@ SEC_API int sec_augment_boxes_f32(const float *boxes, const int *box_offsets, in
     hipLaunchKernelGGL(k_augment_boxes, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, boxes, box_offsets, n_boxes, batch, valid, classes,
                        importance, loc_transform, rot_transform, frame_params, h_bev_range4[0], h_bev_range4[1], h_bev_range4[2],
                        h_bev_range4[3], out_boxes, out_classes, out_importance, out_offsets);
+    return check_launch();
+}
+
+SEC_API int sec_db_sample_select_f32(const float *gt_boxes, const int *gt_offsets, int n_gt, int batch, const int *gt_classes,
+                                     const unsigned char *gt_valid, const float *gt_importance, const float *db_boxes, int n_db,
+                                     const int *candidates, int num_groups, int k, const int *class_of_group, const int *num_table,
+                                     int table_len, float sample_importance, int *accepted, int *accepted_count,
+                                     int *accepted_per_group, float *out_boxes, int out_capacity, int *out_classes,
+                                     unsigned char *out_valid, float *out_importance, unsigned char *out_sampled, int *out_box_offsets,
+                                     void *stream) {
+    if (batch <= 0 || n_gt < 0 || n_db < 0 || num_groups <= 0 || k <= 0 || table_len <= 0 || out_capacity < 0 || !gt_offsets ||
+        !candidates || !class_of_group || !num_table || !accepted || !accepted_count || !accepted_per_group || !out_boxes ||
+        !out_box_offsets || (n_gt > 0 && !gt_boxes) || (n_db > 0 && !db_boxes))
+        return SEC_E_INVALID;
+    if (k > kDbMaxK || num_groups > kDbMaxGroups) return SEC_E_UNSUPPORTED;
+    if ((long long)out_capacity < (long long)n_gt + (long long)batch * num_groups * k) return SEC_E_INVALID;   // every frame may accept all
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_db_select, dim3(batch), dim3(kBlock), 0, st, gt_boxes, gt_offsets, n_gt, gt_classes, db_boxes, n_db, candidates,
+                       num_groups, k, class_of_group, num_table, table_len, accepted, accepted_count, accepted_per_group);
+    int rc = check_launch();
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_db_merge_boxes, dim3(batch), dim3(kBlock), 0, st, gt_boxes, gt_offsets, n_gt, batch, gt_classes, gt_valid,
+                       gt_importance, db_boxes, n_db, num_groups, k, class_of_group, sample_importance, accepted, accepted_count,
+                       accepted_per_group, out_boxes, out_capacity, out_classes, out_valid, out_importance, out_sampled, out_box_offsets);
+    return check_launch();
+}
+
+SEC_API size_t sec_db_sample_merge_points_workspace_bytes(int n_points, int batch, int slots) {
+    if (n_points < 0 || batch <= 0 || slots <= 0 || slots > kDbMaxK * kDbMaxGroups) return 0;
+    return align_up(db_merge_ws_ints(n_points, batch, slots) * sizeof(int));
+}
+
+SEC_API int sec_db_sample_merge_points_f32(const float *points, int point_pitch, const int *point_offsets, int n_points, int batch,
+                                           const int *first_box, const float *pool_points, const int *pool_offsets,
+                                           const float *db_boxes, int n_db, const int *accepted, const int *accepted_count, int slots,
+                                           float *out_points, int out_capacity, int *out_point_offsets, int *overflow, void *workspace,
+                                           size_t workspace_bytes, void *stream) {
+    if (batch <= 0 || n_points < 0 || n_db < 0 || slots <= 0 || out_capacity < 0 || !point_offsets || !accepted || !accepted_count ||
+        !out_point_offsets || !overflow || !workspace || (n_points > 0 && !points) || (out_capacity > 0 && !out_points) ||
+        (n_db > 0 && (!pool_offsets || !db_boxes)))
+        return SEC_E_INVALID;
+    if (point_pitch < 3 || slots > kDbMaxK * kDbMaxGroups) return SEC_E_UNSUPPORTED;
+    if (workspace_bytes < sec_db_sample_merge_points_workspace_bytes(n_points, batch, slots)) return SEC_E_WORKSPACE;
+    if ((long long)div_up(n_points, kBlock) + (long long)batch * slots > 0x7fffffffLL) return SEC_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const int n_blocks = div_up(n_points, kBlock);
+    const DbMergeWs w = db_merge_ws(workspace, n_points, batch, slots);
+    int rc;
+    if (n_blocks > 0) {
+        hipLaunchKernelGGL(k_dbm_count, dim3(n_blocks), dim3(kBlock), 0, st, point_offsets, n_points, batch, first_box, w.blk);
+        if ((rc = check_launch())) return rc;
+    }
+    hipLaunchKernelGGL(k_dbm_scan, dim3(1), dim3(kBlock), 0, st, point_offsets, n_points, batch, first_box, pool_offsets, n_db, accepted,
+                       accepted_count, slots, n_blocks, w, out_capacity, out_point_offsets, overflow);
+    if ((rc = check_launch())) return rc;
+    hipLaunchKernelGGL(k_dbm_scatter, dim3(n_blocks + batch * slots), dim3(kBlock), 0, st, points, point_pitch, point_offsets, n_points,
+                       batch, first_box, pool_points, pool_offsets, db_boxes, n_db, accepted, accepted_count, slots, n_blocks, w,
+                       out_points, out_capacity);
     return check_launch();
 }

@@ -1639,6 +1639,84 @@ def augment_boxes(boxes, box_offsets, frame_params, bev_range, valid=None, class
     return out_boxes, out_offsets, out_classes, out_importance
 
 
+DB_MAX_CANDIDATES, DB_MAX_GROUPS = 64, 16            # limits of sec_db_sample_select_f32 (include/second_hip.h)
+
+
+@_traced("db_sample_select")
+def db_sample_select(gt_boxes, gt_offsets, gt_classes, db_boxes, candidates, class_of_group, num_table, gt_valid=None,
+                     gt_importance=None, sample_importance=1.0):
+    """DataBaseSamplerV2.sample_all's acceptance (second/core/sample_ops.py:95-160, 238-285) and the box side of the merge
+    (second/data/preprocess.py:229-237) for a batch.  candidates [B, C, K] int32 database rows (-1 = absent), class_of_group [C],
+    num_table [C, T] int32 (header).  -> dict: ``accepted`` [B, C*K] rows in acceptance order (-1 behind), ``accepted_count`` [B],
+    ``accepted_per_group`` [B, C]; the merged ``boxes`` [G + B*C*K, 7], ``classes``, ``valid`` (bool), ``importance``, ``sampled``
+    (bool: the accepted rows) and ``box_offsets`` [B+1] -- per frame the gt rows, then the accepted boxes; zero rows behind."""
+    valid, b = _aug_frames(None, None, gt_boxes, gt_offsets, gt_valid)
+    rt.require_gpu(gt_classes, gt_importance, db_boxes, candidates, class_of_group, num_table)
+    g, dev = gt_boxes.shape[0], gt_boxes.device
+    assert db_boxes.dtype == torch.float32 and db_boxes.dim() == 2 and db_boxes.shape[1] == 7 and db_boxes.is_contiguous(), "db_boxes: contiguous fp32 [N, 7]"
+    assert candidates.dtype == torch.int32 and candidates.dim() == 3 and candidates.shape[0] == b and candidates.is_contiguous(), "candidates: contiguous int32 [B, C, K]"
+    c, k = candidates.shape[1], candidates.shape[2]
+    assert class_of_group.dtype == torch.int32 and class_of_group.numel() == c and class_of_group.is_contiguous()
+    assert num_table.dtype == torch.int32 and num_table.dim() == 2 and num_table.shape[0] == c and num_table.is_contiguous()
+    if gt_classes is not None:
+        assert gt_classes.numel() == g
+        gt_classes = gt_classes.to(torch.int32).contiguous()
+    if gt_importance is not None:
+        assert gt_importance.numel() == g
+        gt_importance = gt_importance.to(torch.float32).contiguous()
+    cap = g + b * c * k
+    out = dict(accepted=torch.empty((b, c * k), dtype=torch.int32, device=dev), accepted_count=torch.empty((b,), dtype=torch.int32, device=dev),
+               accepted_per_group=torch.empty((b, c), dtype=torch.int32, device=dev),
+               boxes=torch.empty((cap, 7), dtype=torch.float32, device=dev), classes=torch.empty((cap,), dtype=torch.int32, device=dev),
+               valid=torch.empty((cap,), dtype=torch.bool, device=dev), importance=torch.empty((cap,), dtype=torch.float32, device=dev),
+               sampled=torch.empty((cap,), dtype=torch.bool, device=dev), box_offsets=torch.empty((b + 1,), dtype=torch.int32, device=dev))
+    rc = rt.lib().sec_db_sample_select_f32(rt.ptr(gt_boxes), rt.ptr(gt_offsets), g, b, rt.ptr(gt_classes), rt.ptr(valid), rt.ptr(gt_importance),
+                                           rt.ptr(db_boxes), db_boxes.shape[0], rt.ptr(candidates), c, k, rt.ptr(class_of_group),
+                                           rt.ptr(num_table), num_table.shape[1], float(sample_importance), rt.ptr(out["accepted"]),
+                                           rt.ptr(out["accepted_count"]), rt.ptr(out["accepted_per_group"]), rt.ptr(out["boxes"]), cap,
+                                           rt.ptr(out["classes"]), rt.ptr(out["valid"]), rt.ptr(out["importance"]), rt.ptr(out["sampled"]),
+                                           rt.ptr(out["box_offsets"]), rt.stream())
+    rt.check(rc, "sec_db_sample_select_f32")
+    return out
+
+
+@_traced("db_sample_merge_points")
+def db_sample_merge_points(points, point_offsets, first_box, pool_points, pool_offsets, db_boxes, accepted, accepted_count,
+                           out_capacity=None, out=None, overflow=None):
+    """points = [accepted objects' points, moved to their box centre] + [scene points with first_box < 0] per frame
+    (second/data/preprocess.py:244-249); ``first_box`` None keeps every scene point.  -> (out_points [out_capacity, pitch],
+    out_point_offsets [B+1] int32, overflow [1] int32).  ``out`` (rows = out_capacity) / ``overflow`` may be given; a fresh ``out``
+    is zero-filled.  If the batch needs more than out_capacity rows its tail is cut, the offsets are clamped and overflow is 1."""
+    rt.require_gpu(points, point_offsets, first_box, pool_points, pool_offsets, db_boxes, accepted, accepted_count, out, overflow)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous(), "points: contiguous fp32 [N, pitch]"
+    n, pitch, b, dev = points.shape[0], points.shape[1], point_offsets.numel() - 1, points.device
+    assert point_offsets.dtype == torch.int32 and b >= 1
+    assert pool_points.dtype == torch.float32 and pool_points.dim() == 2 and pool_points.shape[1] == pitch and pool_points.is_contiguous(), \
+        "pool_points: contiguous fp32 [P, pitch of the scene points]"
+    n_db = db_boxes.shape[0]
+    assert pool_offsets.dtype == torch.int32 and pool_offsets.numel() == n_db + 1 and db_boxes.dtype == torch.float32 and db_boxes.is_contiguous()
+    assert accepted.dtype == torch.int32 and accepted.dim() == 2 and accepted.shape[0] == b and accepted.is_contiguous()
+    assert accepted_count.dtype == torch.int32 and accepted_count.numel() == b
+    if first_box is not None:
+        assert first_box.dtype == torch.int32 and first_box.numel() == n
+    slots = accepted.shape[1]
+    if out is None:
+        assert out_capacity is not None, "out_capacity or out"
+        out = torch.zeros((int(out_capacity), pitch), dtype=torch.float32, device=dev)
+    cap = out.shape[0] if out_capacity is None else int(out_capacity)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[1] == pitch and out.is_contiguous() and 0 <= cap <= out.shape[0]
+    if overflow is None:
+        overflow = torch.empty((1,), dtype=torch.int32, device=dev)
+    assert overflow.dtype == torch.int32 and overflow.numel() >= 1
+    offsets = torch.empty((b + 1,), dtype=torch.int32, device=dev)
+    ws = rt.workspace(rt.lib().sec_db_sample_merge_points_workspace_bytes(n, b, slots), dev)
+    rc = rt.lib().sec_db_sample_merge_points_f32(rt.ptr(points), pitch, rt.ptr(point_offsets), n, b, rt.ptr(first_box), rt.ptr(pool_points),
+                                                 rt.ptr(pool_offsets), rt.ptr(db_boxes), n_db, rt.ptr(accepted), rt.ptr(accepted_count), slots,
+                                                 rt.ptr(out), cap, rt.ptr(offsets), rt.ptr(overflow), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, "sec_db_sample_merge_points_f32")
+    return out, offsets, overflow
+
+
 LOSS_DEFAULTS = dict(alpha=0.25, gamma=2.0, sigma=3.0, pos_cls_weight=1.0, neg_cls_weight=1.0, classification_weight=1.0,
                      localization_weight=2.0, direction_loss_weight=0.2, direction_offset=0.0, sin_error_factor=1.0,
                      code_weights=(1.0,) * 7)   # second/configs/car.fhd.config:35-68

@@ -37,6 +37,7 @@ SYMBOLS = [
     "sec_conv2d_pack_weight_train", "sec_conv2d_pack_weight_train_multi", "sec_pack_conv_weight_train_multi", "sec_conv2d_wgrad_workspace_bytes", "sec_conv2d_wgrad_nhwc", "sec_bn_train_workspace_bytes", "sec_bn_relu_fwd_nhwc",
     "sec_bn_relu_bwd_nhwc", "sec_flat_adamw_workspace_bytes", "sec_flat_adamw_f32", "sec_flat_adamw_dev_f32",
     "sec_points_in_boxes_f32", "sec_noise_per_box_f32", "sec_augment_points_f32", "sec_augment_boxes_f32",
+    "sec_db_sample_select_f32", "sec_db_sample_merge_points_workspace_bytes", "sec_db_sample_merge_points_f32",
 ]
 
 _lib = None
@@ -106,7 +107,7 @@ def lib():
                      "sec_conv2d_packed_weight_bytes", "sec_indice_conv_bwd_workspace_bytes",
                      "sec_assign_targets_workspace_bytes", "sec_second_loss_workspace_bytes", "sec_heads_loss_workspace_bytes",
                      "sec_conv2d_wgrad_workspace_bytes", "sec_bn_train_workspace_bytes", "sec_pfn_train_workspace_bytes",
-                     "sec_flat_adamw_workspace_bytes"):
+                     "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes"):
             getattr(l, name).restype = ctypes.c_size_t
         if os.environ.get("SEC_FP32_MODE", "").lower() == "exact":      # process default of ops.set_fp32_mode
             l.sec_set_fp32_mode(1)
@@ -220,6 +221,9 @@ def lib():
         l.sec_noise_per_box_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp]
         l.sec_augment_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
         l.sec_augment_boxes_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        l.sec_db_sample_select_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp, ci, cf, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        l.sec_db_sample_merge_points_workspace_bytes.argtypes = [ci, ci, ci]
+        l.sec_db_sample_merge_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, sz, vp]
         _lib = l
     return _lib
 
