@@ -701,13 +701,60 @@ def exact_rpn_default():
     return v
 
 
+class _Fp32Arithmetic:
+    """How RPNInference's fp32 block represents an activation map ``a`` ([B, 128, H, W] channels_last) and which ops compute on it: a
+    (hi, lo) pair of bf16 planes, or one fp32 map.  Backgrounds and empty-frame maps are in the same representation."""
+
+    def __init__(self, name, planes, pack, conv, conv_tiles, chain):
+        self.name, self._planes, self._pack, self._conv, self._conv_tiles, self._chain = name, planes, pack, conv, conv_tiles, chain
+
+    def _args(self, a):
+        return a if self._planes == 2 else (a,)
+
+    def pack(self, weight):
+        """Folded fp32 weight [Cout, 128, k, k] -> the packed image the convs / the chain read; None for a shape they do not take."""
+        return self._pack(weight)
+
+    def zeros(self, h, w, device):
+        """The input of a frame without sites."""
+        z = torch.zeros((1, 128, h, w), dtype=torch.bfloat16 if self._planes == 2 else torch.float32, device=device)
+        z = z.contiguous(memory_format=torch.channels_last)
+        return (z, z.clone()) if self._planes == 2 else z
+
+    def enter(self, x):
+        return ops.split_bf16x2(x) if self._planes == 2 else x
+
+    def leave(self, a):
+        return ops.merge_bf16x2(*a) if self._planes == 2 else a
+
+    def conv(self, a, packed, bias, cout, sparse_input=False):
+        return self._conv(*self._args(a), packed, bias, cout, relu=True, sparse_input=sparse_input)
+
+    def conv_tiles(self, a, packed, bias, cout, tile_order, live_counts, background, nbr_masks, background_in):
+        return self._conv_tiles(*self._args(a), packed, bias, cout, tile_order, live_counts, background=background, relu=True,
+                                nbr_masks=nbr_masks, background_in=background_in)
+
+    def chain(self, a, w1, b1, w2, b2):
+        """Deblock + merged heads (padded to 64 channels) in one launch: fp32 [B, 64, H, W] channels_last."""
+        return self._chain(*self._args(a), w1, b1, w2, b2, 64, relu1=True)
+
+
+# fp32 storage on the bf16 matrix pipe with split operands (v = hi + lo, three passes, fp32 accumulation): the fp32 default
+_BF16X3 = _Fp32Arithmetic("bf16x3", 2, ops.conv2d_pack_weight_x3, ops.conv2d_nhwc_x3, ops.conv2d_nhwc_x3_tiles, ops.conv1x1_chain_x3)
+# IEEE fp32 products on the fp32 MFMA (v_mfma_f32_32x32x2_f32): the exact mode's RPN
+_FP32 = _Fp32Arithmetic("fp32", 1, ops.conv2d_pack_weight_f32, ops.conv2d_nhwc_f32, ops.conv2d_nhwc_f32_tiles, ops.conv1x1_chain_f32)
+
+
 class RPNInference(nn.Module):
     """Inference form of a single-block RPNV2: BatchNorm2d folded into the conv weights (scale) and a float32
     bias, ZeroPad2d merged into the conv padding, the stride-1 1x1 ConvTranspose2d rewritten as a 1x1 conv, the three
     1x1 heads merged into one conv (output channels padded to a multiple of 64).  Every 3x3 conv runs on the
     hand-written MFMA kernel with bias + ReLU fused (sec_conv2d_nhwc), the deblock + heads as one fused kernel
     (sec_conv1x1_chain_nhwc); backend="miopen" keeps torch convs + one fused bias/ReLU pass for A/B runs.
-    Same arithmetic as RPNV2.forward (rpn.py:314-331,393-420) up to bf16 rounding of the folded weights."""
+    Same arithmetic as RPNV2.forward (rpn.py:314-331,393-420) up to bf16 rounding of the folded weights.
+    A float32 network runs the same block in one of two fp32 arithmetics (``self.fp32``, a :class:`_Fp32Arithmetic`, with its packed
+    weights in ``fp32_packed`` / ``fp32_chain``; None for the 16-bit and torch forms): "bf16x3" = split bf16 operands (backend="hip"),
+    "fp32" = IEEE fp32 products on the fp32 MFMA (backend="hip_f32").  One forward, :meth:`_forward_fp32`, serves both."""
 
     @staticmethod
     def supports(rpn):
@@ -782,10 +829,22 @@ class RPNInference(nn.Module):
         hb = torch.cat([h.bias.detach().float() for h in heads] + [torch.zeros(padc, device=heads[0].weight.device)], 0)
         self.head_w = nn.Parameter(hw.to(dtype).contiguous(memory_format=torch.channels_last), requires_grad=False)
         self.head_b = nn.Parameter(hb.contiguous(), requires_grad=False)
+        convs = [i for kind, i in self.plan if kind == "c"]      # the block convs' layer indices
+
+        def conv3x3_128(i, cout128=False):
+            """layer i is 3x3 / stride 1 / pad 1 on 128 input channels, no depth-to-space, Cout a multiple of 128 (cout128: exactly 128)"""
+            w = self.ws[i]
+            return (tuple(w.shape[1:]) == (128, 3, 3) and (w.shape[0] == 128 if cout128 else w.shape[0] % 128 == 0)
+                    and self.cfgs[i] == ([1, 1], [1, 1]) and self.ups[i] == 1)
+        # the convs the live-tile machinery serves: layers 0 .. n-1, 2 <= n <= 8, all 128 -> 128 (0: none)
+        live_convs = len(convs) if (convs == list(range(len(convs))) and 2 <= len(convs) <= 8
+                                    and all(conv3x3_128(i, cout128=True) for i in convs)) else 0
+        wl = self.ws[-1]
+        deblock_1x1_128 = tuple(wl.shape) == (128, 128, 1, 1) and self.cfgs[-1] == ([1, 1], [0, 0]) and self.ups[-1] == 1
         # hand-written MFMA conv (sec_conv2d_nhwc, bias + ReLU fused) when shapes allow
         self.return_views = True   # the fused predict kernels read the head output in place through strides
         self.use_hip = backend == "hip" and dtype in (torch.bfloat16, torch.float16)
-        self.packed, self.head_packed = [], None
+        self.packed, self.head_packed, self.head_b64, self.head_cout = [], None, None, 0
         if self.use_hip:
             for w in self.ws:
                 pk = ops.conv2d_pack_weight(w.detach().contiguous())
@@ -794,67 +853,38 @@ class RPNInference(nn.Module):
                     break
                 self.packed.append(pk)
         if self.use_hip:
-            cpad = (-hw.shape[0]) % 64
-            hw64 = torch.cat([hw, torch.zeros(cpad, *hw.shape[1:], device=hw.device)], 0).to(dtype).contiguous()
-            self.head_cout = hw64.shape[0]
-            self.head_packed = ops.conv2d_pack_weight(hw64)
-            self.head_b64 = torch.cat([hb, torch.zeros(cpad, device=hb.device)]).contiguous()
+            self.head_cout = hw.shape[0] + (-hw.shape[0]) % 64
+            hw64, self.head_b64 = self._padded_heads(self.head_cout)
+            self.head_packed = ops.conv2d_pack_weight(hw64.to(dtype))
             self.use_hip = self.head_packed is not None
-        # fp32 networks (the reference's default precision): every 3x3 / s1 / p1 128 -> Cout conv of a single-block RPN on the bf16
-        # matrix pipe with split operands (sec_conv2d_nhwc_x3: v = hi + lo, three passes, fp32 accumulation); the 1x1 deblock and
-        # heads stay torch fp32 convolutions (9 GFLOP against the blocks' 500)
-        self.packed_x3 = None
-        if backend == "hip" and dtype == torch.float32 and single and next(rpn.parameters()).is_cuda:
-            convs = [i for kind, i in self.plan if kind == "c"]
-            if all(tuple(self.ws[i].shape[1:]) == (128, 3, 3) and self.ws[i].shape[0] % 128 == 0 and self.cfgs[i] == ([1, 1], [1, 1])
-                   and self.ups[i] == 1 for i in convs):
-                pk = {i: ops.conv2d_pack_weight_x3(self.ws[i]) for i in convs}
-                if all(v is not None for v in pk.values()):
-                    self.packed_x3 = pk
-                    self._x3_convs = len(convs) if (convs == list(range(len(convs))) and 2 <= len(convs) <= 8
-                                                    and all(self.ws[i].shape[0] == 128 for i in convs)) else 0
-                    # the 1x1 deblock + merged heads as ONE split-operand launch (sec_conv1x1_chain_x3) when the shapes allow
-                    wl_ = self.ws[-1]
-                    self.chain_x3 = None
-                    if (self.plan[-1][0] == "u" and tuple(wl_.shape) == (128, 128, 1, 1) and self.cfgs[-1] == ([1, 1], [0, 0])
-                            and self.ups[-1] == 1 and hw.shape[0] <= 64):
-                        pad = 64 - hw.shape[0]
-                        hw64 = torch.cat([hw, torch.zeros(pad, *hw.shape[1:], device=hw.device)], 0).contiguous()
-                        hb64 = torch.cat([hb, torch.zeros(pad, device=hb.device)]).contiguous()
-                        self.chain_x3 = [ops.conv2d_pack_weight_x3(wl_), ops.conv2d_pack_weight_x3(hw64), hb64]
-        # backend "hip_f32" (the exact mode's RPN, prepare_inference(exact_rpn="hip")): the same layers with IEEE fp32 products on the
-        # fp32 MFMA (sec_conv2d_nhwc_f32 / _tiles, sec_conv1x1_chain_f32); shapes the kernels do not take keep the torch path
-        self.packed_f32, self.chain_f32, self._f32_convs = None, None, 0
+        # fp32 networks: every 3x3 / s1 / p1 128 -> Cout conv of a single-block RPN on the matrix pipe in one of two arithmetics.
+        # backend "hip" with dtype float32 (the reference's default precision): split bf16 operands ("bf16x3").  backend "hip_f32" (the
+        # exact mode's RPN, prepare_inference(exact_rpn="hip")): IEEE fp32 products on the fp32 MFMA.  Shapes the kernels do not take
+        # keep the torch path.
+        self.fp32, self.fp32_packed, self.fp32_chain = None, {}, None
         if backend == "hip_f32":
             assert dtype == torch.float32, "RPNInference(backend='hip_f32') is the fp32 form"
-            convs = [i for kind, i in self.plan if kind == "c"]
-            if (single and next(rpn.parameters()).is_cuda
-                    and all(tuple(self.ws[i].shape[1:]) == (128, 3, 3) and self.ws[i].shape[0] % 128 == 0 and self.cfgs[i] == ([1, 1], [1, 1])
-                            and self.ups[i] == 1 for i in convs)):
-                self.packed_f32 = {i: ops.conv2d_pack_weight_f32(self.ws[i]) for i in convs}
-                self._f32_convs = len(convs) if (convs == list(range(len(convs))) and 2 <= len(convs) <= 8
-                                                 and all(self.ws[i].shape[0] == 128 for i in convs)) else 0
-                wl_ = self.ws[-1]
-                if (self.plan[-1][0] == "u" and tuple(wl_.shape) == (128, 128, 1, 1) and self.cfgs[-1] == ([1, 1], [0, 0])
-                        and self.ups[-1] == 1 and hw.shape[0] <= 64):
-                    hw64, hb64 = self._heads64()
-                    self.chain_f32 = [ops.conv2d_pack_weight_f32(wl_), ops.conv2d_pack_weight_f32(hw64), hb64]
-        # deblock (1x1, stride 1, 128 -> 128) + heads (<= 128 padded channels) run as ONE kernel (sec_conv1x1_chain_nhwc)
-        wl = self.ws[-1]
+        arith = _FP32 if backend == "hip_f32" else _BF16X3 if (backend == "hip" and dtype == torch.float32) else None
+        if arith is not None and single and next(rpn.parameters()).is_cuda and all(conv3x3_128(i) for i in convs):
+            pk, chain = {i: arith.pack(self.ws[i]) for i in convs}, None
+            # the 1x1 deblock + merged heads as ONE launch (sec_conv1x1_chain_x3 / _f32) when the shapes allow; otherwise they stay
+            # torch fp32 GEMMs (9 GFLOP against the blocks' 500)
+            if self.plan[-1][0] == "u" and deblock_1x1_128 and hw.shape[0] <= 64:
+                hw64, hb64 = self._padded_heads(64)
+                chain = [arith.pack(wl), arith.pack(hw64), hb64]
+            if all(t is not None for t in list(pk.values()) + (chain or [])):
+                self.fp32, self.fp32_packed, self.fp32_chain = arith, pk, chain
         self.concat_in_place = True      # multi-block RPNs: the deblocks write into the concatenated map (False: torch.cat of their outputs)
         self.pillar_rows_first = True    # a PillarBEV input: the first conv reads the pillar rows through a site map when the shapes allow (False: the scattered canvas)
         self.sparse_input = True   # forward()'s input comes from SparseConvTensor.dense(): all-zero halo tiles skip their MFMA loop (bit-identical)
         # first conv straight from the sparse rows (sec_conv2d_nhwc_gather): 3x3 / s1 / p1 on 2 planes x 64 channels; its weights
         # are packed a second time with the input channels in plane-major order (gather_first=False: always the dense image)
         self.gather_packed = None
-        w0 = self.ws[0]
-        if (self.use_hip and self.plan[0][0] == "c" and tuple(w0.shape[1:]) == (128, 3, 3) and w0.shape[0] % 128 == 0
-                and self.cfgs[0] == ([1, 1], [1, 1]) and self.ups[0] == 1 and gather_first):
-            perm = ops.gather_channel_perm(64, 2).to(w0.device)
-            self.gather_packed = ops.conv2d_pack_weight(w0.detach()[:, perm].contiguous())
-        self.chain_tail = (single and self.use_hip and tuple(wl.shape) == (128, 128, 1, 1) and self.cfgs[-1] == ([1, 1], [0, 0])
-                           and self.ups[-1] == 1
-                           and self.head_cout in (64, 128))
+        if self.use_hip and self.plan[0][0] == "c" and conv3x3_128(0) and gather_first:
+            perm = ops.gather_channel_perm(64, 2).to(self.ws[0].device)
+            self.gather_packed = ops.conv2d_pack_weight(self.ws[0].detach()[:, perm].contiguous())
+        # deblock (1x1, stride 1, 128 -> 128) + heads (<= 128 padded channels) run as ONE kernel (sec_conv1x1_chain_nhwc)
+        self.chain_tail = single and self.use_hip and deblock_1x1_128 and self.head_cout in (64, 128)
         # Background tiles (sec_conv2d_nhwc_tiles): with the first conv gathered from the sparse rows the site map is at hand, and a
         # tile of conv j's output that no site can reach (j + 1 steps) holds exactly what the network computes for an EMPTY frame at
         # that position -- any weights.  The empty frame's activations are computed once per map size by the
@@ -876,22 +906,15 @@ class RPNInference(nn.Module):
         self.last_tiles_per_frame = None   # tiles of one frame's map in that forward
         self._empty_maps = {}
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._repack())
-        convs = [i for kind, i in self.plan if kind == "c"]
-        self.background_convs = len(convs) if (
-            self.gather_packed is not None and 2 <= len(convs) <= 8 and convs == list(range(len(convs)))
-            and all(tuple(self.ws[i].shape) == (128, 128, 3, 3) and self.cfgs[i] == ([1, 1], [1, 1]) and self.ups[i] == 1 for i in convs)) else 0
-        if self.packed_x3 is not None:          # fp32: the same live-tile machinery on the split-operand convs (always the lazy form)
-            self.background_convs = getattr(self, "_x3_convs", 0)
-        if self.packed_f32 is not None:         # ... and on the fp32-MFMA convs
-            self.background_convs = self._f32_convs
+        # (the fp32 forms: the same live-tile machinery on the split-operand / fp32-MFMA convs, always lazy)
+        self.background_convs = live_convs if (self.gather_packed is not None or self.fp32 is not None) else 0
 
-    def _heads64(self):
-        """Merged head weights / biases in fp32, zero-padded to 64 output channels (the second GEMM of sec_conv1x1_chain_f32)."""
-        pad = 64 - self.head_w.shape[0]
-        hw = self.head_w.detach().float()
-        hw64 = torch.cat([hw, torch.zeros(pad, *hw.shape[1:], device=hw.device)], 0).contiguous()
-        hb64 = torch.cat([self.head_b.detach().float(), torch.zeros(pad, device=hw.device)]).contiguous()
-        return hw64, hb64
+    def _padded_heads(self, cout):
+        """(weight, bias) of the merged heads in fp32, zero-padded to ``cout`` output channels: the last GEMM of the fused 1x1 tails."""
+        hw, hb = self.head_w.detach().float(), self.head_b.detach().float()
+        pad = cout - hw.shape[0]
+        return (torch.cat([hw, torch.zeros(pad, *hw.shape[1:], device=hw.device)], 0).contiguous(),
+                torch.cat([hb, torch.zeros(pad, device=hb.device)]).contiguous())
 
     # The packed weight images (MFMA slab order, the gather permutation, the hi | lo pairs of the fp32 form) are derived from the
     # folded parameters at construction: keep them in step with the parameters.  In place, so that captured graphs stay valid.
@@ -900,47 +923,29 @@ class RPNInference(nn.Module):
             if self.use_hip:
                 for i, w in enumerate(self.ws):
                     self.packed[i].copy_(ops.conv2d_pack_weight(w.detach().contiguous()))
-                pad = self.head_cout - self.head_w.shape[0]
-                hw64 = torch.cat([self.head_w.detach().float(), torch.zeros(pad, *self.head_w.shape[1:], device=self.head_w.device)], 0)
-                self.head_packed.copy_(ops.conv2d_pack_weight(hw64.to(self.head_w.dtype).contiguous()))
-                self.head_b64[:self.head_b.numel()].copy_(self.head_b)
+                hw64, hb64 = self._padded_heads(self.head_cout)
+                self.head_packed.copy_(ops.conv2d_pack_weight(hw64.to(self.head_w.dtype)))
+                self.head_b64.copy_(hb64)
                 if self.gather_packed is not None:
                     perm = ops.gather_channel_perm(64, 2).to(self.ws[0].device)
                     self.gather_packed.copy_(ops.conv2d_pack_weight(self.ws[0].detach()[:, perm].contiguous()))
-            if self.packed_x3 is not None:
-                for i, pk in self.packed_x3.items():
-                    pk.copy_(ops.conv2d_pack_weight_x3(self.ws[i]))
-                if getattr(self, "chain_x3", None) is not None:
-                    pad = 64 - self.head_w.shape[0]
-                    hw64 = torch.cat([self.head_w.detach().float(), torch.zeros(pad, *self.head_w.shape[1:], device=self.head_w.device)], 0)
-                    self.chain_x3[0].copy_(ops.conv2d_pack_weight_x3(self.ws[-1]))
-                    self.chain_x3[1].copy_(ops.conv2d_pack_weight_x3(hw64.contiguous()))
-                    self.chain_x3[2][:self.head_b.numel()].copy_(self.head_b)
-            if self.packed_f32 is not None:
-                for i, pk in self.packed_f32.items():
-                    pk.copy_(ops.conv2d_pack_weight_f32(self.ws[i]))
-                if self.chain_f32 is not None:
-                    hw64, hb64 = self._heads64()
-                    self.chain_f32[0].copy_(ops.conv2d_pack_weight_f32(self.ws[-1]))
-                    self.chain_f32[1].copy_(ops.conv2d_pack_weight_f32(hw64))
-                    self.chain_f32[2].copy_(hb64)
+            if self.fp32 is not None:
+                for i, pk in self.fp32_packed.items():
+                    pk.copy_(self.fp32.pack(self.ws[i]))
+                if self.fp32_chain is not None:
+                    hw64, hb64 = self._padded_heads(64)
+                    for dst, src in zip(self.fp32_chain, (self.fp32.pack(self.ws[-1]), self.fp32.pack(hw64), hb64)):
+                        dst.copy_(src)
         self._empty_maps.clear()
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)
         move = lambda t: fn(t) if isinstance(t, torch.Tensor) else t
         self.packed = [move(t) for t in self.packed]
-        for name in ("head_packed", "head_b64", "gather_packed"):
-            if getattr(self, name, None) is not None:
-                setattr(self, name, move(getattr(self, name)))
-        if self.packed_x3 is not None:
-            self.packed_x3 = {i: move(t) for i, t in self.packed_x3.items()}
-            if getattr(self, "chain_x3", None) is not None:
-                self.chain_x3 = [move(t) for t in self.chain_x3]
-        if getattr(self, "packed_f32", None) is not None:
-            self.packed_f32 = {i: move(t) for i, t in self.packed_f32.items()}
-            if self.chain_f32 is not None:
-                self.chain_f32 = [move(t) for t in self.chain_f32]
+        self.head_packed, self.head_b64, self.gather_packed = move(self.head_packed), move(self.head_b64), move(self.gather_packed)
+        self.fp32_packed = {i: move(t) for i, t in self.fp32_packed.items()}
+        if self.fp32_chain is not None:
+            self.fp32_chain = [move(t) for t in self.fp32_chain]
         self._empty_maps.clear()
         return self
 
@@ -999,115 +1004,53 @@ class RPNInference(nn.Module):
             y = y.permute(0, 3, 1, 2)        # a channels_last [B,co,H*u,W*u] tensor
         return y
 
-    def empty_frame_maps_x3(self, h, w):
-        """(hi, lo) plane pairs of every 3x3 conv's output for a frame WITHOUT sites, from the split-operand kernel itself (a copied or
-        lazily read tile is then bit-identical to a computed one).  Cached per map size and weight version; not inside a capture."""
-        src = [self.ws[i] for i in self.packed_x3] + [self.bs[i] for i in self.packed_x3]
-        key = ("x3", int(h), int(w), str(self.ws[0].device), tuple((t.data_ptr(), t._version) for t in src))
+    def empty_frame_maps_fp32(self, h, w):
+        """Output of every 3x3 conv of the fp32 forms for a frame WITHOUT sites, in the arithmetic's representation ((hi, lo) plane pairs
+        or fp32 maps, channels_last [1, 128, h, w]), from the forward's own kernel (a copied or lazily read tile is then bit-identical
+        to a computed one).  Cached per map size and weight version; not inside a capture."""
+        src = [self.ws[i] for i in self.fp32_packed] + [self.bs[i] for i in self.fp32_packed]
+        key = (self.fp32.name, int(h), int(w), str(self.ws[0].device), tuple((t.data_ptr(), t._version) for t in src))
         if key not in self._empty_maps:
-            assert not torch.cuda.is_current_stream_capturing(), "RPNInference.empty_frame_maps_x3: run one eager forward before capturing"
-            self._empty_maps = {k: v for k, v in self._empty_maps.items() if k[0] != "x3"}
-            dev = self.ws[0].device
+            assert not torch.cuda.is_current_stream_capturing(), "RPNInference.empty_frame_maps_fp32: run one eager forward before capturing"
+            self._empty_maps.clear()
             with torch.no_grad():
-                z = torch.zeros((1, 128, h, w), dtype=torch.bfloat16, device=dev).contiguous(memory_format=torch.channels_last)
-                hi, lo, maps = z, z.clone(), []
-                for kind, i in self.plan:
-                    if kind == "c":
-                        hi, lo = ops.conv2d_nhwc_x3(hi, lo, self.packed_x3[i], self.bs[i], self.ws[i].shape[0], relu=True)
-                        maps.append((hi, lo))
+                a, maps = self.fp32.zeros(h, w, self.ws[0].device), []
+                for i, pk in self.fp32_packed.items():
+                    a = self.fp32.conv(a, pk, self.bs[i], self.ws[i].shape[0])
+                    maps.append(a)
             self._empty_maps[key] = maps
         return self._empty_maps[key]
 
-    def _forward_x3(self, x):
-        """fp32 activations as bf16 (hi, lo) plane pairs through the 3x3 convs; merged back to fp32 for the 1x1 tail.  Given the sparse
-        middle's rows (a SparseBEV) the convs run on the tiles a site can reach only, exactly like the 16-bit path: conv j computes
-        the tiles within j + 1 steps of a site, reads halo pixels of unwritten tiles from the empty frame's planes, and only the last
-        conv materialises its background (the torch 1x1 tail reads the whole map)."""
-        lists = None
+    def _forward_fp32(self, x):
+        """The single block in one of the fp32 arithmetics (``self.fp32``).  Given the sparse middle's rows (a SparseBEV) the convs run on
+        the tiles a site can reach only, exactly like the 16-bit path: conv j computes the tiles within j + 1 steps of a site, reads
+        halo pixels of unwritten tiles from the empty frame's maps, and only the last conv materialises its background, because the
+        1x1 tail (deblock + heads: one launch, or torch fp32 GEMMs on the map merged back to fp32) reads the whole map."""
+        ar, lists = self.fp32, None
         if isinstance(x, SparseBEV):
-            convs = [i for kind, i in self.plan if kind == "c"]
-            if self.background_convs and self.skip_background and convs == list(range(len(convs))):
+            if self.background_convs and self.skip_background:
                 sm = x.site_map()
-                empty = self.empty_frame_maps_x3(sm.shape[2], sm.shape[3])
+                empty = self.empty_frame_maps_fp32(sm.shape[2], sm.shape[3])
                 live, self.last_live_counts, nbr = x.tile_lists(self.background_convs, masks=True)
                 lists = (live, nbr, empty)
             x = x.dense()
-        hi, lo = ops.split_bf16x2(x.float().contiguous(memory_format=torch.channels_last))
-        first, ups = self.sparse_input, []
-        for kind, i in self.plan:
-            if kind == "c" and lists is not None:
+        a = ar.enter(x.float().contiguous(memory_format=torch.channels_last))
+        first = self.sparse_input
+        for i, pk in self.fp32_packed.items():
+            if lists is not None:
                 live, nbr, empty = lists
                 last = i == self.background_convs - 1
-                hi, lo = ops.conv2d_nhwc_x3_tiles(hi, lo, self.packed_x3[i], self.bs[i], self.ws[i].shape[0], live[i], self.last_live_counts[i],
-                                                  background=empty[i] if last else None, relu=True,
-                                                  nbr_masks=nbr[i] if (i > 0 and nbr is not None) else None,
-                                                  background_in=empty[i - 1] if (i > 0 and nbr is not None) else None)
-            elif kind == "c":
-                hi, lo = ops.conv2d_nhwc_x3(hi, lo, self.packed_x3[i], self.bs[i], self.ws[i].shape[0], relu=True, sparse_input=first)
-                first = False
-            elif getattr(self, "chain_x3", None) is not None:
-                w1, w2, b2 = self.chain_x3            # deblock + heads in one launch, straight from the two planes
-                return self._split_heads(ops.conv1x1_chain_x3(hi, lo, w1, self.bs[i], w2, b2, 64, relu1=True))
+                a = ar.conv_tiles(a, pk, self.bs[i], self.ws[i].shape[0], live[i], self.last_live_counts[i],
+                                  background=empty[i] if last else None, nbr_masks=nbr[i] if i > 0 else None,
+                                  background_in=empty[i - 1] if i > 0 else None)
             else:
-                ups.append(self._conv(ops.merge_bf16x2(hi, lo), i))
-        f = ups[0] if len(ups) == 1 else torch.cat(ups, dim=1)
-        if f.is_cuda and f.is_contiguous(memory_format=torch.channels_last):
-            y = self._conv1x1_gemm(f, self.head_w, self.head_b, relu=False)
-        else:
-            y = ops.bias_act_(F.conv2d(f, self.head_w, None), self.head_b, relu=False)
-        return self._split_heads(y)
-
-    def empty_frame_maps_f32(self, h, w):
-        """Output of every 3x3 conv for a frame WITHOUT sites, fp32 channels_last [1, 128, h, w] each, from the fp32-MFMA kernel itself
-        (a copied or lazily read tile is then bit-identical to a computed one).  Cached per map size and weight version; not inside
-        a capture."""
-        src = [self.ws[i] for i in self.packed_f32] + [self.bs[i] for i in self.packed_f32]
-        key = ("f32", int(h), int(w), str(self.ws[0].device), tuple((t.data_ptr(), t._version) for t in src))
-        if key not in self._empty_maps:
-            assert not torch.cuda.is_current_stream_capturing(), "RPNInference.empty_frame_maps_f32: run one eager forward before capturing"
-            self._empty_maps = {k: v for k, v in self._empty_maps.items() if k[0] != "f32"}
-            with torch.no_grad():
-                x = torch.zeros((1, 128, h, w), dtype=torch.float32, device=self.ws[0].device).contiguous(memory_format=torch.channels_last)
-                maps = []
-                for kind, i in self.plan:
-                    if kind == "c":
-                        x = ops.conv2d_nhwc_f32(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], relu=True)
-                        maps.append(x)
-            self._empty_maps[key] = maps
-        return self._empty_maps[key]
-
-    def _forward_f32(self, x):
-        """The block in IEEE fp32 on the fp32 MFMA, structured like :meth:`_forward_x3`: given the sparse middle's rows (a SparseBEV)
-        conv j computes the tiles within j + 1 steps of a site and reads halo pixels of unwritten tiles from the empty frame's map;
-        the last conv materialises its background, because the 1x1 tail (one launch: deblock + heads) reads the whole map."""
-        lists = None
-        if isinstance(x, SparseBEV):
-            convs = [i for kind, i in self.plan if kind == "c"]
-            if self.background_convs and self.skip_background and convs == list(range(len(convs))):
-                sm = x.site_map()
-                empty = self.empty_frame_maps_f32(sm.shape[2], sm.shape[3])
-                live, self.last_live_counts, nbr = x.tile_lists(self.background_convs, masks=True)
-                lists = (live, nbr, empty)
-            x = x.dense()
-        x = x.float().contiguous(memory_format=torch.channels_last)
-        first, ups = self.sparse_input, []
-        for kind, i in self.plan:
-            if kind == "c" and lists is not None:
-                live, nbr, empty = lists
-                last = i == self.background_convs - 1
-                x = ops.conv2d_nhwc_f32_tiles(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], live[i], self.last_live_counts[i],
-                                              background=empty[i] if last else None, relu=True,
-                                              nbr_masks=nbr[i] if (i > 0 and nbr is not None) else None,
-                                              background_in=empty[i - 1] if (i > 0 and nbr is not None) else None)
-            elif kind == "c":
-                x = ops.conv2d_nhwc_f32(x, self.packed_f32[i], self.bs[i], self.ws[i].shape[0], relu=True, sparse_input=first)
+                a = ar.conv(a, pk, self.bs[i], self.ws[i].shape[0], sparse_input=first)
                 first = False
-            elif self.chain_f32 is not None:
-                w1, w2, b2 = self.chain_f32
-                return self._split_heads(ops.conv1x1_chain_f32(x, w1, self.bs[i], w2, b2, 64, relu1=True))
-            else:
-                ups.append(self._conv(x, i))
-        f = ups[0] if len(ups) == 1 else torch.cat(ups, dim=1)
+        i = len(self.ws) - 1                       # the one deblock of the single block
+        if self.fp32_chain is not None:
+            w1, w2, b2 = self.fp32_chain
+            return self._split_heads(ar.chain(a, w1, self.bs[i], w2, b2))
+        f = self._conv(ar.leave(a), i)
         if f.is_cuda and f.is_contiguous(memory_format=torch.channels_last):
             y = self._conv1x1_gemm(f, self.head_w, self.head_b, relu=False)
         else:
@@ -1125,10 +1068,8 @@ class RPNInference(nn.Module):
         return ret
 
     def forward(self, x):
-        if self.packed_x3 is not None:
-            return self._forward_x3(x.dense() if isinstance(x, PillarBEV) else x)
-        if self.packed_f32 is not None:
-            return self._forward_f32(x.dense() if isinstance(x, PillarBEV) else x)
+        if self.fp32 is not None:
+            return self._forward_fp32(x.dense() if isinstance(x, PillarBEV) else x)
         ups = []
         first = self.sparse_input     # x is the scattered sparse-middle output: mostly empty tiles
         gather = None
@@ -1227,7 +1168,6 @@ class RPNInference(nn.Module):
     def _tail_in_last_conv(self, i, x, nbr):
         """Conv ``i`` is the last 3x3 conv of a single-block RPN whose consumers are all lazy (lazy heads on the same lists): it then runs
         with the 1x1 tail in its epilogue.  SEC_RPN_FUSED_TAIL=0: the two launches (A/B, bit-identical)."""
-        import os
         return (self.fused_tail and i == self.background_convs - 1 and self.chain_tail and self.lazy_heads and self.head_cout == 64
                 and nbr.shape[0] > self.background_convs and x is not None and x.shape[1] == 128
                 and x.dtype in (torch.bfloat16, torch.float16) and os.environ.get("SEC_RPN_FUSED_TAIL", "1") != "0")
@@ -1354,7 +1294,7 @@ class SecondDetector(nn.Module):
         pitch = {} if in_pitch is None else {"in_pitch": in_pitch}
         if self.pillars:
             mfe = self.middle_feature_extractor
-            if (dt in (torch.bfloat16, torch.float16) and isinstance(self.rpn, RPNInference) and self.rpn.use_hip and self.rpn.packed_x3 is None
+            if (dt in (torch.bfloat16, torch.float16) and isinstance(self.rpn, RPNInference) and self.rpn.use_hip and self.rpn.fp32 is None
                     and isinstance(mfe, PointPillarsScatter) and not torch.is_grad_enabled()):
                 # no canvas: the RPN's first conv gathers the pillar rows (PillarBEV.dense() is the scatter for the shapes it does not take)
                 return self.rpn(PillarBEV(voxel_features.to(dt), coors, batch_size, mfe.ny, mfe.nx, num_dev=num_active_dev))
@@ -1374,8 +1314,7 @@ class SecondDetector(nn.Module):
         """The RPN consumes the sparse middle's rows + site map (SparseBEV) instead of the dense image: the 16-bit gathered first conv, or
         the fp32 split-operand / fp32-MFMA convs on live tiles."""
         return getattr(self.rpn, "gather_packed", None) is not None or (
-            (getattr(self.rpn, "packed_x3", None) is not None or getattr(self.rpn, "packed_f32", None) is not None)
-            and getattr(self.rpn, "background_convs", 0) > 0)
+            getattr(self.rpn, "fp32", None) is not None and getattr(self.rpn, "background_convs", 0) > 0)
 
     def forward(self, example):
         voxels, num_points, coors = example["voxels"], example["num_points"], example["coordinates"]

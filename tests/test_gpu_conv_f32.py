@@ -115,7 +115,7 @@ def test_fp32_mfma_rpn_on_live_tiles_is_bit_identical_to_the_full_convolutions(b
     from second_amd.models import RPNInference, SparseBEV
     rpn, g = _bn_rpn(4, bias=True)
     inf = RPNInference(rpn.cuda(), torch.float32, backend="hip_f32")
-    assert inf.packed_f32 is not None and len(inf.packed_f32) == 6 and inf.chain_f32 is not None and inf.packed_x3 is None
+    assert inf.fp32 is not None and inf.fp32.name == "fp32" and len(inf.fp32_packed) == 6 and inf.fp32_chain is not None
     assert inf.background_convs == 6
     idx = _sites(batch, h, w, n, seed=h + n).cuda()
     feats = torch.randn(idx.shape[0], 64, generator=g).abs().cuda()
@@ -186,7 +186,7 @@ def test_fp32_mfma_rpn_inference_matches_the_torch_block():
     with torch.no_grad():
         want = rpn(x)
         inf = RPNInference(rpn, torch.float32, backend="hip_f32")
-        assert inf.packed_f32 is not None and len(inf.packed_f32) == 6 and inf.chain_f32 is not None
+        assert inf.fp32 is not None and inf.fp32.name == "fp32" and len(inf.fp32_packed) == 6 and inf.fp32_chain is not None
         got = inf(x.contiguous(memory_format=torch.channels_last))
     for k in ("box_preds", "cls_preds", "dir_cls_preds"):
         a, b = got[k].float().cpu().numpy(), want[k].float().cpu().numpy()
@@ -207,7 +207,7 @@ def test_head_tensors_of_the_exact_mode_on_the_fp32_mfma_rpn(setup):
     head: see DESIGN.md section 2; torch's fp32 convolutions give 2.6e-6 / 2.5e-6)."""
     state, feats, coors, ref = setup
     det = _detector(state, "hip")
-    assert det.arithmetic() == "fp32" and det.rpn.packed_f32 is not None
+    assert det.arithmetic() == "fp32" and det.rpn.fp32 is not None and det.rpn.fp32.name == "fp32"
     with torch.no_grad():
         got = {k: v.double().contiguous() for k, v in det.network_forward(feats, coors, 2).items()}
     bmax, brms = BOUNDS["fp32"]

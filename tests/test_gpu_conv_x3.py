@@ -92,7 +92,7 @@ def test_fp32_rpn_inference_on_split_convs_matches_the_torch_block():
     with torch.no_grad():
         want = rpn(x)
         inf = RPNInference(rpn, torch.float32)
-        assert inf.packed_x3 is not None and len(inf.packed_x3) == 6
+        assert inf.fp32 is not None and inf.fp32.name == "bf16x3" and len(inf.fp32_packed) == 6
         got = inf(x.contiguous(memory_format=torch.channels_last))
     for k in ("box_preds", "cls_preds", "dir_cls_preds"):
         a, b = got[k].float().cpu().numpy(), want[k].float().cpu().numpy()
@@ -129,7 +129,7 @@ def test_fp32_rpn_on_live_tiles_is_bit_identical_to_the_full_convolutions(batch,
             m.running_var.copy_(torch.empty_like(m.running_var).uniform_(0.5, 1.5, generator=g))
             m.bias.data.uniform_(-0.1, 0.3, generator=g)                   # a non-zero background and border imprint
     inf = RPNInference(rpn.cuda(), torch.float32)
-    assert inf.packed_x3 is not None and inf.background_convs == 6
+    assert inf.fp32 is not None and inf.fp32.name == "bf16x3" and inf.background_convs == 6
     idx = _sites(batch, h, w, n, seed=h + n).cuda()
     feats = torch.randn(idx.shape[0], 64, generator=g).abs().cuda()
     sp = spconv.SparseConvTensor(feats, idx, [2, h, w], batch)

@@ -371,12 +371,16 @@ def _tail_vs_two_launches(dtype, setenv):
     for k in outs["0"]:
         assert torch.equal(outs["1"][k], outs["0"][k]), k
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-def test_prepared_rpn_follows_a_state_dict_loaded_later(dtype):
-    """RPNInference keeps packed copies of its folded weights (MFMA slab order, gather permutation, hi | lo pairs of the fp32
-    form) and the empty frame's activations of the background tiles: load_state_dict into a PREPARED network re-packs them in
-    place -- the next forward is the other network's, bit for bit, including its background tiles."""
+@pytest.mark.parametrize("dtype,backend", [(torch.bfloat16, "hip"), (torch.float32, "hip"), (torch.float32, "hip_f32")],
+                         ids=["dtype0", "dtype1", "dtype1-hip_f32"])     # (the first two: the ids of the dtype-only parametrisation)
+def test_prepared_rpn_follows_a_state_dict_loaded_later(dtype, backend):
+    """RPNInference keeps packed copies of its folded weights (MFMA slab order, gather permutation, hi | lo pairs or fp32 images of
+    the fp32 forms) and the empty frame's activations of the background tiles: load_state_dict into a PREPARED network re-packs
+    them in place -- the next forward is the other network's, bit for bit, including its background tiles.  Every form is fed the
+    sparse rows, so that its live-tile convs read the empty frame's maps; the fp32 forms on a small ragged map (partial edge tiles in
+    both directions, an empty last frame)."""
     from second_amd.models import RPNV2, RPNInference, SparseBEV
+    from test_gpu_conv_x3 import _sites
     import spconv
 
     def make(seed):
@@ -388,19 +392,23 @@ def test_prepared_rpn_follows_a_state_dict_loaded_later(dtype):
                 m.running_mean.copy_(torch.empty_like(m.running_mean).uniform_(-0.3, 0.1, generator=g))
                 m.running_var.copy_(torch.empty_like(m.running_var).uniform_(0.5, 1.5, generator=g))
                 m.bias.data.uniform_(-0.1, 0.3, generator=g)               # a non-zero background
-        return RPNInference(rpn.cuda(), dtype)
+        return RPNInference(rpn.cuda(), dtype, backend=backend)
     a, b = make(1), make(2)
     g = torch.Generator().manual_seed(5)
     n = 600
     idx = torch.stack([torch.randint(0, 2, (n,), generator=g), torch.randint(0, 2, (n,), generator=g),
                        torch.randint(20, 90, (n,), generator=g), torch.randint(30, 120, (n,), generator=g)], 1).int()
-    idx = torch.unique(idx, dim=0).cuda()
+    idx, grid = torch.unique(idx, dim=0).cuda(), [2, 200, 176]
+    if dtype == torch.float32:
+        idx, grid = _sites(2, 37, 50, 12, seed=37 + 12).cuda(), [2, 37, 50]
     feats = torch.randn(idx.shape[0], 64, generator=g).abs().cuda().to(torch.bfloat16 if dtype != torch.float32 else torch.float32)
-    sp = spconv.SparseConvTensor(feats, idx, [2, 200, 176], 2)
+    sp = spconv.SparseConvTensor(feats, idx, grid, 2)
+    takes_rows = a.gather_packed is not None or (a.fp32 is not None and a.background_convs > 0)
+    assert takes_rows
 
     def run(net):
         with torch.no_grad():
-            x = SparseBEV(sp) if net.gather_packed is not None else sp.dense_channels_last_2d()
+            x = SparseBEV(sp) if takes_rows else sp.dense_channels_last_2d()
             return {k: v.float().clone() for k, v in net(x).items()}
     out_a, out_b = run(a), run(b)
     assert not torch.equal(out_a["cls_preds"], out_b["cls_preds"])
