@@ -668,6 +668,16 @@ int sec_predict_select_lazy(const void *cls, const int64_t *h_cls_strides5, int 
                             int h, int w, int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx,
                             float *top_score, int *top_label, int *counts, int dtype, const unsigned short *tile_live,
                             const void *cls_background, void *stream);
+/* The select with the anchor-area mask of sec_anchor_area_mask (KITTI PointPillars, voxelnet.py:397-439): frame b keeps the anchors
+ * with anchor_mask[b][n] != 0 ([batch, anchors_per_loc * h * w] bytes), everything after that is unchanged and indices stay indices
+ * into the full anchor list -- a masked-out anchor gets the smallest key, so it never reaches the score threshold, in the 32-bit,
+ * the 16-bit register and the chunked form alike.  tile_live / cls_background: both NULL (sec_predict_select) or both set
+ * (sec_predict_select_lazy), else SEC_E_INVALID; anchor_mask NULL: exactly those entry points.  A mask with score_thr <= 0 (no shipped
+ * config): SEC_E_UNSUPPORTED before anything is enqueued. */
+int sec_predict_select_masked(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc,
+                              int h, int w, int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                              float *top_score, int *top_label, int *counts, int dtype, const unsigned short *tile_live,
+                              const void *cls_background, const unsigned char *anchor_mask /* NULL = none */, void *stream);
 int sec_predict_decode_lazy(const void *box, const int64_t *h_box_strides5, const void *dir,
                             const int64_t *h_dir_strides5, int num_dir_bins, int batch, int anchors_per_loc,
                             int h, int w, int k, const float *anchors, const int *top_idx,
@@ -715,6 +725,34 @@ int sec_assign_targets_per_class_f32(const float *anchors, int n_anchor, const f
                                      const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
                                      const float *h_unmatched, int *labels, float *bbox_targets, float *importance,
                                      void *workspace, size_t workspace_bytes, void *stream);
+/* The same with create_target_np's prune_anchor_fn = where(anchors_mask) (target_assigner.py:63-64, 119-123; target_ops.py:71-81,
+ * 208-215): anchors with anchors_mask[b][n] == 0 ([batch, n_anchor] bytes) take part in neither the per-anchor argmax nor a ground
+ * truth's best overlap and come back as label -1, bbox_targets 0, importance 0 (the `unmap` fills); the other anchors behave as
+ * without a mask.  assign_per_class slices the mask by the class's anchor range.  anchors_mask NULL: the entry point above. */
+int sec_assign_targets_masked_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                  const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                                  const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                                  const float *h_unmatched, int *labels, float *bbox_targets, float *importance,
+                                  void *workspace, size_t workspace_bytes, const unsigned char *anchors_mask /* NULL = none */,
+                                  void *stream);
+/* ---------------------------------------------------------------------------------------------
+ * Anchor-area mask (`anchor_area_threshold` of the KITTI PointPillars configs; second/data/preprocess.py:345-357,
+ * box_np_ops.py:917-946): mask[b][n] = 1 when more than `threshold` voxels of frame b lie under anchor n's near box.
+ *   count map  D[y][x] = voxels of the frame in BEV cell (y, x); D = D.cumsum(0).cumsum(1)       (int32: exact, deterministic)
+ *   near box   rbbox2d_to_near_bbox(anchors[:, [0, 1, 3, 4, 6]])
+ *   cells      c0 = floor((x1 - offset[0]) / voxel_size[0]), c1 = floor((y1 - offset[1]) / voxel_size[1]), c2, c3 likewise from
+ *              (x2, y2) -- in FLOAT32, one subtraction and one division each (the mask flips on the rounding); clamped to the map
+ *   area       D[c3][c2] - D[c3][c0] - D[c1][c2] + D[c1][c0]: the row and the column of the min cell are excluded, as in the reference
+ * coords [rows, 4] int32 (b, z, y, x), 16-byte aligned; only rows below *num_dev count (num_dev NULL: rows_cap); rows whose b, y or x
+ * is out of range are skipped.  h_voxel_size2 / h_offset2 (host): (x, y) of the voxel size and of the point-cloud range's minimum.
+ * threshold >= 0; an empty frame's mask is all zero.  Everything is enqueued on the stream, nothing is read back (capturable).
+ * NULL mask / anchors / host arrays: SEC_E_INVALID; workspace below sec_anchor_area_mask_workspace_bytes: SEC_E_WORKSPACE.
+ * --------------------------------------------------------------------------------------------- */
+size_t sec_anchor_area_mask_workspace_bytes(int batch, int grid_y, int grid_x);
+int sec_anchor_area_mask(const int *coords, int rows_cap, const int *num_dev, int batch, int grid_y, int grid_x,
+                         const float *anchors, int n_anchor, const float *h_voxel_size2, const float *h_offset2,
+                         float threshold, unsigned char *mask /* [batch, n_anchor] */, void *workspace,
+                         size_t workspace_bytes, void *stream);
 size_t sec_second_loss_workspace_bytes(int batch, int n_anchor);
 int sec_second_loss_f32(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
                         const float *reg_targets, const float *anchors, const float *importance, int batch,

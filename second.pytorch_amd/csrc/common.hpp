@@ -198,6 +198,21 @@ int exclusive_scan_i32(const int *in, int *out, long long n, int *total_out, int
 // after some tens of replays; round 6: atomics that followed it accumulated onto the previous replay's values).
 int fill_words(void *p, size_t bytes, unsigned v, hipStream_t st);
 
+// ---------------------------------------------------------------- box helpers shared by train.hip and anchor_mask.hip (fp32, numpy order)
+__device__ __forceinline__ float limit_period_f(float v, float offset, float period) {
+    return __fsub_rn(v, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(v, period), offset)), period));
+}
+
+// rbbox2d_to_near_bbox of (x, y, w, l, r): the axis-aligned box of the nearer of the "standing" / "lying" orientation
+__device__ __forceinline__ float4 near_bbox(float x, float y, float w, float l, float r) {
+    const float kPi = 3.14159274101257324f;
+    const float a = fabsf(limit_period_f(r, 0.5f, kPi));
+    const bool swap = a > 0.785398185253143311f;      // np.pi / 4 in fp32
+    const float dx = swap ? l : w, dy = swap ? w : l;
+    return make_float4(__fsub_rn(x, __fdiv_rn(dx, 2.0f)), __fsub_rn(y, __fdiv_rn(dy, 2.0f)), __fadd_rn(x, __fdiv_rn(dx, 2.0f)),
+                       __fadd_rn(y, __fdiv_rn(dy, 2.0f)));
+}
+
 // voxelize.hip: hash table left in the workspace of sec_voxelize_f32 (see sec_rulebook_subm3d_after_voxelize)
 bool vox_slots_of(const void *ws, size_t bytes, int n, int batch, int max_voxels, int max_points, const int **count,
                   const int **slot_idx);

@@ -24,7 +24,11 @@ struct View5 {          // element strides of a [B, A, H, W, C] view
     long long bg;
     const unsigned short *live;
     int tiles_x, tpf;
+    // anchor-area mask (sec_predict_select_masked): amask[b * A*H*W + n] == 0 takes anchor n of frame b out of the selection -- its key
+    // is the smallest one (0: below every logit's, the key of the slots past a frame's end), whose score never reaches a threshold > 0
+    const unsigned char *amask;
 };
+__device__ __forceinline__ bool anchor_kept(const View5 &v, long long slot) { return !v.amask || v.amask[slot] != 0; }
 // element offset of frame b as seen from pixel (y, x): the frame itself, or the empty frame's map for a tile that was never written
 __device__ __forceinline__ long long frame_off(const View5 &v, int b, int y, int x) {
     if (v.live) {
@@ -85,6 +89,7 @@ __device__ __forceinline__ unsigned anchor_key(const T *cls, const View5 &v, con
         if (f > best) { best = f; lab = c; }
     }
     if (label) *label = lab;
+    if (!anchor_kept(v, (long long)b * g.A * g.H * g.W + n)) return 0u;
     return f2key(best);
 }
 
@@ -111,7 +116,8 @@ __global__ __launch_bounds__(kBlock) void k_predict_keys16(const T *__restrict__
     long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (t >= (long long)g.batch * ns) return;
     const int b = (int)(t / ns), n = (int)(t % ns);
-    keys[t] = n < N ? (unsigned short)key16_of<T>(key2f(anchor_key(cls, v, g, b, n, nullptr))) : (unsigned short)0;
+    const unsigned k32 = n < N ? anchor_key(cls, v, g, b, n, nullptr) : 0u;                  // 0: past the frame, or masked out
+    keys[t] = k32 ? (unsigned short)key16_of<T>(key2f(k32)) : (unsigned short)0;
 }
 
 // one workgroup per frame
@@ -590,7 +596,7 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
 #pragma unroll
     for (int i0 = 0; i0 < KP; i0 += PB) {
         long long off[2 * PB];
-        bool ok[2 * PB];
+        bool ok[2 * PB], keep[2 * PB];
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             const int a0 = base + n_base + (i0 + j) * 128;
@@ -602,6 +608,16 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
             off[2 * j + 1] = ok[2 * j + 1] ? frame_off(v, b, by, bx) + (long long)ba * v.sa + (long long)by * v.sy + (long long)bx * v.sx : 0;
             ax += 128;
             while (ax >= g.W) { ax -= g.W; if (++ay >= g.H) { ay = 0; ++aa; } }
+        }
+#pragma unroll
+        for (int j = 0; j < 2 * PB; ++j) keep[j] = ok[j];
+        if (v.amask) {                                                   // as anchor_key(): a masked-out anchor holds key 0 too
+            unsigned char m[2 * PB];
+#pragma unroll
+            for (int j = 0; j < 2 * PB; ++j)
+                m[j] = v.amask[ok[j] ? (long long)b * N + base + n_base + (i0 + j / 2) * 128 + (j & 1) : 0];
+#pragma unroll
+            for (int j = 0; j < 2 * PB; ++j) keep[j] = ok[j] && m[j] != 0;
         }
         float best[2 * PB];
 #pragma unroll
@@ -615,8 +631,8 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
         }
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
-            const unsigned ka = ok[2 * j] ? key16_of<T>(best[2 * j]) : 0u;
-            const unsigned kb = ok[2 * j + 1] ? key16_of<T>(best[2 * j + 1]) : 0u;
+            const unsigned ka = keep[2 * j] ? key16_of<T>(best[2 * j]) : 0u;
+            const unsigned kb = keep[2 * j + 1] ? key16_of<T>(best[2 * j + 1]) : 0u;
             k2[i0 + j] = ka | (kb << 16);
         }
     }
@@ -784,7 +800,7 @@ __global__ __launch_bounds__(kBlock) void k_predict_finalize(const float *__rest
 
 using namespace sec;
 
-static View5 mkview(const int64_t *s) { return View5{s[0], s[1], s[2], s[3], s[4], 0, nullptr, 0, 0}; }
+static View5 mkview(const int64_t *s) { return View5{s[0], s[1], s[2], s[3], s[4], 0, nullptr, 0, 0, nullptr}; }
 // the lazy form of a view: `base` is the view's pointer, `background` the same element of the empty frame's map
 static View5 mkview_lazy(const int64_t *s, const void *base, const void *background, const unsigned short *tile_live, int h, int w, int elt) {
     View5 v = mkview(s);
@@ -822,14 +838,17 @@ static unsigned conservative_thr16(float thr, int dtype) {
 static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                int *top_label, int *counts, int dtype, void *stream, const unsigned short *tile_live,
-                               const void *cls_background) {
+                               const void *cls_background, const unsigned char *anchor_mask) {
     if (!key_scratch) return SEC_E_WORKSPACE;
     if (!cls || !h_cls_strides5 || batch <= 0 || anchors_per_loc <= 0 || h <= 0 || w <= 0 || num_class <= 0 || k <= 0 ||
         k > kSelThreads || !top_idx || !top_score || !top_label || !counts)
         return SEC_E_INVALID;
     if ((tile_live != nullptr) != (cls_background != nullptr) || dtype < SEC_F32 || dtype > SEC_BF16) return SEC_E_INVALID;
+    // a masked-out anchor's key stands for no score; with a threshold <= 0 (no shipped config has one) it would be counted
+    if (anchor_mask && !(score_thr > 0.0f)) return SEC_E_UNSUPPORTED;
     PredGeom g{batch, anchors_per_loc, h, w, num_class};
     View5 v = mkview_lazy(h_cls_strides5, cls, cls_background, tile_live, h, w, elt_bytes(dtype));
+    v.amask = anchor_mask;
     hipStream_t st = (hipStream_t)stream;
     const long long total = (long long)batch * anchors_per_loc * h * w;
 #define SEC_SEL(T, K16)                                                                                                         \
@@ -921,7 +940,7 @@ SEC_API int sec_predict_select(const void *cls, const int64_t *h_cls_strides5, i
                                int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                int *top_label, int *counts, int dtype, void *stream) {
     return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, nullptr, nullptr);
+                               top_label, counts, dtype, stream, nullptr, nullptr, nullptr);
 }
 SEC_API int sec_predict_select_lazy(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                     int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
@@ -929,7 +948,17 @@ SEC_API int sec_predict_select_lazy(const void *cls, const int64_t *h_cls_stride
                                     void *stream) {
     if (!tile_live || !cls_background) return SEC_E_INVALID;
     return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, tile_live, cls_background);
+                               top_label, counts, dtype, stream, tile_live, cls_background, nullptr);
+}
+// sec_predict_select / _lazy with the anchor-area mask of sec_anchor_area_mask: frame b keeps the anchors with anchor_mask[b][n] != 0
+// (voxelnet.py:429-439 indexes the frame's head rows by the mask before the score threshold); indices stay indices into the full
+// anchor list.  tile_live / cls_background both NULL (eager heads) or both set (lazy heads); anchor_mask NULL: exactly those two.
+SEC_API int sec_predict_select_masked(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
+                                      int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
+                                      int *top_label, int *counts, int dtype, const unsigned short *tile_live, const void *cls_background,
+                                      const unsigned char *anchor_mask, void *stream) {
+    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
+                               top_label, counts, dtype, stream, tile_live, cls_background, anchor_mask);
 }
 
 static int predict_decode_impl(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,

@@ -18,19 +18,7 @@ namespace sec {
 
 constexpr int kMaxGtLds = 256;          // ground-truth boxes of one frame processed per LDS chunk
 
-__device__ __forceinline__ float limit_period_f(float v, float offset, float period) {
-    return __fsub_rn(v, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(v, period), offset)), period));
-}
-
-// rbbox2d_to_near_bbox of (x, y, w, l, r): the axis-aligned box of the nearer of the "standing" / "lying" orientation
-__device__ __forceinline__ float4 near_bbox(float x, float y, float w, float l, float r) {
-    const float kPi = 3.14159274101257324f;
-    const float a = fabsf(limit_period_f(r, 0.5f, kPi));
-    const bool swap = a > 0.785398185253143311f;      // np.pi / 4 in fp32
-    const float dx = swap ? l : w, dy = swap ? w : l;
-    return make_float4(__fsub_rn(x, __fdiv_rn(dx, 2.0f)), __fsub_rn(y, __fdiv_rn(dy, 2.0f)), __fadd_rn(x, __fdiv_rn(dx, 2.0f)),
-                       __fadd_rn(y, __fdiv_rn(dy, 2.0f)));
-}
+// limit_period_f() and near_bbox() (rbbox2d_to_near_bbox) live in common.hpp: anchor_mask.hip needs the same near box
 
 // iou_jit(boxes = anchor, query = gt, eps = 0)
 __device__ __forceinline__ float iou_eps0(const float4 a, const float4 q) {
@@ -55,13 +43,16 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
                                                       const float *__restrict__ gt, const int *__restrict__ gt_classes,
                                                       const int *__restrict__ gt_offsets, AssignRange R,
                                                       float *__restrict__ a_max, int *__restrict__ a_arg,
-                                                      int *__restrict__ gt_max_bits) {
+                                                      int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask) {
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ unsigned char s_on[kMaxGtLds];
     const int b = blockIdx.y, a = R.a_begin + blockIdx.x * kBlock + threadIdx.x;
     const int g0 = gt_offsets[b], g1 = gt_offsets[b + 1];
     const int n_total = n_anchor;            // row pitch of the per-(frame, anchor) arrays
     n_anchor = min(n_anchor, R.a_end);       // below: a < n_anchor == this launch owns the anchor
+    // prune_anchor_fn (target_ops.py:71-81): a masked-out anchor is not part of the matching at all -- neither its own argmax nor
+    // any ground truth's best overlap sees it
+    if (a < n_anchor && amask && !amask[(size_t)b * n_total + a]) n_anchor = 0;
     float4 abv = make_float4(0, 0, 0, 0);
     if (a < n_anchor) {
         const float *p = anchors + (size_t)a * 7;
@@ -101,7 +92,8 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
                                                         const float *__restrict__ a_max,
                                                         const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
                                                         float matched, float unmatched, int *__restrict__ labels,
-                                                        float *__restrict__ targets, float *__restrict__ importance) {
+                                                        float *__restrict__ targets, float *__restrict__ importance,
+                                                        const unsigned char *__restrict__ amask) {
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ float s_gmax[kMaxGtLds];
     __shared__ int s_any;
@@ -135,7 +127,9 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     int label = -1;
     float imp = 1.0f;
     float t[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (s_any) {
+    if (amask && !amask[o]) {                 // unmap() fills of a pruned anchor (target_ops.py:208-215): -1 / 0 / 0
+        imp = 0.0f;
+    } else if (s_any) {
         const float best = a_max[o];
         const int arg = a_arg[o];
         const bool pos = best >= matched;
@@ -674,19 +668,18 @@ SEC_API int sec_assign_targets_f32(const float *anchors, int n_anchor, const flo
     dim3 grid(div_up(n_anchor, kBlock), batch);
     const AssignRange all{0, n_anchor, 0};
     hipLaunchKernelGGL(k_assign_max, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, all, a_max,
-                       a_arg, gt_max);
+                       a_arg, gt_max, nullptr);
     hipLaunchKernelGGL(k_assign_write, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_importance,
                        gt_offsets, all, a_max, a_arg, gt_max, matched_threshold, unmatched_threshold, labels, bbox_targets,
-                       importance);
+                       importance, nullptr);
     return check_launch();
 }
 
-SEC_API int sec_assign_targets_per_class_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
-                                             const float *gt_importance, const int *gt_offsets, int n_gt, int batch,
-                                             int n_class, const int *h_class_anchor_begin, const int *h_class_ids,
-                                             const float *h_matched, const float *h_unmatched, int *labels,
-                                             float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
-                                             void *stream) {
+static int assign_targets_ranges(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                 const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                                 const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                                 const float *h_unmatched, int *labels, float *bbox_targets, float *importance, void *workspace,
+                                 size_t workspace_bytes, void *stream, const unsigned char *anchors_mask) {
     if (n_anchor <= 0 || batch <= 0 || n_gt < 0 || n_class <= 0 || !anchors || !gt_offsets || !labels || !bbox_targets ||
         !importance || !h_class_anchor_begin || !h_class_ids || !h_matched || !h_unmatched || (n_gt > 0 && (!gt_boxes || !gt_classes)))
         return SEC_E_INVALID;
@@ -711,13 +704,38 @@ SEC_API int sec_assign_targets_per_class_f32(const float *anchors, int n_anchor,
             dim3 grid(div_up(R.a_end - R.a_begin, kBlock), batch);
             if (pass == 0)
                 hipLaunchKernelGGL(k_assign_max, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, R,
-                                   a_max, a_arg, gt_max);
+                                   a_max, a_arg, gt_max, anchors_mask);
             else
                 hipLaunchKernelGGL(k_assign_write, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes,
                                    gt_importance, gt_offsets, R, a_max, a_arg, gt_max, h_matched[c], h_unmatched[c], labels,
-                                   bbox_targets, importance);
+                                   bbox_targets, importance, anchors_mask);
         }
     return check_launch();
+}
+
+SEC_API int sec_assign_targets_per_class_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                             const float *gt_importance, const int *gt_offsets, int n_gt, int batch,
+                                             int n_class, const int *h_class_anchor_begin, const int *h_class_ids,
+                                             const float *h_matched, const float *h_unmatched, int *labels,
+                                             float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
+                                             void *stream) {
+    return assign_targets_ranges(anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, n_gt, batch, n_class,
+                                 h_class_anchor_begin, h_class_ids, h_matched, h_unmatched, labels, bbox_targets, importance, workspace,
+                                 workspace_bytes, stream, nullptr);
+}
+
+// create_target_np with prune_anchor_fn = where(anchors_mask) (target_assigner.py:63-64, 119-123): anchors with anchors_mask[b][n] == 0
+// take part in neither the per-anchor argmax nor a ground truth's best overlap and come back as label -1, targets 0, importance 0;
+// assign_per_class slices the mask by the class's anchor range (the ranges index the same [batch, n_anchor] array).  NULL mask:
+// sec_assign_targets_per_class_f32.  One range with class id 0 and the two thresholds is sec_assign_targets_f32 with a mask.
+SEC_API int sec_assign_targets_masked_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                          const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                                          const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                                          const float *h_unmatched, int *labels, float *bbox_targets, float *importance,
+                                          void *workspace, size_t workspace_bytes, const unsigned char *anchors_mask, void *stream) {
+    return assign_targets_ranges(anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, n_gt, batch, n_class,
+                                 h_class_anchor_begin, h_class_ids, h_matched, h_unmatched, labels, bbox_targets, importance, workspace,
+                                 workspace_bytes, stream, anchors_mask);
 }
 
 SEC_API size_t sec_second_loss_workspace_bytes(int batch, int n_anchor) {

@@ -24,8 +24,12 @@ strided layer, three modules per layer, the dense [B, 128, 200, 176] image and p
     ``fp32_exact=True`` computes IEEE fp32 products (sparse convs on the fp32 MFMA, RPN on torch's fp32 convolutions or, with
     SEC_FP32_RPN=hip, on the fp32-MFMA kernels);
   * training mode: opt-in (``train_dtype``), served by :mod:`second_amd.dropin_train`; otherwise the original forward;
-  * DataParallel-padded examples (``num_points`` 2-D, voxelnet.py:346), ``anchors_mask`` and per-frame anchor
-    sets keep the original forward.
+  * examples that carry ``anchors_mask`` (the KITTI PointPillars configs: ``anchor_area_threshold: 1``, preprocess.py:345-357) are
+    served: the example's uint8 / bool mask is copied into a static [B, A] buffer of the session and the captured select drops the
+    masked-out anchors before the score threshold (voxelnet.py:397-439; sec_predict_select_masked) -- the mask is taken from the
+    example, not recomputed;
+  * DataParallel-padded examples (``num_points`` 2-D, voxelnet.py:346), a mask whose shape is not [B, A] (or that is not on the
+    GPU) and per-frame anchor sets keep the original forward.
 
 There is no CPU fallback inside the fused path: static capacities and graphs need the HIP library; a CPU network is served
 in the dynamic-shape eager mode only when a test installs the oracle backend.
@@ -234,9 +238,11 @@ class DeferredDetection(dict):
 class _Session:
     """Static buffers + captured graph for one (batch size, row capacity, voxel tensor layout)."""
 
-    def __init__(self, eng, batch, cap, vox_shape, vox_dtype, anchors0):
+    def __init__(self, eng, batch, cap, vox_shape, vox_dtype, anchors0, has_mask=False):
         self.eng, self.batch, self.cap = eng, batch, cap
         dev = anchors0.device
+        # the example's anchors_mask [B, A] (uint8; a bool mask is converted by the copy): read by the captured select
+        self.mask = torch.ones((batch, anchors0.shape[0]), dtype=torch.uint8, device=dev) if has_mask else None
         self.voxels = torch.zeros((cap,) + tuple(vox_shape), dtype=vox_dtype, device=dev)
         self.num_points = torch.ones((cap,), dtype=torch.int32, device=dev)      # rows past the live count: 0 / 1, never 0 / 0
         self.coors = torch.zeros((cap, 4), dtype=torch.int32, device=dev)
@@ -299,7 +305,7 @@ class _Session:
                     feats = feats.to(dt)
         with det.lazy_heads():          # the head tensor's background tiles stay unwritten: predict_device reads them from the empty frame's map
             preds = det.network_forward(feats, self.coors, b, num_active_dev=self.n_dev, in_pitch=pitch)
-        out = det.predict_device(preds, b, self.anchors)
+        out = det.predict_device(preds, b, self.anchors, anchors_mask=self.mask)
         checks = list(getattr(det.middle_feature_extractor, "last_overflow_checks", [])) if not det.pillars else []
         packed = torch.cat([out["boxes"].reshape(b, -1).float(), out["scores"].float(), out["labels"].float(),
                             out["valid"].float()], 1)
@@ -464,7 +470,20 @@ class FusedVoxelNet:
         for k in ("voxels", "num_points", "coordinates", "anchors"):
             if not isinstance(example.get(k), torch.Tensor):
                 return False
-        return example["num_points"].dim() == 1 and "anchors_mask" not in example and example["voxels"].shape[0] > 0
+        return example["num_points"].dim() == 1 and self._mask_ok(example) and example["voxels"].shape[0] > 0
+
+    def _mask_ok(self, example):
+        """No ``anchors_mask``, or one the fused select takes: a bool / uint8 CUDA tensor of [B, A] entries beside the anchors (the
+        masked select is a device kernel; the CPU mode of the tests' oracle backend keeps refusing masks) and a score threshold
+        above 0 (a masked-out anchor must not pass it).  Anything else keeps the original forward."""
+        if "anchors_mask" not in example:
+            return True
+        m, anc = example["anchors_mask"], example["anchors"]
+        if not isinstance(m, torch.Tensor) or m.dtype not in (torch.bool, torch.uint8) or not m.is_cuda or m.device != anc.device or anc.dim() < 2:
+            return False
+        batch = anc.shape[0]
+        n_anchor = anc.numel() // (batch * 7) if batch else 0
+        return m.dim() >= 2 and m.shape[0] == batch and m.numel() == batch * n_anchor and self.cfg["nms_score_threshold"] > 0
 
     def _accepts_training(self, example):
         if self.train_dtype is None or self.trainer is False:
@@ -521,7 +540,8 @@ class FusedVoxelNet:
             else:
                 feats = det.voxel_feature_extractor(voxels.float(), example["num_points"], example["coordinates"])
             preds = det.network_forward(feats, example["coordinates"], batch, in_pitch=pitch)
-            out = det.predict_device(preds, batch, anchors)
+            mask = example.get("anchors_mask")
+            out = det.predict_device(preds, batch, anchors, anchors_mask=None if mask is None else mask.reshape(batch, -1))
         self.stats["fused_calls"] += 1
         res = []
         for b, meta in zip(range(batch), self._meta(example, batch)):
@@ -534,12 +554,13 @@ class FusedVoxelNet:
         voxels = example["voxels"]
         n = voxels.shape[0]
         anchors0 = example["anchors"].reshape(batch, -1, 7)[0]
-        key = (batch, tuple(voxels.shape[1:]), voxels.dtype, voxels.device, int(anchors0.shape[0]), lane)
+        has_mask = "anchors_mask" in example
+        key = (batch, tuple(voxels.shape[1:]), voxels.dtype, voxels.device, int(anchors0.shape[0]), lane, has_mask)
         sess = self._sessions.get(key)
         if sess is not None and sess.cap >= n:
             return sess
         cap = -(-int(n * (1.0 if sess is None else self.margin)) // self.row_bucket) * self.row_bucket
-        new = _Session(self, batch, cap, voxels.shape[1:], voxels.dtype, anchors0)
+        new = _Session(self, batch, cap, voxels.shape[1:], voxels.dtype, anchors0, has_mask)
         new.caps = self._calibrate(det, example, batch)
         self._fill(new, example)
         new.build(self.graph)
@@ -581,6 +602,8 @@ class FusedVoxelNet:
         if anc.dtype != torch.float32 or not anc.is_contiguous():
             anc = anc.float().contiguous()
         ops.rows_differ_(sess.anchor_flag, anc, sess.anchors)
+        if sess.mask is not None:
+            sess.mask.copy_(example["anchors_mask"].reshape(sess.mask.shape), non_blocking=True)
 
     def _static(self, det, example):
         batch = example["anchors"].shape[0]

@@ -337,7 +337,9 @@ class FusedTrainStep:
             v = example.get(k)
             if not isinstance(v, torch.Tensor) or not v.is_cuda:
                 return False
-        return (example["num_points"].dim() == 1 and "anchors_mask" not in example and example["voxels"].shape[0] > 0
+        # (an ``anchors_mask`` in the example is fine: VoxelNet.loss never reads it -- it only appears in predict, voxelnet.py:397-439 --
+        # and the example's ``labels`` already carry its effect, -1 for the pruned anchors, target_ops.py:208-215)
+        return (example["num_points"].dim() == 1 and example["voxels"].shape[0] > 0
                 and example["labels"].dim() == 2 and torch.is_grad_enabled())
 
     def _calibrate(self, det, example, batch):

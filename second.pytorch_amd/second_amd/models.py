@@ -146,6 +146,32 @@ ALL_FHD_KITTI = dict(
 )  # second/configs/all.fhd.config (KITTI, four classes, two-block RPN, 160 x 132 feature map)
 
 
+KITTI_PP_CAR_16 = dict(
+    name="pointpillars/car/xyres_16",
+    point_cloud_range=[0, -39.68, -3, 69.12, 39.68, 1], voxel_size=[0.16, 0.16, 4], max_points_per_voxel=100,
+    max_voxels=12000, num_point_features=4,
+    vfe="PillarFeatureNet", vfe_filters=[64], middle="PointPillarsScatter", middle_in=64,
+    rpn=dict(layer_nums=[3, 5, 5], layer_strides=[2, 2, 2], num_filters=[64, 128, 256],
+             upsample_strides=[1, 2, 4], num_upsample_filters=[128, 128, 128], num_input_features=64),
+    downsample_factor=2,
+    # anchor_generator_stride: centres = index * stride + offset in fp32 (box_np_ops.create_anchors_3d_stride), not a linspace over a range
+    anchor_sizes=[[1.6, 3.9, 1.56]], anchor_strides=[[0.32, 0.32, 0.0]], anchor_offsets=[[0.16, -39.52, -1.78]], rotations=[0, 1.57],
+    matched_thresholds=[0.6], unmatched_thresholds=[0.45], assign_per_class=True,
+    num_class=1, num_direction_bins=2, direction_offset=0.0, direction_limit_offset=1.0,
+    nms_score_threshold=0.05, nms_pre_max_size=1000, nms_post_max_size=300, nms_iou_threshold=0.5,
+    use_rotate_nms=False, post_center_range=[0, -39.68, -5, 69.12, 39.68, 5],
+    # both input readers set it: anchors over (nearly) empty ground are dropped before the score threshold of predict and pruned from
+    # the target assignment (preprocess.py:345-357).  Absent or negative = no mask (every other config)
+    anchor_area_threshold=1,
+)  # second/configs/pointpillars/car/xyres_16.config (432 x 496 pillars, 216 x 248 feature map)
+
+
+def anchor_area_threshold_of(cfg):
+    """The config's ``anchor_area_threshold`` when it asks for the anchor-area mask (>= 0), else None."""
+    thr = cfg.get("anchor_area_threshold", -1)
+    return float(thr) if thr is not None and thr >= 0 else None
+
+
 def anchors_per_location(cfg):
     """target_assigner.num_anchors_per_location (target_assigner.py:249-254): sum over generators of sizes x rotations."""
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
@@ -176,10 +202,17 @@ def generate_anchors(cfg, feature_map_size):
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
     for gi, grp in enumerate(groups):   # one anchor generator: (size, rotation) major, then z, y, x
         rots = np.array(cfg.get("group_rotations", {}).get(gi, cfg["rotations"]), np.float32)
-        rng = np.array(cfg["anchor_ranges"][grp[0]], np.float32)
-        zc = np.linspace(rng[2], rng[5], d, dtype=np.float32)
-        yc = np.linspace(rng[1], rng[4], h, dtype=np.float32)
-        xc = np.linspace(rng[0], rng[3], w, dtype=np.float32)
+        if cfg.get("anchor_strides"):      # anchor_generator_stride (box_np_ops.create_anchors_3d_stride :561-604): fp32 index * stride + offset
+            sx, sy, sz_ = cfg["anchor_strides"][grp[0]]
+            ox, oy, oz = cfg["anchor_offsets"][grp[0]]
+            zc = np.arange(d, dtype=np.float32) * sz_ + oz
+            yc = np.arange(h, dtype=np.float32) * sy + oy
+            xc = np.arange(w, dtype=np.float32) * sx + ox
+        else:
+            rng = np.array(cfg["anchor_ranges"][grp[0]], np.float32)
+            zc = np.linspace(rng[2], rng[5], d, dtype=np.float32)
+            yc = np.linspace(rng[1], rng[4], h, dtype=np.float32)
+            xc = np.linspace(rng[0], rng[3], w, dtype=np.float32)
         a = np.zeros((len(grp), len(rots), d, h, w, 7), np.float32)
         a[..., 0] = xc[None, None, None, None, :]
         a[..., 1] = yc[None, None, None, :, None]
@@ -1327,7 +1360,7 @@ class SecondDetector(nn.Module):
                 feats = self.voxel_feature_extractor(voxels, num_points, coors)
         preds = self.network_forward(feats, coors, batch_size, in_pitch=pitch)
         with torch.no_grad():
-            return self.predict(preds, example["anchors"].view(batch_size, -1, 7))
+            return self.predict(preds, example["anchors"].view(batch_size, -1, 7), example.get("anchors_mask"))
 
     def forward_points(self, points, point_offsets, static=False):
         """points [N,4] cuda float32 (clouds concatenated), point_offsets [B+1] cuda int32.
@@ -1386,18 +1419,32 @@ class SecondDetector(nn.Module):
                 feats = self.voxel_feature_extractor(vox["voxels"], vox["num_points_per_voxel"], vox["coordinates"],
                                                      out_dtype=self._infer_dtype, num_dev=nd)
             preds = self.network_forward(feats, vox["coordinates"], batch_size, num_active_dev=nd)
-            return self.predict_device(preds, batch_size)
+            return self.predict_device(preds, batch_size, anchors_mask=self.anchor_area_mask(vox["coordinates"], batch_size, nd))
         # SimpleVoxelRadius: rows [r, z, w, 0] from the voxeliser's epilogue, declared to the middle as pitch-4 rows
         enc, pitch = ({}, {}) if self.encoder == "SimpleVoxel" else ({"encoder": self.encoder}, {"in_pitch": SimpleVoxelRadius.ROW_PITCH})
         if not static:
             vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, mean_dtype=self._infer_dtype, **enc)
             preds = self.network_forward(vox["mean"], vox["coordinates"], batch_size, site_table=vox.get("site_table"), **pitch)
+            nd = None
         else:
             # (the voxel means are stored in the sparse stack's dtype by the voxeliser itself: no cast launch inside the captured step)
             vox = self.voxel_generator.generate_device(points, point_offsets, mean_features=nf, sync=False, mean_dtype=self._infer_dtype, **enc)
+            nd = vox["voxel_offsets"][batch_size:]
             preds = self.network_forward(vox["mean"], vox["coordinates"], batch_size,
-                                         num_active_dev=vox["voxel_offsets"][batch_size:], site_table=vox.get("site_table"), **pitch)
-        return self.predict_device(preds, batch_size)
+                                         num_active_dev=nd, site_table=vox.get("site_table"), **pitch)
+        return self.predict_device(preds, batch_size, anchors_mask=self.anchor_area_mask(vox["coordinates"], batch_size, nd))
+
+    def anchor_area_mask(self, coors, batch_size, num_dev=None):
+        """The config's anchor-area mask [B, A] uint8 from voxel coordinates [rows, 4] (b, z, y, x) -- what prep_pointcloud puts into the
+        example as ``anchors_mask`` (preprocess.py:345-357) -- on the caller's stream (part of a captured forward_points); None when
+        the config asks for none.  Kept as ``last_anchors_mask``."""
+        thr = anchor_area_threshold_of(self.cfg)
+        if thr is None:
+            return None
+        vs, rng = self.voxel_generator.voxel_size, self.voxel_generator.point_cloud_range       # float32, as the reference's generator keeps them
+        gs = self.grid_size
+        self.last_anchors_mask = ops.anchor_area_mask(coors, num_dev, batch_size, (int(gs[1]), int(gs[0])), self.anchors, vs[:2], rng[:2], thr)
+        return self.last_anchors_mask
 
     def calibrate(self, points, point_offsets, margin=1.25):
         """Size the static-capacity buffers of the strided layers from one eager forward of representative
@@ -1531,8 +1578,9 @@ class SecondDetector(nn.Module):
         return (ga.replay, gb.replay, gc.replay), out
 
     # -- post-processing -----------------------------------------------------------------------------
-    def _select(self, preds, batch_size, anchors):
-        """score filter + top-k + decode of the selected boxes, all on device, fixed shapes."""
+    def _select(self, preds, batch_size, anchors, anchors_mask=None):
+        """score filter + top-k + decode of the selected boxes, all on device, fixed shapes.  ``anchors_mask`` [B, A]: anchors with a zero
+        entry are dropped before the score threshold (voxelnet.py:429-439)."""
         cfg = self.cfg
         nc = cfg["num_class"]
         box = preds["box_preds"].reshape(batch_size, -1, 7)
@@ -1542,7 +1590,10 @@ class SecondDetector(nn.Module):
         else:   # class-agnostic selection: best class per anchor (voxelnet.py:545-553)
             scores, labels = torch.sigmoid(preds["cls_preds"].reshape(batch_size, -1, nc).float()).max(-1)
         k = min(cfg["nms_pre_max_size"], scores.shape[1])
-        masked = torch.where(scores >= cfg["nms_score_threshold"], scores, torch.full_like(scores, -1.0))
+        passing = scores >= cfg["nms_score_threshold"]
+        if anchors_mask is not None:
+            passing = passing & (anchors_mask.reshape(batch_size, -1) != 0)
+        masked = torch.where(passing, scores, torch.full_like(scores, -1.0))
         top_scores, top_idx = torch.topk(masked, k, dim=1)
         counts = (top_scores >= cfg["nms_score_threshold"]).sum(1).to(torch.int32)
         enc = torch.gather(box, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7)).float()
@@ -1557,15 +1608,16 @@ class SecondDetector(nn.Module):
         top_labels = torch.gather(labels, 1, top_idx) if labels is not None else torch.zeros_like(top_idx)
         return dec, top_scores, counts, dir_labels, top_labels
 
-    def predict_device(self, preds, batch_size, anchors=None):
-        """-> dict of padded device tensors: boxes [B,P,7], scores [B,P], labels [B,P], valid [B,P] (bool)."""
+    def predict_device(self, preds, batch_size, anchors=None, anchors_mask=None):
+        """-> dict of padded device tensors: boxes [B,P,7], scores [B,P], labels [B,P], valid [B,P] (bool).
+        ``anchors_mask`` [B, A] bool / uint8 (the example's, or :meth:`anchor_area_mask`): frame b keeps the anchors with a non-zero entry."""
         cfg = self.cfg
         anchors = self.anchors if anchors is None else anchors
         if preds["cls_preds"].is_cuda and self.fused_predict and cfg["nms_pre_max_size"] <= 1024:
             # (sec_predict_select ranks up to 1024 candidates per frame; larger nms_pre_max_size takes the torch.topk path
             # below, which honours it -- never a silent truncation)
-            return self._predict_fused(preds, batch_size, anchors)
-        dec, top_scores, counts, dir_labels, top_labels = self._select(preds, batch_size, anchors)
+            return self._predict_fused(preds, batch_size, anchors, anchors_mask)
+        dec, top_scores, counts, dir_labels, top_labels = self._select(preds, batch_size, anchors, anchors_mask)
         if cfg["use_rotate_nms"]:
             # (x, y, w, l, r, score): boxes_for_nms = box[:, [0, 1, 3, 4, 6]] (voxelnet.py:570); slices, not index
             # lists, so that nothing is staged from the host (hipGraph capture)
@@ -1595,7 +1647,7 @@ class SecondDetector(nn.Module):
         valid = valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
         return {"boxes": boxes, "scores": scores, "labels": torch.gather(top_labels, 1, sel), "valid": valid}
 
-    def _predict_fused(self, preds, batch_size, anchors):
+    def _predict_fused(self, preds, batch_size, anchors, anchors_mask=None):
         """select -> decode -> NMS -> finalize: five launches, no host sync, no torch glue."""
         cfg = self.cfg
         a_per_loc = self.num_anchor_per_loc
@@ -1617,7 +1669,8 @@ class SecondDetector(nn.Module):
             bg = lz[1]
             lz_cls = (lz[0], view5(bg["cls_preds"], cfg["num_class"]))
             lz_box = (lz[0], (view5(bg["box_preds"], 7), view5(bg["dir_cls_preds"], cfg["num_direction_bins"]) if dirp is not None else None))
-        top_idx, top_score, top_label, counts = ops.predict_select(cls, cfg["nms_pre_max_size"], cfg["nms_score_threshold"], lazy=lz_cls)
+        top_idx, top_score, top_label, counts = ops.predict_select(cls, cfg["nms_pre_max_size"], cfg["nms_score_threshold"], lazy=lz_cls,
+                                                                  anchor_mask=None if anchors_mask is None else anchors_mask.reshape(batch_size, -1))
         dec, dets, dlab = ops.predict_decode(box, dirp, anchors, top_idx, top_score, rotate=cfg["use_rotate_nms"], lazy=lz_box)
         if cfg["use_rotate_nms"]:
             keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], "rotate", "cpu", post_max=cfg["nms_post_max_size"])
@@ -1628,8 +1681,8 @@ class SecondDetector(nn.Module):
                                     dirp is not None, cfg["direction_offset"], cfg["direction_limit_offset"],
                                     cfg["num_direction_bins"], self.post_center_range)
 
-    def predict(self, preds, anchors):
-        out = self.predict_device(preds, anchors.shape[0], anchors)
+    def predict(self, preds, anchors, anchors_mask=None):
+        out = self.predict_device(preds, anchors.shape[0], anchors, anchors_mask)
         res = []
         for b in range(anchors.shape[0]):
             m = out["valid"][b]

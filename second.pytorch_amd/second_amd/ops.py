@@ -1385,13 +1385,50 @@ def _lazy_args(view, lazy, pick):
     return tile_live, bgv
 
 
+def _mask_u8(mask, shape, dev, what):
+    """A bool or uint8 mask as the contiguous uint8 tensor the kernels read (bool is reinterpreted, not converted)."""
+    rt.require_gpu(mask)
+    assert mask.dtype in (torch.bool, torch.uint8), f"{what}: a bool or uint8 tensor"
+    assert tuple(mask.shape) == tuple(shape) and mask.device == dev, f"{what}: shape {tuple(shape)} on the heads' / anchors' device"
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+@_traced("anchor_area_mask")
+def anchor_area_mask(coords, num_dev, batch, grid_yx, anchors, voxel_size_xy, offset_xy, threshold, out=None):
+    """The reference's ``anchors_mask`` (second/data/preprocess.py:345-357) for a whole batch on the device: mask[b, n] = more than
+    ``threshold`` voxels of frame b lie under the near box of anchor n (float32 cell arithmetic of box_np_ops.fused_get_anchors_area).
+    coords [rows, 4] int32 (b, z, y, x); only rows below ``num_dev`` (int32 device scalar, or None = all rows) count.  grid_yx =
+    (ny, nx); voxel_size_xy / offset_xy = (x, y) of the voxel size and of the point-cloud range's minimum (rounded to float32 as
+    the voxel generator keeps them).  -> uint8 [batch, A]."""
+    rt.require_gpu(coords, anchors)
+    assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.shape[1] == 4 and coords.is_contiguous()
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.dim() == 2 and anchors.shape[1] == 7
+    if num_dev is not None:
+        rt.require_gpu(num_dev)
+        assert num_dev.dtype == torch.int32 and num_dev.numel() == 1
+    gy, gx = int(grid_yx[0]), int(grid_yx[1])
+    a, dev = anchors.shape[0], anchors.device
+    if out is None:
+        out = torch.empty((int(batch), a), dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (int(batch), a) and out.is_contiguous()
+    l = rt.lib()
+    ws = rt.workspace(l.sec_anchor_area_mask_workspace_bytes(int(batch), gy, gx), dev)
+    rc = l.sec_anchor_area_mask(rt.ptr(coords) if coords.shape[0] else None, int(coords.shape[0]), rt.ptr(num_dev), int(batch), gy, gx,
+                                rt.ptr(anchors), a, rt.f_arr([float(v) for v in voxel_size_xy]), rt.f_arr([float(v) for v in offset_xy]),
+                                float(threshold), rt.ptr(out), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, "sec_anchor_area_mask")
+    return out
+
+
 @_traced("predict_select")
-def predict_select(cls, k, score_thr, lazy=None):
+def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     """cls: [B, A, H, W, num_class] view (any strides).  -> (top_idx [B,k] int32 anchor ids sorted by descending
     score, top_score [B,k] sigmoid scores, top_label [B,k], counts [B] = entries with score >= score_thr).  The selection is
     rows [0, counts[b]) of frame b (the reference masks by the threshold before its topk); rows behind them are unspecified.
     ``lazy`` = (tile_live [B, tiles] int16 with bit 4 = "tile written", bg = the empty frame's view [1, A, H, W, num_class] with the
-    strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg`` (sec_predict_select_lazy)."""
+    strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg`` (sec_predict_select_lazy).
+    ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry (sec_predict_select_masked)."""
     rt.require_gpu(cls)
     b, a, h, w, nc = cls.shape
     k = min(int(k), a * h * w, 1024)
@@ -1401,6 +1438,14 @@ def predict_select(cls, k, score_thr, lazy=None):
     top_label = torch.empty((b, k), dtype=torch.int32, device=dev)
     counts = torch.empty((b,), dtype=torch.int32, device=dev)
     keys = torch.empty((b * a * h * w,), dtype=torch.int32, device=dev)
+    if anchor_mask is not None:
+        anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), dev, "anchor_mask")
+        tile_live, bgv = _lazy_args(cls, lazy, lambda t: t) if lazy is not None else (None, None)
+        rc = rt.lib().sec_predict_select_masked(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
+                                                rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype),
+                                                rt.ptr(tile_live), rt.ptr(bgv), rt.ptr(anchor_mask), rt.stream())
+        rt.check(rc, "sec_predict_select_masked")
+        return top_idx, top_score, top_label, counts
     if lazy is not None:
         tile_live, bgv = _lazy_args(cls, lazy, lambda t: t)
         rc = rt.lib().sec_predict_select_lazy(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
@@ -1471,10 +1516,12 @@ def predict_finalize(dec, top_score, top_label, dir_label, keep, num_keep, post_
 # ----------------------------------------------------------------------------- training: targets + loss
 @_traced("assign_targets")
 def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_threshold, gt_classes=None,
-                   gt_importance=None):
+                   gt_importance=None, anchors_mask=None):
     """TargetAssigner.assign -> create_target_np (second/core/target_ops.py:29-229) with NearestIouSimilarity and
     GroundBox3dCoder.encode, for a whole batch on the device.  anchors [A,7] fp32; gt_boxes [G,7] fp32 (frames concatenated),
-    gt_offsets [B+1] int32.  -> labels [B,A] int32, bbox_targets [B,A,7] fp32, importance [B,A] fp32."""
+    gt_offsets [B+1] int32.  -> labels [B,A] int32, bbox_targets [B,A,7] fp32, importance [B,A] fp32.
+    ``anchors_mask`` [B, A] bool / uint8 = create_target_np's prune_anchor_fn (where(mask)): anchors with a zero entry are left out of
+    the matching and come back as label -1, targets 0, importance 0."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
     assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
     assert gt_offsets.dtype == torch.int32
@@ -1495,6 +1542,17 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
     importance = torch.empty((b, a), dtype=torch.float32, device=dev)
     l = rt.lib()
     ws = rt.workspace(l.sec_assign_targets_workspace_bytes(b, a, g), dev)
+    if anchors_mask is not None:            # one range, class id 0 = every ground truth: sec_assign_targets_f32 with the mask
+        anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
+        if gt_classes is None:
+            gt_classes = torch.ones((g,), dtype=torch.int32, device=dev)
+        rc = l.sec_assign_targets_masked_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes), rt.ptr(gt_importance),
+                                             rt.ptr(gt_offsets), g, b, 1, (ctypes.c_int * 2)(0, a), (ctypes.c_int * 1)(0),
+                                             (ctypes.c_float * 1)(float(matched_threshold)), (ctypes.c_float * 1)(float(unmatched_threshold)),
+                                             rt.ptr(labels), rt.ptr(targets), rt.ptr(importance), rt.ptr(ws), ws.numel(),
+                                             rt.ptr(anchors_mask), rt.stream())
+        rt.check(rc, "sec_assign_targets_masked_f32")
+        return labels, targets, importance
     rc = l.sec_assign_targets_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes), rt.ptr(gt_importance),
                                   rt.ptr(gt_offsets), g, b, float(matched_threshold), float(unmatched_threshold), rt.ptr(labels),
                                   rt.ptr(targets), rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.stream())
@@ -1504,11 +1562,11 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
 
 @_traced("assign_targets_per_class")
 def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_anchor_begin, class_ids, matched_thresholds,
-                             unmatched_thresholds, gt_importance=None):
+                             unmatched_thresholds, gt_importance=None, anchors_mask=None):
     """TargetAssigner.assign for multi-class configs, a whole batch on the device.  Range c of the class-major anchor array =
     anchors[class_anchor_begin[c]:class_anchor_begin[c+1]] with its own thresholds; class_ids[c] = k > 0: assign_per_class
     (target_assigner.py:90-160, only ground truth of class k); class_ids[c] = 0: assign_all with per-anchor thresholds
-    (target_assigner.py:53-88).  Same outputs as assign_targets."""
+    (target_assigner.py:53-88).  Same outputs as assign_targets; ``anchors_mask`` [B, A] as there (each range sees its slice)."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
     assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
     assert gt_offsets.dtype == torch.int32
@@ -1527,6 +1585,13 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     ids = (ctypes.c_int * n)(*[int(v) for v in class_ids])
     mt = (ctypes.c_float * n)(*[float(v) for v in matched_thresholds])
     ut = (ctypes.c_float * n)(*[float(v) for v in unmatched_thresholds])
+    if anchors_mask is not None:
+        anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
+        rc = l.sec_assign_targets_masked_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes),
+                                             rt.ptr(gt_importance), rt.ptr(gt_offsets), g, b, n, begin, ids, mt, ut, rt.ptr(labels),
+                                             rt.ptr(targets), rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.ptr(anchors_mask), rt.stream())
+        rt.check(rc, "sec_assign_targets_masked_f32")
+        return labels, targets, importance
     rc = l.sec_assign_targets_per_class_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes),
                                             rt.ptr(gt_importance), rt.ptr(gt_offsets), g, b, n, begin, ids, mt, ut, rt.ptr(labels),
                                             rt.ptr(targets), rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.stream())

@@ -38,6 +38,7 @@ SYMBOLS = [
     "sec_bn_relu_bwd_nhwc", "sec_flat_adamw_workspace_bytes", "sec_flat_adamw_f32", "sec_flat_adamw_dev_f32",
     "sec_points_in_boxes_f32", "sec_noise_per_box_f32", "sec_augment_points_f32", "sec_augment_boxes_f32",
     "sec_db_sample_select_f32", "sec_db_sample_merge_points_workspace_bytes", "sec_db_sample_merge_points_f32",
+    "sec_anchor_area_mask_workspace_bytes", "sec_anchor_area_mask", "sec_predict_select_masked", "sec_assign_targets_masked_f32",
 ]
 
 _lib = None
@@ -107,7 +108,8 @@ def lib():
                      "sec_conv2d_packed_weight_bytes", "sec_indice_conv_bwd_workspace_bytes",
                      "sec_assign_targets_workspace_bytes", "sec_second_loss_workspace_bytes", "sec_heads_loss_workspace_bytes",
                      "sec_conv2d_wgrad_workspace_bytes", "sec_bn_train_workspace_bytes", "sec_pfn_train_workspace_bytes",
-                     "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes"):
+                     "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes",
+                     "sec_anchor_area_mask_workspace_bytes"):
             getattr(l, name).restype = ctypes.c_size_t
         if os.environ.get("SEC_FP32_MODE", "").lower() == "exact":      # process default of ops.set_fp32_mode
             l.sec_set_fp32_mode(1)
@@ -223,6 +225,10 @@ def lib():
         l.sec_augment_boxes_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         l.sec_db_sample_select_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, ci, ci, vp, vp, ci, cf, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
         l.sec_db_sample_merge_points_workspace_bytes.argtypes = [ci, ci, ci]
+        l.sec_anchor_area_mask_workspace_bytes.argtypes = [ci, ci, ci]
+        l.sec_anchor_area_mask.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, vp, vp, cf, vp, vp, sz, vp]
+        l.sec_predict_select_masked.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+        l.sec_assign_targets_masked_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         l.sec_db_sample_merge_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, sz, vp]
         _lib = l
     return _lib

@@ -195,13 +195,17 @@ class DeviceTrainer:
                                                           mean_dtype=self.amp_dtype, sync=not static)
                 if static:
                     nd = vox["voxel_offsets"][batch:]         # live voxel rows stay on the device
+            # anchor_area_threshold >= 0 (the KITTI PointPillars configs): the anchors over (nearly) empty ground are pruned from the matching
+            # (target_assigner.py:63-64, 119-123) -- mask from this step's own voxel coordinates; they come back as label -1, "don't
+            # care", so nothing else in the step changes.  None for every other config.
+            amask = det.anchor_area_mask(vox["coordinates"], batch, nd)
             if self.class_ranges is None:
                 labels, reg_targets, importance = ops.assign_targets(det.anchors, gt_boxes, gt_offsets, *self.thresholds,
-                                                                     gt_classes=gt_classes)
+                                                                     gt_classes=gt_classes, anchors_mask=amask)
             else:
                 begin, ids, mts, uts = self.class_ranges
                 labels, reg_targets, importance = ops.assign_targets_per_class(det.anchors, gt_boxes, gt_offsets, gt_classes,
-                                                                               begin, ids, mts, uts)
+                                                                               begin, ids, mts, uts, anchors_mask=amask)
         if det.pillars:
             # PointPillars (nuscenes/all.pp.largea): PillarFeatureNet on sec_pfn_train_fwd / _bwd (batch statistics; the [P, T, C]
             # tensor of the reference formulation is never built), differentiable pillar scatter (sec_pillar_scatter / sec_dense_to_sparse),
