@@ -905,6 +905,78 @@ int sec_db_sample_merge_points_f32(const float *points, int point_pitch, const i
                                    int out_capacity, int *out_point_offsets, int *overflow, void *workspace, size_t workspace_bytes,
                                    void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * KITTI AP evaluation: second/utils/eval.py -- calculate_iou_partly (:362-445), clean_data (:33-89), compute_statistics_jit
+ * (:182-300), get_thresholds (:12-30), fused_compute_statistics (:313-359) -- for all images and all (class, difficulty, min_overlap)
+ * configurations of one eval_class_v3 call (:479-611).  numba-jitted host loops in the reference.
+ *
+ * Ragged per-image data: int32 prefix offsets [images + 1] for the gt rows, the detection rows, the DontCare boxes and the elements
+ * of the per-image overlap blocks (block i holds dt_i * gt_i float64, detection-major: element [j, g] at ov_offsets[i] + j * gt_i + g).
+ * n_gt / n_dt / n_dc / n_ov are the array lengths (= the last offsets); max_gt / max_dt the largest per-image counts, known to the
+ * host.  Caps: an image may hold up to SEC_KITTI_EVAL_MAX_GT gt rows and SEC_KITTI_EVAL_MAX_DT detections (KITTI keeps 100
+ * detections after NMS, nuScenes 500; the matching kernel keeps 17 KiB of LDS per one-wave workgroup at these caps); above a
+ * cap every entry point returns SEC_E_UNSUPPORTED before any launch.  images == 0 and images without gt, without detections or
+ * without either are valid.  A configuration is cfg = (class * num_difficulty + difficulty) * num_k + k; cfg / num_k indexes the flag
+ * planes, cfg_min_overlap [configs] float64 (device) holds min_overlaps[k, metric, class]; configs is a multiple of num_k.
+ * NULL where an array is needed: SEC_E_INVALID, decided before any launch; all work is enqueued on the stream.
+ *
+ * sec_kitti_eval_overlaps -- one launch writes the [dt_i, gt_i] block of every image (the reference computes the full matrix of
+ *   a part's ~75 images and slices the diagonal blocks out).  The detections are the `boxes`, the gt the `query_boxes`, as
+ *   eval_class_v3 calls calculate_iou_partly(dt_annos, gt_annos).  metric 0: image_box_overlap in float64 on bbox rows [., 4] (x1, y1,
+ *   x2, y2), the reference's operations in its order: bit exact.  metric 1: rotated BEV IoU; rows [., 7] = location, dimensions,
+ *   rotation_y in float64, the two BEV axes (range(3) without z_axis) rounded to float32, the clipper of sec_rotate_iou_f32 (the
+ *   corners from the sine / cosine evaluated in float64 and rounded once: the clipper is ill-conditioned at 60 m), the result widened.  metric 2: the float32 BEV intersection, then box3d_overlap_kernel (criterion -1) with the heights and volumes of the
+ *   float64 rows; inc / ua is rounded to float32 (the reference stores it into its float32 array) and widened.
+ * sec_kitti_eval_flags -- clean_data for num_cd (class, difficulty) pairs (host arrays; at most SEC_KITTI_EVAL_MAX_CD).  Names are
+ *   SEC_KITTI_NAME_* ids of the lower-cased names (the host compares names, not class indices: 'car' is in the reference's table
+ *   twice); occlusion and truncation as float64.  ignored_gt [num_cd, n_gt], ignored_dt [num_cd, n_dt] int8 in {0, 1, -1},
+ *   num_valid_gt [num_cd] (integer atomics).  Which gt rows are DontCare boxes (case-sensitive name) is the host's packing.
+ * sec_kitti_eval_tp_scores -- compute_statistics_jit(compute_fp=False, thresh=0) for every image and configuration: gt in order,
+ *   detections with flag -1 or already assigned skipped, the highest score with overlap > min_overlap wins (first of equals), a match
+ *   with an ignored gt or detection is assigned but not counted.  tp_scores [configs, n_gt] float64: the scores of image i's true
+ *   positives at [cfg, gt_offsets[i] ...), tp_count [configs, images] of them; the rest of tp_scores is not written.
+ * sec_kitti_eval_thresholds -- get_thresholds per configuration on sorted_scores [configs, pitch] (descending; n_scores [configs]
+ *   valid entries each): the sequential float64 scan, `current_recall += 1 / 40.0` accumulated.  thresholds [configs, 41] (zeros
+ *   behind the count), n_thresholds [configs].
+ * sec_kitti_eval_pr -- fused_compute_statistics (compute_fp=True) for every image, configuration and threshold.  pr_counts [configs,
+ *   41, 3] int32 = tp, fp, fn, exact; pr_similarity [configs, 41] float64 = sum of (1 + cos(gt_alpha - dt_alpha)) / 2 over the true
+ *   positives when compute_aos, else 0.  metric 0 runs the DontCare pass (dc_offsets, dc_bbox [n_dc, 4], dt_bbox [n_dt, 4]).
+ *   Deterministic: per image in gt order, per chunk of SEC_KITTI_EVAL_CHUNK images in image order, chunks in order, no floating-point
+ *   atomics.  Entries at or behind n_thresholds[cfg] are zero.  workspace: sec_kitti_eval_pr_workspace_bytes(images, configs).
+ * --------------------------------------------------------------------------------------------- */
+#define SEC_KITTI_EVAL_MAX_GT 512
+#define SEC_KITTI_EVAL_MAX_DT 512
+#define SEC_KITTI_EVAL_MAX_CD 32
+#define SEC_KITTI_EVAL_SAMPLE_PTS 41
+#define SEC_KITTI_EVAL_CHUNK 32
+#define SEC_KITTI_NAME_CAR 0
+#define SEC_KITTI_NAME_PEDESTRIAN 1
+#define SEC_KITTI_NAME_CYCLIST 2
+#define SEC_KITTI_NAME_VAN 3
+#define SEC_KITTI_NAME_PERSON_SITTING 4
+#define SEC_KITTI_NAME_TRACTOR 5
+#define SEC_KITTI_NAME_TRAILER 6
+#define SEC_KITTI_NAME_OTHER 7
+int sec_kitti_eval_overlaps(int metric, int images, const int *dt_offsets, const int *gt_offsets, const int *ov_offsets,
+                            const double *dt_boxes, const double *gt_boxes, int n_dt, int n_gt, long long n_ov, int max_dt, int max_gt,
+                            int z_axis, double z_center, double *overlaps, void *stream);
+int sec_kitti_eval_flags(const int *h_class_names, const int *h_difficulties, int num_cd, int n_gt, int n_dt, const int *gt_name,
+                         const double *gt_bbox, const double *gt_occluded, const double *gt_truncated, const int *dt_name,
+                         const double *dt_bbox, signed char *ignored_gt, signed char *ignored_dt, int *num_valid_gt, void *stream);
+int sec_kitti_eval_tp_scores(int images, const int *gt_offsets, const int *dt_offsets, const int *ov_offsets, const double *overlaps,
+                             long long n_ov, const double *dt_score, const signed char *ignored_gt, const signed char *ignored_dt,
+                             int n_gt, int n_dt, int max_gt, int max_dt, const double *cfg_min_overlap, int num_k, int configs,
+                             double *tp_scores, int *tp_count, void *stream);
+int sec_kitti_eval_thresholds(const double *sorted_scores, long long pitch, const int *n_scores, const int *num_valid_gt, int num_k,
+                              int configs, double *thresholds, int *n_thresholds, void *stream);
+size_t sec_kitti_eval_pr_workspace_bytes(int images, int configs);
+int sec_kitti_eval_pr(int images, const int *gt_offsets, const int *dt_offsets, const int *dc_offsets, const int *ov_offsets,
+                      const double *overlaps, long long n_ov, const double *dt_score, const double *gt_alpha, const double *dt_alpha,
+                      const double *dt_bbox, const double *dc_bbox, int n_dc, const signed char *ignored_gt,
+                      const signed char *ignored_dt, int n_gt, int n_dt, int max_gt, int max_dt, const double *cfg_min_overlap, int num_k,
+                      int configs, const double *thresholds, const int *n_thresholds, int metric, int compute_aos, int *pr_counts,
+                      double *pr_similarity, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

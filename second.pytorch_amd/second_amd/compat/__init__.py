@@ -330,16 +330,35 @@ def rotate_iou_gpu_eval(boxes, query_boxes, criterion=-1, device_id=0):
     return out.cpu().numpy().astype(boxes.dtype)
 
 
-def accelerate_eval():
+def accelerate_eval(statistics=None):
     """Route the KITTI evaluation's rotated-IoU calls to the MI355X: ``second/utils/eval.py:124`` (bev_box_overlap) and
     ``:175`` (box3d_overlap) call ``rotate_iou_gpu_eval(boxes, qboxes, criterion)``, a numba.cuda kernel that cannot run
     here; :func:`rotate_iou_gpu_eval` above replaces it (all four criteria; pinned on the original by
-    tests/golden/rotate_iou.npz).  Call after :func:`install`; returns the patched module."""
+    tests/golden/rotate_iou.npz).  Call after :func:`install`; returns the patched module.
+    ``statistics=True``: ``eval_class_v3`` itself (the overlaps of every image, clean_data, the greedy matching, get_thresholds and
+    the PR statistics -- numba-jitted host loops in the reference, plain Python under the numba stub) is replaced by
+    :func:`second_amd.kitti_eval.eval_class_v3`; the original stays at ``ev._second_amd_original_eval_class_v3``.  ``do_eval_v2`` /
+    ``do_eval_v3`` resolve the name at call time, so ``get_official_eval_result`` and ``get_coco_eval_result`` use it unchanged.
+    (With it ``np.linspace`` accepts an integral float count again, which ``do_coco_style_eval`` passes.)
+    ``statistics=None`` reads SEC_EVAL_DEVICE: only ``1`` turns it on."""
     import importlib
     ev = importlib.import_module("second.utils.eval")
-    if getattr(ev, "_second_amd_accelerated", False):
-        return ev
-    ev._second_amd_original_rotate_iou = ev.rotate_iou_gpu_eval
-    ev.rotate_iou_gpu_eval = rotate_iou_gpu_eval
-    ev._second_amd_accelerated = True
+    if statistics is None:
+        statistics = os.environ.get("SEC_EVAL_DEVICE") == "1"
+    if not getattr(ev, "_second_amd_accelerated", False):
+        ev._second_amd_original_rotate_iou = ev.rotate_iou_gpu_eval
+        ev.rotate_iou_gpu_eval = rotate_iou_gpu_eval
+        ev._second_amd_accelerated = True
+    if statistics and not hasattr(ev, "_second_amd_original_eval_class_v3"):
+        import numpy as np
+        from .. import kitti_eval
+        if not getattr(np.linspace, "_second_amd_int_num", False):
+            _linspace = np.linspace
+
+            def linspace(start, stop, num=50, *a, **k):   # eval.py:704 passes num as a float64 (np.linspace(*row)): a TypeError since numpy 1.18
+                return _linspace(start, stop, int(num) if isinstance(num, (float, np.floating)) and float(num).is_integer() else num, *a, **k)
+            linspace._second_amd_int_num = True
+            np.linspace = linspace
+        ev._second_amd_original_eval_class_v3 = ev.eval_class_v3
+        ev.eval_class_v3 = kitti_eval.eval_class_v3
     return ev

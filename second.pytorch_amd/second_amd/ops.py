@@ -1348,6 +1348,121 @@ def rotate_iou(boxes, qboxes, criterion=-1):
     return out
 
 
+# ----------------------------------------------------------------------------- KITTI AP evaluation (second/utils/eval.py)
+KITTI_EVAL_MAX_GT, KITTI_EVAL_MAX_DT, KITTI_EVAL_SAMPLE_PTS, KITTI_EVAL_CHUNK = 512, 512, 41, 32      # include/second_hip.h
+
+
+def _ke_i32(t, n=None):
+    assert t.dtype == torch.int32 and t.is_contiguous() and (n is None or t.numel() == n)
+    return t
+
+
+def _ke_f64(t, shape):
+    assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape), (t.dtype, tuple(t.shape), tuple(shape))
+    return t
+
+
+def kitti_eval_overlaps(metric, dt_offsets, gt_offsets, ov_offsets, dt_boxes, gt_boxes, n_ov, max_dt, max_gt, z_axis=1, z_center=1.0):
+    """The per-image [dt_i, gt_i] overlap blocks of calculate_iou_partly (eval.py:362-445), block-diagonal only -> float64 [n_ov].
+    metric 0: boxes are bbox rows [., 4]; 1 / 2: [., 7] = location, dimensions, rotation_y.  Offsets int32 [images + 1] on the device;
+    n_ov / max_dt / max_gt are host ints (the last overlap offset, the largest per-image counts)."""
+    rt.require_gpu(dt_offsets, gt_offsets, ov_offsets, dt_boxes, gt_boxes)
+    images = dt_offsets.numel() - 1
+    cols = 4 if int(metric) == 0 else 7
+    n_dt, n_gt = dt_boxes.shape[0], gt_boxes.shape[0]
+    _ke_i32(dt_offsets); _ke_i32(gt_offsets, images + 1); _ke_i32(ov_offsets, images + 1)
+    _ke_f64(dt_boxes, (n_dt, cols)); _ke_f64(gt_boxes, (n_gt, cols))
+    out = torch.empty((int(n_ov),), dtype=torch.float64, device=dt_boxes.device)
+    rc = rt.lib().sec_kitti_eval_overlaps(int(metric), images, rt.ptr(dt_offsets), rt.ptr(gt_offsets), rt.ptr(ov_offsets), rt.ptr(dt_boxes),
+                                          rt.ptr(gt_boxes), n_dt, n_gt, int(n_ov), int(max_dt), int(max_gt), int(z_axis), float(z_center),
+                                          rt.ptr(out), rt.stream())
+    rt.check(rc, "sec_kitti_eval_overlaps")
+    return out
+
+
+def kitti_eval_flags(class_names, difficulties, gt_name, gt_bbox, gt_occluded, gt_truncated, dt_name, dt_bbox):
+    """clean_data (eval.py:33-89) for the (class, difficulty) pairs zip(class_names, difficulties) -- class_names are SEC_KITTI_NAME_*
+    ids -> (ignored_gt int8 [num_cd, n_gt], ignored_dt int8 [num_cd, n_dt], num_valid_gt int32 [num_cd])."""
+    import ctypes
+    rt.require_gpu(gt_name, gt_bbox, gt_occluded, gt_truncated, dt_name, dt_bbox)
+    ncd, n_gt, n_dt, dev = len(class_names), gt_name.numel(), dt_name.numel(), gt_bbox.device
+    assert ncd == len(difficulties) and ncd > 0
+    _ke_i32(gt_name); _ke_i32(dt_name)
+    _ke_f64(gt_bbox, (n_gt, 4)); _ke_f64(gt_occluded, (n_gt,)); _ke_f64(gt_truncated, (n_gt,)); _ke_f64(dt_bbox, (n_dt, 4))
+    ign_gt = torch.empty((ncd, n_gt), dtype=torch.int8, device=dev)
+    ign_dt = torch.empty((ncd, n_dt), dtype=torch.int8, device=dev)
+    nvg = torch.empty((ncd,), dtype=torch.int32, device=dev)
+    rc = rt.lib().sec_kitti_eval_flags((ctypes.c_int * ncd)(*[int(c) for c in class_names]), (ctypes.c_int * ncd)(*[int(d) for d in difficulties]),
+                                       ncd, n_gt, n_dt, rt.ptr(gt_name), rt.ptr(gt_bbox), rt.ptr(gt_occluded), rt.ptr(gt_truncated),
+                                       rt.ptr(dt_name), rt.ptr(dt_bbox), rt.ptr(ign_gt), rt.ptr(ign_dt), rt.ptr(nvg), rt.stream())
+    rt.check(rc, "sec_kitti_eval_flags")
+    return ign_gt, ign_dt, nvg
+
+
+def kitti_eval_tp_scores(gt_offsets, dt_offsets, ov_offsets, overlaps, dt_score, ignored_gt, ignored_dt, max_gt, max_dt, cfg_min_overlap, num_k):
+    """compute_statistics_jit(compute_fp=False) (eval.py:182-300) for every image and configuration.  cfg_min_overlap float64
+    [configs]; configuration cfg uses the flag plane cfg // num_k.  -> (tp_scores float64 [configs, n_gt], -inf where no score was
+    written: image i's scores start at [cfg, gt_offsets[i]]; tp_count int32 [configs, images])."""
+    rt.require_gpu(gt_offsets, dt_offsets, ov_offsets, overlaps, dt_score, ignored_gt, ignored_dt, cfg_min_overlap)
+    images, configs, dev = gt_offsets.numel() - 1, cfg_min_overlap.numel(), cfg_min_overlap.device
+    n_gt, n_dt = ignored_gt.shape[1], ignored_dt.shape[1]
+    _ke_i32(gt_offsets); _ke_i32(dt_offsets, images + 1); _ke_i32(ov_offsets, images + 1)
+    _ke_f64(overlaps, (overlaps.numel(),)); _ke_f64(dt_score, (n_dt,)); _ke_f64(cfg_min_overlap, (configs,))
+    assert ignored_gt.dtype == torch.int8 and ignored_dt.dtype == torch.int8 and ignored_gt.is_contiguous() and ignored_dt.is_contiguous()
+    assert configs % int(num_k) == 0 and ignored_gt.shape[0] == ignored_dt.shape[0] == configs // int(num_k)
+    tp_scores = torch.full((configs, n_gt), float("-inf"), dtype=torch.float64, device=dev)
+    tp_count = torch.zeros((configs, images), dtype=torch.int32, device=dev)
+    rc = rt.lib().sec_kitti_eval_tp_scores(images, rt.ptr(gt_offsets), rt.ptr(dt_offsets), rt.ptr(ov_offsets), rt.ptr(overlaps), overlaps.numel(),
+                                           rt.ptr(dt_score), rt.ptr(ignored_gt), rt.ptr(ignored_dt), n_gt, n_dt, int(max_gt), int(max_dt),
+                                           rt.ptr(cfg_min_overlap), int(num_k), configs, rt.ptr(tp_scores), rt.ptr(tp_count), rt.stream())
+    rt.check(rc, "sec_kitti_eval_tp_scores")
+    return tp_scores, tp_count
+
+
+def kitti_eval_thresholds(tp_scores, tp_count, num_valid_gt, num_k):
+    """get_thresholds (eval.py:12-30) per configuration: the scores (float64 [configs, n], -inf padded as kitti_eval_tp_scores
+    returns them) are sorted descending by torch, the sequential float64 scan runs on the device.
+    -> (thresholds float64 [configs, 41], n_thresholds int32 [configs], sorted scores, n_scores int32 [configs])."""
+    rt.require_gpu(tp_scores, tp_count, num_valid_gt)
+    configs, pitch = tp_scores.shape
+    assert tp_scores.dtype == torch.float64 and tp_count.dtype == torch.int32 and num_valid_gt.dtype == torch.int32
+    assert configs % int(num_k) == 0 and num_valid_gt.numel() == configs // int(num_k) and num_valid_gt.is_contiguous()
+    sorted_scores = torch.sort(tp_scores, dim=1, descending=True).values.contiguous()
+    n_scores = tp_count.reshape(configs, -1).sum(dim=1, dtype=torch.int32).contiguous()
+    thresholds = torch.empty((configs, KITTI_EVAL_SAMPLE_PTS), dtype=torch.float64, device=tp_scores.device)
+    n_thr = torch.empty((configs,), dtype=torch.int32, device=tp_scores.device)
+    rc = rt.lib().sec_kitti_eval_thresholds(rt.ptr(sorted_scores) if pitch else None, pitch, rt.ptr(n_scores), rt.ptr(num_valid_gt), int(num_k),
+                                            configs, rt.ptr(thresholds), rt.ptr(n_thr), rt.stream())
+    rt.check(rc, "sec_kitti_eval_thresholds")
+    return thresholds, n_thr, sorted_scores, n_scores
+
+
+def kitti_eval_pr(gt_offsets, dt_offsets, dc_offsets, ov_offsets, overlaps, dt_score, gt_alpha, dt_alpha, dt_bbox, dc_bbox, ignored_gt,
+                  ignored_dt, max_gt, max_dt, cfg_min_overlap, num_k, thresholds, n_thresholds, metric, compute_aos=False):
+    """fused_compute_statistics (eval.py:313-359) for every image, configuration and threshold -> (counts int32 [configs, 41, 3] =
+    tp, fp, fn; similarity float64 [configs, 41]).  Deterministic (no floating-point atomics)."""
+    rt.require_gpu(gt_offsets, dt_offsets, dc_offsets, ov_offsets, overlaps, dt_score, ignored_gt, ignored_dt, cfg_min_overlap, thresholds)
+    images, configs, dev = gt_offsets.numel() - 1, cfg_min_overlap.numel(), cfg_min_overlap.device
+    n_gt, n_dt, n_dc = ignored_gt.shape[1], ignored_dt.shape[1], dc_bbox.shape[0]
+    _ke_i32(gt_offsets); _ke_i32(dt_offsets, images + 1); _ke_i32(dc_offsets, images + 1); _ke_i32(ov_offsets, images + 1)
+    _ke_f64(overlaps, (overlaps.numel(),)); _ke_f64(dt_score, (n_dt,)); _ke_f64(cfg_min_overlap, (configs,))
+    _ke_f64(gt_alpha, (n_gt,)); _ke_f64(dt_alpha, (n_dt,)); _ke_f64(dt_bbox, (n_dt, 4)); _ke_f64(dc_bbox, (n_dc, 4))
+    _ke_f64(thresholds, (configs, KITTI_EVAL_SAMPLE_PTS)); _ke_i32(n_thresholds, configs)
+    assert ignored_gt.dtype == torch.int8 and ignored_dt.dtype == torch.int8 and ignored_gt.is_contiguous() and ignored_dt.is_contiguous()
+    assert configs % int(num_k) == 0 and ignored_gt.shape[0] == ignored_dt.shape[0] == configs // int(num_k)
+    counts = torch.empty((configs, KITTI_EVAL_SAMPLE_PTS, 3), dtype=torch.int32, device=dev)
+    sim = torch.empty((configs, KITTI_EVAL_SAMPLE_PTS), dtype=torch.float64, device=dev)
+    l = rt.lib()
+    ws = rt.workspace(l.sec_kitti_eval_pr_workspace_bytes(images, configs), dev)
+    rc = l.sec_kitti_eval_pr(images, rt.ptr(gt_offsets), rt.ptr(dt_offsets), rt.ptr(dc_offsets), rt.ptr(ov_offsets), rt.ptr(overlaps),
+                             overlaps.numel(), rt.ptr(dt_score), rt.ptr(gt_alpha), rt.ptr(dt_alpha), rt.ptr(dt_bbox), rt.ptr(dc_bbox), n_dc,
+                             rt.ptr(ignored_gt), rt.ptr(ignored_dt), n_gt, n_dt, int(max_gt), int(max_dt), rt.ptr(cfg_min_overlap), int(num_k),
+                             configs, rt.ptr(thresholds), rt.ptr(n_thresholds), int(metric), int(bool(compute_aos)), rt.ptr(counts),
+                             rt.ptr(sim), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, "sec_kitti_eval_pr")
+    return counts, sim
+
+
 @_traced("nms_sorted")
 def nms_sorted(dets, counts, thresh, kind="rotate", semantics="numba", eps=1.0, post_max=0, exact_clip=False):
     """Greedy NMS of score-sorted boxes. dets [B,max_n,stride] float32, counts [B] int32 (device).
