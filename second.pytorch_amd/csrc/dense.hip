@@ -68,6 +68,20 @@ template <> struct MfmaD<__half> {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8d, a), __builtin_bit_cast(f16x8d, b), c, 0, 0, 0);
     }
 };
+// The 16x16x32 shape: lane l carries row / column (l & 15) and the eight k values 8 (l >> 4) ... + 7 of either operand; the result
+// lane holds column (l & 15), rows 4 (l >> 4) + i.  Half the cycles of the 32x32x16 form for half the MACs.
+typedef float f32x4d __attribute__((ext_vector_type(4)));
+template <typename T> struct MfmaK32;
+template <> struct MfmaK32<__hip_bfloat16> {
+    static __device__ __forceinline__ f32x4d run(uint4 a, uint4 b, f32x4d c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8d, a), __builtin_bit_cast(bf16x8d, b), c, 0, 0, 0);
+    }
+};
+template <> struct MfmaK32<__half> {
+    static __device__ __forceinline__ f32x4d run(uint4 a, uint4 b, f32x4d c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8d, a), __builtin_bit_cast(f16x8d, b), c, 0, 0, 0);
+    }
+};
 
 
 // Two fp32 -> one dword of two 16-bit values with ONE conversion instruction pair (v_cvt_pk_bf16_f32 on gfx950; the scalar
@@ -335,6 +349,12 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 template <int CH, int HW_, bool COLKEY> __device__ __forceinline__ int halo_key(int hp) {
     return (COLKEY && CH == 16) ? ((hp % HW_) & 15) : (hp & (CH - 1));
 }
+// The key of the Cin = 128 loops by halo COLUMN hx, applied on the source side of the halo DMA and on the read side of the loop.
+// ROLL == 2 (32x32x16 fragments, above): hx & 15.  ROLL == 3 (16x16x32): a fragment is ONE halo row, lane l reads pixel
+// (l & 15) + dx, chunk 4 k32 + (l >> 4), so a 16-lane group is eight consecutive columns (mod 16) at chunk c and the other eight
+// at chunk c ^ 1 -- with hx & 15 neighbouring columns of the two halves meet in one slot at odd dx (2-way); 2 hx & 15 keeps the
+// low bit of the slot = the low bit of the chunk and gives the eight columns of either half eight distinct even keys.
+template <int ROLL> __device__ __forceinline__ unsigned halo_colkey(unsigned hx) { return ROLL == 3 ? (2u * hx) & 15u : hx & 15u; }
 
 #ifdef SEC_CONV2D_EXPERIMENTS   // superseded 3x3 kernels (register-staged implicit GEMM, LDS weight slabs / rings): A/B builds only
 #include "../../tools/kernel_experiments/dense_conv2d_ab.inc"
@@ -348,7 +368,14 @@ template <int CH, int HW_, bool COLKEY> __device__ __forceinline__ int halo_key(
 // B fragment and each streams its own from L2 (1 KB coalesced per k-step, prefetched one iteration ahead in VGPRs).
 // LDS holds only the halo (46 KB -> 3 workgroups per CU, 2200 / 768 = 2.9 rounds), the main loop has no barrier,
 // and LDS traffic drops to one conflict-free ds_read_b128 per MFMA.
-// Cin = 128 runs the ROLL == 2 main loop (below): m-tiles pair output rows (mt, mt + 4) so that SIX halo fragments per (dx, k-step)
+// Cin = 128, every call form, runs the ROLL == 3 main loop: v_mfma_f32_16x16x32 with ROW-STREAMED halo fragments -- the instruction's
+// 16 pixels are one tile row, a fragment is one halo row x 32 channels (one ds_read_b128) and feeds the three output rows it
+// belongs to x two channel groups: ten reads + six weight fragments per 48 MFMAs (17 % fewer LDS bytes per MAC than ROLL == 2),
+// key 2 hx & 15 (halo_colkey), accumulators of 4 registers = 4 channels of a pixel, packed into the same LDS output tile through
+// v_permlane16_swap.  Same matrix-pipe cycles as ROLL == 2 (576 x 16 = 288 x 32 per wave), less energy per MAC: the loop is bound by
+// the clock the chip holds under it, and holds 1.68 instead of 1.54 GHz (dense form, batch 8, 200 x 176: 67.2 -> 60.2 us, both loops
+// interleaved in one process; DESIGN_APPENDIX "MFMA shape record").  SEC_CONV2D_MFMA=32 selects ROLL == 2 for A/B (conv2d_c128_roll).
+// ROLL == 2 (the loop until then): m-tiles pair output rows (mt, mt + 4) so that SIX halo fragments per (dx, k-step)
 // feed the twelve MFMAs of the three kernel rows -- half the LDS reads of one fragment per MFMA (ROLL == 1, kept for A/B as
 // SEC_CONV2D_VARIANT=15): 79.9 -> 74.0 us on one box, 76.7 -> 71.8 us on another (batch 8, 200 x 176, 128 -> 128).  Setting wave
 // priorities (prologue / epilogue above the loop, and the reverse) and a 12-deep B ring were measured on that loop: +1 ... +5 % slower.
@@ -387,9 +414,9 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                                                             const T *__restrict__ x_lo = nullptr, T *__restrict__ y_lo = nullptr,
                                                             const T *__restrict__ background_lo = nullptr,
                                                             const T *__restrict__ bg_in_lo = nullptr, ConvTailArgs tail = ConvTailArgs{}) {
-    static_assert(!GATHER || (ROLL == 2 && CIN == 128), "gather prologue: the shared-row loop on two 64-channel planes");
-    static_assert(!TAIL || (ROLL == 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && !X3), "fused 1x1 tail: the lazy list form of the 128-channel conv");
-    static_assert(!X3 || (ROLL == 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && std::is_same<T, __hip_bfloat16>::value),
+    static_assert(!GATHER || (ROLL >= 2 && CIN == 128), "gather prologue: the shared-row loop on two 64-channel planes");
+    static_assert(!TAIL || (ROLL >= 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && !X3), "fused 1x1 tail: the lazy list form of the 128-channel conv");
+    static_assert(!X3 || (ROLL >= 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && std::is_same<T, __hip_bfloat16>::value),
                   "three-pass split-fp32 form: the shared-row bf16 loop");
     constexpr int TW = 16, HW_ = TW + 2, HPIX = (TH + 2) * (TW + 2);
     // NSPLIT == 2: 64 output channels per workgroup -- the waves split the tile's pixels two ways and the channels two ways (the
@@ -452,7 +479,7 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         for (int t = 0; t < (HENT / 64 + 3) / 4; ++t) {
             const int i = wvs + 4 * t;
             if (i < HENT / 64) {
-                const unsigned key = (slot ^ ((unsigned)hx & 15u)) << 4;
+                const unsigned key = (slot ^ halo_colkey<ROLL>((unsigned)hx)) << 4;
                 unsigned off = rowoff + ((unsigned)hx << 8) + key;
                 const unsigned ix = (unsigned)(x0 - 1 + hx);
                 off = ix < (unsigned)p.w ? off : 0xfffffff0u;
@@ -486,7 +513,7 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         for (int t = 0; t < (HENT / 64 + 3) / 4; ++t) {
             const int i = wvs + 4 * t;
             if (i < HENT / 64) {
-                const unsigned key = (slot ^ ((unsigned)hx & 15u)) << 4;
+                const unsigned key = (slot ^ halo_colkey<ROLL>((unsigned)hx)) << 4;
                 unsigned off = rowoff + ((unsigned)hx << 8) + key;
                 const unsigned ix = (unsigned)(x0 - 1 + hx);
                 off = ix < (unsigned)p.w ? off : 0xfffffff0u;
@@ -522,7 +549,7 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
             rowp1[t] = 0;
             coff[t] = 0;
             if (i < HENT / 64) {
-                const unsigned c = slot ^ ((unsigned)hx & 15u);
+                const unsigned c = slot ^ halo_colkey<ROLL>((unsigned)hx);
                 const int ix = x0 - 1 + hx;
                 const bool ok = (unsigned)ix < (unsigned)p.w && (unsigned)iy < (unsigned)p.h;
                 const unsigned moff = ((c >> 3 ? plane : 0u) + (unsigned)(iy * p.w + ix)) * 4u;
@@ -730,12 +757,34 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         // per dx cost 48 VGPRs and spilled)
         typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(wpk), 0, (int)(((X3 ? 18 : 9) * cin8 + 1) * p.cout * 16), 0x00020000);
-        const unsigned wvoff = (unsigned)(hh * p.cout + n0 + r) * 16u;
+        // ROLL == 3: a 16-channel x 32-k fragment = chunk (4 k32 + lane / 16) of output channel n0 + 16 g + (lane & 15): the same packed image
+        const unsigned wvoff = ROLL == 3 ? (unsigned)((lane >> 4) * p.cout + n0 + (lane & 15)) * 16u : (unsigned)(hh * p.cout + n0 + r) * 16u;
         const unsigned wstep = (unsigned)p.cout * 16u;            // bytes per chunk row of the packed weights
         auto ld_b = [&](unsigned chunk) {
             return __builtin_bit_cast(uint4, (u32x4b)__builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, chunk * wstep, 0));
         };
-        if constexpr (ROLL >= 2) {
+        auto ld_w = [&](unsigned chunk, int g) {                  // ... of channel group g (16 channels = 256 bytes on)
+            return __builtin_bit_cast(uint4, (u32x4b)__builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff + (unsigned)g * 256u, chunk * wstep, 0));
+        };
+        uint4 wb[ROLL == 3 ? 2 : 1][3][2];          // ROLL == 3: the six weight fragments (kernel row, channel group) of two (dx, k32) steps
+        f32x4d acc3[ROLL == 3 ? TH : 1][2];         // ... and its accumulators: (tile row, channel group)
+        // steps 0 and 1 = (dx 0, k32 0 / 1) of the weights starting at chunk wp; kernel row 2 of step 1 follows inside step 0
+        auto prime_w = [&](unsigned wp) {
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+#pragma unroll
+                for (int dy = 0; dy < 3; ++dy) wb[0][dy][g] = ld_w(wp + dy * 48, g);
+#pragma unroll
+                for (int dy = 0; dy < 2; ++dy) wb[ROLL == 3][dy][g] = ld_w(wp + dy * 48 + 4, g);
+            }
+        };
+        if constexpr (ROLL == 3) {
+#pragma unroll
+            for (int y = 0; y < TH; ++y)
+#pragma unroll
+                for (int g = 0; g < 2; ++g) acc3[y][g] = f32x4d{0.0f, 0.0f, 0.0f, 0.0f};
+            prime_w(0u);
+        } else if constexpr (ROLL >= 2) {
 #pragma unroll
             for (int f = 0; f < RD - 1; ++f) br[f] = ld_b((f % 3) * 48 + (f / 3) * 2);
         } else if constexpr (ROLL) {
@@ -769,7 +818,84 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         uint4 af[2][MT];
         int tap = 0, kc = 0;
         if (live && !ROLL) load_a(0, 0, 0, af[0]);
-        if constexpr (ROLL >= 2) {
+        if constexpr (ROLL == 3) {
+            // Row-streamed fragments on v_mfma_f32_16x16x32.  The 16-pixel side of the instruction is ONE tile row, so the pixel
+            // fragment of (dx, k32 = 32 input channels) is one halo row F[hy] -- a single ds_read_b128 -- and feeds output rows
+            // y = hy - dy (dy = 0, 1, 2 inside the tile) x 2 channel groups: per step (dx, k32) ten reads and six weight fragments
+            // W[dy][g] for 48 MFMAs of 16 cycles (the 32x32x16 loop: twelve reads per 48 MFMA-equivalents -- 17 % fewer LDS bytes
+            // per MAC here), 3 x 4 steps per tile.  An output element accumulates in the order (dx, k32, dy) in every call form.
+            // Rolled over dx, unrolled over k32 and hy.  The halo rows run through a ring of four, read three rows ahead (over the
+            // step boundaries too); the weights of step s + 2 replace those of step s as their last row retires (W[0] after hy 7,
+            // W[1] after hy 8, W[2] at hy 0 of the next step): every fragment is loaded a step (768 matrix-pipe cycles) and more
+            // ahead of its first use.  The two MFMAs of one (output row, dy) stay together: a wave-uniform row mask can skip them.
+            static_assert(KC == 2 && CH == 16 && TH == 8, "4 k32 steps per tap, ten halo rows");
+            const char *halb = reinterpret_cast<const char *>(hal);
+            const unsigned pxl = lane & 15, kq = lane >> 4;
+            constexpr unsigned ROWB = HW_ * CH * 16;      // bytes per halo row: ds_read immediates up to 9 * 4608
+            // byte address of this lane's 16 bytes of halo row 0: pixel pxl + dx, chunk 4 k32 + kq
+            auto f_addr = [&](int dx, int k32) {
+                return (pxl + (unsigned)dx) * (CH * 16) + (((unsigned)k32 << 6) ^ ((kq ^ halo_colkey<3>(pxl + (unsigned)dx)) << 4));
+            };
+            uint4 fr[4];
+            if (live) {
+                constexpr int NPASS = X3 ? 3 : 1;
+#pragma unroll 1
+                for (int pass = 0; pass < NPASS; ++pass) {
+                    // X3: the passes of the ROLL == 2 loop (below)
+                    const unsigned wp = (X3 && pass == 1) ? 9u * cin8 : 0u;
+                    if (X3 && pass > 0) {
+                        if (pass == 2) {
+                            __syncthreads();                    // every wave is done reading x_hi's halo
+                            if (nbr_masks) issue_halo2_lazy(tile, nmask, x_lo, bg_in_lo);
+                            else issue_halo2(tile, x_lo);
+                        }
+                        prime_w(wp);
+                        if (pass == 2) __syncthreads();         // x_lo's halo landed
+                    }
+                    {
+                        const unsigned a0 = f_addr(0, 0);
+#pragma unroll
+                        for (int h = 0; h < 3; ++h) fr[h] = *reinterpret_cast<const uint4 *>(halb + a0 + h * ROWB);
+                    }
+#pragma unroll 1
+                    for (int dx = 0; dx < 3; ++dx) {
+                        const int dxn = dx < 2 ? dx + 1 : 2;    // unconditional prefetches: the last dx re-reads its own first step
+                        // per step one XOR + one add on (pixel base, key) of this dx; step 4 = the first of the next dx
+                        const unsigned fb[2] = {(pxl + (unsigned)dx) * (CH * 16), (pxl + (unsigned)dxn) * (CH * 16)};
+                        const unsigned fk[2] = {(kq ^ halo_colkey<3>(pxl + (unsigned)dx)) << 4, (kq ^ halo_colkey<3>(pxl + (unsigned)dxn)) << 4};
+                        auto fa = [&](int k) { return fb[k >> 2] + (((unsigned)(k & 3) << 6) ^ fk[k >> 2]); };
+                        const unsigned ct = wp + dx * 16, cn = wp + dxn * 16;
+#pragma unroll
+                        for (int k32 = 0; k32 < 4; ++k32) {
+#pragma unroll
+                            for (int hy = 0; hy < TH + 2; ++hy) {
+                                const int t = k32 * (TH + 2) + hy, cur = k32 & 1;
+                                const unsigned c1 = k32 < 3 ? ct + 4 * (k32 + 1) : cn;                    // step s + 1
+                                const unsigned c2 = k32 < 2 ? ct + 4 * (k32 + 2) : cn + 4 * (k32 - 2);    // step s + 2
+                                if (hy == 0 || hy >= TH) {
+                                    const int dyl = hy == 0 ? 2 : hy - TH;
+#pragma unroll
+                                    for (int g = 0; g < 2; ++g) wb[hy == 0 ? cur ^ 1 : cur][dyl][g] = ld_w((hy == 0 ? c1 : c2) + dyl * 48, g);
+                                }
+                                {
+                                    const int tn = t + 3;
+                                    fr[tn & 3] = *reinterpret_cast<const uint4 *>(halb + fa(tn / (TH + 2)) + (tn % (TH + 2)) * ROWB);
+                                }
+#pragma unroll
+                                for (int dy = 0; dy < 3; ++dy) {
+                                    const int y = hy - dy;
+                                    if (y < 0 || y >= TH) continue;
+#pragma unroll
+                                    for (int g = 0; g < 2; ++g) acc3[y][g] = MfmaK32<T>::run(wb[cur][dy][g], fr[t & 3], acc3[y][g]);
+                                }
+                                __builtin_amdgcn_sched_barrier(0);      // pins [weight loads, halo read, MFMAs] per halo row, as in the loop below
+                            }
+                        }
+                    }
+                }
+            }
+            live = false;
+        } else if constexpr (ROLL >= 2) {
             // Shared-row fragments.  An m-tile pairs output rows (mt, mt + 4), so its A fragment for kernel row dy is the pair of
             // halo rows (mt + dy, mt + dy + 4) = F[mt + dy]: for one (dx, k-step) SIX fragments F[0..5] feed all 3 x 4 = 12 MFMAs
             // of the three kernel rows -- half the ds_read_b128 traffic of the ROLL == 1 loop (12 reads per 12 MFMAs), same B
@@ -912,7 +1038,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
             uint4 *ot = halo_smem;
             float4 bv[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) bv[g] = bias ? *reinterpret_cast<const float4 *>(bias + n0 + 8 * g + 4 * hh) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            for (int g = 0; g < 4; ++g)     // ROLL == 3 uses bv[0 .. 1]: channels n0 + 16 g + 4 (lane / 16) ...
+                bv[g] = bias ? *reinterpret_cast<const float4 *>(bias + n0 + (ROLL == 3 ? 16 * (g & 1) + 4 * (lane >> 4) : 8 * g + 4 * hh)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             // This phase runs beside two other waves' MFMA loops on the SIMD and gets an issue slot every ~18 clocks (timeline:
             // 7 300 clocks for the ~900 instructions of the first form -- a branch per value for the ReLU, one convert + merge per
             // value, ds_bpermute + selects for the half-wave exchange).  Here: add, max, one convert per PAIR, and
@@ -921,6 +1048,37 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
             auto put_tile = [&](auto relu_tag, auto lo_tag) {
                 constexpr bool RELU = decltype(relu_tag)::value;
                 constexpr bool LOW = decltype(lo_tag)::value;     // X3: the residual plane v - bf16(v) instead of bf16(v)
+                if constexpr (ROLL == 3) {
+                    // 16x16x32 accumulators: acc3[y][g] = channels n0 + 16 g + 4 (lane / 16) + (0..3) of pixel (y, lane & 15) -- half a
+                    // chunk per lane and group; same add, max, pair converts.  v_permlane16_swap(g 0, g 1) trades the odd 16-lane rows of
+                    // the first for the even rows of the second: rows 0 / 2 then hold both halves of chunks 0 / 1 of group 0, rows 1 / 3 of
+                    // group 1 -- 16-byte writes at pitch 17, conflict-free as in the 32x32 form (8-byte writes from 16 pixels are 2-way)
+                    const int kq = lane >> 4;
+#pragma unroll
+                    for (int y = 0; y < TH; ++y) {
+                        unsigned lo[2], hi[2];
+#pragma unroll
+                        for (int g = 0; g < 2; ++g) {
+                            const float4 b4 = bv[g];
+                            float v[4] = {acc3[y][g][0] + b4.x, acc3[y][g][1] + b4.y, acc3[y][g][2] + b4.z, acc3[y][g][3] + b4.w};
+                            if (RELU) {
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaxf(v[j], 0.0f);
+                            }
+                            lo[g] = pack2<T>(v[0], v[1]);
+                            hi[g] = pack2<T>(v[2], v[3]);
+                            if constexpr (LOW) {
+                                lo[g] = pack2<T>(v[0] - __uint_as_float(lo[g] << 16), v[1] - __uint_as_float(lo[g] & 0xffff0000u));
+                                hi[g] = pack2<T>(v[2] - __uint_as_float(hi[g] << 16), v[3] - __uint_as_float(hi[g] & 0xffff0000u));
+                            }
+                        }
+                        const auto sx = __builtin_amdgcn_permlane16_swap(lo[0], lo[1], false, false);
+                        const auto sy = __builtin_amdgcn_permlane16_swap(hi[0], hi[1], false, false);
+                        ot[(y * 16 + (lane & 15)) * PITCH + wv * 4 + 2 * (kq & 1) + (kq >> 1)] = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+                        __builtin_amdgcn_sched_barrier(0);      // row by row: all 64 sums beside the 64 accumulators X3 keeps spilled
+                    }
+                    return;
+                }
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
                     unsigned lo[4], hi[4];                  // channels 8g+4hh+(0,1) and +(2,3) of this lane's pixel
@@ -1127,6 +1285,23 @@ static int launch_conv2d_halo_reg(const void *x, const void *wpk, const float *b
                        site_map, feat_bytes, tile_order, live_counts, (const T *)background, nbr_masks, (const T *)bg_in, (const T *)x_lo, (T *)y_lo,
                        (const T *)background_lo, (const T *)bg_in_lo, tail);
     return check_launch();
+}
+
+// The 128-channel 3x3 convs (every call form) run ONE main loop per process: the 16x16x32 one (ROLL == 3), or with SEC_CONV2D_MFMA=32
+// the 32x32x16 one (ROLL == 2) for A/B -- read once, before the first launch.  Never a mixture: the two loops group the products of
+// an output element differently, and the list, lazy and plain forms are bit-identical to each other only on the same loop.
+static int conv2d_c128_roll() {
+    static int v = -1;
+    if (v < 0) {
+        const char *e = getenv("SEC_CONV2D_MFMA");
+        v = (e && atoi(e) == 32) ? 2 : 3;
+    }
+    return v;
+}
+template <typename T, bool GATHER = false, bool X3 = false, bool TAIL = false, typename... A>
+static int launch_conv2d_c128(A... a) {
+    return conv2d_c128_roll() == 3 ? launch_conv2d_halo_reg<T, 128, 8, 3, GATHER, 1, X3, TAIL>(a...)
+                                   : launch_conv2d_halo_reg<T, 128, 8, 2, GATHER, 1, X3, TAIL>(a...);
 }
 
 // 1x1 convolutions (the ConvTranspose2d(k=1) "deconv" and the merged heads of the RPN, rpn.py:275-285,386-391) are
@@ -1595,7 +1770,7 @@ static int launch_conv2d(const void *x, const void *wpk, const float *bias, void
     if (conv2d_variant() == 14 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && p.cin == 128)
         return launch_conv2d_halo_reg<T, 128, 8>(x, wpk, bias, y, p, st);   // A/B: the two-stage loop with per-m-tile halo addressing
     if (conv2d_variant() == 13 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && (p.cin == 128 || p.cin == 64))
-        return p.cin == 128 ? launch_conv2d_halo_reg<T, 128, 8, 2>(x, wpk, bias, y, p, st) : launch_conv2d_halo_reg<T, 64, 8>(x, wpk, bias, y, p, st);
+        return p.cin == 128 ? launch_conv2d_c128<T>(x, wpk, bias, y, p, st) : launch_conv2d_halo_reg<T, 64, 8>(x, wpk, bias, y, p, st);
     // 256 input channels (third block of the PointPillars RPN, 50 x 50 maps): 4 x 16 tiles -- 55 KB of halo, two workgroups per CU,
     // 416 workgroups at batch 4 -- on the two-stage loop (the generic implicit GEMM ran these layers at 0.11 of the MFMA peak)
     if (conv2d_variant() == 13 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && p.cin == 256)
@@ -1868,9 +2043,9 @@ static int conv2d_tiles_impl(const void *x, int batch, int h, int w, const void 
     p.m = (long long)batch * h * w;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == SEC_BF16)
-        return launch_conv2d_halo_reg<__hip_bfloat16, 128, 8, 2>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background,
+        return launch_conv2d_c128<__hip_bfloat16>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background,
                                                                  nbr_masks, background_in);
-    return launch_conv2d_halo_reg<__half, 128, 8, 2>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background, nbr_masks,
+    return launch_conv2d_c128<__half>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background, nbr_masks,
                                                      background_in);
 }
 
@@ -1909,9 +2084,9 @@ SEC_API int sec_conv2d_nhwc_tiles_tail(const void *x, int batch, int h, int w, c
     hipStream_t st = (hipStream_t)stream;
     // y of the conv itself does not exist: the kernel's `y` is never dereferenced on the TAIL path (background == NULL: lazy form)
     if (dtype == SEC_BF16)
-        return launch_conv2d_halo_reg<__hip_bfloat16, 128, 8, 2, false, 1, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts,
+        return launch_conv2d_c128<__hip_bfloat16, false, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts,
                                                                                        nullptr, nbr_masks, background_in, nullptr, nullptr, nullptr, nullptr, tail);
-    return launch_conv2d_halo_reg<__half, 128, 8, 2, false, 1, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts, nullptr,
+    return launch_conv2d_c128<__half, false, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts, nullptr,
                                                                            nbr_masks, background_in, nullptr, nullptr, nullptr, nullptr, tail);
 }
 
@@ -2044,7 +2219,7 @@ SEC_API int sec_conv2d_nhwc_x3(const void *x_hi, const void *x_lo, int batch, in
     p.relu = relu & 1; p.zskip = (relu >> 1) & 1; p.stagger = 0;
     p.ho = h; p.wo = w;
     p.m = (long long)batch * h * w;
-    return launch_conv2d_halo_reg<__hip_bfloat16, 128, 8, 2, false, 1, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
+    return launch_conv2d_c128<__hip_bfloat16, false, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
                                                                               nullptr, nullptr, nullptr, nullptr, nullptr, x_lo, y_lo);
 }
 
@@ -2062,7 +2237,7 @@ SEC_API int sec_conv2d_nhwc_x3_tiles(const void *x_hi, const void *x_lo, int bat
     p.relu = relu & 1; p.zskip = 0; p.stagger = 0;
     p.ho = h; p.wo = w;
     p.m = (long long)batch * h * w;
-    return launch_conv2d_halo_reg<__hip_bfloat16, 128, 8, 2, false, 1, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
+    return launch_conv2d_c128<__hip_bfloat16, false, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
                                                                               tile_order, live_counts, background_hi, nbr_masks, background_in_hi,
                                                                               x_lo, y_lo, background_lo, background_in_lo);
 }
@@ -2083,8 +2258,8 @@ SEC_API int sec_conv2d_nhwc_gather(const void *features, long long feature_rows,
     hipStream_t st = (hipStream_t)stream;
     const unsigned fb = (unsigned)(feature_rows * 128);
     if (dtype == SEC_BF16)
-        return launch_conv2d_halo_reg<__hip_bfloat16, 128, 8, 2, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
-    return launch_conv2d_halo_reg<__half, 128, 8, 2, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
+        return launch_conv2d_c128<__hip_bfloat16, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
+    return launch_conv2d_c128<__half, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
 }
 
 SEC_API int sec_conv1x1_chain_nhwc(const void *x, long long pixels, const void *packed_w1, const float *bias1, int relu1,

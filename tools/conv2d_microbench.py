@@ -55,3 +55,31 @@ if os.environ.get("FP32"):
     wfcl = wf.contiguous(memory_format=torch.channels_last)
     t = bench(lambda: ops.bias_act_(torch.nn.functional.conv2d(xf, wfcl, None, 1, 1), b, True))
     print(f"fp32 F.conv2d channels-last + fused bias/relu: {t:.1f} us  {flop / t / 1e6:.1f} TFLOP/s  {flop / t / 1e6 / PEAK:.2f} of peak")
+if os.environ.get("AB_LOOPS"):
+    # Both main loops of the 128-channel conv INTERLEAVED in one process (same clocks, same box state): the switch SEC_CONV2D_MFMA is
+    # read once per loaded library, so a second copy of the library is loaded and latched on the 32x32x16 loop.  Post-ReLU inputs.
+    import ctypes, shutil, tempfile
+    from second_amd import runtime as rt
+    xr = torch.relu(torch.randn(8, 128, 200, 176, device="cuda")).bfloat16().contiguous(memory_format=torch.channels_last)
+    y = torch.empty_like(xr)
+    tmp = tempfile.mkdtemp()
+    lib32 = ctypes.CDLL(shutil.copy(rt.LIB_PATH, os.path.join(tmp, "libsecond_hip_mfma32.so")))
+    lib32.sec_last_kernel_name.restype = ctypes.c_char_p
+    P, I = ctypes.c_void_p, ctypes.c_int
+    def run(l):
+        rc = l.sec_conv2d_nhwc(P(xr.data_ptr()), I(8), I(200), I(176), I(128), P(pk.data_ptr()), P(b.data_ptr()), I(128), I(3), I(1), I(1), I(1),
+                               P(y.data_ptr()), I(rt.dtype_code(xr.dtype)), P(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, rc
+    assert "SEC_CONV2D_MFMA" not in os.environ
+    run(rt.lib())                                     # latches the default loop
+    os.environ["SEC_CONV2D_MFMA"] = "32"
+    run(lib32)
+    del os.environ["SEC_CONV2D_MFMA"]
+    names = {"16x16x32": rt.lib().sec_last_kernel_name().decode(), "32x32x16": lib32.sec_last_kernel_name().decode()}
+    print("loops:", names)
+    assert ", 128, 8, 3, " in names["16x16x32"] and ", 128, 8, 2, " in names["32x32x16"]
+    for rnd in range(int(os.environ.get("AB_ROUNDS", "4"))):
+        t32 = bench(lambda: run(lib32))
+        t16 = bench(lambda: run(rt.lib()))
+        print(f"round {rnd}: 32x32x16 {t32:.2f} us  {flop / t32 / 1e6:.0f} TFLOP/s | 16x16x32 {t16:.2f} us  {flop / t16 / 1e6:.0f} TFLOP/s | ratio {t16 / t32:.4f}")
+    shutil.rmtree(tmp, ignore_errors=True)
