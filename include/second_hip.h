@@ -977,6 +977,37 @@ int sec_kitti_eval_pr(int images, const int *gt_offsets, const int *dt_offsets, 
                       int configs, const double *thresholds, const int *n_thresholds, int metric, int compute_aos, int *pr_counts,
                       double *pr_similarity, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * KITTI annotations from detections: KittiDataset.convert_detection_to_kitti_annos (second/data/kitti_dataset.py:38-107) for all
+ * images of a val pass in one call.  A per-frame host loop of numpy calls and list appends in the reference.
+ *
+ * The n detections of all images lie flat in dataset order: boxes [n, 7] float32 lidar boxes (x, y, z, w, l, h, r), scores [n]
+ * float32, labels [n] int32, det_offsets [images + 1] int32 (image i owns rows [det_offsets[i], det_offsets[i + 1]); rows outside
+ * [det_offsets[0], det_offsets[images]) are dropped).  Per image: lidar2cam [images, 4, 4] float64 = R0_rect @ Tr_velo_to_cam (formed
+ * by the host), P2 [images, 4, 4] float64, image_hw [images, 2] int32 = (height, width).  All device pointers; inputs are never
+ * written.
+ *
+ * Per detection, in float64 unless stated, the reference's operations in its order:
+ *   z' = fl32(z - fl32(h / 2)); location = lidar2cam[:3] . (x, y, z', 1); dimensions = (l, h, w); rotation_y = r;
+ *   corners (+-l/2, {-h, 0}, +-w/2) rotated about axis 1 by rotation_y (float64 sin / cos), + location;
+ *   image point (P2[0,:3].c / P2[2,:3].c, P2[1,:3].c / P2[2,:3].c): the fourth column of P2 takes no part (the reference appends
+ *   zeros), nothing is clamped behind the camera;
+ *   bbox = (min u, min v, max u, max v) over the eight corners, a NaN propagates (np.min / np.max);
+ *   dropped if bbox[0] > W or bbox[1] > H or bbox[2] < 0 or bbox[3] < 0 (false for a NaN: such a row is kept), else
+ *   bbox[2:] = minimum(., (W, H)), bbox[:2] = maximum(., 0), NaN-propagating;
+ *   alpha = -fl32(atan2(-y, x)) + r, the arc tangent evaluated in float64 and rounded to float32 once.
+ * Outputs, the kept rows compacted in order (each array has room for n rows): out_bbox [., 4], out_alpha [.], out_box3d [., 7] =
+ * location, dimensions, rotation_y (float64); out_score (float32), out_label, out_src = the flat input row (int32); out_offsets
+ * [images + 1] int32, image i's kept rows are [out_offsets[i], out_offsets[i + 1]).  Three launches on the stream, no host read.
+ * NULL where an array is needed or a negative count: SEC_E_INVALID; workspace under sec_kitti_annos_workspace_bytes(n):
+ * SEC_E_WORKSPACE; both decided before any launch.  n == 0 or images == 0: out_offsets all zero.
+ * --------------------------------------------------------------------------------------------- */
+size_t sec_kitti_annos_workspace_bytes(int n);
+int sec_kitti_annos_f64(const float *boxes, const float *scores, const int *labels, int n, const int *det_offsets, int images,
+                        const double *lidar2cam, const double *P2, const int *image_hw, double *out_bbox, double *out_alpha,
+                        double *out_box3d, float *out_score, int *out_label, int *out_src, int *out_offsets, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -330,7 +330,7 @@ def rotate_iou_gpu_eval(boxes, query_boxes, criterion=-1, device_id=0):
     return out.cpu().numpy().astype(boxes.dtype)
 
 
-def accelerate_eval(statistics=None):
+def accelerate_eval(statistics=None, annos=None):
     """Route the KITTI evaluation's rotated-IoU calls to the MI355X: ``second/utils/eval.py:124`` (bev_box_overlap) and
     ``:175`` (box3d_overlap) call ``rotate_iou_gpu_eval(boxes, qboxes, criterion)``, a numba.cuda kernel that cannot run
     here; :func:`rotate_iou_gpu_eval` above replaces it (all four criteria; pinned on the original by
@@ -340,11 +340,23 @@ def accelerate_eval(statistics=None):
     :func:`second_amd.kitti_eval.eval_class_v3`; the original stays at ``ev._second_amd_original_eval_class_v3``.  ``do_eval_v2`` /
     ``do_eval_v3`` resolve the name at call time, so ``get_official_eval_result`` and ``get_coco_eval_result`` use it unchanged.
     (With it ``np.linspace`` accepts an integral float count again, which ``do_coco_style_eval`` passes.)
-    ``statistics=None`` reads SEC_EVAL_DEVICE: only ``1`` turns it on."""
+    ``statistics=None`` reads SEC_EVAL_DEVICE: only ``1`` turns it on.
+    ``annos=True``: ``KittiDataset.convert_detection_to_kitti_annos`` (the per-frame host loop between the detector and the
+    evaluation) is replaced by :func:`second_amd.kitti_annos.convert_detection_to_kitti_annos`; the original stays at
+    ``KittiDataset._second_amd_original_convert_detection_to_kitti_annos`` and serves what is outside the kernel's contract.
+    ``annos=None`` reads SEC_EVAL_ANNOS: only ``1`` turns it on; off, nothing of ``second.data.kitti_dataset`` is touched."""
     import importlib
     ev = importlib.import_module("second.utils.eval")
     if statistics is None:
         statistics = os.environ.get("SEC_EVAL_DEVICE") == "1"
+    if annos is None:
+        annos = os.environ.get("SEC_EVAL_ANNOS") == "1"
+    if annos:
+        from .. import kitti_annos
+        cls = importlib.import_module("second.data.kitti_dataset").KittiDataset
+        if not hasattr(cls, kitti_annos.ORIGINAL):
+            setattr(cls, kitti_annos.ORIGINAL, cls.convert_detection_to_kitti_annos)
+            cls.convert_detection_to_kitti_annos = kitti_annos.convert_detection_to_kitti_annos
     if not getattr(ev, "_second_amd_accelerated", False):
         ev._second_amd_original_rotate_iou = ev.rotate_iou_gpu_eval
         ev.rotate_iou_gpu_eval = rotate_iou_gpu_eval

@@ -40,8 +40,14 @@ def _offsets(counts):
 
 
 def pack(gt_annos, dt_annos):
-    """The annotation dicts (kitti_common.get_label_annos format) as flat float64 / int32 numpy arrays with per-image offsets."""
+    """The annotation dicts (kitti_common.get_label_annos format) as flat float64 / int32 numpy arrays with per-image offsets.
+    ``dt_annos`` a ``kitti_annos.DeviceAnnoList`` that is still as it was built (its ``handoff()``): the detection side is not packed
+    again -- see :func:`_pack_handoff`."""
     assert len(gt_annos) == len(dt_annos)
+    handoff = getattr(dt_annos, "handoff", None)
+    held = handoff() if callable(handoff) else None
+    if held is not None:
+        return _pack_handoff(gt_annos, dt_annos, held)
     gt_num = np.array([len(a["name"]) for a in gt_annos], np.int64)
     dt_num = np.array([len(a["name"]) for a in dt_annos], np.int64)
     gt_names = [n for a in gt_annos for n in a["name"]]
@@ -60,6 +66,30 @@ def pack(gt_annos, dt_annos):
     dontcare = np.array([n == "DontCare" for n in gt_names], bool)               # case-sensitive, as clean_data
     p["dc_bbox"] = np.ascontiguousarray(p["gt_bbox"][dontcare])
     p["dc_off"] = _offsets(np.array([int(dontcare[a:b].sum()) for a, b in zip(p["gt_off"][:-1], p["gt_off"][1:])], np.int64))
+    return p
+
+
+_NO_DETECTIONS = {"name": np.zeros(0, "U1"), "bbox": np.zeros((0, 4)), "alpha": np.zeros(0), "score": np.zeros(0), "location": np.zeros((0, 3)),
+                  "dimensions": np.zeros((0, 3)), "rotation_y": np.zeros(0)}
+
+
+def _pack_handoff(gt_annos, dt_annos, held):
+    """:func:`pack` for detections that are on the device already (``held``: dt_bbox, dt_alpha, dt_score, dt_box3d, dt_name, dt_off as
+    device tensors, dt_num / max_dt on the host).  The gt side is packed by the plain route against images without detections; the
+    dt_* arrays are left out of the result and the tensors travel under ``"_device"``, where :func:`run_stages` also leaves what it
+    uploads.  The result is cached on the list, keyed by the identity and length of ``gt_annos``: the six eval_class_v3 calls of a val
+    pass (get_official_eval_result, get_coco_eval_result) pack and upload the gt once."""
+    cache = dt_annos.pack_cache
+    if cache is not None and cache[0] is gt_annos and cache[1] == len(gt_annos):
+        return cache[2]
+    p = pack(gt_annos, [_NO_DETECTIONS] * len(gt_annos))
+    for k in ("dt_name", "dt_bbox", "dt_alpha", "dt_score", "dt_box3d"):
+        del p[k]
+    dt_num = np.asarray(held["dt_num"], np.int64)
+    p["dt_off"], p["max_dt"] = _offsets(dt_num), int(held["max_dt"])
+    p["ov_off"] = _offsets(np.diff(p["gt_off"].astype(np.int64)) * dt_num)
+    p["_device"] = {k: held[k] for k in ("dt_name", "dt_bbox", "dt_alpha", "dt_score", "dt_box3d", "dt_off")}
+    dt_annos.pack_cache = (gt_annos, len(gt_annos), p)
     return p
 
 
@@ -84,7 +114,11 @@ def run_stages(p, current_classes, difficultys, metric, min_overlaps, compute_ao
     import torch
     from . import ops
     dev = torch.device(device if device is not None else "cuda")
-    t = {k: torch.from_numpy(v).to(dev) for k, v in p.items() if isinstance(v, np.ndarray)}
+    held = p.get("_device")                                             # a hand-off pack: tensors that are on the device already
+    t = {k: torch.from_numpy(v).to(dev) for k, v in p.items() if isinstance(v, np.ndarray) and (held is None or k not in held)}
+    if held is not None:
+        held.update(t)                                                  # the gt side is uploaded once per cached pack
+        t = {k: v.to(dev) for k, v in held.items()}
     metric = int(metric)
     min_overlaps = np.asarray(min_overlaps, np.float64)
     num_k = min_overlaps.shape[0]

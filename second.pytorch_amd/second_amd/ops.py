@@ -1463,6 +1463,62 @@ def kitti_eval_pr(gt_offsets, dt_offsets, dc_offsets, ov_offsets, overlaps, dt_s
     return counts, sim
 
 
+def kitti_annos(boxes, scores, labels, det_offsets, lidar2cam, P2, image_hw):
+    """KittiDataset.convert_detection_to_kitti_annos (kitti_dataset.py:38-107) for the flat detections of all images: boxes float32
+    [n, 7], scores float32 [n], labels int32 [n], det_offsets int32 [images + 1], lidar2cam / P2 float64 [images, 4, 4], image_hw int32
+    [images, 2] (include/second_hip.h, sec_kitti_annos_f64).  No synchronisation.  -> dict of views of ONE uint8 device buffer
+    (``packed``, so that a single copy brings everything to the host; :func:`kitti_annos_views` cuts a host copy the same way):
+    bbox f64 [n, 4], alpha f64 [n], box3d f64 [n, 7], score f32 [n], label / src int32 [n] -- kept rows first, in order, the rest
+    undefined -- and out_off int32 [images + 1]."""
+    rt.require_gpu(boxes, scores, labels, det_offsets, lidar2cam, P2, image_hw)
+    n, images, dev = boxes.shape[0], det_offsets.numel() - 1, boxes.device
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and tuple(boxes.shape) == (n, 7)
+    assert scores.dtype == torch.float32 and scores.is_contiguous() and tuple(scores.shape) == (n,)
+    _ke_i32(labels, n); _ke_i32(det_offsets); _ke_i32(image_hw, images * 2)
+    _ke_f64(lidar2cam, (images, 4, 4)); _ke_f64(P2, (images, 4, 4))
+    assert images >= 0
+    packed = torch.empty((kitti_annos_layout(n, images)["bytes"],), dtype=torch.uint8, device=dev)
+    v = kitti_annos_views(packed, n, images)
+    l = rt.lib()
+    ws = rt.workspace(l.sec_kitti_annos_workspace_bytes(n), dev)
+    rc = l.sec_kitti_annos_f64(rt.ptr(boxes), rt.ptr(scores), rt.ptr(labels), n, rt.ptr(det_offsets), images, rt.ptr(lidar2cam), rt.ptr(P2),
+                               rt.ptr(image_hw), rt.ptr(v["bbox"]), rt.ptr(v["alpha"]), rt.ptr(v["box3d"]), rt.ptr(v["score"]), rt.ptr(v["label"]),
+                               rt.ptr(v["src"]), rt.ptr(v["out_off"]), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, "sec_kitti_annos_f64")
+    v["packed"] = packed
+    return v
+
+
+_KITTI_ANNOS_FIELDS = (("bbox", "float64", 4), ("alpha", "float64", 1), ("box3d", "float64", 7), ("score", "float32", 1), ("label", "int32", 1),
+                       ("src", "int32", 1))
+
+
+def kitti_annos_layout(n, images):
+    """Byte offsets of the sections of :func:`kitti_annos`' buffer (each 256-byte aligned) -> {name: (offset, dtype name, shape), 'bytes'}."""
+    out, off = {}, 0
+    for name, dt, cols in _KITTI_ANNOS_FIELDS + (("out_off", "int32", 1),):
+        rows = images + 1 if name == "out_off" else n
+        out[name] = (off, dt, (rows,) if cols == 1 else (rows, cols))
+        off += (rows * cols * (8 if dt == "float64" else 4) + 255) // 256 * 256
+    out["bytes"] = max(off, 256)
+    return out
+
+
+def kitti_annos_views(packed, n, images):
+    """The sections of :func:`kitti_annos`' buffer as typed views: ``packed`` is the uint8 device tensor or a uint8 numpy copy of it."""
+    import numpy as np
+    views = {}
+    for name, section in kitti_annos_layout(n, images).items():
+        if name == "bytes":
+            continue
+        off, dt, shape = section
+        count = int(np.prod(shape))
+        nbytes = count * (8 if dt == "float64" else 4)
+        sec = packed[off:off + nbytes]
+        views[name] = (sec.view(getattr(torch, dt)) if torch.is_tensor(packed) else sec.view(getattr(np, dt))).reshape(shape)
+    return views
+
+
 @_traced("nms_sorted")
 def nms_sorted(dets, counts, thresh, kind="rotate", semantics="numba", eps=1.0, post_max=0, exact_clip=False):
     """Greedy NMS of score-sorted boxes. dets [B,max_n,stride] float32, counts [B] int32 (device).

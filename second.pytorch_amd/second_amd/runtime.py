@@ -40,7 +40,7 @@ SYMBOLS = [
     "sec_db_sample_select_f32", "sec_db_sample_merge_points_workspace_bytes", "sec_db_sample_merge_points_f32",
     "sec_anchor_area_mask_workspace_bytes", "sec_anchor_area_mask", "sec_predict_select_masked", "sec_assign_targets_masked_f32",
     "sec_kitti_eval_overlaps", "sec_kitti_eval_flags", "sec_kitti_eval_tp_scores", "sec_kitti_eval_thresholds",
-    "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr",
+    "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr", "sec_kitti_annos_workspace_bytes", "sec_kitti_annos_f64",
 ]
 
 _lib = None
@@ -111,7 +111,8 @@ def lib():
                      "sec_assign_targets_workspace_bytes", "sec_second_loss_workspace_bytes", "sec_heads_loss_workspace_bytes",
                      "sec_conv2d_wgrad_workspace_bytes", "sec_bn_train_workspace_bytes", "sec_pfn_train_workspace_bytes",
                      "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes",
-                     "sec_anchor_area_mask_workspace_bytes", "sec_kitti_eval_pr_workspace_bytes"):
+                     "sec_anchor_area_mask_workspace_bytes", "sec_kitti_eval_pr_workspace_bytes",
+                     "sec_kitti_annos_workspace_bytes"):
             getattr(l, name).restype = ctypes.c_size_t
         if os.environ.get("SEC_FP32_MODE", "").lower() == "exact":      # process default of ops.set_fp32_mode
             l.sec_set_fp32_mode(1)
@@ -240,6 +241,8 @@ def lib():
         l.sec_kitti_eval_pr_workspace_bytes.argtypes = [ci, ci]
         l.sec_kitti_eval_pr.argtypes = [ci, vp, vp, vp, vp, vp, ll, vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, ci, ci, vp, vp, ci, ci, vp,
                                         vp, vp, sz, vp]
+        l.sec_kitti_annos_workspace_bytes.argtypes = [ci]
+        l.sec_kitti_annos_f64.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         _lib = l
     return _lib
 
