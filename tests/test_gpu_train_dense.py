@@ -506,7 +506,8 @@ def test_two_graph_form_of_the_captured_step_equals_the_one_graph_form(monkeypat
 
 
 def test_flat_adamw_matches_torch_adamw_with_clipping():
-    """sec_flat_adamw_f32 (clip_grad_norm_ + AdamW on one flat buffer, two launches) against torch.nn.utils.clip_grad_norm_ +
+    """FlatAdamW.step = sec_flat_adamw_dev_f32 (clip_grad_norm_ + AdamW on one flat buffer, two launches, hyper-parameters read from
+    device memory; the by-value entry sec_flat_adamw_f32 is pinned to it bit for bit in tests/test_gpu_train_edges.py) against torch.nn.utils.clip_grad_norm_ +
     torch.optim.AdamW on the same tensors for four steps: gradients large enough to be clipped in some steps and not in others."""
     from second_amd.training import FlatAdamW
     g = torch.Generator().manual_seed(3)
