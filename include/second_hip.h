@@ -498,6 +498,33 @@ int sec_conv2d_nhwc(const void *x, int batch, int h, int w, int cin, const void 
                     const float *bias, int cout, int ksize, int stride, int pad, int relu, void *y,
                     int dtype, void *stream);
 
+/* Which kernel a 16-bit conv2d entry point dispatches for a shape (no launch, no HIP call): the instantiation as sec_last_kernel_name
+ * reports it after the call, e.g. "k_conv2d_halo_reg<__half, 128, 8, 3, false>"; "" where the entry point would return
+ * SEC_E_UNSUPPORTED or SEC_E_INVALID for these arguments.  The launch and this query ask the same decision function.  `call_form`
+ * names the entry point:
+ *    SEC_CONV2D_FORM_PLAIN      sec_conv2d_nhwc
+ *    SEC_CONV2D_FORM_INTO       sec_conv2d_nhwc_into
+ *    SEC_CONV2D_FORM_ROWS       sec_conv2d_nhwc_rows
+ *    SEC_CONV2D_FORM_TILES      sec_conv2d_nhwc_tiles, sec_conv2d_nhwc_tiles_lazy
+ *    SEC_CONV2D_FORM_TAIL       sec_conv2d_nhwc_tiles_tail
+ *    SEC_CONV2D_FORM_X3         sec_conv2d_nhwc_x3
+ *    SEC_CONV2D_FORM_X3_TILES   sec_conv2d_nhwc_x3_tiles
+ *    SEC_CONV2D_FORM_GATHER     sec_conv2d_nhwc_gather
+ * The forms from TILES on exist for one layer (cin 128, 3x3 / stride 1 / pad 1; TAIL: cout 128; X3: SEC_BF16 planes) and answer ""
+ * for any other.  Limits on arguments the query does not take (feature_rows, cout2) stay with the entry points.  The answer depends
+ * on two switches read once per process: SEC_CONV2D_PATCH=0 (no strided / patch kernel on the plain form) and SEC_CONV2D_MFMA=32
+ * (the 32x32x16 loop for the 128-channel 3x3 layers). */
+#define SEC_CONV2D_FORM_PLAIN 0
+#define SEC_CONV2D_FORM_INTO 1
+#define SEC_CONV2D_FORM_ROWS 2
+#define SEC_CONV2D_FORM_TILES 3
+#define SEC_CONV2D_FORM_TAIL 4
+#define SEC_CONV2D_FORM_X3 5
+#define SEC_CONV2D_FORM_X3_TILES 6
+#define SEC_CONV2D_FORM_GATHER 7
+const char *sec_conv2d_fwd_plan_name(int batch, int h, int w, int cin, int cout, int ksize, int stride, int pad, int dtype,
+                                     int call_form);
+
 /* The same 3x3 / stride 1 / pad 1, 128-input-channel convolution for fp32 networks -- the reference's default precision
  * (second/pytorch/train.py:232-235, 497-500: float_dtype = torch.float32 unless mixed precision is enabled; rpn.py:468-497) -- on
  * the bf16 matrix pipe: every fp32 operand travels as TWO bf16 planes, v = hi + lo with hi = bf16(v), lo = bf16(v - hi), and

@@ -5,7 +5,6 @@
 #include <type_traits>
 #include <stdio.h>
 #include <stdlib.h>
-#include <stdlib.h>
 
 namespace sec {
 
@@ -356,10 +355,6 @@ template <int CH, int HW_, bool COLKEY> __device__ __forceinline__ int halo_key(
 // low bit of the slot = the low bit of the chunk and gives the eight columns of either half eight distinct even keys.
 template <int ROLL> __device__ __forceinline__ unsigned halo_colkey(unsigned hx) { return ROLL == 3 ? (2u * hx) & 15u : hx & 15u; }
 
-#ifdef SEC_CONV2D_EXPERIMENTS   // superseded 3x3 kernels (register-staged implicit GEMM, LDS weight slabs / rings): A/B builds only
-#include "../../tools/kernel_experiments/dense_conv2d_ab.inc"
-#endif
-
 // ---- halo kernel with register-resident weights ----------------------------------------------------------------
 // PMC on the LDS-slab kernels (profiles/r01_g_pmc_conv2d.txt): MFMA pipe 38 % busy, waves parked 48 % of their
 // cycles (one s_barrier per 16 KB weight slab keeps all eight waves in lock-step) and only 12 of 16 wave slots
@@ -376,8 +371,8 @@ template <int ROLL> __device__ __forceinline__ unsigned halo_colkey(unsigned hx)
 // the clock the chip holds under it, and holds 1.68 instead of 1.54 GHz (dense form, batch 8, 200 x 176: 67.2 -> 60.2 us, both loops
 // interleaved in one process; DESIGN_APPENDIX "MFMA shape record").  SEC_CONV2D_MFMA=32 selects ROLL == 2 for A/B (conv2d_c128_roll).
 // ROLL == 2 (the loop until then): m-tiles pair output rows (mt, mt + 4) so that SIX halo fragments per (dx, k-step)
-// feed the twelve MFMAs of the three kernel rows -- half the LDS reads of one fragment per MFMA (ROLL == 1, kept for A/B as
-// SEC_CONV2D_VARIANT=15): 79.9 -> 74.0 us on one box, 76.7 -> 71.8 us on another (batch 8, 200 x 176, 128 -> 128).  Setting wave
+// feed the twelve MFMAs of the three kernel rows -- half the LDS reads of one fragment per MFMA (the loop before it: DESIGN_APPENDIX):
+// 79.9 -> 74.0 us on one box, 76.7 -> 71.8 us on another (batch 8, 200 x 176, 128 -> 128).  Setting wave
 // priorities (prologue / epilogue above the loop, and the reverse) and a 12-deep B ring were measured on that loop: +1 ... +5 % slower.
 // Both ROLL loops: B fragments in an 8-deep ring loaded 7 fragments ahead, and halo addresses built
 // from a per-lane base, a dx-only swizzle key and ds_read immediates.  The first version recomputed `hp % HW_` per m-tile and
@@ -414,6 +409,7 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                                                             const T *__restrict__ x_lo = nullptr, T *__restrict__ y_lo = nullptr,
                                                             const T *__restrict__ background_lo = nullptr,
                                                             const T *__restrict__ bg_in_lo = nullptr, ConvTailArgs tail = ConvTailArgs{}) {
+    static_assert(ROLL == 0 || ROLL == 2 || ROLL == 3, "main loops: 0 two-stage, 2 shared-row 32x32x16, 3 row-streamed 16x16x32");
     static_assert(!GATHER || (ROLL >= 2 && CIN == 128), "gather prologue: the shared-row loop on two 64-channel planes");
     static_assert(!TAIL || (ROLL >= 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && !X3), "fused 1x1 tail: the lazy list form of the 128-channel conv");
     static_assert(!X3 || (ROLL >= 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && std::is_same<T, __hip_bfloat16>::value),
@@ -787,9 +783,6 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         } else if constexpr (ROLL >= 2) {
 #pragma unroll
             for (int f = 0; f < RD - 1; ++f) br[f] = ld_b((f % 3) * 48 + (f / 3) * 2);
-        } else if constexpr (ROLL) {
-#pragma unroll
-            for (int f = 0; f < RD - 1; ++f) br[f] = wlane[(size_t)f * 2 * p.cout];
         } else {
             load_b(0, bq[0]);
         }
@@ -898,7 +891,7 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         } else if constexpr (ROLL >= 2) {
             // Shared-row fragments.  An m-tile pairs output rows (mt, mt + 4), so its A fragment for kernel row dy is the pair of
             // halo rows (mt + dy, mt + dy + 4) = F[mt + dy]: for one (dx, k-step) SIX fragments F[0..5] feed all 3 x 4 = 12 MFMAs
-            // of the three kernel rows -- half the ds_read_b128 traffic of the ROLL == 1 loop (12 reads per 12 MFMAs), same B
+            // of the three kernel rows -- half the ds_read_b128 traffic of one fragment per MFMA (12 reads per 12 MFMAs), same B
             // stream (one fragment per four MFMAs), same accumulators.  Rolled over dx, unrolled over 8 k-steps x 3 kernel rows;
             // B fragment j = (k-step, dy) of this dx sits at chunk dy * 48 + dx * 16 + 2 * k-step of the packed [tap][cin8][cout].
             static_assert(ROLL < 2 || (KC == 2 && CH == 16 && TH == 8), "8 k-steps per tap, rows (mt, mt + 4)");
@@ -958,52 +951,6 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                 }
             }
             live = false;
-        } else if constexpr (ROLL) {
-            // Rolled over the kernel ROW dy, unrolled over its 3 taps x 8 k-steps (three turns of the 8-deep B ring; fragment g
-            // of the packed weights [tap][cin8][cout] sits at chunk 2 g).  The halo address of (pixel, tap, chunk) splits into
-            //   lane base + dy * row pitch            (one VGPR, updated per dy)
-            //   ^ chunk swizzle                        (key = halo column & 15 = ((r & 15) + dx) & 15: depends on dx only)
-            //   + (mt * 2 * HW_ + dx) * 256            (ds_read immediate)
-            // so a k-step costs two VALU address instructions instead of a `% HW_` per m-tile (quarter-rate multiplies that
-            // competed with the MFMA issue slots).
-            static_assert(!ROLL || (KC == 2 && CH == 16), "ring of 8 == k-steps per tap");
-            const char *halb = reinterpret_cast<const char *>(hal);
-            const int colr = r & 15;
-            unsigned kk[3];
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) kk[dx] = (unsigned)(hh ^ ((colr + dx) & 15)) << 4;
-            const unsigned base0 = (unsigned)((r >> 4) * HW_ + colr) * (CH * 16);
-            auto load_a2 = [&](unsigned bdy, int dx, int cidx, uint4 (&dst)[MT]) {
-                const unsigned a = bdy + (((unsigned)cidx << 4) ^ kk[dx]);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) dst[mt] = *reinterpret_cast<const uint4 *>(halb + a + (mt * 2 * HW_ + dx) * (CH * 16));
-            };
-            if (live) {
-                load_a2(base0, 0, 0, af[0]);
-#pragma unroll 1
-                for (int dy = 0; dy < 3; ++dy) {
-                    // unconditional prefetches (the last row re-reads its own first fragments): static wait counts, no branches
-                    const int dyn = dy < 2 ? dy + 1 : 2;
-                    const unsigned bdy = base0 + dy * (HW_ * CH * 16), bdn = base0 + dyn * (HW_ * CH * 16);
-                    const uint4 *wt = wlane + (size_t)dy * 48 * p.cout, *wn = wlane + (size_t)dyn * 48 * p.cout;
-#pragma unroll
-                    for (int j = 0; j < 24; ++j) {
-#if defined(SEC_CONV2D_ABL) && SEC_CONV2D_ABL == 3
-                        br[(j + 7) & 7] = wlane[(size_t)((j + 7) & 1) * 2 * p.cout];   // ablation build: B fragments always from two hot lines
-#else
-                        br[(j + 7) & 7] = j + 7 < 24 ? wt[(size_t)(j + 7) * 2 * p.cout] : wn[(size_t)(j + 7 - 24) * 2 * p.cout];
-#endif
-                        if (j + 1 < 24) load_a2(bdy, (j + 1) / 8, ((j + 1) % 8) * 2, af[(j + 1) & 1]);
-                        else load_a2(bdn, 0, 0, af[0]);
-#pragma unroll
-                        for (int mt = 0; mt < MT; ++mt) acc[mt] = MfmaD<T>::run(br[j & 7], af[j & 1][mt], acc[mt]);
-                        // pins [B prefetch, 4 A reads, 4 MFMAs] per k-step: free scheduling sinks the loads towards their use
-                        // (126 VGPRs, 96 us instead of 84 us); a 3-deep A ring measured no gain
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-            live = false;                           // skip the two-stage loop below
         }
 #pragma unroll 2
         for (int it = 0; live && it < NIT; ++it) {
@@ -1257,17 +1204,26 @@ extern "C" __attribute__((visibility("default"))) int sec__debug_timeline2(long 
 }
 #endif
 
+// What a conv2d launch takes besides (x, weights, bias, y): everything is optional and belongs to one call form or another.
+struct Conv2dExtra {
+    const int *site_map = nullptr;                  // gather / rows forms: [batch][2][h][w] / [batch][h][w] row + 1
+    unsigned feat_bytes = 0;                        // ... and the size of the feature rows `x` then points to
+    const unsigned short *tile_order = nullptr;     // list forms: one layer of sec_rpn_tile_live
+    const int *live_counts = nullptr;
+    const void *background = nullptr;               // this layer's empty-frame output (copied to the other tiles), or none
+    const unsigned short *nbr_masks = nullptr;      // lazy forms: which neighbours the producer wrote ...
+    const void *bg_in = nullptr;                    // ... and the producer's empty-frame output for the others
+    const void *x_lo = nullptr;                     // x3 forms: the lo planes of x, y and the two backgrounds
+    void *y_lo = nullptr;
+    const void *background_lo = nullptr, *bg_in_lo = nullptr;
+    ConvTailArgs tail = ConvTailArgs{};             // tail form: the fused 1x1 pair
+};
+
 template <typename T, int CIN, int TH, int ROLL = 0, bool GATHER = false, int NSPLIT = 1, bool X3 = false, bool TAIL = false>
 static int launch_conv2d_halo_reg(const void *x, const void *wpk, const float *bias, void *y, const Conv2dParams &p, hipStream_t st,
-                                  const int *site_map = nullptr, unsigned feat_bytes = 0, const unsigned short *tile_order = nullptr,
-                                  const int *live_counts = nullptr, const void *background = nullptr,
-                                  const unsigned short *nbr_masks = nullptr, const void *bg_in = nullptr,
-                                  const void *x_lo = nullptr, void *y_lo = nullptr, const void *background_lo = nullptr,
-                                  const void *bg_in_lo = nullptr, const ConvTailArgs &tail = ConvTailArgs{}) {
-    constexpr size_t lds_tile = (size_t)(TH + 2) * 18 * (CIN / 8) * 16;
+                                  const Conv2dExtra &e) {
     // (padding the dynamic LDS to hold 2 instead of 3 workgroups per CU was measured in round 3: slower in every combination)
-    const long lds_pad = 0;
-    const size_t lds = lds_tile + (size_t)lds_pad;
+    constexpr size_t lds = (size_t)(TH + 2) * 18 * (CIN / 8) * 16;
     static bool configured = false;
     auto fn = k_conv2d_halo_reg<T, CIN, TH, ROLL, GATHER, NSPLIT, X3, TAIL>;
     if (!configured) {
@@ -1277,31 +1233,10 @@ static int launch_conv2d_halo_reg(const void *x, const void *wpk, const float *b
     const int ty = div_up(p.h, TH), tx = div_up(p.w, 16);
     const int per_xcd = div_up(p.batch * ty * tx, 8);
     const int gx = per_xcd * 8;
-    if (TAIL) set_last_kernel("k_conv2d_halo_reg<%s, %d, %d, %d, false, 1, false, true>", dtype_name<T>(), CIN, TH, ROLL);
-    else if (X3) set_last_kernel("k_conv2d_halo_reg<%s, %d, %d, %d, false, 1, true>", dtype_name<T>(), CIN, TH, ROLL);
-    else if (NSPLIT == 1) set_last_kernel("k_conv2d_halo_reg<%s, %d, %d, %d, %s>", dtype_name<T>(), CIN, TH, ROLL, GATHER ? "true" : "false");
-    else set_last_kernel("k_conv2d_halo_reg<%s, %d, %d, %d, %s, %d>", dtype_name<T>(), CIN, TH, ROLL, GATHER ? "true" : "false", NSPLIT);
     hipLaunchKernelGGL(fn, dim3(gx, p.cout / (128 / NSPLIT)), dim3(256), lds, st, (const T *)x, (const T *)wpk, bias, (T *)y, p, ty, tx, per_xcd,
-                       site_map, feat_bytes, tile_order, live_counts, (const T *)background, nbr_masks, (const T *)bg_in, (const T *)x_lo, (T *)y_lo,
-                       (const T *)background_lo, (const T *)bg_in_lo, tail);
+                       e.site_map, e.feat_bytes, e.tile_order, e.live_counts, (const T *)e.background, e.nbr_masks, (const T *)e.bg_in,
+                       (const T *)e.x_lo, (T *)e.y_lo, (const T *)e.background_lo, (const T *)e.bg_in_lo, e.tail);
     return check_launch();
-}
-
-// The 128-channel 3x3 convs (every call form) run ONE main loop per process: the 16x16x32 one (ROLL == 3), or with SEC_CONV2D_MFMA=32
-// the 32x32x16 one (ROLL == 2) for A/B -- read once, before the first launch.  Never a mixture: the two loops group the products of
-// an output element differently, and the list, lazy and plain forms are bit-identical to each other only on the same loop.
-static int conv2d_c128_roll() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("SEC_CONV2D_MFMA");
-        v = (e && atoi(e) == 32) ? 2 : 3;
-    }
-    return v;
-}
-template <typename T, bool GATHER = false, bool X3 = false, bool TAIL = false, typename... A>
-static int launch_conv2d_c128(A... a) {
-    return conv2d_c128_roll() == 3 ? launch_conv2d_halo_reg<T, 128, 8, 3, GATHER, 1, X3, TAIL>(a...)
-                                   : launch_conv2d_halo_reg<T, 128, 8, 2, GATHER, 1, X3, TAIL>(a...);
 }
 
 // 1x1 convolutions (the ConvTranspose2d(k=1) "deconv" and the merged heads of the RPN, rpn.py:275-285,386-391) are
@@ -1737,18 +1672,47 @@ static int launch_conv1x1_chain(const void *x, long long m, const void *w1, cons
     return check_launch();
 }
 
-#ifdef SEC_CONV2D_EXPERIMENTS
-constexpr bool kConv2dExperiments = true;
-#else
-constexpr bool kConv2dExperiments = false;   // default build: halo_reg (3x3 s1), 1x1 kernels, LDS-DMA implicit GEMM (everything else)
-#endif
-static int conv2d_variant() {
-    static int v = -1;
-    if (v < 0) v = 13;  // 0 register staged, 1 LDS-DMA implicit GEMM, 2/3/4 halo tile 16x16 / 8x16 / 8x16 with 8 waves
-    return v;
-}
-
 #include "dense_patch.hpp"
+
+// ---- conv2d forward: which kernel a call gets ----------------------------------------------------------------------------------
+// conv2d_fwd_decide holds every shape condition of the 16-bit conv2d entry points; launch_conv2d_plan is a switch over its answer,
+// conv2d_plan_name prints the answer the way a profiler prints the instantiation (sec_last_kernel_name), and
+// sec_conv2d_fwd_plan_name returns that string without a launch.
+enum class Conv2dKernel {
+    kNotTaken,      // no kernel for this (shape, call form, dtype): SEC_E_UNSUPPORTED
+    kHaloReg,       // k_conv2d_halo_reg<T, cin, th, roll, gather, split, x3, tail>: 3x3 / s1 / p1
+    kPatch,         // k_conv2d_patch<T, cin, ks, st, th, tw, split, rows, table>: strided / patch layers (dense_patch.hpp)
+    kConv1x1,       // k_conv1x1_nhwc<T, bn, kConv1x1Tpw>: 1x1 with 128 input channels
+    kGeneric,       // k_conv2d_nhwc_dma<T, bn>: LDS-DMA implicit GEMM, everything else
+};
+enum Conv2dCallForm {   // the entry point that asks (include/second_hip.h)
+    kFormPlain = SEC_CONV2D_FORM_PLAIN, kFormInto = SEC_CONV2D_FORM_INTO, kFormRows = SEC_CONV2D_FORM_ROWS, kFormTiles = SEC_CONV2D_FORM_TILES,
+    kFormTail = SEC_CONV2D_FORM_TAIL, kFormX3 = SEC_CONV2D_FORM_X3, kFormX3Tiles = SEC_CONV2D_FORM_X3_TILES, kFormGather = SEC_CONV2D_FORM_GATHER,
+};
+struct Conv2dPlan {
+    Conv2dKernel kernel = Conv2dKernel::kNotTaken;
+    int cin = 0, th = 0, split = 1;                         // halo_reg and patch (split = NSPLIT / PXS)
+    int roll = 0;                                           // halo_reg
+    bool gather = false, x3 = false, tail = false;
+    int ks = 0, st = 0, tw = 0;                             // patch
+    bool rows = false, table = false;
+    int bn = 0;                                             // conv1x1 and generic: output channels per workgroup
+};
+static Conv2dPlan plan_halo_reg(int cin, int th, int roll, int split = 1) {
+    Conv2dPlan d;
+    d.kernel = Conv2dKernel::kHaloReg; d.cin = cin; d.th = th; d.roll = roll; d.split = split;
+    return d;
+}
+static Conv2dPlan plan_patch(int cin, int ks, int st, int th, int tw, int split, bool rows = false, bool table = false) {
+    Conv2dPlan d;
+    d.kernel = Conv2dKernel::kPatch; d.cin = cin; d.ks = ks; d.st = st; d.th = th; d.tw = tw; d.split = split; d.rows = rows; d.table = table;
+    return d;
+}
+static Conv2dPlan plan_bn(Conv2dKernel k, int bn) {
+    Conv2dPlan d;
+    d.kernel = k; d.bn = bn;
+    return d;
+}
 
 // SEC_CONV2D_PATCH=0: the strided / patch layers of the PointPillars RPN on the generic implicit GEMM (A/B; read once)
 static bool conv2d_patch_enabled() {
@@ -1759,88 +1723,214 @@ static bool conv2d_patch_enabled() {
     }
     return v != 0;
 }
-
-template <typename T>
-static int launch_conv2d(const void *x, const void *wpk, const float *bias, void *y, const Conv2dParams &p, hipStream_t st) {
-    dim3 block(kBlock);
-    if (conv2d_variant() == 13 && conv2d_patch_enabled()) {
-        const int rc = patch::dispatch<T>(x, wpk, bias, y, p, p.cout, st);
-        if (rc != patch::kNotTaken) return rc;
+// The 128-channel 3x3 convs (every call form) run ONE main loop per process: the 16x16x32 one (ROLL == 3), or with SEC_CONV2D_MFMA=32
+// the 32x32x16 one (ROLL == 2) for A/B -- read once, before the first launch.  Never a mixture: the two loops group the products of
+// an output element differently, and the list, lazy and plain forms are bit-identical to each other only on the same loop.
+static int conv2d_c128_roll() {
+    static int v = -1;
+    if (v < 0) {
+        const char *e = getenv("SEC_CONV2D_MFMA");
+        v = (e && atoi(e) == 32) ? 2 : 3;
     }
-    if (conv2d_variant() == 14 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && p.cin == 128)
-        return launch_conv2d_halo_reg<T, 128, 8>(x, wpk, bias, y, p, st);   // A/B: the two-stage loop with per-m-tile halo addressing
-    if (conv2d_variant() == 13 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && (p.cin == 128 || p.cin == 64))
-        return p.cin == 128 ? launch_conv2d_c128<T>(x, wpk, bias, y, p, st) : launch_conv2d_halo_reg<T, 64, 8>(x, wpk, bias, y, p, st);
+    return v;
+}
+
+// more workgroups than two rounds of the chip's slots (two per CU): the case of the patch kernel's TABLE form, and where its stride-1 forms hand over
+static bool several_rounds(const Conv2dParams &p, int th, int tw, int cout_per_wg) {
+    return (long long)p.batch * div_up(p.ho, th) * div_up(p.wo, tw) * (p.cout / cout_per_wg) > 2 * 512;
+}
+constexpr int kConv1x1Tpw = 4;              // pixel tiles a k_conv1x1_nhwc workgroup streams past its resident weights
+constexpr long long kGenericSmallMap = 384; // workgroups of 128-wide cout tiles below which k_conv2d_nhwc_dma takes 64-wide ones
+static int generic_grid_x(const Conv2dParams &p) { return (div_up(p.m, 128) + 7) / 8 * 8; }   // multiple of 8 for the XCD-aware tile order
+
+static Conv2dPlan conv2d_fwd_decide(const Conv2dParams &p, int form, int dtype) {
+    const Conv2dPlan none;
+    if (dtype != SEC_BF16 && dtype != SEC_F16) return none;
+    const bool c128 = p.cout % 128 == 0;
+    const bool k3s1 = p.ksize == 3 && p.stride == 1 && p.pad == 1, k3s2 = p.ksize == 3 && p.stride == 2 && p.pad == 1;
+    const long long hw = (long long)p.h * p.w;
+    switch (form) {
+    case kFormPlain: case kFormInto: break;
+    case kFormRows:
+        // the shapes the row-gathering form exists for (the first conv of the PointPillars RPN: 64 pillar channels, 3x3 / s2 / p1)
+        if (hw * 4 > 0x7fffffffll) return none;                 // a frame of the site map is one buffer resource: 32-bit offsets
+        if (k3s2 && p.cin == 64 && p.cout == 64) return plan_patch(64, 3, 2, 8, 16, 2, true, several_rounds(p, 8, 16, 64));
+        if (k3s2 && p.cin == 64 && c128) return plan_patch(64, 3, 2, 8, 16, 1, true);
+        return none;
+    case kFormTiles: case kFormTail: case kFormX3: case kFormX3Tiles: case kFormGather: {
+        // the list / lazy / tail / split-fp32 / gather forms of the 128-channel 3x3 layer: k_conv2d_halo_reg on the process's loop
+        if (!k3s1 || p.cin != 128 || !c128 || (form == kFormTail && p.cout != 128)) return none;
+        Conv2dPlan d = plan_halo_reg(128, 8, conv2d_c128_roll());
+        d.gather = form == kFormGather; d.x3 = form == kFormX3 || form == kFormX3Tiles; d.tail = form == kFormTail;
+        if (d.x3 && (dtype != SEC_BF16 || hw * 256 >= (1ll << 31))) return none;     // two bf16 planes; a frame is one buffer resource
+        if (d.gather && hw * 8 >= (1ll << 31)) return none;                          // ... and so are the two map planes of a frame
+        return d;
+    }
+    default: return none;
+    }
+    if (p.cin % 64 || p.cout % 64) return none;
+
+    // The layers k_conv2d_patch takes (sec_conv2d_nhwc_into: these and nothing else -- no other kernel writes with a channel pitch)
+    if ((form == kFormInto || conv2d_patch_enabled()) && hw * p.cin * 2 <= 0x7fffffffll) {      // a frame is one buffer resource: 32-bit offsets
+        if (k3s2) {
+            // (far larger maps than any PointPillars config of the reference -- 4 x 800 x 800: 5200 workgroups -- are better off on the generic
+            // implicit GEMM, 137 vs 166 us: a 74 KB footprint per 128 x 64 outputs is a lot of LDS fill when nothing hides it; r06 A/B)
+            if (p.cin == 64 && p.cout == 64 && (long long)p.batch * div_up(p.ho, 8) * div_up(p.wo, 16) <= 2560) return plan_patch(64, 3, 2, 8, 16, 2);
+            if (p.cin == 64 && c128) return plan_patch(64, 3, 2, 8, 16, 1);
+            if (p.cin == 128 && c128) return plan_patch(128, 3, 2, 4, 16, 1);
+        }
+        // stride-1 3x3 layers of the small PointPillars maps (batch 4: one round of workgroups, so a layer's time is one workgroup's time):
+        // 256 channels at 50 x 50 and 64 -> 64 at 200 x 200 run 15 % / 12 % faster here than on k_conv2d_halo_reg's two-stage loop (steady
+        // 8-deep B ring instead of 4-fragment double buffering; r06_pp3 / r06_pp4: 22.3 -> 19.0 us and 22.5 -> 18.6 us); the 128-channel
+        // shared-row loop of k_conv2d_halo_reg stays ahead of this form (17.0 vs 18.3 us at 100 x 100) and keeps its layers.
+        if (k3s1) {
+            // (larger maps -- several rounds of workgroups, config 5's 124 x 124 -- stay on k_conv2d_halo_reg: -0.5 % on nusc.fhd with this form, r06_nusc_ab)
+            if (p.cin == 64 && p.cout == 64 && !several_rounds(p, 16, 16, 64)) return plan_patch(64, 3, 1, 16, 16, 2);
+            if (p.cin == 256 && c128 && !several_rounds(p, 4, 16, 128)) return plan_patch(256, 3, 1, 4, 16, 1);
+#ifdef SEC_PATCH_S1     // experiment builds: the 128-channel layers on this form too (A/B against k_conv2d_halo_reg)
+            if (p.cin == 128 && c128) return plan_patch(128, 3, 1, 8, 16, 1);
+#endif
+        }
+        if (p.ksize == 4 && p.stride == 4 && p.pad == 0 && p.cin == 64 && c128) return plan_patch(64, 4, 4, 2, 16, 1);
+        if (p.ksize == 2 && p.stride == 2 && p.pad == 0 && p.cin == 128 && c128)       // config 5's deblock (248 -> 124): 64-pixel tiles, half the weight re-reads
+            return several_rounds(p, 2, 16, 128) ? plan_patch(128, 2, 2, 4, 16, 1) : plan_patch(128, 2, 2, 2, 16, 1);
+        if (p.ksize == 1 && p.stride == 1 && p.pad == 0 && c128 && (p.cin == 256 || p.cin == 384)) return plan_patch(p.cin, 1, 1, 2, 16, 1);
+    }
+    if (form == kFormInto) return none;
+
+    if (k3s1 && c128 && p.cin == 128) return plan_halo_reg(128, 8, conv2d_c128_roll());
+    if (k3s1 && c128 && p.cin == 64) return plan_halo_reg(64, 8, 0);
     // 256 input channels (third block of the PointPillars RPN, 50 x 50 maps): 4 x 16 tiles -- 55 KB of halo, two workgroups per CU,
     // 416 workgroups at batch 4 -- on the two-stage loop (the generic implicit GEMM ran these layers at 0.11 of the MFMA peak)
-    if (conv2d_variant() == 13 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && p.cin == 256)
-        return launch_conv2d_halo_reg<T, 256, 4>(x, wpk, bias, y, p, st);
+    if (k3s1 && c128 && p.cin == 256) return plan_halo_reg(256, 4, 0);
     // 64 -> 64 (first block of the PointPillars RPN, 200 x 200 maps): 64 output channels per workgroup, the waves split the pixels
-    if (conv2d_variant() == 13 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout == 64 && p.cin == 64)
-        return launch_conv2d_halo_reg<T, 64, 8, 0, false, 2>(x, wpk, bias, y, p, st);
-    if (conv2d_variant() == 15 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 && p.cin == 128)
-        return launch_conv2d_halo_reg<T, 128, 8, 1>(x, wpk, bias, y, p, st);   // A/B: one A fragment per MFMA (12 LDS reads per 12 MFMAs)
-#ifdef SEC_CONV2D_EXPERIMENTS   // earlier 3x3 kernels (LDS weight slabs / rings), kept for A/B builds: DESIGN.md section 4
-    if (conv2d_variant() >= 5 && conv2d_variant() <= 12 && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.cout % 128 == 0 &&
-        (p.cin == 128 || p.cin == 64)) {
-        // 8 waves / 16 KB slabs / ring 2 with: 5 linear key   10 column key   11 fragment pipelining   12 both
-        // 8: 4 waves (64 px x 64 cout per wave), column key
-#define SEC_HALO_PIPE(NQ_, KS_, NB_, CK_, FP_)                                                                  \
-    return p.cin == 128 ? launch_conv2d_halo_pipe<T, 128, 8, NQ_, KS_, NB_, CK_, FP_>(x, wpk, bias, y, p, st)   \
-                        : launch_conv2d_halo_pipe<T, 64, 8, NQ_, KS_, NB_, CK_, FP_>(x, wpk, bias, y, p, st)
-        switch (conv2d_variant()) {
-        case 5: SEC_HALO_PIPE(4, 64, 2, false, false);
-        case 8: SEC_HALO_PIPE(2, 64, 2, true, false);
-        case 10: SEC_HALO_PIPE(4, 64, 2, true, false);
-        case 11: SEC_HALO_PIPE(4, 64, 2, false, true);
-        default: SEC_HALO_PIPE(4, 64, 2, true, true);
+    if (k3s1 && p.cout == 64 && p.cin == 64) return plan_halo_reg(64, 8, 0, 2);
+    if (p.ksize == 1 && p.stride == 1 && p.pad == 0 && p.cin == 128) return plan_bn(Conv2dKernel::kConv1x1, c128 ? 128 : 64);
+    // small images (the 50 x 50 third block of the PointPillars RPN: 80 pixel tiles x 2 cout tiles = 160 workgroups for 256 CUs):
+    // 64-wide cout tiles double the workgroups; the input tile is re-read from L2
+    return plan_bn(Conv2dKernel::kGeneric, c128 && (long long)generic_grid_x(p) * (p.cout / 128) >= kGenericSmallMap ? 128 : 64);
+}
+
+// The instantiation as rocprofv3 prints it: trailing template arguments at their defaults are left out
+static void conv2d_plan_name(const Conv2dPlan &d, int dtype, char *buf, size_t n) {
+    const char *t = dtype == SEC_BF16 ? dtype_name<__hip_bfloat16>() : dtype_name<__half>();
+    buf[0] = 0;
+    switch (d.kernel) {
+    case Conv2dKernel::kNotTaken: break;
+    case Conv2dKernel::kHaloReg:
+        if (d.tail) snprintf(buf, n, "k_conv2d_halo_reg<%s, %d, %d, %d, false, 1, false, true>", t, d.cin, d.th, d.roll);
+        else if (d.x3) snprintf(buf, n, "k_conv2d_halo_reg<%s, %d, %d, %d, false, 1, true>", t, d.cin, d.th, d.roll);
+        else if (d.split == 1) snprintf(buf, n, "k_conv2d_halo_reg<%s, %d, %d, %d, %s>", t, d.cin, d.th, d.roll, d.gather ? "true" : "false");
+        else snprintf(buf, n, "k_conv2d_halo_reg<%s, %d, %d, %d, %s, %d>", t, d.cin, d.th, d.roll, d.gather ? "true" : "false", d.split);
+        break;
+    case Conv2dKernel::kPatch:
+        snprintf(buf, n, "k_conv2d_patch<%s, %d, %d, %d, %d, %d, %d%s>", t, d.cin, d.ks, d.st, d.th, d.tw, d.split,
+                 d.table ? (d.rows ? ", true, true" : ", false, true") : (d.rows ? ", true" : ""));
+        break;
+    case Conv2dKernel::kConv1x1: snprintf(buf, n, "k_conv1x1_nhwc<%s, %d, %d>", t, d.bn, kConv1x1Tpw); break;
+    case Conv2dKernel::kGeneric: snprintf(buf, n, "k_conv2d_nhwc_dma<%s, %d>", t, d.bn); break;
+    }
+}
+
+// One integer per instantiation, so that the launch is a switch whose case label and template arguments are the same list
+constexpr int halo_reg_key(int cin, int th, int roll, bool gather, int split, bool x3, bool tail) {
+    return cin | th << 10 | roll << 15 | split << 18 | (int)gather << 21 | (int)x3 << 22 | (int)tail << 23;
+}
+constexpr int patch_key(int cin, int ks, int st, int th, int tw, int split, bool rows = false, bool table = false) {
+    return cin | ks << 10 | st << 13 | th << 16 | tw << 21 | split << 26 | (int)rows << 28 | (int)table << 29;
+}
+
+template <typename T>
+static int launch_conv2d_plan_t(const Conv2dPlan &d, const void *x, const void *wpk, const float *bias, void *y, const Conv2dParams &p, int ldc,
+                                const Conv2dExtra &e, hipStream_t st) {
+    const dim3 block(kBlock);
+#define SEC_HALO_REG_CASE(...) case halo_reg_key(__VA_ARGS__): return launch_conv2d_halo_reg<T, __VA_ARGS__>(x, wpk, bias, y, p, st, e)
+#define SEC_PATCH_CASE(...) case patch_key(__VA_ARGS__): return patch::launch<T, __VA_ARGS__>(x, wpk, bias, y, p, ldc, st, e.site_map, e.feat_bytes)
+    switch (d.kernel) {
+    case Conv2dKernel::kHaloReg:
+        if constexpr (std::is_same<T, __hip_bfloat16>::value) {     // the split-fp32 form exists on bf16 planes only
+            if (d.x3 && d.roll == 3) return launch_conv2d_halo_reg<T, 128, 8, 3, false, 1, true>(x, wpk, bias, y, p, st, e);
+            if (d.x3 && d.roll == 2) return launch_conv2d_halo_reg<T, 128, 8, 2, false, 1, true>(x, wpk, bias, y, p, st, e);
         }
-#undef SEC_HALO_PIPE
-    }
-    if (conv2d_variant() >= 2 && conv2d_variant() <= 4 && p.ksize == 3 && p.stride == 1 && p.pad == 1 &&
-        p.cout % 128 == 0 && (p.cin == 128 || p.cin == 64)) {
-        if (conv2d_variant() == 2)
-            return p.cin == 128 ? launch_conv2d_halo<T, 128, 16, 2>(x, wpk, bias, y, p, st) : launch_conv2d_halo<T, 64, 16, 2>(x, wpk, bias, y, p, st);
-        if (conv2d_variant() == 4)   // 8 waves on a 16x8 tile: 64 px x 32 cout per wave, 4 waves / SIMD at 2 workgroups per CU
-            return p.cin == 128 ? launch_conv2d_halo<T, 128, 8, 4>(x, wpk, bias, y, p, st) : launch_conv2d_halo<T, 64, 8, 4>(x, wpk, bias, y, p, st);
-        return p.cin == 128 ? launch_conv2d_halo<T, 128, 8, 2>(x, wpk, bias, y, p, st) : launch_conv2d_halo<T, 64, 8, 2>(x, wpk, bias, y, p, st);
-    }
+        switch (halo_reg_key(d.cin, d.th, d.roll, d.gather, d.split, d.x3, d.tail)) {
+            SEC_HALO_REG_CASE(128, 8, 3, false, 1, false, false);
+            SEC_HALO_REG_CASE(128, 8, 2, false, 1, false, false);
+            SEC_HALO_REG_CASE(128, 8, 3, true, 1, false, false);
+            SEC_HALO_REG_CASE(128, 8, 2, true, 1, false, false);
+            SEC_HALO_REG_CASE(128, 8, 3, false, 1, false, true);
+            SEC_HALO_REG_CASE(128, 8, 2, false, 1, false, true);
+            SEC_HALO_REG_CASE(64, 8, 0, false, 1, false, false);
+            SEC_HALO_REG_CASE(256, 4, 0, false, 1, false, false);
+            SEC_HALO_REG_CASE(64, 8, 0, false, 2, false, false);
+        }
+        break;
+    case Conv2dKernel::kPatch:
+        switch (patch_key(d.cin, d.ks, d.st, d.th, d.tw, d.split, d.rows, d.table)) {
+            SEC_PATCH_CASE(64, 3, 2, 8, 16, 2);
+            SEC_PATCH_CASE(64, 3, 2, 8, 16, 1);
+            SEC_PATCH_CASE(128, 3, 2, 4, 16, 1);
+            SEC_PATCH_CASE(64, 3, 1, 16, 16, 2);
+            SEC_PATCH_CASE(256, 3, 1, 4, 16, 1);
+#ifdef SEC_PATCH_S1
+            SEC_PATCH_CASE(128, 3, 1, 8, 16, 1);
 #endif
-    if (conv2d_variant() >= 1 && p.ksize == 1 && p.stride == 1 && p.pad == 0 && p.cin == 128) {
-        constexpr int TPW = 4;
-        const int gx1 = div_up(div_up(p.m, 128), TPW);
-        if (p.cout % 128 == 0)
-            hipLaunchKernelGGL((k_conv1x1_nhwc<T, 128, TPW>), dim3(gx1, p.cout / 128), block, 0, st, (const T *)x, (const T *)wpk,
-                               bias, (T *)y, p);
+            SEC_PATCH_CASE(64, 4, 4, 2, 16, 1);
+            SEC_PATCH_CASE(128, 2, 2, 4, 16, 1);
+            SEC_PATCH_CASE(128, 2, 2, 2, 16, 1);
+            SEC_PATCH_CASE(256, 1, 1, 2, 16, 1);
+            SEC_PATCH_CASE(384, 1, 1, 2, 16, 1);
+            SEC_PATCH_CASE(64, 3, 2, 8, 16, 2, true, true);
+            SEC_PATCH_CASE(64, 3, 2, 8, 16, 2, true);
+            SEC_PATCH_CASE(64, 3, 2, 8, 16, 1, true);
+        }
+        break;
+    case Conv2dKernel::kConv1x1: {
+        const int gx = div_up(div_up(p.m, 128), kConv1x1Tpw);
+        if (d.bn == 128)
+            hipLaunchKernelGGL((k_conv1x1_nhwc<T, 128, kConv1x1Tpw>), dim3(gx, p.cout / 128), block, 0, st, (const T *)x, (const T *)wpk, bias, (T *)y, p);
         else
-            hipLaunchKernelGGL((k_conv1x1_nhwc<T, 64, TPW>), dim3(gx1, p.cout / 64), block, 0, st, (const T *)x, (const T *)wpk,
-                               bias, (T *)y, p);
+            hipLaunchKernelGGL((k_conv1x1_nhwc<T, 64, kConv1x1Tpw>), dim3(gx, p.cout / 64), block, 0, st, (const T *)x, (const T *)wpk, bias, (T *)y, p);
         return check_launch();
     }
-    if (conv2d_variant() >= 1 || !kConv2dExperiments) {
-        const int gx = (div_up(p.m, 128) + 7) / 8 * 8;   // multiple of 8 for the XCD-aware tile order
-        // small images (the 50 x 50 third block of the PointPillars RPN: 80 pixel tiles x 2 cout tiles = 160 workgroups for 256 CUs):
-        // 64-wide cout tiles double the workgroups; the input tile is re-read from L2.  (small_split = 0: always 128.
-        static int small_split = -1;
-        if (small_split < 0) small_split = 1;
-        if (p.cout % 128 == 0 && !(small_split && (long long)gx * (p.cout / 128) < 384))
-            hipLaunchKernelGGL((k_conv2d_nhwc_dma<T, 128>), dim3(gx, p.cout / 128), block, 0, st, (const T *)x,
-                               (const T *)wpk, bias, (T *)y, p);
+    case Conv2dKernel::kGeneric:
+        if (d.bn == 128)
+            hipLaunchKernelGGL((k_conv2d_nhwc_dma<T, 128>), dim3(generic_grid_x(p), p.cout / 128), block, 0, st, (const T *)x, (const T *)wpk, bias, (T *)y, p);
         else
-            hipLaunchKernelGGL((k_conv2d_nhwc_dma<T, 64>), dim3(gx, p.cout / 64), block, 0, st, (const T *)x,
-                               (const T *)wpk, bias, (T *)y, p);
+            hipLaunchKernelGGL((k_conv2d_nhwc_dma<T, 64>), dim3(generic_grid_x(p), p.cout / 64), block, 0, st, (const T *)x, (const T *)wpk, bias, (T *)y, p);
         return check_launch();
+    case Conv2dKernel::kNotTaken: break;
     }
-#ifdef SEC_CONV2D_EXPERIMENTS
-    if (p.cout % 128 == 0) {
-        hipLaunchKernelGGL((k_conv2d_nhwc<T, 128>), dim3(div_up(p.m, 128), p.cout / 128), block, 0, st, (const T *)x,
-                           (const T *)wpk, bias, (T *)y, p);
-    } else {
-        hipLaunchKernelGGL((k_conv2d_nhwc<T, 64>), dim3(div_up(p.m, 128), p.cout / 64), block, 0, st, (const T *)x,
-                           (const T *)wpk, bias, (T *)y, p);
-    }
-#endif
-    return check_launch();
+#undef SEC_HALO_REG_CASE
+#undef SEC_PATCH_CASE
+    return SEC_E_UNSUPPORTED;       // not taken, or a plan without an instantiation
+}
+
+template <typename T> struct TypeTag { using type = T; };
+// f(TypeTag<element type>) for a 16-bit dtype code (the caller has refused every other code)
+template <typename F> static int by_dtype16(int dtype, F &&f) { return dtype == SEC_BF16 ? f(TypeTag<__hip_bfloat16>{}) : f(TypeTag<__half>{}); }
+
+// `ldc`: channel pitch of y in elements (sec_conv2d_nhwc_into; p.cout everywhere else)
+static int launch_conv2d_plan(const Conv2dPlan &d, int dtype, const void *x, const void *wpk, const float *bias, void *y, const Conv2dParams &p,
+                              int ldc, const Conv2dExtra &e, void *stream) {
+    if (d.kernel == Conv2dKernel::kNotTaken) return SEC_E_UNSUPPORTED;
+    char name[192];
+    conv2d_plan_name(d, dtype, name, sizeof(name));
+    set_last_kernel("%s", name);
+    return by_dtype16(dtype, [&](auto t) {
+        return launch_conv2d_plan_t<typename decltype(t)::type>(d, x, wpk, bias, y, p, ldc, e, (hipStream_t)stream);
+    });
+}
+
+// Conv2dParams of a call (relu_bits: bit 0 = ReLU, bit 1 = all-zero input tiles skip the MFMA loop); false when the output would be empty
+static bool conv2d_params(Conv2dParams &p, int batch, int h, int w, int cin, int cout, int ksize, int stride, int pad, int relu_bits) {
+    p.batch = batch; p.h = h; p.w = w; p.cin = cin; p.cout = cout; p.ksize = ksize; p.stride = stride; p.pad = pad;
+    p.relu = relu_bits & 1;
+    p.zskip = (relu_bits >> 1) & 1;
+    p.stagger = 0;
+    p.ho = (h + 2 * pad - ksize) / stride + 1;
+    p.wo = (w + 2 * pad - ksize) / stride + 1;
+    p.m = (long long)batch * p.ho * p.wo;
+    return p.ho > 0 && p.wo > 0;
 }
 
 // ---- which 8 x 16 tiles of the RPN's feature maps can differ from the empty frame's -------------------------------------------
@@ -2034,19 +2124,12 @@ static int conv2d_tiles_impl(const void *x, int batch, int h, int w, const void 
                              const unsigned short *tile_order, const int *live_counts, const void *background,
                              const unsigned short *nbr_masks, const void *background_in, void *y, int dtype, void *stream) {
     if (!x || !packed_weight || !y || batch <= 0 || h <= 0 || w <= 0 || (tile_order && !live_counts)) return SEC_E_INVALID;
-    if (cout % 128 || (dtype != SEC_BF16 && dtype != SEC_F16)) return SEC_E_UNSUPPORTED;
     apply_list_threshold_env();
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = 128; p.cout = cout; p.ksize = 3; p.stride = 1; p.pad = 1;
-    p.relu = relu & 1; p.zskip = 0; p.stagger = 0;
-    p.ho = h; p.wo = w;
-    p.m = (long long)batch * h * w;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SEC_BF16)
-        return launch_conv2d_c128<__hip_bfloat16>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background,
-                                                                 nbr_masks, background_in);
-    return launch_conv2d_c128<__half>(x, packed_weight, bias, y, p, st, nullptr, 0, tile_order, live_counts, background, nbr_masks,
-                                                     background_in);
+    if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.tile_order = tile_order; e.live_counts = live_counts; e.background = background; e.nbr_masks = nbr_masks; e.bg_in = background_in;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormTiles, dtype), dtype, x, packed_weight, bias, y, p, cout, e, stream);
 }
 
 SEC_API int sec_conv2d_nhwc_tiles(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int cout,
@@ -2073,21 +2156,15 @@ SEC_API int sec_conv2d_nhwc_tiles_tail(const void *x, int batch, int h, int w, c
     if (!x || !packed_weight || !tile_order || !live_counts || !nbr_masks || !background_in || !packed_w1 || !bias1 || !packed_w2 || !y_heads ||
         batch <= 0 || h <= 0 || w <= 0)
         return SEC_E_INVALID;
-    if (cout2 != 64 || (dtype != SEC_BF16 && dtype != SEC_F16)) return SEC_E_UNSUPPORTED;
+    if (cout2 != 64) return SEC_E_UNSUPPORTED;
     apply_list_threshold_env();
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = 128; p.cout = 128; p.ksize = 3; p.stride = 1; p.pad = 1;
-    p.relu = relu & 1; p.zskip = 0; p.stagger = 0;
-    p.ho = h; p.wo = w;
-    p.m = (long long)batch * h * w;
-    const ConvTailArgs tail{packed_w1, packed_w2, bias1, bias2, y_heads, relu1 & 1};
-    hipStream_t st = (hipStream_t)stream;
+    if (!conv2d_params(p, batch, h, w, 128, 128, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.tile_order = tile_order; e.live_counts = live_counts; e.nbr_masks = nbr_masks; e.bg_in = background_in;
+    e.tail = ConvTailArgs{packed_w1, packed_w2, bias1, bias2, y_heads, relu1 & 1};
     // y of the conv itself does not exist: the kernel's `y` is never dereferenced on the TAIL path (background == NULL: lazy form)
-    if (dtype == SEC_BF16)
-        return launch_conv2d_c128<__hip_bfloat16, false, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts,
-                                                                                       nullptr, nbr_masks, background_in, nullptr, nullptr, nullptr, nullptr, tail);
-    return launch_conv2d_c128<__half, false, false, true>(x, packed_weight, bias, nullptr, p, st, nullptr, 0, tile_order, live_counts, nullptr,
-                                                                           nbr_masks, background_in, nullptr, nullptr, nullptr, nullptr, tail);
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormTail, dtype), dtype, x, packed_weight, bias, nullptr, p, 128, e, stream);
 }
 
 SEC_API size_t sec_conv2d_packed_weight_bytes(int cout, int cin, int ksize, int dtype) {
@@ -2100,31 +2177,20 @@ SEC_API int sec_conv2d_pack_weight(const void *weight, int cout, int cin, int ks
     long long total = (long long)ksize * ksize * cin * cout;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync((char *)packed + total * 2, 0, 16, st) != hipSuccess) return SEC_E_LAUNCH;
-    if (dtype == SEC_BF16)
-        hipLaunchKernelGGL(k_conv2d_pack<__hip_bfloat16>, dim3(div_up(total, kBlock)), dim3(kBlock), 0, st,
-                           (const __hip_bfloat16 *)weight, cout, cin, ksize, (__hip_bfloat16 *)packed);
-    else
-        hipLaunchKernelGGL(k_conv2d_pack<__half>, dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const __half *)weight,
-                           cout, cin, ksize, (__half *)packed);
-    return check_launch();
+    return by_dtype16(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k_conv2d_pack<T>, dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const T *)weight, cout, cin, ksize, (T *)packed);
+        return check_launch();
+    });
 }
 
 SEC_API int sec_conv2d_nhwc(const void *x, int batch, int h, int w, int cin, const void *packed_weight, const float *bias,
                             int cout, int ksize, int stride, int pad, int relu, void *y, int dtype, void *stream) {
     if (!x || !packed_weight || !y || batch <= 0 || h <= 0 || w <= 0 || ksize <= 0 || stride <= 0 || pad < 0) return SEC_E_INVALID;
-    if (cin % 64 || cout % 64 || (dtype != SEC_BF16 && dtype != SEC_F16)) return SEC_E_UNSUPPORTED;
+    if (cin % 64 || cout % 64 || (dtype != SEC_BF16 && dtype != SEC_F16)) return SEC_E_UNSUPPORTED;     // (answered before an empty output is)
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = cin; p.cout = cout; p.ksize = ksize; p.stride = stride; p.pad = pad;
-    p.relu = relu & 1;
-    p.zskip = (relu >> 1) & 1;
-    p.stagger = 0;
-    p.ho = (h + 2 * pad - ksize) / stride + 1;
-    p.wo = (w + 2 * pad - ksize) / stride + 1;
-    if (p.ho <= 0 || p.wo <= 0) return SEC_E_INVALID;
-    p.m = (long long)batch * p.ho * p.wo;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == SEC_BF16) return launch_conv2d<__hip_bfloat16>(x, packed_weight, bias, y, p, st);
-    return launch_conv2d<__half>(x, packed_weight, bias, y, p, st);
+    if (!conv2d_params(p, batch, h, w, cin, cout, ksize, stride, pad, relu & 3)) return SEC_E_INVALID;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormPlain, dtype), dtype, x, packed_weight, bias, y, p, cout, Conv2dExtra{}, stream);
 }
 
 SEC_API int sec_conv2d_nhwc_into(const void *x, int batch, int h, int w, int cin, const void *packed_weight, const float *bias, int cout,
@@ -2134,20 +2200,10 @@ SEC_API int sec_conv2d_nhwc_into(const void *x, int batch, int h, int w, int cin
         return SEC_E_INVALID;
     if (cin % 64 || cout % 64 || (y_channel_offset % 8) || (y_channels % 8) || (dtype != SEC_BF16 && dtype != SEC_F16)) return SEC_E_UNSUPPORTED;
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = cin; p.cout = cout; p.ksize = ksize; p.stride = stride; p.pad = pad;
-    p.relu = relu & 1;
-    p.zskip = 0;
-    p.stagger = 0;
-    p.ho = (h + 2 * pad - ksize) / stride + 1;
-    p.wo = (w + 2 * pad - ksize) / stride + 1;
-    if (p.ho <= 0 || p.wo <= 0) return SEC_E_INVALID;
-    p.m = (long long)batch * p.ho * p.wo;
-    hipStream_t st = (hipStream_t)stream;
-    // only k_conv2d_patch writes with a channel pitch: the shapes of patch::dispatch (the deblocks of the multi-block RPNs among them)
-    const int rc = dtype == SEC_BF16
-                       ? patch::dispatch<__hip_bfloat16>(x, packed_weight, bias, (__hip_bfloat16 *)y + y_channel_offset, p, y_channels, st)
-                       : patch::dispatch<__half>(x, packed_weight, bias, (__half *)y + y_channel_offset, p, y_channels, st);
-    return rc == patch::kNotTaken ? SEC_E_UNSUPPORTED : rc;
+    if (!conv2d_params(p, batch, h, w, cin, cout, ksize, stride, pad, relu & 1)) return SEC_E_INVALID;
+    // only k_conv2d_patch writes with a channel pitch (the deblocks of the multi-block RPNs among its shapes); 16-bit elements
+    void *yc = (char *)y + (size_t)y_channel_offset * 2;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormInto, dtype), dtype, x, packed_weight, bias, yc, p, y_channels, Conv2dExtra{}, stream);
 }
 
 SEC_API int sec_conv2d_nhwc_rows(const void *rows, long long feature_rows, const int *site_map, int batch, int h, int w, int cin,
@@ -2158,19 +2214,10 @@ SEC_API int sec_conv2d_nhwc_rows(const void *rows, long long feature_rows, const
     if (dtype != SEC_BF16 && dtype != SEC_F16) return SEC_E_UNSUPPORTED;
     if (feature_rows * cin * 2 > 0x7fffffffll || (long long)h * w * 4 > 0x7fffffffll) return SEC_E_UNSUPPORTED;     // 32-bit buffer offsets
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = cin; p.cout = cout; p.ksize = ksize; p.stride = stride; p.pad = pad;
-    p.relu = relu & 1;
-    p.zskip = 0;
-    p.stagger = 0;
-    p.ho = (h + 2 * pad - ksize) / stride + 1;
-    p.wo = (w + 2 * pad - ksize) / stride + 1;
-    if (p.ho <= 0 || p.wo <= 0) return SEC_E_INVALID;
-    p.m = (long long)batch * p.ho * p.wo;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned fb = (unsigned)(feature_rows * cin * 2);
-    const int rc = dtype == SEC_BF16 ? patch::dispatch_rows<__hip_bfloat16>(rows, fb, site_map, packed_weight, bias, y, p, st)
-                                     : patch::dispatch_rows<__half>(rows, fb, site_map, packed_weight, bias, y, p, st);
-    return rc == patch::kNotTaken ? SEC_E_UNSUPPORTED : rc;
+    if (!conv2d_params(p, batch, h, w, cin, cout, ksize, stride, pad, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.site_map = site_map; e.feat_bytes = (unsigned)(feature_rows * cin * 2);
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormRows, dtype), dtype, rows, packed_weight, bias, y, p, cout, e, stream);
 }
 
 // fp32 <-> two bf16 planes (hi = bf16(v), lo = bf16(v - hi)): the operand form of sec_conv2d_nhwc_x3.  Element-wise, HBM bound.
@@ -2213,14 +2260,11 @@ SEC_API int sec_merge_bf16x2_f32(const void *hi, const void *lo, long long n, fl
 SEC_API int sec_conv2d_nhwc_x3(const void *x_hi, const void *x_lo, int batch, int h, int w, const void *packed_weight_hi_lo, const float *bias,
                                int cout, int relu, void *y_hi, void *y_lo, void *stream) {
     if (!x_hi || !x_lo || !packed_weight_hi_lo || !y_hi || !y_lo || batch <= 0 || h <= 0 || w <= 0) return SEC_E_INVALID;
-    if (cout % 128 || (long long)h * w * 256 >= (1ll << 31)) return SEC_E_UNSUPPORTED;
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = 128; p.cout = cout; p.ksize = 3; p.stride = 1; p.pad = 1;
-    p.relu = relu & 1; p.zskip = (relu >> 1) & 1; p.stagger = 0;
-    p.ho = h; p.wo = w;
-    p.m = (long long)batch * h * w;
-    return launch_conv2d_c128<__hip_bfloat16, false, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
-                                                                              nullptr, nullptr, nullptr, nullptr, nullptr, x_lo, y_lo);
+    if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 3)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.x_lo = x_lo; e.y_lo = y_lo;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormX3, SEC_BF16), SEC_BF16, x_hi, packed_weight_hi_lo, bias, y_hi, p, cout, e, stream);
 }
 
 SEC_API int sec_conv2d_nhwc_x3_tiles(const void *x_hi, const void *x_lo, int batch, int h, int w, const void *packed_weight_hi_lo,
@@ -2230,16 +2274,13 @@ SEC_API int sec_conv2d_nhwc_x3_tiles(const void *x_hi, const void *x_lo, int bat
     if (!x_hi || !x_lo || !packed_weight_hi_lo || !y_hi || !y_lo || !tile_order || !live_counts || batch <= 0 || h <= 0 || w <= 0) return SEC_E_INVALID;
     if ((background_hi == nullptr) != (background_lo == nullptr)) return SEC_E_INVALID;
     if (nbr_masks && (!background_in_hi || !background_in_lo)) return SEC_E_INVALID;
-    if (cout % 128 || (long long)h * w * 256 >= (1ll << 31)) return SEC_E_UNSUPPORTED;
     apply_list_threshold_env();
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = 128; p.cout = cout; p.ksize = 3; p.stride = 1; p.pad = 1;
-    p.relu = relu & 1; p.zskip = 0; p.stagger = 0;
-    p.ho = h; p.wo = w;
-    p.m = (long long)batch * h * w;
-    return launch_conv2d_c128<__hip_bfloat16, false, true>(x_hi, packed_weight_hi_lo, bias, y_hi, p, (hipStream_t)stream, nullptr, 0,
-                                                                              tile_order, live_counts, background_hi, nbr_masks, background_in_hi,
-                                                                              x_lo, y_lo, background_lo, background_in_lo);
+    if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.tile_order = tile_order; e.live_counts = live_counts; e.background = background_hi; e.nbr_masks = nbr_masks; e.bg_in = background_in_hi;
+    e.x_lo = x_lo; e.y_lo = y_lo; e.background_lo = background_lo; e.bg_in_lo = background_in_lo;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormX3Tiles, SEC_BF16), SEC_BF16, x_hi, packed_weight_hi_lo, bias, y_hi, p, cout, e, stream);
 }
 
 SEC_API int sec_conv2d_nhwc_gather(const void *features, long long feature_rows, const int *site_map, int batch, int h, int w,
@@ -2247,19 +2288,23 @@ SEC_API int sec_conv2d_nhwc_gather(const void *features, long long feature_rows,
                                    const int *live_counts, const void *background, void *y, int dtype, void *stream) {
     if (!site_map || !packed_weight || !y || batch <= 0 || h <= 0 || w <= 0 || feature_rows < 0 || (!features && feature_rows > 0)) return SEC_E_INVALID;
     if (tile_order && !live_counts) return SEC_E_INVALID;       // background == NULL with lists: the other tiles are left unwritten (lazy consumers)
-    if (cout % 128 || (dtype != SEC_BF16 && dtype != SEC_F16) || feature_rows * 128 >= (1ll << 31) ||
-        (long long)h * w * 8 >= (1ll << 31)) return SEC_E_UNSUPPORTED;
+    if (feature_rows * 128 >= (1ll << 31)) return SEC_E_UNSUPPORTED;         // the rows are one buffer resource: 32-bit offsets
     apply_list_threshold_env();
     Conv2dParams p;
-    p.batch = batch; p.h = h; p.w = w; p.cin = 128; p.cout = cout; p.ksize = 3; p.stride = 1; p.pad = 1;
-    p.relu = relu & 1; p.zskip = 0; p.stagger = 0;
-    p.ho = h; p.wo = w;
-    p.m = (long long)batch * h * w;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned fb = (unsigned)(feature_rows * 128);
-    if (dtype == SEC_BF16)
-        return launch_conv2d_c128<__hip_bfloat16, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
-    return launch_conv2d_c128<__half, true>(features, packed_weight, bias, y, p, st, site_map, fb, tile_order, live_counts, background);
+    if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.site_map = site_map; e.feat_bytes = (unsigned)(feature_rows * 128);
+    e.tile_order = tile_order; e.live_counts = live_counts; e.background = background;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormGather, dtype), dtype, features, packed_weight, bias, y, p, cout, e, stream);
+}
+
+SEC_API const char *sec_conv2d_fwd_plan_name(int batch, int h, int w, int cin, int cout, int ksize, int stride, int pad, int dtype, int call_form) {
+    static thread_local char name[192];
+    name[0] = 0;
+    Conv2dParams p;
+    if (batch <= 0 || h <= 0 || w <= 0 || ksize <= 0 || stride <= 0 || pad < 0 || !conv2d_params(p, batch, h, w, cin, cout, ksize, stride, pad, 0)) return name;
+    conv2d_plan_name(conv2d_fwd_decide(p, call_form, dtype), dtype, name, sizeof(name));
+    return name;
 }
 
 SEC_API int sec_conv1x1_chain_nhwc(const void *x, long long pixels, const void *packed_w1, const float *bias1, int relu1,

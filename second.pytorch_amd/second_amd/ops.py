@@ -916,6 +916,16 @@ def conv2d_nhwc(x, packed, bias, cout, ksize, stride=1, pad=0, relu=False, spars
     return y
 
 
+CONV2D_FORMS = {"plain": 0, "into": 1, "rows": 2, "tiles": 3, "tail": 4, "x3": 5, "x3_tiles": 6, "gather": 7}      # SEC_CONV2D_FORM_* (include/second_hip.h)
+
+
+def conv2d_plan_name(batch, h, w, cin, cout, ksize, stride, pad, dtype, form="plain"):
+    """The kernel instantiation the conv2d op of call form ``form`` (a key of CONV2D_FORMS) would report through
+    :func:`last_kernel_name` for this shape; "" where it would refuse the call.  Host-only (sec_conv2d_fwd_plan_name)."""
+    return rt.lib().sec_conv2d_fwd_plan_name(int(batch), int(h), int(w), int(cin), int(cout), int(ksize), int(stride), int(pad),
+                                             rt.dtype_code(dtype), CONV2D_FORMS[form]).decode()
+
+
 def conv2d_pack_weight_x3(weight):
     """fp32 [Cout, 128, 3, 3] -> the packed (hi | lo) bf16 weight pair of :func:`conv2d_nhwc_x3`: W = bf16(W) + bf16(W - bf16(W))."""
     rt.require_gpu(weight)
@@ -1182,7 +1192,7 @@ def conv2d_nhwc_rows(rows, site_map, packed, bias, cout, ksize, stride, pad, rel
 
 
 def conv2d_into_supported(cin, cout, ksize, stride, pad, dtype):
-    """Shapes :func:`conv2d_nhwc_into` serves (the strided / patch conv kernel, csrc/dense_patch.hpp patch::dispatch)."""
+    """Shapes :func:`conv2d_nhwc_into` serves (the strided / patch conv kernel; csrc/dense.hip conv2d_fwd_decide, call form "into")."""
     if dtype not in (torch.bfloat16, torch.float16):
         return False
     c128 = cout % 128 == 0

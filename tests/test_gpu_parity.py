@@ -938,6 +938,15 @@ def test_pointpillars_detector_runs_fused_equals_module_path(syn):
         assert torch.equal(out["scores"][m], other["scores"][m]) and torch.equal(out["boxes"][m], other["boxes"][m])
 
 
+def conv2d_per_element_bound(x, w, ref, stride, pad, dtype):
+    """|out - ref| allowed per element of a 16-bit conv2d against torch's fp32 convolution `ref` of the same inputs: one rounding to the
+    output dtype, and fp32 accumulation of K = cin k^2 exact products on both sides (gamma_K * sum |x| |w| of that element each)."""
+    cin, k = w.shape[1], w.shape[2]
+    mag = torch.nn.functional.conv2d(x.float().abs(), w.float().abs(), None, stride, pad)
+    u_out = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+    return u_out * ref.abs() + 2 * (cin * k * k + 2) * 2.0 ** -24 * mag + 1e-30
+
+
 @pytest.mark.parametrize("cin,cout,k,stride,pad,hw", [(128, 128, 3, 1, 1, (200, 176)), (64, 64, 3, 2, 1, (37, 29)),
                                                      (128, 256, 3, 2, 1, (50, 50)), (128, 64, 1, 1, 0, (33, 17)),
                                                      (128, 128, 1, 1, 0, (61, 43)),
@@ -972,9 +981,7 @@ def test_conv2d_nhwc_mfma_vs_torch(ops, cin, cout, k, stride, pad, hw, dtype):
     np.testing.assert_allclose(nob.float().cpu().numpy(), ref2.cpu().numpy(), rtol=tol, atol=tol * ref2.abs().max().item())
     # PER ELEMENT (the lines above are relative to the tensor's maximum): exact 16-bit products, fp32 accumulation of K = cin k^2 terms
     # on both sides (gamma_K * sum |x| |w| of that output element each), one rounding to the output dtype
-    mag = torch.nn.functional.conv2d(x.float().abs(), w.float().abs(), None, stride, pad)
-    u_out = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
-    bound = u_out * ref2.abs() + 2 * (cin * k * k + 2) * 2.0 ** -24 * mag + 1e-30
+    bound = conv2d_per_element_bound(x, w, ref2, stride, pad, dtype)
     assert bool(((nob.float() - ref2).abs() <= bound).all()), float(((nob.float() - ref2).abs() / bound).max())
 
 
