@@ -721,8 +721,9 @@ int sec_predict_finalize(const float *decoded, const float *top_score, const int
  * Training side: what the reference computes in DataLoader workers (numpy) and in ~40 torch kernels.
  *
  * sec_assign_targets_f32 -- replaces TargetAssigner.assign / assign_per_class -> create_target_np
- *   (second/core/target_assigner.py:51-88, second/core/target_ops.py:29-229) for the configuration every shipped config
- *   uses: NearestIouSimilarity (second/core/region_similarity.py:73-93), GroundBox3dCoder.encode
+ *   (second/core/target_assigner.py:51-88, second/core/target_ops.py:29-229) with NearestIouSimilarity
+ *   (second/core/region_similarity.py:73-93; every KITTI config, and every nuScenes class but pedestrian and traffic_cone,
+ *   which get a DistanceSimilarity: sec_assign_targets_sim_f32 below), GroundBox3dCoder.encode
  *   (second/core/box_np_ops.py:36-81), sample_positive_fraction = -1 (no sub-sampling), no anchor pruning.
  *   anchors [n_anchor,7]; the ground truth of frame b is gt_boxes[gt_offsets[b] .. gt_offsets[b+1]) (x,y,z,w,l,h,r),
  *   gt_classes (1-based, NULL = all 1), gt_importance (NULL = all 1).  Outputs per (frame, anchor): labels
@@ -762,6 +763,36 @@ int sec_assign_targets_masked_f32(const float *anchors, int n_anchor, const floa
                                   const float *h_unmatched, int *labels, float *bbox_targets, float *importance,
                                   void *workspace, size_t workspace_bytes, const unsigned char *anchors_mask /* NULL = none */,
                                   void *stream);
+/* Region similarities (second/core/region_similarity.py).  NEAREST_IOU: NearestIouSimilarity, what the entry points above compute.
+ * DISTANCE: DistanceSimilarity (:96-122 -> box_np_ops.distance_similarity :950-973) on (x, y, r):
+ *     s = 0 unless |dx| <= dist_norm and |dy| <= dist_norm;  d = dx*dx + dy*dy;  x = min(d / dist_norm, dist_norm)
+ *     s = 1 - x   or, with_rotation,   1 - (1 - rot_alpha) * x - rot_alpha * |sin(r_n - r_k)|
+ *   in the arithmetic numba compiles, which is what the reference's users run: dx, dy, d and |sin| float32, the comparisons with
+ *   dist_norm and everything from the division on float64, one rounding into the float32 result.  (Executed as plain Python
+ *   under numpy 2 the whole chain is float32 with float32(dist_norm); the two differ in the last place.)  The parameters
+ *   are float64 for that reason.  Similarities inside the window can be negative; outside it they are 0.
+ * RotateIouSimilarity is not offered. */
+#define SEC_SIM_NEAREST_IOU 0
+#define SEC_SIM_DISTANCE 1
+/* RegionSimilarityCalculator.compare: out[i * k + j] = similarity of anchors[i] ([n,7]) with gt_boxes[j] ([k,7]).  dist_norm,
+ * with_rotation, rot_alpha are read for SEC_SIM_DISTANCE only.  Unknown kind, or dist_norm <= 0 for DISTANCE: SEC_E_INVALID;
+ * n or k == 0: nothing to do. */
+int sec_region_similarity_f32(const float *anchors, int n, const float *gt_boxes, int k, int kind, double dist_norm,
+                              int with_rotation, double rot_alpha, float *out, void *stream);
+/* sec_assign_targets_masked_f32 (anchors_mask may be NULL) with a region similarity per range: h_sim_kind[c] (SEC_SIM_*) and
+ * h_sim_params[c * 3 ..] = dist_norm, with_rotation (0 / non-zero), rot_alpha, read for DISTANCE ranges.  With DISTANCE the matching
+ * follows create_target_np for similarities of either sign: a ground truth's best similarity is the plain maximum over the range
+ * (negative when every anchor lies inside its window), anchors that tie with it are positive, and the reference's "-1 when the
+ * maximum is 0" fill matches anchors whose similarity is exactly -1, as it does there.
+ * SEC_E_INVALID before any launch: an unknown kind; dist_norm <= 0 on a DISTANCE range; a range with class id 0 (assign_all, which
+ * uses the first calculator for all anchors, target_assigner.py:68-71) whose similarity differs from range 0's; two ranges of one
+ * class id with different kinds. */
+int sec_assign_targets_sim_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                               const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                               const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                               const float *h_unmatched, const int *h_sim_kind, const double *h_sim_params, int *labels,
+                               float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
+                               const unsigned char *anchors_mask /* NULL = none */, void *stream);
 /* ---------------------------------------------------------------------------------------------
  * Anchor-area mask (`anchor_area_threshold` of the KITTI PointPillars configs; second/data/preprocess.py:345-357,
  * box_np_ops.py:917-946): mask[b][n] = 1 when more than `threshold` voxels of frame b lie under anchor n's near box.

@@ -4,6 +4,9 @@
 //                              second/core/target_ops.py:29-229 (create_target_np) with NearestIouSimilarity
 //                              (second/core/region_similarity.py:73-93 -> box_np_ops.rbbox2d_to_near_bbox :286-298 +
 //                              iou_jit(eps=0) :697-725) and GroundBox3dCoder.encode (box_np_ops.second_box_encode :36-81).
+//   sec_assign_targets_sim_f32 -- the same with a region similarity per anchor range: NearestIouSimilarity or DistanceSimilarity
+//                              (region_similarity.py:96-122 -> box_np_ops.distance_similarity :950-973), which every nuScenes
+//                              config gives pedestrian and traffic_cone.  sec_region_similarity_f32: the [N, K] matrix itself.
 //   sec_second_loss_f32     -- VoxelNet.loss (second/pytorch/models/voxelnet.py:239-312): sigmoid focal classification loss
 //                              (core/losses.py:236-296), smooth-L1 localisation loss on the sin-difference encoding
 //                              (losses.py:135-185, voxelnet.py:704-754), direction softmax cross-entropy (:814-829,
@@ -31,19 +34,65 @@ __device__ __forceinline__ float iou_eps0(const float4 a, const float4 q) {
     return __fdiv_rn(__fmul_rn(iw, ih), ua);
 }
 
-// pass 1: per (frame, anchor) best ground truth (first index on ties, like np.argmax) and, per ground truth, the best overlap
-// over all anchors (atomicMax on the float bits: overlaps are >= 0, so integer order == float order)
+// The region similarity is a compile-time parameter of the assignment kernels.  Sim<kind>::stage() is what one box keeps in LDS,
+// value() the similarity of an anchor with a ground truth, both in the reference's operation order.
+struct SimParams { double dist_norm, rot_alpha; int with_rotation; };
+
+// box_np_ops.distance_similarity (:950-973) on (x, y, r) as numba compiles it -- the meaning the reference's users run: the
+// differences and d = dx*dx + dy*dy are float32; dist_norm is a Python float, so both window tests, d / dist_norm, the min and the
+// combination are float64, rounded once on the store into the float32 matrix.  np.sin of a float32 is float32: |sin| is taken of
+// the float32 difference and rounded to float32 first (here the float64 sine rounded once, i.e. the correctly rounded float32
+// sine up to double rounding; numpy's own float32 sine is within an ulp or two of it).
+// Outside the window the similarity is 0, inside it can be NEGATIVE (down to 1 - dist_norm, lower with rotation).
+__device__ __forceinline__ float distance_sim(const float4 a, const float4 q, const SimParams &P) {
+    const float dx = __fsub_rn(a.x, q.x);
+    if (!((double)fabsf(dx) <= P.dist_norm)) return 0.0f;
+    const float dy = __fsub_rn(a.y, q.y);
+    if (!((double)fabsf(dy) <= P.dist_norm)) return 0.0f;
+    const float d = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+    const double dn = __ddiv_rn((double)d, P.dist_norm);
+    const double x = P.dist_norm < dn ? P.dist_norm : dn;                // min(dist / dist_norm, dist_norm)
+    if (!P.with_rotation) return (float)__dsub_rn(1.0, x);
+    const float rot = fabsf((float)sin((double)__fsub_rn(a.z, q.z)));
+    return (float)__dsub_rn(__dsub_rn(1.0, __dmul_rn(__dsub_rn(1.0, P.rot_alpha), x)), __dmul_rn(P.rot_alpha, (double)rot));
+}
+
+// A ground truth's best similarity over all anchors is an atomicMax on one 32-bit word, zero-filled before the first pass.
+//   NearestIou: overlaps are >= 0, so the raw float bits order like the floats and 0 is both "no overlap" and the fill.
+//   Distance:   values of either sign -> the order-preserving key below (negative floats: all bits flipped; others: sign bit set).
+//               No float maps to key 0, so the zero fill means "no anchor took part" (a wholly masked range).
+__device__ __forceinline__ unsigned ord_key(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord_val(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+template <int SIM> struct Sim;
+template <> struct Sim<SEC_SIM_NEAREST_IOU> {
+    static __device__ __forceinline__ float4 stage(const float *q) { return near_bbox(q[0], q[1], q[3], q[4], q[6]); }
+    static __device__ __forceinline__ float value(const float4 a, const float4 q, const SimParams &) { return iou_eps0(a, q); }
+};
+template <> struct Sim<SEC_SIM_DISTANCE> {
+    static __device__ __forceinline__ float4 stage(const float *q) { return make_float4(q[0], q[1], q[6], 0.0f); }
+    static __device__ __forceinline__ float value(const float4 a, const float4 q, const SimParams &P) { return distance_sim(a, q, P); }
+};
+
+// pass 1: per (frame, anchor) best ground truth (first index on ties, like np.argmax) and, per ground truth, the best similarity
+// over all anchors (atomicMax on the float bits, NearestIou: overlaps are >= 0, so integer order == float order; Distance: on
+// the order-preserving key)
 //
 // assign_per_class (target_assigner.py:90-160): one launch pair per class handles the class's anchor range
 // [a_begin, a_end) against the ground truth of that class only (`filter` = its 1-based id, 0 = every ground truth); boxes of
 // other classes are skipped, and a frame without a box of the class labels the whole range background (len(gt_boxes) == 0).
 struct AssignRange { int a_begin, a_end, filter; };
 
+template <int SIM>
 __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__ anchors, int n_anchor,
                                                       const float *__restrict__ gt, const int *__restrict__ gt_classes,
                                                       const int *__restrict__ gt_offsets, AssignRange R,
                                                       float *__restrict__ a_max, int *__restrict__ a_arg,
-                                                      int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask) {
+                                                      int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask,
+                                                      SimParams P) {
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ unsigned char s_on[kMaxGtLds];
     const int b = blockIdx.y, a = R.a_begin + blockIdx.x * kBlock + threadIdx.x;
@@ -55,8 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
     if (a < n_anchor && amask && !amask[(size_t)b * n_total + a]) n_anchor = 0;
     float4 abv = make_float4(0, 0, 0, 0);
     if (a < n_anchor) {
-        const float *p = anchors + (size_t)a * 7;
-        abv = near_bbox(p[0], p[1], p[3], p[4], p[6]);
+        abv = Sim<SIM>::stage(anchors + (size_t)a * 7);
     }
     float best = -1.0f;
     int arg = -1;
@@ -64,17 +112,22 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
         const int cn = min(kMaxGtLds, g1 - c0);
         __syncthreads();
         for (int i = threadIdx.x; i < cn; i += kBlock) {
-            const float *q = gt + (size_t)(c0 + i) * 7;
-            s_gt[i] = near_bbox(q[0], q[1], q[3], q[4], q[6]);
+            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * 7);
             s_on[i] = (R.filter == 0 || (gt_classes ? gt_classes[c0 + i] : 1) == R.filter) ? 1 : 0;
         }
         __syncthreads();
         if (a < n_anchor) {
             for (int i = 0; i < cn; ++i) {
                 if (!s_on[i]) continue;
-                const float v = iou_eps0(abv, s_gt[i]);
-                if (v > best) { best = v; arg = c0 + i - g0; }
-                if (v > 0.0f) atomicMax(&gt_max_bits[c0 + i], __float_as_int(v));
+                const float v = Sim<SIM>::value(abv, s_gt[i], P);
+                if (SIM == SEC_SIM_NEAREST_IOU) {
+                    if (v > best) { best = v; arg = c0 + i - g0; }
+                    if (v > 0.0f) atomicMax(&gt_max_bits[c0 + i], __float_as_int(v));
+                } else {
+                    // no floor under a similarity that can be negative: the first ground truth of the class starts the maximum
+                    if (arg < 0 || v > best) { best = v; arg = c0 + i - g0; }
+                    atomicMax(reinterpret_cast<unsigned *>(gt_max_bits) + c0 + i, ord_key(v));
+                }
             }
         }
     }
@@ -85,6 +138,12 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
 }
 
 // pass 2: labels / box targets / importance of create_target_np (positive_fraction = None, no anchor pruning)
+//
+// Distance: create_target_np has no guard for negative similarities, and neither has this.  gt_to_anchor_max is the plain column
+// maximum (negative when every anchor of the range lies inside the box's window), every anchor that ties with it is forced
+// positive, and the reference's -1 fill for a maximum of exactly 0 also matches a genuine similarity of exactly -1
+// (dist_norm = 2, dx = 2, dy = 0).  A box of another class gets NaN, which no similarity equals.
+template <int SIM>
 __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict__ anchors, int n_anchor,
                                                         const float *__restrict__ gt, const int *__restrict__ gt_classes,
                                                         const float *__restrict__ gt_importance,
@@ -93,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
                                                         const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
                                                         float matched, float unmatched, int *__restrict__ labels,
                                                         float *__restrict__ targets, float *__restrict__ importance,
-                                                        const unsigned char *__restrict__ amask) {
+                                                        const unsigned char *__restrict__ amask, SimParams P) {
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ float s_gmax[kMaxGtLds];
     __shared__ int s_any;
@@ -104,23 +163,30 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     if (threadIdx.x == 0) s_any = 0;
     float4 abv = make_float4(0, 0, 0, 0);
     const float *p = anchors + (size_t)(a < n_anchor ? a : 0) * 7;
-    if (a < n_anchor) abv = near_bbox(p[0], p[1], p[3], p[4], p[6]);
+    if (a < n_anchor) abv = Sim<SIM>::stage(p);
     bool force = false;                       // "anchors_with_max_overlap": ties with some ground truth's best overlap
     for (int c0 = g0; c0 < g1; c0 += kMaxGtLds) {
         const int cn = min(kMaxGtLds, g1 - c0);
         __syncthreads();
         for (int i = threadIdx.x; i < cn; i += kBlock) {
-            const float *q = gt + (size_t)(c0 + i) * 7;
-            s_gt[i] = near_bbox(q[0], q[1], q[3], q[4], q[6]);
-            const float m = __int_as_float(gt_max_bits[c0 + i]);
+            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * 7);
             const bool on = R.filter == 0 || (gt_classes ? gt_classes[c0 + i] : 1) == R.filter;
-            // a ground truth no anchor overlaps matches nothing (-1); one of another class can never be matched (-2: an IoU is >= 0)
-            s_gmax[i] = !on ? -2.0f : (m == 0.0f ? -1.0f : m);
+            if (SIM == SEC_SIM_NEAREST_IOU) {
+                const float m = __int_as_float(gt_max_bits[c0 + i]);
+                // a ground truth no anchor overlaps matches nothing (-1); one of another class can never be matched (-2: an IoU is >= 0)
+                s_gmax[i] = !on ? -2.0f : (m == 0.0f ? -1.0f : m);
+            } else {
+                const unsigned key = (unsigned)gt_max_bits[c0 + i];
+                const float m = ord_val(key);
+                // the reference's fill: a maximum of exactly 0 becomes -1 (which a similarity CAN equal, see above); another class,
+                // or a box no anchor took part for, matches nothing (NaN)
+                s_gmax[i] = (!on || key == 0u) ? __uint_as_float(0x7fc00000u) : (m == 0.0f ? -1.0f : m);
+            }
             if (on) s_any = 1;
         }
         __syncthreads();
         if (a < n_anchor)
-            for (int i = 0; i < cn; ++i) force |= iou_eps0(abv, s_gt[i]) == s_gmax[i];
+            for (int i = 0; i < cn; ++i) force |= Sim<SIM>::value(abv, s_gt[i], P) == s_gmax[i];
     }
     __syncthreads();
     if (a >= n_anchor) return;
@@ -163,6 +229,16 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     importance[o] = imp;
 #pragma unroll
     for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
+}
+
+// RegionSimilarityCalculator.compare: out[n, k] = similarity of anchor n with ground truth k; consecutive lanes walk k (the row)
+template <int SIM>
+__global__ __launch_bounds__(kBlock) void k_region_similarity(const float *__restrict__ anchors, int n, const float *__restrict__ gt,
+                                                             int k, SimParams P, float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (size_t)n * k) return;
+    const size_t row = i / k, col = i - row * k;
+    out[i] = Sim<SIM>::value(Sim<SIM>::stage(anchors + row * 7), Sim<SIM>::stage(gt + col * 7), P);
 }
 
 // ------------------------------------------------------------------------------------------------ loss
@@ -667,11 +743,11 @@ SEC_API int sec_assign_targets_f32(const float *anchors, int n_anchor, const flo
     if ((rc = fill_words(gt_max, (size_t)(n_gt > 0 ? n_gt : 1) * sizeof(int), 0u, st))) return rc;     // (a kernel: this runs inside captured training steps)
     dim3 grid(div_up(n_anchor, kBlock), batch);
     const AssignRange all{0, n_anchor, 0};
-    hipLaunchKernelGGL(k_assign_max, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, all, a_max,
-                       a_arg, gt_max, nullptr);
-    hipLaunchKernelGGL(k_assign_write, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_importance,
-                       gt_offsets, all, a_max, a_arg, gt_max, matched_threshold, unmatched_threshold, labels, bbox_targets,
-                       importance, nullptr);
+    hipLaunchKernelGGL(k_assign_max<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes,
+                       gt_offsets, all, a_max, a_arg, gt_max, nullptr, SimParams{});
+    hipLaunchKernelGGL(k_assign_write<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes,
+                       gt_importance, gt_offsets, all, a_max, a_arg, gt_max, matched_threshold, unmatched_threshold, labels,
+                       bbox_targets, importance, nullptr, SimParams{});
     return check_launch();
 }
 
@@ -679,13 +755,40 @@ static int assign_targets_ranges(const float *anchors, int n_anchor, const float
                                  const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
                                  const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
                                  const float *h_unmatched, int *labels, float *bbox_targets, float *importance, void *workspace,
-                                 size_t workspace_bytes, void *stream, const unsigned char *anchors_mask) {
+                                 size_t workspace_bytes, void *stream, const unsigned char *anchors_mask,
+                                 const int *h_sim_kind = nullptr, const double *h_sim_params = nullptr) {
     if (n_anchor <= 0 || batch <= 0 || n_gt < 0 || n_class <= 0 || !anchors || !gt_offsets || !labels || !bbox_targets ||
         !importance || !h_class_anchor_begin || !h_class_ids || !h_matched || !h_unmatched || (n_gt > 0 && (!gt_boxes || !gt_classes)))
         return SEC_E_INVALID;
     if (h_class_anchor_begin[0] != 0 || h_class_anchor_begin[n_class] != n_anchor) return SEC_E_INVALID;
     for (int c = 0; c < n_class; ++c)
         if (h_class_anchor_begin[c + 1] < h_class_anchor_begin[c] || h_class_ids[c] < 0) return SEC_E_INVALID;
+    // the similarity of every range (h_sim_kind NULL: NearestIou throughout, the entry points without one), all decided before any launch
+    auto sim_of = [&](int c, SimParams &P) {
+        P = SimParams{};
+        if (!h_sim_kind || h_sim_kind[c] == SEC_SIM_NEAREST_IOU) return (int)SEC_SIM_NEAREST_IOU;
+        P.dist_norm = h_sim_params[c * 3 + 0];
+        P.with_rotation = h_sim_params[c * 3 + 1] != 0.0 ? 1 : 0;
+        P.rot_alpha = h_sim_params[c * 3 + 2];
+        return h_sim_kind[c];
+    };
+    if (h_sim_kind) {
+        if (!h_sim_params) return SEC_E_INVALID;
+        SimParams P0, Pc, Pd;
+        const int k0 = sim_of(0, P0);
+        for (int c = 0; c < n_class; ++c) {
+            const int kc = sim_of(c, Pc);
+            if (kc != SEC_SIM_NEAREST_IOU && kc != SEC_SIM_DISTANCE) return SEC_E_INVALID;
+            if (kc == SEC_SIM_DISTANCE && !(Pc.dist_norm > 0.0)) return SEC_E_INVALID;
+            // assign_all compares with _sim_calcs[0] whatever the range (target_assigner.py:68-71)
+            if (h_class_ids[c] == 0 && (kc != k0 || Pc.dist_norm != P0.dist_norm || Pc.with_rotation != P0.with_rotation ||
+                                        Pc.rot_alpha != P0.rot_alpha))
+                return SEC_E_INVALID;
+            // ranges of one class share that class's best-similarity words, which the two kinds encode differently
+            for (int d = 0; d < c; ++d)
+                if (h_class_ids[d] == h_class_ids[c] && sim_of(d, Pd) != kc) return SEC_E_INVALID;
+        }
+    }
     if (!workspace || workspace_bytes < sec_assign_targets_workspace_bytes(batch, n_anchor, n_gt)) return SEC_E_WORKSPACE;
     Arena ar(workspace, workspace_bytes);
     float *a_max = ar.take<float>((size_t)batch * n_anchor);
@@ -702,13 +805,15 @@ static int assign_targets_ranges(const float *anchors, int n_anchor, const float
             const AssignRange R{h_class_anchor_begin[c], h_class_anchor_begin[c + 1], h_class_ids[c]};
             if (R.a_end == R.a_begin) continue;
             dim3 grid(div_up(R.a_end - R.a_begin, kBlock), batch);
+            SimParams P;
+            const bool dist = sim_of(c, P) == SEC_SIM_DISTANCE;
             if (pass == 0)
-                hipLaunchKernelGGL(k_assign_max, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, R,
-                                   a_max, a_arg, gt_max, anchors_mask);
+                hipLaunchKernelGGL(dist ? k_assign_max<SEC_SIM_DISTANCE> : k_assign_max<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock), 0,
+                                   st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, R, a_max, a_arg, gt_max, anchors_mask, P);
             else
-                hipLaunchKernelGGL(k_assign_write, grid, dim3(kBlock), 0, st, anchors, n_anchor, gt_boxes, gt_classes,
-                                   gt_importance, gt_offsets, R, a_max, a_arg, gt_max, h_matched[c], h_unmatched[c], labels,
-                                   bbox_targets, importance, anchors_mask);
+                hipLaunchKernelGGL(dist ? k_assign_write<SEC_SIM_DISTANCE> : k_assign_write<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock),
+                                   0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, R, a_max, a_arg, gt_max,
+                                   h_matched[c], h_unmatched[c], labels, bbox_targets, importance, anchors_mask, P);
         }
     return check_launch();
 }
@@ -736,6 +841,35 @@ SEC_API int sec_assign_targets_masked_f32(const float *anchors, int n_anchor, co
     return assign_targets_ranges(anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, n_gt, batch, n_class,
                                  h_class_anchor_begin, h_class_ids, h_matched, h_unmatched, labels, bbox_targets, importance, workspace,
                                  workspace_bytes, stream, anchors_mask);
+}
+
+// sec_assign_targets_masked_f32 with a region similarity per range (h_sim_kind[c], h_sim_params[c] = dist_norm, with_rotation,
+// rot_alpha as float64, the type the reference's Python floats have inside the compiled distance_similarity)
+SEC_API int sec_assign_targets_sim_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                       const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                                       const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                                       const float *h_unmatched, const int *h_sim_kind, const double *h_sim_params, int *labels,
+                                       float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
+                                       const unsigned char *anchors_mask, void *stream) {
+    if (!h_sim_kind || !h_sim_params) return SEC_E_INVALID;
+    return assign_targets_ranges(anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, n_gt, batch, n_class,
+                                 h_class_anchor_begin, h_class_ids, h_matched, h_unmatched, labels, bbox_targets, importance, workspace,
+                                 workspace_bytes, stream, anchors_mask, h_sim_kind, h_sim_params);
+}
+
+SEC_API int sec_region_similarity_f32(const float *anchors, int n, const float *gt_boxes, int k, int kind, double dist_norm,
+                                      int with_rotation, double rot_alpha, float *out, void *stream) {
+    if (n < 0 || k < 0 || (kind != SEC_SIM_NEAREST_IOU && kind != SEC_SIM_DISTANCE)) return SEC_E_INVALID;
+    if (kind == SEC_SIM_DISTANCE && !(dist_norm > 0.0)) return SEC_E_INVALID;
+    if (n == 0 || k == 0) return 0;
+    if (!anchors || !gt_boxes || !out) return SEC_E_INVALID;
+    const long long blocks = ((long long)n * k + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffLL) return SEC_E_UNSUPPORTED;
+    SimParams P{};
+    if (kind == SEC_SIM_DISTANCE) { P.dist_norm = dist_norm; P.with_rotation = with_rotation ? 1 : 0; P.rot_alpha = rot_alpha; }
+    hipLaunchKernelGGL(kind == SEC_SIM_DISTANCE ? k_region_similarity<SEC_SIM_DISTANCE> : k_region_similarity<SEC_SIM_NEAREST_IOU>,
+                       dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, anchors, n, gt_boxes, k, P, out);
+    return check_launch();
 }
 
 SEC_API size_t sec_second_loss_workspace_bytes(int batch, int n_anchor) {

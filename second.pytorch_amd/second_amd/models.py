@@ -93,6 +93,13 @@ ALL_FHD_NUSC = dict(
     use_rotate_nms=False, post_center_range=[-59.6, -59.6, -10, 59.6, 59.6, 10],
 )  # second/configs/nuscenes/all.fhd.config
 
+# The region_similarity_calculator of every anchor generator of all.fhd.config (:85-295): pedestrian and traffic_cone (groups 5, 6)
+# get distance_similarity { distance_norm: 1.414, with_rotation: false, rotation_alpha: 0.0 }, every other class
+# nearest_iou_similarity.  ALL_FHD_NUSC itself carries no ``group_similarity`` key and therefore matches those two classes by
+# near-box IoU; dict(ALL_FHD_NUSC, group_similarity=NUSC_FHD_GROUP_SIMILARITY) is the reference's assignment.
+NUSC_FHD_GROUP_SIMILARITY = [None if gi not in (5, 6) else dict(kind="distance", distance_norm=1.414, with_rotation=False,
+                                                                rotation_alpha=0.0) for gi in range(10)]
+
 
 CAR_LITE = dict(
     name="car.lite",

@@ -1695,14 +1695,73 @@ def predict_finalize(dec, top_score, top_label, dir_label, keep, num_keep, post_
 
 
 # ----------------------------------------------------------------------------- training: targets + loss
+SIM_NEAREST_IOU, SIM_DISTANCE = 0, 1         # include/second_hip.h SEC_SIM_*
+
+
+def similarity_spec(sim):
+    """One region similarity as (kind, distance_norm, with_rotation, rotation_alpha).  ``sim``: None / "nearest_iou"; "distance"
+    needs its parameters, so it comes as dict(kind="distance", distance_norm=, with_rotation=False, rotation_alpha=0.5)
+    (DistanceSimilarity's own defaults) or as such a 4-tuple.  Python floats stay float64 up to the kernel, as in the reference."""
+    if sim is None or sim == "nearest_iou":
+        return (SIM_NEAREST_IOU, 0.0, False, 0.0)
+    if isinstance(sim, dict):
+        kind = sim.get("kind")
+        if kind == "nearest_iou":
+            return (SIM_NEAREST_IOU, 0.0, False, 0.0)
+        if kind != "distance":
+            raise ValueError(f"region similarity kind {kind!r}: expected 'nearest_iou' or 'distance'")
+        unknown = set(sim) - {"kind", "distance_norm", "with_rotation", "rotation_alpha"}
+        if unknown or "distance_norm" not in sim:
+            raise ValueError(f"distance similarity {sim!r}: needs distance_norm, takes with_rotation and rotation_alpha")
+        sim = (SIM_DISTANCE, sim["distance_norm"], sim.get("with_rotation", False), sim.get("rotation_alpha", 0.5))
+    if isinstance(sim, (tuple, list)) and len(sim) == 4 and sim[0] in (SIM_NEAREST_IOU, SIM_DISTANCE):
+        kind, dn, rot, alpha = sim
+        if kind == SIM_DISTANCE and not float(dn) > 0.0:
+            raise ValueError(f"distance similarity: distance_norm must be > 0, got {dn!r}")
+        return (int(kind), float(dn), bool(rot), float(alpha))
+    raise ValueError(f"region similarity {sim!r}: expected None, 'nearest_iou' or dict(kind='distance', distance_norm=...)")
+
+
+@_traced("region_similarity")
+def region_similarity(anchors, gt, kind="nearest_iou", distance_norm=None, with_rotation=False, rotation_alpha=0.5):
+    """RegionSimilarityCalculator.compare on the device: [N, K] fp32 similarities of anchors [N,7] with boxes [K,7].
+    kind "nearest_iou": NearestIouSimilarity; "distance": DistanceSimilarity(distance_norm, with_rotation, rotation_alpha) in the
+    arithmetic numba compiles (float32 differences and squared distance, float64 from the division on, one rounding)."""
+    rt.require_gpu(anchors, gt)
+    if kind not in ("nearest_iou", "distance"):
+        raise ValueError(f"region similarity kind {kind!r}: expected 'nearest_iou' or 'distance'")
+    spec = similarity_spec(None if kind == "nearest_iou" else dict(kind="distance", distance_norm=distance_norm,
+                                                                   with_rotation=with_rotation, rotation_alpha=rotation_alpha))
+    anchors, gt = anchors.float().contiguous(), gt.float().contiguous()
+    assert anchors.dim() == 2 and anchors.shape[1] == 7 and gt.dim() == 2 and gt.shape[1] == 7 and gt.device == anchors.device
+    n, k = anchors.shape[0], gt.shape[0]
+    out = torch.empty((n, k), dtype=torch.float32, device=anchors.device)
+    rc = rt.lib().sec_region_similarity_f32(rt.ptr(anchors) if n else None, n, rt.ptr(gt) if k else None, k, spec[0], spec[1],
+                                            int(spec[2]), spec[3], rt.ptr(out) if n * k else None, rt.stream())
+    rt.check(rc, "sec_region_similarity_f32")
+    return out
+
+
+def _assign_sim(l, specs, anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, n, begin, ids, mt, ut, labels, targets,
+                importance, ws, anchors_mask):
+    kinds = (ctypes.c_int * n)(*[s[0] for s in specs])
+    params = (ctypes.c_double * (3 * n))(*[v for s in specs for v in (s[1], 1.0 if s[2] else 0.0, s[3])])
+    rc = l.sec_assign_targets_sim_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes), rt.ptr(gt_importance),
+                                      rt.ptr(gt_offsets), g, b, n, begin, ids, mt, ut, kinds, params, rt.ptr(labels), rt.ptr(targets),
+                                      rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.ptr(anchors_mask), rt.stream())
+    rt.check(rc, "sec_assign_targets_sim_f32")
+
+
 @_traced("assign_targets")
 def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_threshold, gt_classes=None,
-                   gt_importance=None, anchors_mask=None):
+                   gt_importance=None, anchors_mask=None, similarity=None):
     """TargetAssigner.assign -> create_target_np (second/core/target_ops.py:29-229) with NearestIouSimilarity and
     GroundBox3dCoder.encode, for a whole batch on the device.  anchors [A,7] fp32; gt_boxes [G,7] fp32 (frames concatenated),
     gt_offsets [B+1] int32.  -> labels [B,A] int32, bbox_targets [B,A,7] fp32, importance [B,A] fp32.
     ``anchors_mask`` [B, A] bool / uint8 = create_target_np's prune_anchor_fn (where(mask)): anchors with a zero entry are left out of
-    the matching and come back as label -1, targets 0, importance 0."""
+    the matching and come back as label -1, targets 0, importance 0.
+    ``similarity``: None = NearestIouSimilarity through the entry points that know nothing else; otherwise what
+    :func:`similarity_spec` takes, through sec_assign_targets_sim_f32."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
     assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
     assert gt_offsets.dtype == torch.int32
@@ -1723,6 +1782,15 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
     importance = torch.empty((b, a), dtype=torch.float32, device=dev)
     l = rt.lib()
     ws = rt.workspace(l.sec_assign_targets_workspace_bytes(b, a, g), dev)
+    if similarity is not None:              # one range, class id 0 = every ground truth, with the similarity asked for
+        if anchors_mask is not None:
+            anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
+        if gt_classes is None:
+            gt_classes = torch.ones((g,), dtype=torch.int32, device=dev)
+        _assign_sim(l, [similarity_spec(similarity)], anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, 1,
+                    (ctypes.c_int * 2)(0, a), (ctypes.c_int * 1)(0), (ctypes.c_float * 1)(float(matched_threshold)),
+                    (ctypes.c_float * 1)(float(unmatched_threshold)), labels, targets, importance, ws, anchors_mask)
+        return labels, targets, importance
     if anchors_mask is not None:            # one range, class id 0 = every ground truth: sec_assign_targets_f32 with the mask
         anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
         if gt_classes is None:
@@ -1743,11 +1811,13 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
 
 @_traced("assign_targets_per_class")
 def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_anchor_begin, class_ids, matched_thresholds,
-                             unmatched_thresholds, gt_importance=None, anchors_mask=None):
+                             unmatched_thresholds, gt_importance=None, anchors_mask=None, similarities=None):
     """TargetAssigner.assign for multi-class configs, a whole batch on the device.  Range c of the class-major anchor array =
     anchors[class_anchor_begin[c]:class_anchor_begin[c+1]] with its own thresholds; class_ids[c] = k > 0: assign_per_class
     (target_assigner.py:90-160, only ground truth of class k); class_ids[c] = 0: assign_all with per-anchor thresholds
-    (target_assigner.py:53-88).  Same outputs as assign_targets; ``anchors_mask`` [B, A] as there (each range sees its slice)."""
+    (target_assigner.py:53-88).  Same outputs as assign_targets; ``anchors_mask`` [B, A] as there (each range sees its slice).
+    ``similarities``: None = NearestIouSimilarity for every range, through the entry points that know nothing else; otherwise one
+    :func:`similarity_spec` entry per range (the reference's region_similarity_calculators), through sec_assign_targets_sim_f32."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
     assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
     assert gt_offsets.dtype == torch.int32
@@ -1766,6 +1836,16 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     ids = (ctypes.c_int * n)(*[int(v) for v in class_ids])
     mt = (ctypes.c_float * n)(*[float(v) for v in matched_thresholds])
     ut = (ctypes.c_float * n)(*[float(v) for v in unmatched_thresholds])
+    if similarities is not None:
+        assert len(similarities) == n, "similarities: one entry per anchor range"
+        if gt_importance is not None:
+            rt.require_gpu(gt_importance)
+            gt_importance = gt_importance.to(torch.float32).contiguous()
+        if anchors_mask is not None:
+            anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
+        _assign_sim(l, [similarity_spec(s) for s in similarities], anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, n,
+                    begin, ids, mt, ut, labels, targets, importance, ws, anchors_mask)
+        return labels, targets, importance
     if anchors_mask is not None:
         anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
         rc = l.sec_assign_targets_masked_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes),

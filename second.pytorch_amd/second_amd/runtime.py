@@ -41,6 +41,7 @@ SYMBOLS = [
     "sec_anchor_area_mask_workspace_bytes", "sec_anchor_area_mask", "sec_predict_select_masked", "sec_assign_targets_masked_f32",
     "sec_kitti_eval_overlaps", "sec_kitti_eval_flags", "sec_kitti_eval_tp_scores", "sec_kitti_eval_thresholds",
     "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr", "sec_kitti_annos_workspace_bytes", "sec_kitti_annos_f64",
+    "sec_region_similarity_f32", "sec_assign_targets_sim_f32",
 ]
 
 _lib = None
@@ -234,6 +235,8 @@ def lib():
         l.sec_anchor_area_mask.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, vp, vp, cf, vp, vp, sz, vp]
         l.sec_predict_select_masked.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
         l.sec_assign_targets_masked_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+        l.sec_region_similarity_f32.argtypes = [vp, ci, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp]
+        l.sec_assign_targets_sim_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         l.sec_db_sample_merge_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, sz, vp]
         cd = ctypes.c_double
         l.sec_kitti_eval_overlaps.argtypes = [ci, ci, vp, vp, vp, vp, vp, ci, ci, ll, ci, ci, ci, cd, vp, vp]

@@ -117,6 +117,22 @@ class FlatAdamW:
         self.sync_hyper()
 
 
+def group_similarities(cfg, n_groups):
+    """The config's optional ``group_similarity`` as one validated ops.similarity_spec per anchor group, or None when the key is
+    absent (then the trainer makes exactly the calls it made before the key existed)."""
+    sims = cfg.get("group_similarity")
+    if sims is None:
+        return None
+    if len(sims) != n_groups:
+        raise ValueError(f"group_similarity has {len(sims)} entries for {n_groups} anchor groups")
+    specs = [ops.similarity_spec(s) for s in sims]
+    if not cfg.get("assign_per_class", True) and any(s != specs[0] for s in specs):
+        # assign_all compares every anchor with the FIRST calculator (target_assigner.py:68-71)
+        raise ValueError("group_similarity: assign_per_class is false, so every group is matched with group 0's similarity; "
+                         "the entries must be equal")
+    return specs
+
+
 class DeviceTrainer:
     def __init__(self, det, lr=3e-3, weight_decay=0.01, max_grad_norm=10.0, matched_threshold=None, unmatched_threshold=None,
                  loss_cfg=None, amp_dtype=None, init_loss_scale=2.0 ** 12):
@@ -145,6 +161,9 @@ class DeviceTrainer:
         if len(mts) > 1:
             ids = self.cfg["group_class_ids"] if self.cfg.get("assign_per_class", True) else [0] * len(mts)
             self.class_ranges = (models.anchor_class_ranges(self.cfg, det.feature_map_size), ids, mts, uts)
+        # optional ``group_similarity``: the region similarity of every anchor group (ops.similarity_spec entries, e.g.
+        # models.NUSC_FHD_GROUP_SIMILARITY).  Absent: NearestIouSimilarity through the calls that know nothing else.
+        self.similarities = group_similarities(self.cfg, len(mts))
         self.loss_cfg = dict(ops.LOSS_DEFAULTS, direction_offset=self.cfg["direction_offset"], num_class=self.cfg["num_class"],
                              num_direction_bins=self.cfg["num_direction_bins"], **(loss_cfg or {}))
         self.amp_dtype = amp_dtype
@@ -200,12 +219,14 @@ class DeviceTrainer:
             # care", so nothing else in the step changes.  None for every other config.
             amask = det.anchor_area_mask(vox["coordinates"], batch, nd)
             if self.class_ranges is None:
+                sim = {} if self.similarities is None else dict(similarity=self.similarities[0])
                 labels, reg_targets, importance = ops.assign_targets(det.anchors, gt_boxes, gt_offsets, *self.thresholds,
-                                                                     gt_classes=gt_classes, anchors_mask=amask)
+                                                                     gt_classes=gt_classes, anchors_mask=amask, **sim)
             else:
                 begin, ids, mts, uts = self.class_ranges
+                sim = {} if self.similarities is None else dict(similarities=self.similarities)
                 labels, reg_targets, importance = ops.assign_targets_per_class(det.anchors, gt_boxes, gt_offsets, gt_classes,
-                                                                               begin, ids, mts, uts, anchors_mask=amask)
+                                                                               begin, ids, mts, uts, anchors_mask=amask, **sim)
         if det.pillars:
             # PointPillars (nuscenes/all.pp.largea): PillarFeatureNet on sec_pfn_train_fwd / _bwd (batch statistics; the [P, T, C]
             # tensor of the reference formulation is never built), differentiable pillar scatter (sec_pillar_scatter / sec_dense_to_sparse),
