@@ -276,7 +276,10 @@ int sec_get_fp32_mode(void);
  * For 16-bit dtypes dfeat runs on the MFMA forward kernels over re-packed transposed weights, which live in
  * `workspace` (sec_indice_conv_bwd_workspace_bytes; NULL / too small selects the slower generic kernel).
  * dweight is accumulated with atomics into a zeroed buffer: `dweight_zeroed` != 0 says the caller zeroed it already (the
- * forward's sec_pack_conv_weight_train does, in the launch it runs anyway); 0: the call zeroes it (one memset node). */
+ * forward's sec_pack_conv_weight_train does, in the launch it runs anyway); 0: the call zeroes it (one memset node).
+ * n_out == 0 (no output rows; nbr_out and dout may then be NULL): dweight is all zero and so is dfeat.
+ * sec_last_kernel_name() afterwards: the weight-gradient kernel and its rows per chunk ("k_conv_wgrad_tr<__hip_bfloat16, 32, 32>
+ * chunk=1024") when dweight was asked for, else the data-gradient kernel where that one reports itself. */
 size_t sec_indice_conv_bwd_workspace_bytes(int kvol, int cin, int cout, int dtype);
 int sec_indice_conv_bwd(const void *features, int n_in, int cin, const void *weight, int kvol, int cout,
                         const int *nbr_out, const int *nbr_in, int n_out, const void *dout,

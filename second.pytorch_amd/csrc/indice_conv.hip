@@ -2256,12 +2256,14 @@ static bool launch_wgrad_tiled(const void *feat, const void *dout, const int *nb
     if constexpr (!std::is_same<T, float>::value) {            // 16-bit dtypes: matrix cores
 #define SEC_WM(CI, CO)                                                                                                    \
         if (cin == CI && cout == CO) {                                                                                    \
+            set_last_kernel("k_conv_wgrad_mfma<%s, %d, %d> chunk=%d", dtype_name<T>(), CI, CO, chunk);                    \
             hipLaunchKernelGGL((k_conv_wgrad_mfma<T, CI, CO>), grid, dim3(kBlock), 0, st, (const T *)feat, (const T *)dout, nbr, \
                                n_out, kvol, chunk, dw);                                                                   \
             return true;                                                                                                  \
         }
 #define SEC_WT(CI, CO)                                                                                                    \
         if (cin == CI && cout == CO && conv_variant() != kVarWgradCompact) {                                                     \
+            set_last_kernel("k_conv_wgrad_tr<%s, %d, %d> chunk=%d", dtype_name<T>(), CI, CO, chunk);                             \
             hipLaunchKernelGGL((k_conv_wgrad_tr<T, CI, CO>), grid, dim3(kBlock), 0, st, (const T *)feat, (const T *)dout, nbr,   \
                                n_out, kvol, chunk, dw);                                                                   \
             return true;                                                                                                  \
@@ -2273,6 +2275,7 @@ static bool launch_wgrad_tiled(const void *feat, const void *dout, const int *nb
     }
 #define SEC_WG(CI, CO)                                                                                                    \
     if (cin == CI && cout == CO) {                                                                                        \
+        set_last_kernel("k_conv_wgrad_tiled<%s, %d, %d> chunk=%d", dtype_name<T>(), CI, CO, chunk);                       \
         hipLaunchKernelGGL((k_conv_wgrad_tiled<T, CI, CO>), grid, dim3(kBlock), 0, st, (const T *)feat, (const T *)dout, nbr,  \
                            n_out, kvol, chunk, dw);                                                                       \
         return true;                                                                                                      \
@@ -2507,6 +2510,7 @@ static int run_bwd(const void *features, int n_in, int cin, const void *weight, 
         if (!dweight_zeroed && (rc = fill_words(dweight, (size_t)kvol * cin * cout * sizeof(float), 0u, st))) return rc;
         if (n_out > 0 && !launch_wgrad_tiled<T>(features, dout, nbr_out, n_out, cin, cout, kvol, dweight, st)) {
             int rows_per_chunk = 512;
+            set_last_kernel("k_conv_wgrad<%s> chunk=%d", dtype_name<T>(), rows_per_chunk);
             hipLaunchKernelGGL(k_conv_wgrad<T>, dim3(div_up(n_out, rows_per_chunk), kvol), dim3(kBlock), 0, st,
                                (const T *)features, (const T *)dout, nbr_out, n_out, cin, cout, kvol, rows_per_chunk, dweight);
         }
@@ -2522,7 +2526,10 @@ SEC_API int sec_indice_conv_bwd(const void *features, int n_in, int cin, const v
                                 const int *nbr_out, const int *nbr_in, int n_out, const void *dout, void *dfeat,
                                 float *dweight, int dtype, void *workspace, size_t workspace_bytes, const void *packed_dgrad,
                                 int dweight_zeroed, void *stream) {
-    if (n_in < 0 || n_out < 0 || cin <= 0 || cout <= 0 || kvol <= 0 || !weight || !nbr_out || !dout) return SEC_E_INVALID;
+    if (n_in < 0 || n_out < 0 || cin <= 0 || cout <= 0 || kvol <= 0 || !weight) return SEC_E_INVALID;
+    // no output rows (an empty frame behind a strided conv): empty tensors carry null pointers; dweight is all zero and the data gradient
+    // runs the kernels that read the plain weight on a table of -1, which write zeros and never touch dout
+    if (n_out > 0 && (!nbr_out || !dout)) return SEC_E_INVALID;
     if (!nbr_in && n_in != n_out) return SEC_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == SEC_F32) return run_bwd<float>(features, n_in, cin, weight, kvol, cout, nbr_out, nbr_in, n_out, dout, dfeat, dweight, workspace, workspace_bytes, dtype, st, nullptr, dweight_zeroed != 0);
