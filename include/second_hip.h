@@ -1069,6 +1069,39 @@ int sec_kitti_annos_f64(const float *boxes, const float *scores, const int *labe
                         double *out_box3d, float *out_score, int *out_label, int *out_src, int *out_offsets, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training metrics: VoxelNet.update_metrics (second/pytorch/models/voxelnet.py:654-679) with torchplus/metrics.py Accuracy,
+ * PrecisionRecall and two Scalars -- about 150 launches and 23 device-to-host reads per optimisation step in the reference; two
+ * launches and no read here.
+ *
+ * cls_preds [num_anchors, num_class] float32 logits (num_anchors = B * N, background encoded as all zeros: no background column),
+ * labels [num_anchors] int32 or int64 (labels_are_i64), cared [num_anchors] bytes, non-zero = the anchor counts (NULL: labels >= 0);
+ * cls_loss / loc_loss: one float32 each.  All device pointers, never written.  h_thresholds [num_thresholds] and acc_threshold are
+ * HOST values, already rounded to float32 (what torch compares a float32 tensor with a Python float as).
+ * h_state10: HOST array of ten DEVICE pointers to the float32 state, updated in place, in this order:
+ *   Accuracy total [1], count [1]; PrecisionRecall prec_total [T], prec_count [T], rec_total [T], rec_count [T];
+ *   Scalar(cls) total [1], count [1]; Scalar(loc) total [1], count [1].
+ * out [5 + 2 T] float32 (device): rpn_acc, cls_loss, cls_loss_rt, loc_loss, loc_loss_rt, prec [T], rec [T].
+ *
+ * Per anchor: s = 1 / (1 + expf(-m)) in float32 for m = the largest logit; pred = (lowest index of m) + 1 if s > acc_threshold else
+ * 0; hit_t = s > threshold_t.  Accuracy: count += max(number cared, 1), total += number of anchors with pred == label over ALL
+ * anchors (the reference does not weight that sum), value total / count.  PrecisionRecall per threshold, over cared anchors: tp =
+ * label > 0 and hit, fp = label == 0 and hit, fn = label > 0 and no hit; rec_count += tp + fn, rec_total += tp only when tp + fn >
+ * 0, likewise prec_* with tp + fp; values total / max(count, 1).  Scalar: count += 1, total += loss unless loss == 0 (a NaN is
+ * added); value total / count, NaN while count is 0.  A NaN logit: hit_t is false at every threshold (the maximum of the scores is
+ * NaN); for pred the NaN class itself does not exceed the threshold, the other classes still can, and the index is that of the
+ * first NaN (torch.max).  The counts are int32 sums, so the result does not depend on the launch order.
+ *
+ * workspace: sec_train_metrics_workspace_bytes(T) bytes that are ZERO before the first call; every call leaves them zero.
+ * Before any launch: NULL state / out / loss pointers, negative counts, num_class < 1: SEC_E_INVALID; num_thresholds > 16 or
+ * num_anchors > 2^24 (beyond which the reference's float32 sums are not exact): SEC_E_UNSUPPORTED; workspace: SEC_E_WORKSPACE.
+ * --------------------------------------------------------------------------------------------- */
+size_t sec_train_metrics_workspace_bytes(int num_thresholds);
+int sec_train_metrics_f32(const float *cls_preds, const void *labels, int labels_are_i64, const unsigned char *cared,
+                          long long num_anchors, int num_class, const float *h_thresholds, int num_thresholds, float acc_threshold,
+                          const float *cls_loss, const float *loc_loss, float *const *h_state10, float *out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,7 +295,8 @@ def accelerate_nms():
     return bto
 
 
-def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None):
+def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None,
+                     train_metrics=None):
     """Serve a reference-built ``VoxelNet``'s ``net(example)`` in eval mode (voxelnet.py:339-375, called by train.py:524) from the
     fused static-capacity, graph-captured pipeline: parameters adopted by state-dict key, same return value
     (voxelnet.py:616-643), fp32 by default and 16-bit after ``net.half()``.  See :mod:`second_amd.dropin`.  Call after the
@@ -307,10 +308,13 @@ def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, trai
     arithmetic) instead of the default split-operand bf16 passes ("bf16x3", 16 significant bits per operand).  ``deferred=True``
     (SEC_ACCELERATE_DEFERRED=1; what ``second_amd.launch evaluate`` uses): eval-mode calls return at once with dicts that fill
     themselves when read -- evaluate() only collects them while it loops (train.py:519-524) -- and consecutive calls overlap on two
-    lanes; anything that reads a result gets exactly what the synchronous call returns."""
+    lanes; anything that reads a result gets exactly what the synchronous call returns.  ``train_metrics=True``
+    (SEC_TRAIN_METRICS=1): ``net.update_metrics`` (voxelnet.py:654-679, called by train.py:327) writes the network's own metric
+    buffers from two launches and returns the same dict after one host read instead of 23 (:mod:`second_amd.train_metrics`);
+    calls outside the kernel's contract go to the reference's method and are counted in the engine's ``stats``."""
     from ..dropin import accelerate_model as _acc
     return _acc(net, dtype=dtype, graph=graph, static=static, strict=strict, train_dtype=train_dtype, fp32_exact=fp32_exact,
-                deferred=deferred)
+                deferred=deferred, train_metrics=train_metrics)
 
 
 def rotate_iou_gpu_eval(boxes, query_boxes, criterion=-1, device_id=0):

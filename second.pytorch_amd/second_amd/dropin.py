@@ -701,13 +701,19 @@ class FusedVoxelNet:
         return res
 
 
-def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None):
+def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None,
+                     train_metrics=None):
     """Serve ``net(example)`` (eval mode) from the fused pipeline; see the module docstring.  ``train_dtype`` (torch.bfloat16 /
     torch.float16, or SEC_ACCELERATE_TRAIN=bf16|fp16 in the environment): training-mode calls are served too -- loss dict out of one
     graph replay, ``loss.backward()`` a second one that leaves the gradients on the network's own parameters (dropin_train).  Returns ``net`` (its ``forward`` is
     shadowed on the instance; ``net._second_amd_engine`` is the :class:`FusedVoxelNet`, ``net._second_amd_original_forward`` the
-    reference's method).  ``strict=False``: a network outside the fused path is returned unchanged instead of raising."""
+    reference's method).  ``strict=False``: a network outside the fused path is returned unchanged instead of raising.
+    ``train_metrics=True`` (SEC_TRAIN_METRICS=1): ``net.update_metrics`` (train.py:327) from two launches and one host read
+    (:mod:`second_amd.train_metrics`) -- fused forward or not; its counters land in the engine's ``stats`` when there is one."""
+    want_metrics = _env_train_metrics() if train_metrics is None else bool(train_metrics)
     if getattr(net, "_second_amd_engine", None) is not None:
+        if want_metrics:
+            _hook_train_metrics(net, net._second_amd_engine.stats, explicit=train_metrics is not None)
         return net
     train_dtype = train_dtype if train_dtype is not None else _env_train_dtype()
     try:
@@ -717,7 +723,11 @@ def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, trai
     except NotAccelerable:
         if strict:
             raise
+        if want_metrics:
+            _hook_train_metrics(net, None, explicit=train_metrics is not None)
         return net
+    if want_metrics:
+        _hook_train_metrics(net, eng.stats, explicit=train_metrics is not None)
     original = net.forward
 
     def forward(example):
@@ -736,6 +746,20 @@ def _env_train_dtype():
     import os
     v = os.environ.get("SEC_ACCELERATE_TRAIN", "").lower()
     return {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.float16, "float16": torch.float16, "half": torch.float16}.get(v)
+
+
+def _env_train_metrics():
+    import os
+    return os.environ.get("SEC_TRAIN_METRICS", "0") == "1"          # unset: second_amd.train_metrics is never imported
+
+
+def _hook_train_metrics(net, stats, explicit):
+    """``explicit``: asked for by argument -- a network without the reference's metric modules is an error then; through the
+    environment such a network is left alone."""
+    from . import train_metrics
+    if not explicit and not all(hasattr(net, n) for n in ("rpn_acc", "rpn_metrics", "rpn_cls_loss", "rpn_loc_loss", "update_metrics")):
+        return None
+    return train_metrics.install(net, stats)
 
 
 def accelerate_class(cls):

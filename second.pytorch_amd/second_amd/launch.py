@@ -20,7 +20,9 @@ GPU and this module patches five seams around it -- no file of the reference is 
                         the gradients of all ranks with ONE RCCL all-reduce of a flat bucket (distributed.GradBucket); with
                         SEC_ACCELERATE_TRAIN=bf16 the network ``build_network`` returns is also passed through
                         ``compat.accelerate_model`` -- forward and backward of every step are two hipGraph replays
-                        (second_amd/dropin_train.py) whose gradients are born in that bucket;
+                        (second_amd/dropin_train.py) whose gradients are born in that bucket; SEC_TRAIN_METRICS=1, with it
+                        or alone: ``net.update_metrics`` (train.py:327) in two launches and one host read
+                        (second_amd/train_metrics.py);
   4. data sharding      ``torch.utils.data.DataLoader`` with ``shuffle=True`` (the training loader, train.py:262-270) gets an
                         epoch-advancing DistributedSampler; loaders with workers use the ``spawn`` start method, because the
                         workers call ``spconv.utils.VoxelGeneratorV2.generate`` (second/data/preprocess.py:301-316), which
@@ -89,11 +91,14 @@ def patch_reference(train_module, rank, world, device=None, backend=None):
         # SEC_ACCELERATE_TRAIN=bf16|fp16: training-mode net(example) (train.py:306) from the captured device step -- and the
         # periodic evaluation inside train() from the inference graph.  The gradient seam below finds the gradients already packed
         # in the engine's bucket (dropin_train registers it as net._sec_grad_bucket).
-        from .dropin import _env_train_dtype
+        from .dropin import _env_train_dtype, _env_train_metrics
         if _env_train_dtype() is not None:
             from . import compat
             compat.accelerate_model(net, strict=False)
             state["train_accelerated"] = getattr(net, "_second_amd_engine", None) is not None
+        elif _env_train_metrics() and hasattr(net, "rpn_metrics"):
+            from . import train_metrics                   # SEC_TRAIN_METRICS=1 alone: update_metrics (train.py:327) only, forward untouched
+            train_metrics.install(net)
         return net
 
     def restore(model_dir, objs, *a, **k):

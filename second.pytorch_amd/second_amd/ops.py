@@ -1529,6 +1529,49 @@ def kitti_annos_views(packed, n, images):
     return views
 
 
+TRAIN_METRICS_MAX_THRESHOLDS = 16
+TRAIN_METRICS_MAX_ANCHORS = 1 << 24
+TRAIN_METRICS_STATE = ("acc_total", "acc_count", "prec_total", "prec_count", "rec_total", "rec_count", "cls_total", "cls_count",
+                       "loc_total", "loc_count")
+
+
+def train_metrics(cls_preds, labels, cared, thresholds, acc_threshold, cls_loss, loc_loss, state, out, workspace):
+    """VoxelNet.update_metrics (voxelnet.py:654-679) on the device, two launches and no host read (include/second_hip.h,
+    sec_train_metrics_f32): ``cls_preds`` float32, contiguous, [B, ..., C] with ``labels`` int32 / int64 [B, N] and ``cared`` bool /
+    uint8 [B, N] or None (= labels >= 0); ``thresholds`` the PrecisionRecall thresholds (Python floats), ``acc_threshold`` Accuracy's;
+    ``cls_loss`` / ``loc_loss`` float32 tensors of one element; ``state`` the ten float32 buffers in the order of
+    ``TRAIN_METRICS_STATE``, updated in place; ``out`` float32 [5 + 2 T] <- rpn_acc, cls_loss, cls_loss_rt, loc_loss, loc_loss_rt,
+    prec [T], rec [T]; ``workspace`` = :func:`train_metrics_workspace`, zero before the first call and left zero.  Returns ``out``."""
+    rt.require_gpu(cls_preds, labels, cared, cls_loss, loc_loss, out, workspace, *state)
+    t = len(thresholds)
+    total = labels.numel()
+    assert cls_preds.dtype == torch.float32 and cls_preds.is_contiguous() and total >= 0
+    assert labels.dtype in (torch.int32, torch.int64) and labels.is_contiguous()
+    c = cls_preds.numel() // total if total else int(cls_preds.shape[-1])
+    assert c * total == cls_preds.numel(), "cls_preds is not [labels.numel(), C]"
+    if cared is not None:
+        assert cared.dtype in (torch.bool, torch.uint8) and cared.is_contiguous() and cared.numel() == total
+    assert len(state) == 10 and all(s.dtype == torch.float32 and s.is_contiguous() for s in state)
+    assert all(s.numel() == (t if 2 <= k < 6 else 1) for k, s in enumerate(state)), "state buffer sizes"
+    for x in (cls_loss, loc_loss):
+        assert x.dtype == torch.float32 and x.numel() == 1
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 5 + 2 * t and workspace.dtype == torch.uint8
+    ptrs = (ctypes.c_void_p * 10)(*[s.data_ptr() for s in state])
+    rc = rt.lib().sec_train_metrics_f32(rt.ptr(cls_preds), rt.ptr(labels), int(labels.dtype == torch.int64), rt.ptr(cared), total, c,
+                                        rt.f_arr(thresholds), t, float(acc_threshold), rt.ptr(cls_loss), rt.ptr(loc_loss), ptrs,
+                                        rt.ptr(out), rt.ptr(workspace), workspace.numel(), rt.stream())
+    rt.check(rc, "sec_train_metrics_f32")
+    return out
+
+
+def train_metrics_workspace(num_thresholds, device):
+    """The zeroed counter block :func:`train_metrics` keeps between its two launches (it leaves it zero: allocate once)."""
+    nbytes = rt.lib().sec_train_metrics_workspace_bytes(int(num_thresholds))
+    if nbytes == 0:
+        raise rt.SecondHipError(f"train_metrics: {num_thresholds} thresholds (at most {TRAIN_METRICS_MAX_THRESHOLDS})")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
 @_traced("nms_sorted")
 def nms_sorted(dets, counts, thresh, kind="rotate", semantics="numba", eps=1.0, post_max=0, exact_clip=False):
     """Greedy NMS of score-sorted boxes. dets [B,max_n,stride] float32, counts [B] int32 (device).

@@ -41,7 +41,7 @@ SYMBOLS = [
     "sec_anchor_area_mask_workspace_bytes", "sec_anchor_area_mask", "sec_predict_select_masked", "sec_assign_targets_masked_f32",
     "sec_kitti_eval_overlaps", "sec_kitti_eval_flags", "sec_kitti_eval_tp_scores", "sec_kitti_eval_thresholds",
     "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr", "sec_kitti_annos_workspace_bytes", "sec_kitti_annos_f64",
-    "sec_region_similarity_f32", "sec_assign_targets_sim_f32",
+    "sec_region_similarity_f32", "sec_assign_targets_sim_f32", "sec_train_metrics_workspace_bytes", "sec_train_metrics_f32",
 ]
 
 _lib = None
@@ -113,7 +113,7 @@ def lib():
                      "sec_conv2d_wgrad_workspace_bytes", "sec_bn_train_workspace_bytes", "sec_pfn_train_workspace_bytes",
                      "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes",
                      "sec_anchor_area_mask_workspace_bytes", "sec_kitti_eval_pr_workspace_bytes",
-                     "sec_kitti_annos_workspace_bytes"):
+                     "sec_kitti_annos_workspace_bytes", "sec_train_metrics_workspace_bytes"):
             getattr(l, name).restype = ctypes.c_size_t
         if os.environ.get("SEC_FP32_MODE", "").lower() == "exact":      # process default of ops.set_fp32_mode
             l.sec_set_fp32_mode(1)
@@ -248,6 +248,8 @@ def lib():
                                         vp, vp, sz, vp]
         l.sec_kitti_annos_workspace_bytes.argtypes = [ci]
         l.sec_kitti_annos_f64.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        l.sec_train_metrics_workspace_bytes.argtypes = [ci]
+        l.sec_train_metrics_f32.argtypes = [vp, vp, ci, vp, ll, ci, vp, ci, cf, vp, vp, vp, vp, vp, sz, vp]
         _lib = l
     return _lib
 
