@@ -450,6 +450,20 @@ int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox
                       const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
                       const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
                       int out_dtype, void *stream);
+/* PillarFeatureNetRadius.forward (pointpillars.py:290-325; config nuscenes/all.pp.mhead.config), the same way and with the same
+ * arguments: the decorated row is [sqrt(x^2 + y^2), z, f3 .. f(F-1), x - mean_x, y - mean_y, z - mean_z, x - centre_x, y - centre_y],
+ * so weight_t is [F+4, C].  Cluster mean and pillar centre are taken on the Cartesian x, y, z exactly as sec_pfn_fwd takes them; the
+ * radius is rounded like torch.norm's (multiply, add, square root, each correctly rounded).  _slots: bit-identical to the tensor
+ * form. */
+int sec_pfn_radius_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars,
+                       const int *num_dev, int max_points, int num_features, const float *weight_t,
+                       const float *scale, const float *shift, int channels, float vx, float vy,
+                       float x_offset, float y_offset, void *out, int out_dtype, void *stream);
+int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+                             int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
+                             const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
+                             const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
+                             int out_dtype, void *stream);
 
 /* PillarFeatureNet in TRAINING mode (PFNLayer.forward under train(), pointpillars.py:51-65, trained by train.py:316-322):
  * Linear(9, C, bias=False) on the decorated, masked points, BatchNorm1d with BATCH statistics over all P * T rows (padded slots
@@ -714,6 +728,22 @@ int sec_predict_decode_lazy(const void *box, const int64_t *h_box_strides5, cons
                             const float *top_score, int rotate, float *decoded, float *dets, int *dir_label,
                             int dtype, const unsigned short *tile_live, const void *box_background,
                             const void *dir_background, void *stream);
+/* Select / decode over SEVERAL head tensors of different map size (multi-head networks: nuscenes/all.pp.mhead predicts 12 anchors
+ * per cell on a 100 x 100 map and 8 per cell on a 160 x 160 map).  1 <= num_segments <= 4; segment s has its own device pointer
+ * cls[s] (host array of device pointers), strides h_*_strides5[5 s ..] = {sb, sa, sy, sx, sc} and h_dims3[3 s ..] = {A_s, H_s, W_s};
+ * dtype, batch, num_class, k and the threshold are shared.  The GLOBAL anchor index is base_s + (a * H_s + y) * W_s + x with base_s
+ * the number of anchors of the segments before s -- target_assigner.generate_anchors' class-major concatenation: top_idx holds
+ * global indices, `anchors` is the flat [N, 7] list, key_scratch has batch * N words (N = all anchors).  Ranking, ties (by global
+ * index), counts and the unspecified rows behind counts[b] are those of sec_predict_select; with one segment the results equal
+ * sec_predict_select / sec_predict_decode bit for bit.  No lazy form, no anchor mask.  Checked on the host before anything is
+ * enqueued: SEC_E_INVALID for num_segments outside 1..4 or a NULL segment, SEC_E_UNSUPPORTED for k > 1024. */
+int sec_predict_select_segments(int num_segments, const void *const *cls, const int64_t *h_cls_strides5, const int *h_dims3,
+                                int batch, int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                                float *top_score, int *top_label, int *counts, int dtype, void *stream);
+int sec_predict_decode_segments(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+                                const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
+                                const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                float *dets, int *dir_label, int dtype, void *stream);
 int sec_predict_finalize(const float *decoded, const float *top_score, const int *top_label,
                          const int *dir_label, const int *keep, const int *num_keep, int batch, int k,
                          int post_max, int use_direction, float dir_offset, float dir_limit_offset,

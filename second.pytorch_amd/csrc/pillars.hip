@@ -26,7 +26,10 @@ template <> __device__ __forceinline__ __half cvt_out(float v) { return __float2
 // t-th point, vox_slots_of): the pillar's points are fetched through the list instead of from a [P, T, 4] tensor -- the same
 // values in the same positions (slots >= n read as zero), so the result is bit-identical, and the voxeliser need not write (nor
 // this kernel re-read) that tensor: 98 MB each way at 100 k pillars x 60 slots.
-template <typename OT, bool SLOTS = false>
+// RADIUS: PillarFeatureNetRadius (pointpillars.py:290-325): the decorated row is [hypot(x, y), z, w, x - mx, y - my, z - mz, x - cx,
+// y - cy] (IN = 8; the raw x, y give way to their radius, in the arithmetic store_radius_row4 pins to torch.norm); the cluster mean
+// and the pillar centre stay Cartesian, as above.
+template <typename OT, bool SLOTS = false, bool RADIUS = false>
 __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                    const int *__restrict__ coords, int P, const int *__restrict__ num_dev,
                                                    int T, const float *__restrict__ wt, const float *__restrict__ scale,
@@ -58,9 +61,10 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
     for (int c0 = 0; c0 < C; c0 += 64) {
         const int c = c0 + lane;
         const bool live = c < C;
-        float w[9];
+        constexpr int IN = RADIUS ? 8 : 9;
+        float w[IN];
 #pragma unroll
-        for (int j = 0; j < 9; ++j) w[j] = live ? wt[(size_t)j * C + c] : 0.f;
+        for (int j = 0; j < IN; ++j) w[j] = live ? wt[(size_t)j * C + c] : 0.f;
         const float sc = live ? scale[c] : 0.f, sh = live ? shift[c] : 0.f;
         float best = (n < T) ? fmaxf(sh, 0.f) : -INFINITY;   // padded slots: relu(bn(linear(0)))
         for (int t = 0; t < n && t < T; ++t) {
@@ -75,10 +79,17 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
             } else {
                 q = SLOTS ? pv[sl[t]] : pv[t];            // wave-uniform address: one broadcast load
             }
-            float f[9] = {q.x, q.y, q.z, q.w, q.x - mx, q.y - my, q.z - mz, q.x - cx, q.y - cy};
+            float f[IN];
+            if constexpr (RADIUS) {
+                f[0] = __fsqrt_rn(__fadd_rn(__fmul_rn(q.x, q.x), __fmul_rn(q.y, q.y)));
+                f[1] = q.z; f[2] = q.w;
+            } else {
+                f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
+            }
+            f[IN - 5] = q.x - mx; f[IN - 4] = q.y - my; f[IN - 3] = q.z - mz; f[IN - 2] = q.x - cx; f[IN - 1] = q.y - cy;
             float y = 0.f;
 #pragma unroll
-            for (int j = 0; j < 9; ++j) y = fmaf(f[j], w[j], y);
+            for (int j = 0; j < IN; ++j) y = fmaf(f[j], w[j], y);
             y = fmaxf(fmaf(y, sc, sh), 0.f);
             best = fmaxf(best, y);
         }
@@ -477,7 +488,8 @@ static BfWorkspace carve_bf(void *ws, size_t cap, int rows, int batch, int bx, i
 
 using namespace sec;
 
-SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+template <bool RADIUS>
+static int pfn_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
                         int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
                         int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
                         void *stream) {
@@ -486,7 +498,7 @@ SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *c
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL(k_pfn_fwd<OT>, grid, block, 0, st, voxels, num_points, coords, num_pillars, num_dev, \
+#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, false, RADIUS>), grid, block, 0, st, voxels, num_points, coords, num_pillars, num_dev, \
                                        max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out)
     if (out_dtype == SEC_F32) SEC_PFN(float);
     else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
@@ -496,7 +508,8 @@ SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *c
     return check_launch();
 }
 
-SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+template <bool RADIUS>
+static int pfn_fwd_slots_any(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
                               int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
                               const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
                               const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
@@ -512,7 +525,7 @@ SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, si
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, true>), grid, block, 0, st, points, num_points_per_voxel, coords, num_pillars, num_dev, \
+#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, true, RADIUS>), grid, block, 0, st, points, num_points_per_voxel, coords, num_pillars, num_dev, \
                                        max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out, slots)
     if (out_dtype == SEC_F32) SEC_PFN(float);
     else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
@@ -520,6 +533,40 @@ SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, si
     else return SEC_E_UNSUPPORTED;
 #undef SEC_PFN
     return check_launch();
+}
+
+SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
+                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
+                        void *stream) {
+    return pfn_fwd_any<false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
+                               vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
+                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
+                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
+                              int out_dtype, void *stream) {
+    return pfn_fwd_slots_any<false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
+                                     num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
+                                     vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+// PillarFeatureNetRadius (k_pfn_fwd<.., RADIUS>): the same arguments, weight_t is [num_features + 4][channels]
+SEC_API int sec_pfn_radius_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
+                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
+                        void *stream) {
+    return pfn_fwd_any<true>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
+                               vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
+                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
+                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
+                              int out_dtype, void *stream) {
+    return pfn_fwd_slots_any<true>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
+                                     num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
+                                     vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
 
 SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {

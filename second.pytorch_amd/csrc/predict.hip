@@ -12,6 +12,7 @@
 // Tensors are addressed as logit(b, anchor n = (a, y, x), c) = base[b*sb + a*sa + y*sy + x*sx + c*sc] so the RPN head
 // output is consumed in place (no permute / contiguous copies).
 #include "common.hpp"
+#include <type_traits>
 
 namespace sec {
 
@@ -93,13 +94,87 @@ __device__ __forceinline__ unsigned anchor_key(const T *cls, const View5 &v, con
     return f2key(best);
 }
 
+// ---- several head tensors (sec_predict_select_segments / _decode_segments) ------------------------------------------------
+// A multi-head network (nuscenes/all.pp.mhead: a 100 x 100 map with 12 anchors per cell next to a 160 x 160 map with 8) predicts
+// into S tensors of different map size; target_assigner.generate_anchors concatenates their anchors class-major, so the global
+// anchor n lies in the segment s with start[s] <= n < start[s + 1] and is that segment's anchor n - start[s] = (a * H_s + y) * W_s
+// + x.  SegView stands where a View5 stands in the kernels below (template parameter V): keys, ranking and ties are by GLOBAL index
+// and never see the segments; only the address of an anchor's logits does.  No lazy form, no anchor mask.
+constexpr int kMaxSegments = 4;
+struct Seg {
+    const void *base;
+    long long sb, sa, sy, sx, sc;
+    int H, W;
+    int start;                        // anchors before this segment; the total for an unused entry
+};
+struct SegView {                      // named members, no arrays: as a kernel argument it is read field by field, never copied to scratch
+    Seg g0, g1, g2, g3;
+    int total;
+};
+// The segment a thread currently walks: frame b's first element of it, its strides and map, and where its anchors end
+template <typename T> struct SegCur {
+    const T *frame;
+    long long sa, sy, sx, sc;
+    int H, W, end;
+};
+template <typename X> __device__ __forceinline__ X seg_pick(int s, X a, X b, X c, X d) {   // the s-th of four VALUES
+    X r = a;
+    r = s >= 1 ? b : r;
+    r = s >= 2 ? c : r;
+    r = s >= 3 ? d : r;
+    return r;
+}
+// enter the segment of global anchor n (a chain of selects over the four named segments); (a, y, x) of n by division
+template <typename T>
+__device__ __forceinline__ void seg_enter(const SegView &v, int b, int n, SegCur<T> &c, int &x, int &y, int &a) {
+    // every field is read from the kernel argument unconditionally and the segment's picked by value: conditional reads made the
+    // compiler keep a per-lane copy of the table in scratch memory (232 bytes) and select between addresses into it
+    const int s = (n >= v.g1.start ? 1 : 0) + (n >= v.g2.start ? 1 : 0) + (n >= v.g3.start ? 1 : 0);
+#define SEC_SEG_PICK(F) seg_pick(s, v.g0.F, v.g1.F, v.g2.F, v.g3.F)
+    const void *base = SEC_SEG_PICK(base);
+    const long long sb = SEC_SEG_PICK(sb);
+    const int first = SEC_SEG_PICK(start);
+    c.sa = SEC_SEG_PICK(sa); c.sy = SEC_SEG_PICK(sy); c.sx = SEC_SEG_PICK(sx); c.sc = SEC_SEG_PICK(sc);
+    c.H = SEC_SEG_PICK(H); c.W = SEC_SEG_PICK(W);
+    c.end = seg_pick(s, v.g1.start, v.g2.start, v.g3.start, v.total);
+#undef SEC_SEG_PICK
+    static_assert(kMaxSegments == 4, "SegView names four segments");
+    c.frame = static_cast<const T *>(base) + (long long)b * sb;
+    const int l = n - first;
+    x = l % c.W;
+    const int t = l / c.W;
+    y = t % c.H;
+    a = t / c.H;
+}
+// the logits of global anchor n in frame b, and their channel stride
+template <typename T> __device__ __forceinline__ const T *seg_anchor(const SegView &v, int b, int n, long long *sc) {
+    SegCur<T> c;
+    int x, y, a;
+    seg_enter(v, b, n, c, x, y, a);
+    *sc = c.sc;
+    return c.frame + a * c.sa + y * c.sy + x * c.sx;
+}
+template <typename T>
+__device__ __forceinline__ unsigned anchor_key(const T *, const SegView &v, const PredGeom &g, int b, int n, int *label) {
+    long long sc;
+    const T *p = seg_anchor<T>(v, b, n, &sc);
+    float best = ldf(p);
+    int lab = 0;
+    for (int c = 1; c < g.nc; ++c) {
+        float f = ldf(p + c * sc);
+        if (f > best) { best = f; lab = c; }
+    }
+    if (label) *label = lab;
+    return f2key(best);
+}
+
 constexpr int kSelThreads = 1024;
 constexpr int kCandCap = 2048;      // k_predict_select_reg: keys kept in LDS once that few remain above the bisection bound
 
 // pass 0 (whole chip): compact, coalesced key array (the RPN head is channels-last: one anchor's logit per 128-byte
 // pixel row, far too scattered to be re-read by the single workgroup that owns a frame in the select kernel)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_predict_keys(const T *__restrict__ cls, View5 v, PredGeom g,
+template <typename T, typename V = View5>
+__global__ __launch_bounds__(kBlock) void k_predict_keys(const T *__restrict__ cls, V v, PredGeom g,
                                                         unsigned *__restrict__ keys) {
     const int N = g.A * g.H * g.W;
     long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -109,8 +184,8 @@ __global__ __launch_bounds__(kBlock) void k_predict_keys(const T *__restrict__ c
 
 // 16-bit form for 16-bit logits (the low half of such a key is implied by its sign bit): half the bytes, and two
 // consecutive anchors' keys arrive in one dword load in k_predict_select_reg.  Frame stride `ns` is N rounded up to even.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_predict_keys16(const T *__restrict__ cls, View5 v, PredGeom g, int ns,
+template <typename T, typename V = View5>
+__global__ __launch_bounds__(kBlock) void k_predict_keys16(const T *__restrict__ cls, V v, PredGeom g, int ns,
                                                           unsigned short *__restrict__ keys) {
     const int N = g.A * g.H * g.W;
     long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -121,8 +196,8 @@ __global__ __launch_bounds__(kBlock) void k_predict_keys16(const T *__restrict__
 }
 
 // one workgroup per frame
-template <typename T, bool KEY16>
-__global__ __launch_bounds__(kSelThreads) void k_predict_select(const T *__restrict__ cls, View5 v, PredGeom g, int K,
+template <typename T, bool KEY16, typename V = View5>
+__global__ __launch_bounds__(kSelThreads) void k_predict_select(const T *__restrict__ cls, V v, PredGeom g, int K,
                                                                 float score_thr, const unsigned *__restrict__ keys,
                                                                 int *__restrict__ top_idx,
                                                                 float *__restrict__ top_score, int *__restrict__ top_label,
@@ -307,8 +382,8 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select(const T *__restr
 // INDIRECT (second stage of the chunked select): `keys` are the per-chunk candidate keys written by k_predict_select_chunk
 // (n_keys of them per frame, chunk-major, ascending anchor index among equal keys inside and across chunks -- which is all the
 // tie ranking needs), slot_anchor their anchor ids.
-template <typename T, int KP, bool INDIRECT = false>     // 16-bit logits (bf16 / fp16: key16_of); KP = key PAIRS (dwords) per thread
-__global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__restrict__ cls, View5 v, PredGeom g, int K,
+template <typename T, int KP, bool INDIRECT = false, typename V = View5>   // 16-bit logits (bf16 / fp16: key16_of); KP = key PAIRS (dwords) per thread
+__global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__restrict__ cls, V v, PredGeom g, int K,
                                                                     float score_thr, const unsigned short *__restrict__ keys,
                                                                     int ns, int *__restrict__ top_idx,
                                                                     float *__restrict__ top_score, int *__restrict__ top_label,
@@ -565,8 +640,8 @@ constexpr int kSelChunk = 8192;                  // 16 waves x 4 key pairs x 128
 // before its topk).
 // KP = key pairs per thread: 4 (8192-anchor chunks, the usual heads) or 36 (73 728-anchor chunks: heads of > 600 k anchors per
 // frame -- nuScenes all.fhd has 1.23 M -- whose 8192-anchor chunks would hand the second stage more candidate slots than it holds).
-template <typename T, int KP>
-__global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *__restrict__ cls, View5 v, PredGeom g, int N, int K,
+template <typename T, int KP, typename V = View5>
+__global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *__restrict__ cls, V v, PredGeom g, int N, int K,
                                                                       int chunks, unsigned thr16, unsigned short *__restrict__ cand_key,
                                                                       int *__restrict__ cand_idx) {
     constexpr int kChunk = kSelThreads * 2 * KP;
@@ -580,8 +655,15 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
     unsigned k2[KP];
     // (a, y, x) of the thread's first anchor by division, of the others by stepping (anchor n = (a * H + y) * W + x): the runtime
     // divisions of anchor_key() were a third of this kernel's instructions
-    int ax, ay, aa;
-    {
+    // segments: the same stepping inside the segment the thread is in (`cur`); a step across a segment border enters the next one by
+    // division again (rare), and pointers stand for the offsets because every segment has a base of its own
+    constexpr bool SEG = std::is_same<V, SegView>::value;
+    int ax = 0, ay = 0, aa = 0;
+    SegCur<T> cur{};
+    if constexpr (SEG) {
+        const int n0 = base + n_base;
+        seg_enter(v, b, n0 < N ? n0 : 0, cur, ax, ay, aa);
+    } else {
         const int n0 = base + n_base;
         ax = n0 % g.W;
         const int t0 = n0 / g.W;
@@ -597,6 +679,32 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
     for (int i0 = 0; i0 < KP; i0 += PB) {
         long long off[2 * PB];
         bool ok[2 * PB], keep[2 * PB];
+        const T *src[2 * PB];
+        long long csc[2 * PB];
+        if constexpr (SEG) {
+#pragma unroll
+            for (int j = 0; j < PB; ++j) {
+                const int a0 = base + n_base + (i0 + j) * 128;          // a0 < N: `cur` is a0's segment and (aa, ay, ax) its place there
+                ok[2 * j] = a0 < N;
+                ok[2 * j + 1] = a0 + 1 < N;
+                src[2 * j] = ok[2 * j] ? cur.frame + aa * cur.sa + ay * cur.sy + ax * cur.sx : cur.frame;
+                csc[2 * j] = csc[2 * j + 1] = cur.sc;
+                if (ok[2 * j + 1] && a0 + 1 >= cur.end) {                // the pair straddles a segment border
+                    src[2 * j + 1] = seg_anchor<T>(v, b, a0 + 1, &csc[2 * j + 1]);
+                } else {
+                    int bx = ax + 1, by = ay, ba = aa;
+                    if (bx >= cur.W) { bx = 0; if (++by >= cur.H) { by = 0; ++ba; } }
+                    src[2 * j + 1] = ok[2 * j + 1] ? cur.frame + ba * cur.sa + by * cur.sy + bx * cur.sx : cur.frame;
+                }
+                const int an = a0 + 128;                                 // the thread's next pair
+                if (an < N && an >= cur.end) {
+                    seg_enter(v, b, an, cur, ax, ay, aa);
+                } else {
+                    ax += 128;
+                    while (ax >= cur.W) { ax -= cur.W; if (++ay >= cur.H) { ay = 0; ++aa; } }
+                }
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             const int a0 = base + n_base + (i0 + j) * 128;
@@ -609,9 +717,10 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
             ax += 128;
             while (ax >= g.W) { ax -= g.W; if (++ay >= g.H) { ay = 0; ++aa; } }
         }
+        }
 #pragma unroll
         for (int j = 0; j < 2 * PB; ++j) keep[j] = ok[j];
-        if (v.amask) {                                                   // as anchor_key(): a masked-out anchor holds key 0 too
+        if constexpr (!SEG) if (v.amask) {                               // as anchor_key(): a masked-out anchor holds key 0 too
             unsigned char m[2 * PB];
 #pragma unroll
             for (int j = 0; j < 2 * PB; ++j)
@@ -621,11 +730,17 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
         }
         float best[2 * PB];
 #pragma unroll
-        for (int j = 0; j < 2 * PB; ++j) best[j] = ldf(cls + off[j]);
+        for (int j = 0; j < 2 * PB; ++j) {
+            if constexpr (SEG) best[j] = ldf(src[j]);
+            else best[j] = ldf(cls + off[j]);
+        }
         for (int c2 = 1; c2 < g.nc; ++c2) {                              // as anchor_key()
             float f[2 * PB];
 #pragma unroll
-            for (int j = 0; j < 2 * PB; ++j) f[j] = ldf(cls + off[j] + (ok[j] ? (long long)c2 * v.sc : 0));
+            for (int j = 0; j < 2 * PB; ++j) {
+                if constexpr (SEG) f[j] = ldf(src[j] + (ok[j] ? (long long)c2 * csc[j] : 0));
+                else f[j] = ldf(cls + off[j] + (ok[j] ? (long long)c2 * v.sc : 0));
+            }
 #pragma unroll
             for (int j = 0; j < 2 * PB; ++j) if (f[j] > best[j]) best[j] = f[j];
         }
@@ -712,9 +827,9 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__ box, View5 vb, const T *__restrict__ dir,
-                                                          View5 vd, int ndir, PredGeom g, int K,
+template <typename T, typename V = View5>
+__global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__ box, V vb, const T *__restrict__ dir,
+                                                          V vd, int ndir, PredGeom g, int K,
                                                           const float *__restrict__ anchors, const int *__restrict__ top_idx,
                                                           const float *__restrict__ top_score, int rotate,
                                                           float *__restrict__ dec, float *__restrict__ dets,
@@ -723,14 +838,23 @@ __global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__
     if (t >= g.batch * K) return;
     int b = t / K;
     int n = top_idx[t];
-    int x = n % g.W;
-    int q = n / g.W;
-    int y = q % g.H;
-    int a = q / g.H;
-    const T *pb = box + frame_off(vb, b, y, x) + a * vb.sa + y * vb.sy + x * vb.sx;
+    constexpr bool SEG = std::is_same<V, SegView>::value;
+    int x = 0, y = 0, a = 0;
+    const T *pb;
+    long long bsc;
+    if constexpr (SEG) {
+        pb = seg_anchor<T>(vb, b, n, &bsc);
+    } else {
+        x = n % g.W;
+        int q = n / g.W;
+        y = q % g.H;
+        a = q / g.H;
+        pb = box + frame_off(vb, b, y, x) + a * vb.sa + y * vb.sy + x * vb.sx;
+        bsc = vb.sc;
+    }
     float e[7];
 #pragma unroll
-    for (int c = 0; c < 7; ++c) e[c] = ldf(pb + c * vb.sc);
+    for (int c = 0; c < 7; ++c) e[c] = ldf(pb + c * bsc);
     const float *an = anchors + (size_t)n * 7;
     float xa = an[0], ya = an[1], za = an[2], wa = an[3], la = an[4], ha = an[5], ra = an[6];
     float diag = sqrtf(__fadd_rn(__fmul_rn(la, la), __fmul_rn(wa, wa)));
@@ -755,10 +879,17 @@ __global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__
     }
     int dl = 0;
     if (dir) {
-        const T *pd = dir + frame_off(vd, b, y, x) + a * vd.sa + y * vd.sy + x * vd.sx;
+        const T *pd;
+        long long dsc;
+        if constexpr (SEG) {
+            pd = seg_anchor<T>(vd, b, n, &dsc);
+        } else {
+            pd = dir + frame_off(vd, b, y, x) + a * vd.sa + y * vd.sy + x * vd.sx;
+            dsc = vd.sc;
+        }
         float best = ldf(pd);
         for (int c = 1; c < ndir; ++c) {
-            float f = ldf(pd + c * vd.sc);
+            float f = ldf(pd + c * dsc);
             if (f > best) { best = f; dl = c; }
         }
     }
@@ -835,6 +966,10 @@ static unsigned conservative_thr16(float thr, int dtype) {
     return k16 > 2u ? k16 - 2u : 0u;                 // two key steps down: covers the rounding of the conversions above
 }
 
+template <typename V>
+static int predict_select_launch(const void *cls, const V &v, const PredGeom &g, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                                 float *top_score, int *top_label, int *counts, int dtype, void *stream);
+
 static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                int *top_label, int *counts, int dtype, void *stream, const unsigned short *tile_live,
@@ -849,15 +984,23 @@ static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, i
     PredGeom g{batch, anchors_per_loc, h, w, num_class};
     View5 v = mkview_lazy(h_cls_strides5, cls, cls_background, tile_live, h, w, elt_bytes(dtype));
     v.amask = anchor_mask;
+    return predict_select_launch(cls, v, g, k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, stream);
+}
+
+// the select of a validated call; V = View5 (one head tensor, g = its geometry) or SegView (cls unused, g.A * g.H * g.W = all anchors)
+template <typename V>
+static int predict_select_launch(const void *cls, const V &v, const PredGeom &g, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                                 float *top_score, int *top_label, int *counts, int dtype, void *stream) {
+    const int batch = g.batch;
     hipStream_t st = (hipStream_t)stream;
-    const long long total = (long long)batch * anchors_per_loc * h * w;
+    const long long nfr = (long long)g.A * g.H * g.W;
+    const long long total = (long long)batch * nfr;
 #define SEC_SEL(T, K16)                                                                                                         \
     do {                                                                                                                        \
-        hipLaunchKernelGGL(k_predict_keys<T>, dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, key_scratch); \
-            hipLaunchKernelGGL((k_predict_select<T, K16>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k,        \
+        hipLaunchKernelGGL((k_predict_keys<T, V>), dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, key_scratch); \
+            hipLaunchKernelGGL((k_predict_select<T, K16, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k,        \
                                score_thr, key_scratch, top_idx, top_score, top_label, counts, thr_key32);                        \
     } while (0)
-    const long long nfr = (long long)anchors_per_loc * h * w;
     // 32-bit key of a logit safely below the score threshold's (k_predict_select's shortcut; 0: none)
     unsigned thr_key32 = 0u;
     if (score_thr > 0.0f && score_thr < 1.0f) {
@@ -891,15 +1034,15 @@ static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, i
             unsigned short *ck = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(key_scratch) + (size_t)batch * n2 * 4);
             int *ci = reinterpret_cast<int *>(key_scratch);
             const int pairs = (int)((n2 / 2 + kSelThreads - 1) / kSelThreads);
-#define SEC_SEL2(T, KP2) hipLaunchKernelGGL((k_predict_select_reg<T, KP2, true>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, \
+#define SEC_SEL2(T, KP2) hipLaunchKernelGGL((k_predict_select_reg<T, KP2, true, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, \
                                             score_thr, ck, (int)n2, top_idx, top_score, top_label, counts, (int)n2, ci, thr16)
 #define SEC_CHUNKED(T)                                                                                                                      \
     do {                                                                                                                                    \
         if (kp == 4)                                                                                                                        \
-            hipLaunchKernelGGL((k_predict_select_chunk<T, 4>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
+            hipLaunchKernelGGL((k_predict_select_chunk<T, 4, V>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
                                chunks, thr16, ck, ci);                                                                                      \
         else                                                                                                                                \
-            hipLaunchKernelGGL((k_predict_select_chunk<T, 36>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
+            hipLaunchKernelGGL((k_predict_select_chunk<T, 36, V>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
                                chunks, thr16, ck, ci);                                                                                      \
         if (pairs <= 5) SEC_SEL2(T, 5);                                                                                                     \
         else if (pairs <= 10) SEC_SEL2(T, 10);                                                                                              \
@@ -917,9 +1060,9 @@ static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, i
         const int ns = (int)((nfr + 1) & ~1ll);
 #define SEC_REG(T)                                                                                                                          \
     do {                                                                                                                                    \
-        hipLaunchKernelGGL(k_predict_keys16<T>, dim3(div_up((long long)batch * ns, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, ns, \
+        hipLaunchKernelGGL((k_predict_keys16<T, V>), dim3(div_up((long long)batch * ns, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, ns, \
                            reinterpret_cast<unsigned short *>(key_scratch));                                                                \
-        hipLaunchKernelGGL((k_predict_select_reg<T, 36>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, score_thr,       \
+        hipLaunchKernelGGL((k_predict_select_reg<T, 36, false, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, score_thr,       \
                            reinterpret_cast<const unsigned short *>(key_scratch), ns, top_idx, top_score, top_label, counts, 0,            \
                            (const int *)nullptr, thr16);                                                                                    \
     } while (0)
@@ -1011,5 +1154,67 @@ SEC_API int sec_predict_finalize(const float *decoded, const float *top_score, c
     hipLaunchKernelGGL(k_predict_finalize, dim3(div_up((long long)batch * post_max, kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
                        decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
                        dir_limit_offset, period, range6, boxes, scores, labels, valid);
+    return check_launch();
+}
+
+// ---- several head tensors ---------------------------------------------------------------------------------------------------
+// strides5 [S][5] = {sb, sa, sy, sx, sc} and dims3 [S][3] = {A_s, H_s, W_s} are host arrays; the segment pointers are device pointers
+static int mksegs(int num_segments, const void *const *ptrs, const int64_t *strides5, const int *dims3, SegView *out, long long *total) {
+    if (num_segments < 1 || num_segments > kMaxSegments || !ptrs || !strides5 || !dims3) return SEC_E_INVALID;
+    long long n = 0;
+    Seg g[kMaxSegments];
+    for (int s = 0; s < kMaxSegments; ++s) {
+        const int j = s < num_segments ? s : 0;                 // unused entries repeat segment 0 and are never selected
+        if (!ptrs[j] || dims3[3 * j] <= 0 || dims3[3 * j + 1] <= 0 || dims3[3 * j + 2] <= 0) return SEC_E_INVALID;
+        g[s] = Seg{ptrs[j], strides5[5 * j], strides5[5 * j + 1], strides5[5 * j + 2], strides5[5 * j + 3], strides5[5 * j + 4],
+                   dims3[3 * j + 1], dims3[3 * j + 2], (int)n};       // (start = the total for the unused entries)
+        if (s < num_segments) n += (long long)dims3[3 * j] * dims3[3 * j + 1] * dims3[3 * j + 2];
+        if (n > 0x7fffffffll) return SEC_E_UNSUPPORTED;
+    }
+    SegView v{g[0], g[1], g[2], g[3], (int)n};
+    *out = v;
+    *total = n;
+    return SEC_OK;
+}
+
+SEC_API int sec_predict_select_segments(int num_segments, const void *const *cls, const int64_t *h_cls_strides5, const int *h_dims3,
+                                        int batch, int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                                        float *top_score, int *top_label, int *counts, int dtype, void *stream) {
+    SegView v;
+    long long n;
+    if (int rc = mksegs(num_segments, cls, h_cls_strides5, h_dims3, &v, &n)) return rc;
+    if (k > kSelThreads) return SEC_E_UNSUPPORTED;
+    if (batch <= 0 || num_class <= 0 || k <= 0 || !top_idx || !top_score || !top_label || !counts || dtype < SEC_F32 || dtype > SEC_BF16)
+        return SEC_E_INVALID;
+    if ((long long)batch * n > 0x7fffffffll) return SEC_E_UNSUPPORTED;
+    if (!key_scratch) return SEC_E_WORKSPACE;
+    PredGeom g{batch, 1, 1, (int)n, num_class};                  // the kernels take N = A * H * W from it; addresses come from the segments
+    return predict_select_launch((const void *)nullptr, v, g, k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, stream);
+}
+
+SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+                                        const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
+                                        const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                        float *dets, int *dir_label, int dtype, void *stream) {
+    SegView vb{}, vd{};
+    long long n;
+    if (int rc = mksegs(num_segments, box, h_box_strides5, h_dims3, &vb, &n)) return rc;
+    if (dir)
+        if (int rc = mksegs(num_segments, dir, h_dir_strides5, h_dims3, &vd, &n)) return rc;
+    if (k > kSelThreads) return SEC_E_UNSUPPORTED;
+    if (batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label || dtype < SEC_F32 || dtype > SEC_BF16 ||
+        (dir && num_dir_bins <= 0))
+        return SEC_E_INVALID;
+    PredGeom g{batch, 1, 1, (int)n, 1};
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(div_up((long long)batch * k, kBlock));
+    // `dir` of the kernel only says whether there is a direction head; its address comes from vd
+#define SEC_DEC(T) hipLaunchKernelGGL((k_predict_decode<T, SegView>), grid, dim3(kBlock), 0, st, (const T *)nullptr, vb,                    \
+                                      (const T *)(dir ? dir[0] : nullptr), vd, num_dir_bins, g, k, anchors, top_idx, top_score, rotate, decoded, \
+                                      dets, dir_label)
+    if (dtype == SEC_F32) SEC_DEC(float);
+    else if (dtype == SEC_BF16) SEC_DEC(__hip_bfloat16);
+    else SEC_DEC(__half);
+#undef SEC_DEC
     return check_launch();
 }

@@ -53,22 +53,65 @@ def _seq(v):
     return [float(x) for x in np.asarray(v).reshape(-1)]
 
 
+def head_weight(net):
+    """A classification-head weight of the network: its dtype / device are the network's (``net.half()``, ``.to(device)``).  RPNV2 carries
+    the heads itself; the multi-head network keeps them beside its head-less RPN (net_multi_head.py:131-148)."""
+    owner = net.rpn if hasattr(net.rpn, "conv_cls") else net.large_head
+    return owner.conv_cls.weight
+
+
+def _multi_head_config(net, why):
+    """The ``heads`` entry of a VoxelNetNuscenesMultiHead (net_multi_head.py:121-176): large_head on the trunk's concatenated map,
+    small_head on block 0's cropped output; appends to ``why`` what the fused pipeline does not reproduce."""
+    small, large = getattr(net, "small_head", None), getattr(net, "large_head", None)
+    if type(small).__name__ != "SmallObjectHead" or type(large).__name__ != "DefaultHead":
+        why.append(f"rpn RPNNoHead with heads {type(large).__name__} / {type(small).__name__} (DefaultHead on 'out' + SmallObjectHead on 'stage0' only)")
+        return None
+    ta = net.target_assigner
+    classes, sizes = list(ta.classes), [[int(v) for v in f] for f in (ta._feature_map_sizes or [])]
+    if len(sizes) != len(classes) or not all(len(f) == 3 for f in sizes):
+        why.append("multi-head network without a feature_map_size per class")
+        return None
+    on_small = [c in net.small_classes for c in classes]
+    unknown = [c for c in classes if c not in net.small_classes and c not in net.large_classes]
+    if unknown:
+        why.append(f"classes {unknown} belong to neither head")
+        return None
+    # predictions are concatenated large first, then small (:170-176): the anchors (class order of the config) must be laid out the same
+    if on_small != sorted(on_small):
+        first_small = classes[on_small.index(True)]
+        late = [c for c, s_ in zip(classes, on_small) if not s_ and classes.index(c) > on_small.index(True)]
+        why.append(f"class order: {late} (large_head, the 'out' map) come after {first_small} (small_head, the 'stage0' map); predictions are "
+                   "concatenated large first")
+        return None
+    heads = []
+    for name, head, pick in (("large_head", large, False), ("small_head", small, True)):
+        fms = [f for f, s_ in zip(sizes, on_small) if s_ == pick]
+        if not fms or any(f != fms[0] for f in fms):
+            why.append(f"{name}: its classes' feature_map_size differ ({fms})")
+            return None
+        heads.append(dict(name=name, source="stage0" if pick else "out", num_anchor_per_loc=int(head._num_anchor_per_loc), feature_map_size=fms[0]))
+    return heads
+
+
 def model_config(net):
     """The ``SecondDetector`` configuration of a reference-built VoxelNet (attribute names of voxelnet.py:100-171, rpn.py:202-300,
     spconv.utils.VoxelGeneratorV2).  Raises :class:`NotAccelerable` for networks outside the fused path."""
     why = []
     vfe, mid, rpn = net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn
     vfe_t, mid_t, rpn_t = type(vfe).__name__, type(mid).__name__, type(rpn).__name__
-    if vfe_t not in ("SimpleVoxel", "SimpleVoxelRadius", "PillarFeatureNet"):
+    pillar_vfes = ("PillarFeatureNet", "PillarFeatureNetRadius")
+    if vfe_t not in ("SimpleVoxel", "SimpleVoxelRadius") + pillar_vfes:
         why.append(f"voxel feature extractor {vfe_t}")
     if mid_t not in SPARSE_MIDDLE_STRIDE and mid_t != "PointPillarsScatter":
         why.append(f"middle feature extractor {mid_t}")
     if vfe_t == "SimpleVoxelRadius" and int(getattr(net, "_num_input_features", 4)) != 4:
         why.append(f"SimpleVoxelRadius on {int(net._num_input_features)} point features (x, y, z and one more only)")
-    if (vfe_t == "PillarFeatureNet") != (mid_t == "PointPillarsScatter"):
+    if (vfe_t in pillar_vfes) != (mid_t == "PointPillarsScatter"):
         why.append(f"{vfe_t} with {mid_t}")
-    if rpn_t != "RPNV2" or getattr(rpn, "_use_groupnorm", False) or not getattr(rpn, "_use_norm", True):
-        why.append(f"rpn {rpn_t} (BatchNorm RPNV2 only)")
+    if rpn_t not in ("RPNV2", "RPNNoHead") or getattr(rpn, "_use_groupnorm", False) or not getattr(rpn, "_use_norm", True):
+        why.append(f"rpn {rpn_t} (BatchNorm RPNV2 / RPNNoHead only)")
+    heads = _multi_head_config(net, why) if rpn_t == "RPNNoHead" else None
     if getattr(net, "_multiclass_nms", False):
         why.append("multiclass_nms")
     if not getattr(net, "_use_sigmoid_score", True) or not getattr(net, "_encode_background_as_zeros", True):
@@ -79,8 +122,9 @@ def model_config(net):
     if why:
         raise NotAccelerable("accelerate_model: not reproducible by the fused pipeline: " + "; ".join(why))
     vg = net.voxel_generator
-    pillars = vfe_t == "PillarFeatureNet"
+    pillars = vfe_t in pillar_vfes
     ups = [float(u) for u in rpn._upsample_strides]
+    use_dir = bool(net._use_direction_classifier if heads else rpn._use_direction_classifier)
     mid_stride = 1 if pillars else SPARSE_MIDDLE_STRIDE[mid_t]
     # input channels of the sparse middle: what its first conv takes (SimpleVoxelRadius feeds 3 of the 4 point features' means)
     first = next((m for m in mid.modules() if hasattr(m, "in_channels") and hasattr(m, "indice_key")), None)
@@ -100,9 +144,9 @@ def model_config(net):
         rpn=dict(layer_nums=[int(v) for v in rpn._layer_nums], layer_strides=[int(v) for v in rpn._layer_strides],
                  num_filters=[int(v) for v in rpn._num_filters], upsample_strides=ups,
                  num_upsample_filters=[int(v) for v in rpn._num_upsample_filters], num_input_features=int(rpn._num_input_features),
-                 use_direction_classifier=bool(rpn._use_direction_classifier)),
+                 use_direction_classifier=use_dir),
         downsample_factor=int(round(factor)),
-        num_anchor_per_loc=int(rpn._num_anchor_per_loc),
+        num_anchor_per_loc=sum(h["num_anchor_per_loc"] for h in heads) if heads else int(rpn._num_anchor_per_loc),
         num_class=int(net._num_class), num_direction_bins=int(net._num_direction_bins),
         direction_offset=float(net._dir_offset), direction_limit_offset=float(net._dir_limit_offset),
         nms_score_threshold=float(net._nms_score_thresholds[0]), nms_pre_max_size=int(net._nms_pre_max_sizes[0]),
@@ -114,10 +158,13 @@ def model_config(net):
         cfg.update(vfe="SimpleVoxelRadius")
     if pillars:
         lin = vfe.pfn_layers[0].linear
-        if len(vfe.pfn_layers) != 1 or lin.in_features != int(net._num_input_features) + 5:
-            raise NotAccelerable("accelerate_model: PillarFeatureNet other than one layer on (x, y, z, r) + 5 decorations")
-        cfg.update(vfe="PillarFeatureNet", vfe_filters=[int(lin.out_features)])
-    if not bool(rpn._use_direction_classifier):
+        extra = 5 if vfe_t == "PillarFeatureNet" else 4          # PillarFeatureNetRadius: (x, y) -> r
+        if len(vfe.pfn_layers) != 1 or lin.in_features != int(net._num_input_features) + extra:
+            raise NotAccelerable(f"accelerate_model: {vfe_t} other than one layer on (x, y, z, r) + {extra} decorations")
+        cfg.update(vfe=vfe_t, vfe_filters=[int(lin.out_features)])
+    if heads:
+        cfg.update(rpn_class="RPNNoHead", heads=heads)
+    if not use_dir:
         raise NotAccelerable("accelerate_model: networks without the direction classifier")   # (every shipped config has it)
     return cfg
 
@@ -378,9 +425,13 @@ class FusedVoxelNet:
     def _tensors(self):
         net = self.net
         out = []
-        for m in (net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn):
+        for m in (net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn) + self._head_modules():
             out += list(m.parameters()) + list(m.buffers())
         return out
+
+    def _head_modules(self):
+        """The multi-head network's heads, which live beside its RPN (net_multi_head.py:131-148); () for every other network."""
+        return (self.net.small_head, self.net.large_head) if self.cfg.get("heads") else ()
 
     def _weights_key(self):
         """Host-side fingerprint of the three sub-modules' parameters and buffers, per call: every tensor's version counter
@@ -389,7 +440,7 @@ class FusedVoxelNet:
         (`p.data.copy_()`, `p.data.mul_()`: the reference's torchplus optimizers, EMA swap-ins) bump no counter -- those are caught
         by the CONTENT check that rides with every call (:meth:`weights_changed_flag`)."""
         w = self._watch
-        return (sum(t._version for t in w), len(w), tuple(t.data_ptr() for t in w), w[0].dtype, self.net.rpn.conv_cls.weight.dtype,
+        return (sum(t._version for t in w), len(w), tuple(t.data_ptr() for t in w), w[0].dtype, head_weight(self.net).dtype,
                 w[0].device)
 
     def _checksum(self):
@@ -422,7 +473,7 @@ class FusedVoxelNet:
         NMS stay fp32 either way, as after the reference's ``convert_norm_to_float``)."""
         if self.forced_dtype is not None:
             return None if self.forced_dtype == torch.float32 else self.forced_dtype
-        wd = self.net.rpn.conv_cls.weight.dtype
+        wd = head_weight(self.net).dtype
         return None if wd == torch.float32 else wd
 
     def refresh(self, force=False):
@@ -435,12 +486,13 @@ class FusedVoxelNet:
         self._watch = self._tensors()          # (parameters may have been replaced as objects: re-enumerate, then fingerprint again)
         key = self._weights_key()
         net = self.net
-        dev = net.rpn.conv_cls.weight.device
+        dev = head_weight(net).device
         det = SecondDetector(self.cfg).eval()
         mine = det.state_dict()
         theirs = net.state_dict()
         absent = [k for k in mine if k not in theirs and k != "global_step"]
-        extra = [k for k in theirs if k.split(".")[0] in ("voxel_feature_extractor", "middle_feature_extractor", "rpn") and k not in mine
+        parts = ("voxel_feature_extractor", "middle_feature_extractor", "rpn") + (("small_head", "large_head") if self.cfg.get("heads") else ())
+        extra = [k for k in theirs if k.split(".")[0] in parts and k not in mine
                  and not k.endswith("num_batches_tracked")]
         if absent or extra:
             raise NotAccelerable(f"accelerate_model: state dict differs from the fused pipeline's (missing {absent[:4]}, unknown {extra[:4]})")

@@ -268,6 +268,9 @@ class FusedTrainStep:
         the parameters stay the reference's fp32 tensors."""
         if dtype not in (torch.bfloat16, torch.float16):
             raise NotTrainable("accelerate_model(training): 16-bit features only (train_dtype=torch.bfloat16 / torch.float16)")
+        if cfg.get("heads"):
+            raise NotTrainable("accelerate_model(training): multi-head network (VoxelNetNuscenesMultiHead: RPNNoHead + small_head / large_head) "
+                               "has no captured training step")
         if cfg.get("vfe") == "PillarFeatureNet":
             raise NotTrainable("accelerate_model(training): PointPillars networks train through second_amd.training.DeviceTrainer")
         # the captured step is built for SimpleVoxel + SpMiddleFHD; the other networks the inference path adopts are refused HERE,

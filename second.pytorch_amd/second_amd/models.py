@@ -173,6 +173,39 @@ KITTI_PP_CAR_16 = dict(
 )  # second/configs/pointpillars/car/xyres_16.config (432 x 496 pillars, 216 x 248 feature map)
 
 
+ALL_PP_MHEAD = dict(
+    name="nuscenes/all.pp.mhead",
+    point_cloud_range=[-50, -50, -5, 50, 50, 3], voxel_size=[0.25, 0.25, 8], max_points_per_voxel=60,
+    max_voxels=30000, num_point_features=4,
+    vfe="PillarFeatureNetRadius", vfe_filters=[64], middle="PointPillarsScatter", middle_in=64,
+    # RPNNoHead (rpn.py:500-529): the trunk only; its heads are the network's (net_multi_head.py:121-176)
+    rpn_class="RPNNoHead",
+    rpn=dict(layer_nums=[3, 5, 5], layer_strides=[2, 2, 2], num_filters=[64, 128, 256],
+             upsample_strides=[0.5, 1, 2], num_upsample_filters=[128, 128, 128], num_input_features=64,
+             use_direction_classifier=True),
+    downsample_factor=4,       # of the trunk's concatenated map (400 -> 100), the large head's
+    # the two heads in prediction order (large first, then small): which map each reads, its anchors per cell, its anchor map.
+    # small_head reads block 0's output (200 x 200) cropped by round(0.1 * 200) = 20 cells per side
+    heads=[dict(name="large_head", source="out", num_anchor_per_loc=12, feature_map_size=[1, 100, 100]),
+           dict(name="small_head", source="stage0", num_anchor_per_loc=8, feature_map_size=[1, 160, 160])],
+    # bus, car, construction_vehicle, trailer (2 sizes), truck | barrier, bicycle, motorcycle, pedestrian, traffic_cone
+    anchor_sizes=[[2.94046906, 11.1885991, 3.47030982], [1.95017717, 4.60718145, 1.72270761], [2.73050468, 6.38352896, 3.13312415],
+                  [3, 15, 3.8], [2, 3, 3.8], [2.4560939, 6.73778078, 2.73004906],
+                  [2.49008838, 0.48578221, 0.98297065], [0.60058911, 1.68452161, 1.27192197], [0.76279481, 2.09973778, 1.44403034],
+                  [0.66344886, 0.7256437, 1.75748069], [0.39694519, 0.40359262, 1.06232151]],
+    anchor_ranges=[[-50, -50, z, 50, 50, z] for z in (-0.0715754, -0.93897414, -0.08168083, 0.22228277, 0.22228277, -0.37937912)]
+    + [[-40, -40, z, 40, 40, z] for z in (-1.27247968, -1.03743013, -0.99194854, -0.73911038, -1.27868911)],
+    anchor_groups=[[0], [1], [2], [3, 4], [5], [6], [7], [8], [9], [10]],
+    group_feature_map_sizes=[[1, 100, 100]] * 5 + [[1, 160, 160]] * 5,      # class_settings.feature_map_size (:94 ... :284)
+    rotations=[0, 1.57], group_rotations={8: [0], 9: [0]},   # pedestrian / traffic_cone: one rotation
+    group_class_ids=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10], matched_thresholds=[0.5, 0.4, 0.4, 0.5, 0.5, 0.3, 0.3, 0.3, 0.2, 0.5],
+    unmatched_thresholds=[0.35, 0.3, 0.3, 0.35, 0.35, 0.2, 0.2, 0.2, 0.1, 0.35], assign_per_class=True,
+    num_class=10, num_direction_bins=2, direction_offset=0.78, direction_limit_offset=0.0,
+    nms_score_threshold=0.05, nms_pre_max_size=1000, nms_post_max_size=300, nms_iou_threshold=0.5,
+    use_rotate_nms=False, post_center_range=[-59.6, -59.6, -10, 59.6, 59.6, 10],
+)  # second/configs/nuscenes/all.pp.mhead.config (VoxelNetNuscenesMultiHead: 120 000 + 204 800 anchors)
+
+
 def anchor_area_threshold_of(cfg):
     """The config's ``anchor_area_threshold`` when it asks for the anchor-area mask (>= 0), else None."""
     thr = cfg.get("anchor_area_threshold", -1)
@@ -185,12 +218,19 @@ def anchors_per_location(cfg):
     return sum(len(g) * len(cfg.get("group_rotations", {}).get(gi, cfg["rotations"])) for gi, g in enumerate(groups))
 
 
+def group_feature_map_size(cfg, gi, feature_map_size):
+    """The anchor map of generator ``gi``: its own ``feature_map_size`` when the config gives one per class (class_settings.feature_map_size,
+    target_assigner.py:179-189: the multi-head networks), else the network's."""
+    sizes = cfg.get("group_feature_map_sizes")
+    return [int(v) for v in (sizes[gi] if sizes and sizes[gi] else feature_map_size)]
+
+
 def anchor_class_ranges(cfg, feature_map_size):
     """Start of every anchor generator's range in the class-major anchor array of generate_anchors (+ the total)."""
-    d, h, w = feature_map_size
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
     begin = [0]
     for gi, g in enumerate(groups):
+        d, h, w = group_feature_map_size(cfg, gi, feature_map_size)
         begin.append(begin[-1] + len(g) * len(cfg.get("group_rotations", {}).get(gi, cfg["rotations"])) * d * h * w)
     return begin
 
@@ -204,10 +244,10 @@ def grid_size_of(cfg):
 def generate_anchors(cfg, feature_map_size):
     """[A*D*H*W, 7] anchors ordered (anchor, z, y, x) like target_assigner.generate_anchors
     (second/core/target_assigner.py:169-207 over box_np_ops.create_anchors_3d_range :606-638)."""
-    d, h, w = feature_map_size
     out = []
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
     for gi, grp in enumerate(groups):   # one anchor generator: (size, rotation) major, then z, y, x
+        d, h, w = group_feature_map_size(cfg, gi, feature_map_size)
         rots = np.array(cfg.get("group_rotations", {}).get(gi, cfg["rotations"]), np.float32)
         if cfg.get("anchor_strides"):      # anchor_generator_stride (box_np_ops.create_anchors_3d_stride :561-604): fp32 index * stride + offset
             sx, sy, sz_ = cfg["anchor_strides"][grp[0]]
@@ -352,6 +392,42 @@ class PillarFeatureNet(nn.Module):
         return x.max(dim=1)[0]
 
 
+class PillarFeatureNetRadius(PillarFeatureNet):
+    """One-layer PillarFeatureNetRadius (pointpillars.py:240-325; nuscenes/all.pp.mhead): the raw (x, y) of every point give way to
+    their radius, so the layer is Linear(num_input_features + 4, C); same keys pfn_layers.0.{linear,norm}.  Inference on the GPU runs
+    sec_pfn_radius_fwd (forward_slots: sec_pfn_radius_fwd_slots); everything else -- CPU, grad mode, training -- the torch
+    formulation below (there is no training kernel for it)."""
+
+    def __init__(self, num_input_features=4, num_filters=(64,), voxel_size=(0.2, 0.2, 4), pc_range=(0, -40, -3, 70.4, 40, 1)):
+        super().__init__(num_input_features, num_filters, voxel_size, pc_range)
+        self.pfn_layers = nn.ModuleList([PFNLayer(num_input_features + 4, num_filters[0])])
+
+    def forward_slots(self, points, vox, out_dtype=None, num_dev=None):
+        wt, scale, shift = self.folded()
+        return ops.pfn_forward_slots(points, vox, wt, scale, shift, self.vx, self.vy, self.x_offset, self.y_offset,
+                                     out_dtype=out_dtype, num_dev=num_dev, radius=True)
+
+    def forward(self, features, num_voxels, coors, out_dtype=None, num_dev=None):
+        l = self.pfn_layers[0]
+        if features.is_cuda and not self.training and not torch.is_grad_enabled():
+            wt, scale, shift = self.folded()
+            return ops.pfn_radius_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
+                                          self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
+        n = num_voxels.to(features.dtype).view(-1, 1, 1)
+        xyz = features[:, :, :3]
+        mean = xyz.sum(1, keepdim=True) / n
+        cx = coors[:, 3].to(features.dtype).view(-1, 1) * self.vx + self.x_offset
+        cy = coors[:, 2].to(features.dtype).view(-1, 1) * self.vy + self.y_offset
+        radius = torch.linalg.vector_norm(features[:, :, :2], ord=2, dim=2, keepdim=True)
+        dec = torch.cat([radius, features[:, :, 2:], xyz - mean, (features[:, :, 0] - cx).unsqueeze(-1),
+                         (features[:, :, 1] - cy).unsqueeze(-1)], -1)
+        t = features.shape[1]
+        mask = (torch.arange(t, device=features.device).view(1, -1) < num_voxels.view(-1, 1)).to(features.dtype)
+        x = l.linear(dec * mask.unsqueeze(-1))
+        x = F.relu(l.norm(x.permute(0, 2, 1)).permute(0, 2, 1))
+        return x.max(dim=1)[0]
+
+
 class PointPillarsScatter(nn.Module):
     """pointpillars.py:420-476: pillars -> [B, C, ny, nx] pseudo image, one launch (sec_pillar_scatter)."""
 
@@ -473,7 +549,9 @@ class SpMiddleFHDPeople(SpMiddlePlanned):
     plan_name = "SpMiddleFHDPeople"
 
 
-VFES = {"SimpleVoxel": SimpleVoxel, "SimpleVoxelRadius": SimpleVoxelRadius}
+VFES = {"SimpleVoxel": SimpleVoxel, "SimpleVoxelRadius": SimpleVoxelRadius, "PillarFeatureNet": PillarFeatureNet,
+        "PillarFeatureNetRadius": PillarFeatureNetRadius}
+PILLAR_VFES = ("PillarFeatureNet", "PillarFeatureNetRadius")
 MIDDLES = {"SpMiddleFHD": SpMiddleFHD, "SpMiddleFHDLite": SpMiddleFHDLite, "SpMiddleFHDPeople": SpMiddleFHDPeople}
 
 
@@ -581,6 +659,103 @@ class RPNV2(nn.Module):
         if self._use_direction_classifier:
             ret["dir_cls_preds"] = head(self.conv_dir_cls, self._num_direction_bins)
         return ret
+
+
+class RPNNoHead(nn.Module):
+    """The trunk of RPNV2 without heads (rpn.py:202-331, 500-529): same blocks / deblocks and keys; forward returns every block's
+    output ("stage<i>"), every deblock's ("up<i>") and their concatenation ("out").  The heads belong to the network
+    (net_multi_head.py: SmallObjectHead on stage0, DefaultHead on out)."""
+
+    def __init__(self, num_class=2, layer_nums=(3, 5, 5), layer_strides=(2, 2, 2), num_filters=(128, 128, 256), upsample_strides=(1, 2, 4),
+                 num_upsample_filters=(256, 256, 256), num_input_features=128, num_anchor_per_loc=2, box_code_size=7,
+                 num_direction_bins=2, use_direction_classifier=True):
+        super().__init__()
+        self._layer_nums, self._layer_strides, self._num_filters = list(layer_nums), list(layer_strides), list(num_filters)
+        self._upsample_strides, self._num_upsample_filters = list(upsample_strides), list(num_upsample_filters)
+        self._num_input_features, self._use_norm, self._use_groupnorm = num_input_features, True, False
+        self._use_direction_classifier = use_direction_classifier
+        trunk = RPNV2(num_class, layer_nums, layer_strides, num_filters, upsample_strides, num_upsample_filters, num_input_features,
+                      num_anchor_per_loc, box_code_size, num_direction_bins, use_direction_classifier)
+        self.blocks, self.deblocks, self._upsample_start_idx = trunk.blocks, trunk.deblocks, trunk._upsample_start_idx
+
+    def forward(self, x):
+        ups, res = [], {}
+        for i, blk in enumerate(self.blocks):
+            x = blk(x)
+            res[f"stage{i}"] = x
+            if i - self._upsample_start_idx >= 0:
+                ups.append(self.deblocks[i - self._upsample_start_idx](x))
+        for i, up in enumerate(ups):
+            res[f"up{i}"] = up
+        res["out"] = torch.cat(ups, dim=1) if ups else x
+        return res
+
+
+class DefaultHead(nn.Module):
+    """net_multi_head.py:74-119: the three 1x1 heads on a feature map; predictions flattened to [B, A * H * W, code]."""
+
+    def __init__(self, num_filters, num_class, num_anchor_per_loc, box_code_size=7, num_direction_bins=2, use_direction_classifier=True,
+                 encode_background_as_zeros=True):
+        super().__init__()
+        assert encode_background_as_zeros, "sigmoid scores without a background class (every shipped config)"
+        self._num_anchor_per_loc, self._num_class, self._box_code_size = num_anchor_per_loc, num_class, box_code_size
+        self._num_direction_bins, self._use_direction_classifier = num_direction_bins, use_direction_classifier
+        self._build_heads(int(num_filters))
+
+    def _build_heads(self, cin):
+        a = self._num_anchor_per_loc
+        self.conv_cls = nn.Conv2d(cin, a * self._num_class, 1)
+        self.conv_box = nn.Conv2d(cin, a * self._box_code_size, 1)
+        if self._use_direction_classifier:
+            self.conv_dir_cls = nn.Conv2d(cin, a * self._num_direction_bins, 1)
+
+    def features(self, x):
+        return x
+
+    def forward(self, x):
+        x = self.features(x)
+        b, a = x.shape[0], self._num_anchor_per_loc
+
+        def head(conv, code):
+            y = conv(x)
+            h, w = y.shape[2:]
+            return y.view(-1, a, code, h, w).permute(0, 1, 3, 4, 2).contiguous().view(b, -1, code)
+        ret = {"box_preds": head(self.conv_box, self._box_code_size), "cls_preds": head(self.conv_cls, self._num_class)}
+        if self._use_direction_classifier:
+            ret["dir_cls_preds"] = head(self.conv_dir_cls, self._num_direction_bins)
+        return ret
+
+
+class SmallObjectHead(DefaultHead):
+    """net_multi_head.py:14-71: three Conv2d(3x3, pad 1) + BatchNorm2d + ReLU of 64 channels (``net``), then the 1x1 heads.  The
+    norms are torch's DEFAULT nn.BatchNorm2d(64) -- eps 1e-5, momentum 0.1 -- not the eps 1e-3 of every other norm of the network."""
+
+    def __init__(self, num_filters, num_class, num_anchor_per_loc, box_code_size=7, num_direction_bins=2, use_direction_classifier=True,
+                 encode_background_as_zeros=True):
+        nn.Module.__init__(self)
+        assert encode_background_as_zeros, "sigmoid scores without a background class (every shipped config)"
+        self._num_anchor_per_loc, self._num_class, self._box_code_size = num_anchor_per_loc, num_class, box_code_size
+        self._num_direction_bins, self._use_direction_classifier = num_direction_bins, use_direction_classifier
+        mods, cin = [], int(num_filters)
+        for _ in range(3):
+            mods += [nn.Conv2d(cin, 64, 3, bias=False, padding=1), nn.BatchNorm2d(64), nn.ReLU()]
+            cin = 64
+        self.net = nn.Sequential(*mods)
+        self._build_heads(64)
+
+    def features(self, x):
+        return self.net(x)
+
+
+def stage0_crop(height):
+    """Cells the multi-head network cuts from every side of block 0's output before the small-object head: round(0.1 * H) with
+    numpy's rounding, taken from the HEIGHT and applied to both axes (net_multi_head.py:163-165).  0 would make the reference slice
+    ``[0:-0]`` -- an empty tensor: refused."""
+    c = int(np.round(height * 0.1))
+    if c == 0:
+        raise ValueError(f"multi-head network: stage0 crop round(0.1 * {height}) is 0 (the reference's slice [0:-0] is empty); "
+                         "block 0's output must be at least 5 cells high")
+    return c
 
 
 RPN_TRAIN_BACKEND = "hip"
@@ -806,7 +981,8 @@ class RPNInference(nn.Module):
             if isinstance(m, nn.ConvTranspose2d) and (m.kernel_size != m.stride or m.kernel_size[0] != m.kernel_size[1]
                                                       or m.padding != (0, 0) or m.output_padding != (0, 0)):
                 return False
-        return len(rpn.blocks) >= 1 and len(rpn.deblocks) >= 1
+        # (a head-only tower -- _TowerAsRPN: one block, heads straight on its output -- has no deblock)
+        return len(rpn.blocks) >= 1 and (len(rpn.deblocks) >= 1 or getattr(rpn, "_heads_on_last_block", False))
 
     def __init__(self, rpn, dtype, backend="hip", gather_first=True):
         """``backend``: "hip" = the hand-written MFMA convs (default), "miopen" = torch convolutions + one fused bias / ReLU pass (the
@@ -847,11 +1023,14 @@ class RPNInference(nn.Module):
         # execution plan over a flat layer list: ("c", i) = conv layer i of a block, ("u", i) = deblock conv i whose output
         # is one of the concatenated feature maps
         layers, self.plan = [], []
+        self.block_last = []             # layer index of every block's last conv
+        self.stage0_layer = None         # a layer index: forward() also returns that conv's output as preds["stage0"] (MultiHeadInference)
         up0 = rpn._upsample_start_idx
         for bi, blk in enumerate(rpn.blocks):
             for l in fold(list(blk.children())):
                 self.plan.append(("c", len(layers)))
                 layers.append(l)
+            self.block_last.append(len(layers) - 1)
             if bi - up0 >= 0:
                 (l,) = fold(list(rpn.deblocks[bi - up0].children()))
                 self.plan.append(("u", len(layers)))
@@ -1128,9 +1307,11 @@ class RPNInference(nn.Module):
                 x = x.dense()
         else:
             pillars = None
-        live = nbr = fused_heads = None
+        live = nbr = fused_heads = stage0 = None
         catbuf, coff = None, 0
         for kind, i in self.plan:
+            if self.stage0_layer is not None and i == self.stage0_layer + 1:
+                stage0 = x               # layers run in index order: the output of layer ``stage0_layer``
             if kind == "c" and x is None:
                 # the first conv straight from the pillar rows (sec_conv2d_nhwc_rows): no zero fill, no scatter, no 82 MB canvas
                 x = ops.conv2d_nhwc_rows(pillars.features, pillars.site_map(), self.packed[i], self.bs[i], self.ws[i].shape[0],
@@ -1194,7 +1375,7 @@ class RPNInference(nn.Module):
         elif self.chain_tail:
             y = ops.conv1x1_chain(x, self.packed[-1], self.bs[-1], self.head_packed, self.head_b64, self.head_cout)
         else:
-            f = catbuf if catbuf is not None else (ups[0] if len(ups) == 1 else torch.cat(ups, dim=1))    # channels_last in, channels_last out
+            f = catbuf if catbuf is not None else (x if not ups else ups[0] if len(ups) == 1 else torch.cat(ups, dim=1))    # channels_last in, channels_last out
             if self.use_hip:
                 y = ops.conv2d_nhwc(f.contiguous(memory_format=torch.channels_last), self.head_packed, self.head_b64,
                                     self.head_cout, 1, 1, 0, relu=False)
@@ -1203,6 +1384,8 @@ class RPNInference(nn.Module):
         ret = self._split_heads(y)
         if lazy_heads is not None:
             ret["lazy_heads"] = lazy_heads          # consumed by SecondDetector._predict_fused (ops.predict_select / predict_decode lazy=)
+        if stage0 is not None:
+            ret["stage0"] = stage0
         return ret
 
     def _tail_in_last_conv(self, i, x, nbr):
@@ -1231,6 +1414,72 @@ class RPNInference(nn.Module):
         return self.background_convs + (1 if (self.lazy_heads and self.chain_tail and self.background_convs < 8) else 0)
 
 
+class _TrunkAsRPN(nn.Module):
+    """An RPNNoHead trunk with a DefaultHead's three convs, presented to RPNInference as the RPNV2 it folds and packs."""
+
+    def __init__(self, trunk, head):
+        super().__init__()
+        self.blocks, self.deblocks, self._upsample_start_idx = trunk.blocks, trunk.deblocks, trunk._upsample_start_idx
+        self.conv_box, self.conv_cls = head.conv_box, head.conv_cls
+        self._num_anchor_per_loc, self._num_class, self._box_code_size = head._num_anchor_per_loc, head._num_class, head._box_code_size
+        self._num_direction_bins, self._use_direction_classifier = head._num_direction_bins, head._use_direction_classifier
+        if head._use_direction_classifier:
+            self.conv_dir_cls = head.conv_dir_cls
+
+
+class _TowerAsRPN(_TrunkAsRPN):
+    """A SmallObjectHead the same way: its tower is the one block, the heads read that block's output (no deblock)."""
+
+    _heads_on_last_block = True
+
+    def __init__(self, head):
+        nn.Module.__init__(self)
+        self.blocks, self.deblocks, self._upsample_start_idx = nn.ModuleList([head.net]), nn.ModuleList(), 1
+        self.conv_box, self.conv_cls = head.conv_box, head.conv_cls
+        self._num_anchor_per_loc, self._num_class, self._box_code_size = head._num_anchor_per_loc, head._num_class, head._box_code_size
+        self._num_direction_bins, self._use_direction_classifier = head._num_direction_bins, head._use_direction_classifier
+        if head._use_direction_classifier:
+            self.conv_dir_cls = head.conv_dir_cls
+
+
+class MultiHeadInference(nn.Module):
+    """Inference form of the multi-head network's dense part (net_multi_head.py:150-176): two RPNInference plans.  ``trunk`` = the
+    RPNNoHead blocks / deblocks with the large head's 1x1 convs on the concatenated map, which also hands out block 0's output;
+    ``tower`` = the small head's three 3x3 convs (BatchNorm folded with the module's own eps, 1e-5) and its 1x1 convs on the crop of
+    that output.  The crop is COPIED to a tensor of its own: the tower's first conv zero-pads at the crop's border, as the
+    reference's does on its slice, and never sees the stage-0 cells outside it.
+    Returns {"box_preds", "cls_preds", "dir_cls_preds"}, each a LIST of [B, A_s, H_s, W_s, code] views, large head first -- the
+    order the reference concatenates in and ops.predict_select / predict_decode take."""
+
+    def __init__(self, trunk, large_head, small_head, dtype, backend="hip"):
+        super().__init__()
+        self.trunk = RPNInference(_TrunkAsRPN(trunk, large_head), dtype, backend=backend, gather_first=False)
+        self.trunk.stage0_layer = self.trunk.block_last[0]
+        self.tower = RPNInference(_TowerAsRPN(small_head), dtype, backend=backend, gather_first=False)
+        self.tower.sparse_input = False
+
+    @property
+    def use_hip(self):
+        return self.trunk.use_hip and self.tower.use_hip
+
+    def small_head_of(self, stage0):
+        """The small head's predictions from block 0's output: the crop as a tensor of its own, then the tower."""
+        c = stage0_crop(stage0.shape[2])
+        return self.tower(stage0[:, :, c:-c, c:-c].contiguous(memory_format=torch.channels_last))
+
+    def forward(self, x):
+        large = self.trunk(x)
+        small = self.small_head_of(large.pop("stage0"))
+        return {k: [large[k], small[k]] for k in large}
+
+
+def flat_preds(preds, batch_size):
+    """Prediction tensors as the reference's [B, N, code] (net_multi_head.py:170-176): lists of per-head views are flattened and
+    concatenated in order; anything else passes."""
+    return {k: (torch.cat([t.reshape(batch_size, -1, t.shape[-1]) for t in v], 1) if isinstance(v, (list, tuple)) else v)
+            for k, v in preds.items()}
+
+
 # ------------------------------------------------------------------------------------------ detector
 def limit_period(val, offset, period):
     return val - torch.floor(val / period + offset) * period
@@ -1248,11 +1497,11 @@ class SecondDetector(nn.Module):
         gs = grid_size_of(cfg)
         self.grid_size = gs
         dense_shape = [1] + gs[::-1].tolist() + [64]
-        self.pillars = cfg.get("vfe") == "PillarFeatureNet"
+        self.pillars = cfg.get("vfe") in PILLAR_VFES
         self.encoder = "SimpleVoxelRadius" if cfg.get("vfe") == "SimpleVoxelRadius" else "SimpleVoxel"
         if self.pillars:
-            self.voxel_feature_extractor = PillarFeatureNet(cfg["num_point_features"], cfg["vfe_filters"], cfg["voxel_size"],
-                                                           cfg["point_cloud_range"])
+            self.voxel_feature_extractor = VFES[cfg["vfe"]](cfg["num_point_features"], cfg["vfe_filters"], cfg["voxel_size"],
+                                                            cfg["point_cloud_range"])
             self.middle_feature_extractor = PointPillarsScatter(dense_shape, cfg["middle_in"])
         else:
             self.voxel_feature_extractor = VFES[cfg.get("vfe", "SimpleVoxel")](cfg["num_point_features"])
@@ -1261,13 +1510,24 @@ class SecondDetector(nn.Module):
                 self.middle_feature_extractor.middle_conv[0].pad_in_channels = 4      # KITTI all.fhd: SubMConv3d(3, 16) on radius rows
         # a config adopted from a reference-built VoxelNet (second_amd.dropin) names the anchor count only: its anchors arrive
         # with every example (voxelnet.py:358), so no anchor table is generated here
-        a_per_loc = int(cfg.get("num_anchor_per_loc") or anchors_per_location(cfg))
+        a_per_loc = int(cfg.get("num_anchor_per_loc") or (sum(h["num_anchor_per_loc"] for h in cfg["heads"]) if cfg.get("heads")
+                                                          else anchors_per_location(cfg)))
         self.num_anchor_per_loc = a_per_loc
-        self.rpn = RPNV2(num_class=cfg["num_class"], num_anchor_per_loc=a_per_loc, num_direction_bins=cfg["num_direction_bins"],
-                         **cfg["rpn"])
-        self.register_buffer("global_step", torch.LongTensor(1).zero_())
         fm = [1, int(gs[1]) // cfg["downsample_factor"], int(gs[0]) // cfg["downsample_factor"]]
         self.feature_map_size = fm
+        self.heads = cfg.get("heads")          # multi-head networks (VoxelNetNuscenesMultiHead): [large_head on "out", small_head on "stage0"]
+        if self.heads:
+            self._check_heads(cfg, fm)
+            self.rpn = RPNNoHead(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"], **cfg["rpn"])
+            kw = dict(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"],
+                      use_direction_classifier=cfg["rpn"].get("use_direction_classifier", True))
+            # at top level, as the reference has them (net_multi_head.py:131-148)
+            self.small_head = SmallObjectHead(cfg["rpn"]["num_filters"][0], num_anchor_per_loc=self.heads[1]["num_anchor_per_loc"], **kw)
+            self.large_head = DefaultHead(sum(cfg["rpn"]["num_upsample_filters"]), num_anchor_per_loc=self.heads[0]["num_anchor_per_loc"], **kw)
+        else:
+            self.rpn = RPNV2(num_class=cfg["num_class"], num_anchor_per_loc=a_per_loc, num_direction_bins=cfg["num_direction_bins"],
+                             **cfg["rpn"])
+        self.register_buffer("global_step", torch.LongTensor(1).zero_())
         if cfg.get("anchor_sizes"):
             self.register_buffer("anchors", torch.from_numpy(generate_anchors(cfg, fm)), persistent=False)
         else:
@@ -1283,6 +1543,31 @@ class SecondDetector(nn.Module):
         self.voxel_generator = spconv.utils.VoxelGeneratorV2(cfg["voxel_size"], cfg["point_cloud_range"],
                                                             cfg["max_points_per_voxel"], cfg["max_voxels"],
                                                             **(dict(bf, block_filtering=True) if bf else {}))
+
+    @staticmethod
+    def _check_heads(cfg, fm):
+        """A multi-head config this mirror reproduces: the large head on the trunk's concatenated map first, the small head on block 0's
+        cropped output second -- the order net_multi_head.py:170-176 concatenates the predictions in -- and, when the config lists
+        anchors, every anchor generator of the ``out`` map before every one of the ``stage0`` map, with matching counts."""
+        heads = cfg["heads"]
+        if [(h["name"], h["source"]) for h in heads] != [("large_head", "out"), ("small_head", "stage0")]:
+            raise ValueError(f"{cfg['name']}: multi-head networks are [large_head on 'out', small_head on 'stage0'], got "
+                             f"{[(h['name'], h['source']) for h in heads]}")
+        if [int(v) for v in heads[0]["feature_map_size"]] != fm:
+            raise ValueError(f"{cfg['name']}: large_head's feature_map_size {heads[0]['feature_map_size']} is not the trunk's map {fm}")
+        if not cfg.get("anchor_sizes"):
+            return
+        groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
+        sizes = [group_feature_map_size(cfg, gi, fm) for gi in range(len(groups))]
+        of_head = [0 if sz == [int(v) for v in heads[0]["feature_map_size"]] else 1 if sz == [int(v) for v in heads[1]["feature_map_size"]] else None
+                   for sz in sizes]
+        if None in of_head or of_head != sorted(of_head):
+            raise ValueError(f"{cfg['name']}: class order: every class of the 'out' map ({heads[0]['feature_map_size']}) must precede every "
+                             f"class of the 'stage0' map ({heads[1]['feature_map_size']}); the classes' maps are {sizes}")
+        for hi, h in enumerate(heads):
+            n = sum(len(g) * len(cfg.get("group_rotations", {}).get(gi, cfg["rotations"])) for gi, g in enumerate(groups) if of_head[gi] == hi)
+            if n != h["num_anchor_per_loc"]:
+                raise ValueError(f"{cfg['name']}: {h['name']} has {h['num_anchor_per_loc']} anchors per cell, its classes generate {n}")
 
     # -- inference preparation: bf16 channels-last RPN with folded BN; sparse stack in bf16 (BN folded at run time)
     def prepare_inference(self, dtype=torch.bfloat16, rpn_backend="hip", gather_first=True, exact=False, exact_rpn=None):
@@ -1301,7 +1586,11 @@ class SecondDetector(nn.Module):
             raise ValueError(f"exact_rpn={exact_rpn!r}: allowed values are 'torch' and 'hip'")
         if self.fp32_exact:
             rpn_backend = "hip_f32" if (exact_rpn or exact_rpn_default()) == "hip" else "miopen"
-        if isinstance(self.rpn, RPNV2) and RPNInference.supports(self.rpn) and next(self.parameters()).is_cuda:
+        if isinstance(self.rpn, RPNNoHead):
+            if not (RPNInference.supports(self.rpn) and next(self.parameters()).is_cuda):
+                raise NotImplementedError(f"{self.cfg['name']}: prepare_inference of a multi-head network needs the GPU and plain-conv deblocks")
+            self.rpn = MultiHeadInference(self.rpn, self.large_head, self.small_head, dtype, backend=rpn_backend)
+        elif isinstance(self.rpn, RPNV2) and RPNInference.supports(self.rpn) and next(self.parameters()).is_cuda:
             self.rpn = RPNInference(self.rpn, dtype, backend=rpn_backend, gather_first=gather_first)
         else:
             self.rpn.blocks = nn.ModuleList([fold_conv_bn_(b) for b in self.rpn.blocks])
@@ -1334,12 +1623,19 @@ class SecondDetector(nn.Module):
         pitch = {} if in_pitch is None else {"in_pitch": in_pitch}
         if self.pillars:
             mfe = self.middle_feature_extractor
-            if (dt in (torch.bfloat16, torch.float16) and isinstance(self.rpn, RPNInference) and self.rpn.use_hip and self.rpn.fp32 is None
+            rows_rpn = self.rpn.trunk if isinstance(self.rpn, MultiHeadInference) else self.rpn
+            if (dt in (torch.bfloat16, torch.float16) and isinstance(rows_rpn, RPNInference) and rows_rpn.use_hip and rows_rpn.fp32 is None
                     and isinstance(mfe, PointPillarsScatter) and not torch.is_grad_enabled()):
                 # no canvas: the RPN's first conv gathers the pillar rows (PillarBEV.dense() is the scatter for the shapes it does not take)
                 return self.rpn(PillarBEV(voxel_features.to(dt), coors, batch_size, mfe.ny, mfe.nx, num_dev=num_active_dev))
             spatial = mfe(voxel_features if dt is None else voxel_features.to(dt), coors,
                           batch_size, channels_last=dt is not None, num_dev=num_active_dev)
+            if isinstance(self.rpn, RPNNoHead):          # the module graph of the multi-head network (net_multi_head.py:150-176)
+                out = self.rpn(spatial)
+                c = stage0_crop(out["stage0"].shape[2])
+                small = self.small_head(out["stage0"][:, :, c:-c, c:-c])
+                large = self.large_head(out["out"])
+                return {k: torch.cat([large[k], small[k]], dim=1) for k in large}
             return self.rpn(spatial)
         if dt is not None:
             spatial = self.middle_feature_extractor(voxel_features.to(dt), coors, batch_size, channels_last=True,
@@ -1620,10 +1916,14 @@ class SecondDetector(nn.Module):
         ``anchors_mask`` [B, A] bool / uint8 (the example's, or :meth:`anchor_area_mask`): frame b keeps the anchors with a non-zero entry."""
         cfg = self.cfg
         anchors = self.anchors if anchors is None else anchors
-        if preds["cls_preds"].is_cuda and self.fused_predict and cfg["nms_pre_max_size"] <= 1024:
+        several = isinstance(preds["cls_preds"], (list, tuple))      # a multi-head network's per-head views (MultiHeadInference)
+        on_gpu = (preds["cls_preds"][0] if several else preds["cls_preds"]).is_cuda
+        if (on_gpu and self.fused_predict and cfg["nms_pre_max_size"] <= 1024 and (several or not self.heads) and not (several and anchors_mask is not None)):
             # (sec_predict_select ranks up to 1024 candidates per frame; larger nms_pre_max_size takes the torch.topk path
-            # below, which honours it -- never a silent truncation)
+            # below, which honours it -- never a silent truncation.  A multi-head network's CONCATENATED predictions -- its module
+            # graph's -- have no single [B, A, H, W, C] view: torch path too)
             return self._predict_fused(preds, batch_size, anchors, anchors_mask)
+        preds = flat_preds(preds, batch_size)
         dec, top_scores, counts, dir_labels, top_labels = self._select(preds, batch_size, anchors, anchors_mask)
         if cfg["use_rotate_nms"]:
             # (x, y, w, l, r, score): boxes_for_nms = box[:, [0, 1, 3, 4, 6]] (voxelnet.py:570); slices, not index
@@ -1661,6 +1961,9 @@ class SecondDetector(nn.Module):
         _, h, w = self.feature_map_size
 
         def view5(t, code):
+            if isinstance(t, (list, tuple)):      # several head tensors: every view has its own [A_s, H_s, W_s] (the *_segments kernels)
+                assert all(v.dim() == 5 for v in t)
+                return list(t)
             if t.dim() == 5:
                 return t
             return t.reshape(batch_size, a_per_loc, h, w, code)

@@ -726,6 +726,25 @@ def pfn_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_of
     return out
 
 
+@_traced("pfn_radius_forward")
+def pfn_radius_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None,
+                       num_dev=None):
+    """Fused PillarFeatureNetRadius (one PFNLayer, eval; pointpillars.py:290-325): :func:`pfn_forward` with the decorated row
+    [hypot(x, y), z, w, x - mean, y - mean, z - mean, x - centre, y - centre], so weight_t is [8, C] = linear.weight.T."""
+    rt.require_gpu(voxels, num_points, coords, weight_t, scale, shift)
+    assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
+    p, t, f = voxels.shape
+    c = weight_t.shape[1]
+    assert weight_t.shape[0] == f + 4 and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
+    out_dtype = out_dtype or torch.float32
+    out = torch.empty((p, c), dtype=out_dtype, device=voxels.device)
+    rc = rt.lib().sec_pfn_radius_fwd(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p, rt.ptr(num_dev), t, f,
+                                     rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset),
+                                     float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
+    rt.check(rc, "sec_pfn_radius_fwd")
+    return out
+
+
 # ---- BatchNorm step counters of the fused training paths ----------------------------------------------------------------------
 # `bn.num_batches_tracked += 1` is one tiny launch per BatchNorm layer (21 per step of the SECOND networks).  Inside
 # deferred_bn_counters() the fused paths only note the counter; leaving the context adds 1 to all of them with one multi-tensor launch.
@@ -817,10 +836,12 @@ class PFNTrainFunction(torch.autograd.Function):
 
 
 @_traced("pfn_forward")
-def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None, num_dev=None):
+def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None, num_dev=None, radius=False):
     """:func:`pfn_forward` straight from the voxeliser's point lists: ``vox`` = the result of ``voxelize(points, ..., fill=False)``
-    (or with fill), ``points`` the array it was called on.  Bit-identical to the tensor form; no [P, T, 4] tensor is read."""
+    (or with fill), ``points`` the array it was called on.  Bit-identical to the tensor form; no [P, T, 4] tensor is read.
+    ``radius``: :func:`pfn_radius_forward` the same way (sec_pfn_radius_fwd_slots)."""
     rt.require_gpu(points, weight_t, scale, shift)
+    assert weight_t.shape[0] == points.shape[1] + (4 if radius else 5) and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
     kind, ws, n, max_voxels, max_points, _ = vox["site_table"]
     assert kind == "vox" and points.shape[0] == n and points.dtype == torch.float32 and points.is_contiguous()
     npv, coords = vox["num_points_per_voxel"], vox["coordinates"].contiguous()
@@ -828,11 +849,12 @@ def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_o
     batch = vox["voxel_offsets"].numel() - 1
     out_dtype = out_dtype or torch.float32
     out = torch.empty((p, c), dtype=out_dtype, device=points.device)
-    rc = rt.lib().sec_pfn_fwd_slots(rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels, max_points, points.shape[1],
-                                    rt.ptr(npv), rt.ptr(coords), p, rt.ptr(num_dev), rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c,
-                                    float(vx), float(vy), float(x_offset), float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype),
-                                    rt.stream())
-    rt.check(rc, "sec_pfn_fwd_slots")
+    name = "sec_pfn_radius_fwd_slots" if radius else "sec_pfn_fwd_slots"
+    rc = getattr(rt.lib(), name)(rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels, max_points, points.shape[1],
+                                 rt.ptr(npv), rt.ptr(coords), p, rt.ptr(num_dev), rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c,
+                                 float(vx), float(vy), float(x_offset), float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype),
+                                 rt.stream())
+    rt.check(rc, name)
     return out
 
 
@@ -1645,6 +1667,61 @@ def anchor_area_mask(coords, num_dev, batch, grid_yx, anchors, voxel_size_xy, of
     return out
 
 
+def _segment_args(views):
+    """(pointer array, strides [S][5], dims [S][3]) of a list of [B, A_s, H_s, W_s, C] views: host arrays for the *_segments entry points."""
+    import ctypes
+    s = len(views)
+    ptrs = (ctypes.c_void_p * s)(*[int(v.data_ptr()) for v in views])
+    strides = (ctypes.c_int64 * (5 * s))(*[int(x) for v in views for x in v.stride()])
+    dims = (ctypes.c_int * (3 * s))(*[int(x) for v in views for x in v.shape[1:4]])
+    return ptrs, strides, dims
+
+
+def _predict_select_segments(views, k, score_thr):
+    rt.require_gpu(*views)
+    b, nc, dt = views[0].shape[0], views[0].shape[4], views[0].dtype
+    assert all(v.dim() == 5 and v.shape[0] == b and v.shape[4] == nc and v.dtype == dt for v in views)
+    n = sum(v.shape[1] * v.shape[2] * v.shape[3] for v in views)
+    k = min(int(k), n, 1024)
+    dev = views[0].device
+    top_idx = torch.empty((b, k), dtype=torch.int32, device=dev)
+    top_score = torch.empty((b, k), dtype=torch.float32, device=dev)
+    top_label = torch.empty((b, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((b,), dtype=torch.int32, device=dev)
+    keys = torch.empty((b * n,), dtype=torch.int32, device=dev)
+    ptrs, strides, dims = _segment_args(views)
+    rc = rt.lib().sec_predict_select_segments(len(views), ptrs, strides, dims, b, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
+                                              rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(dt), rt.stream())
+    rt.check(rc, "sec_predict_select_segments")
+    return top_idx, top_score, top_label, counts
+
+
+def _predict_decode_segments(box, dir_cls, anchors, top_idx, top_score, rotate):
+    rt.require_gpu(*box, anchors, top_idx, top_score)
+    b, dt = box[0].shape[0], box[0].dtype
+    assert all(v.dim() == 5 and v.shape[0] == b and v.shape[4] == 7 and v.dtype == dt for v in box)
+    n = sum(v.shape[1] * v.shape[2] * v.shape[3] for v in box)
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and tuple(anchors.shape) == (n, 7)
+    k = top_idx.shape[1]
+    dev = box[0].device
+    dec = torch.empty((b, k, 7), dtype=torch.float32, device=dev)
+    dets = torch.empty((b, k, 6), dtype=torch.float32, device=dev)
+    dlab = torch.empty((b, k), dtype=torch.int32, device=dev)
+    ptrs, strides, dims = _segment_args(box)
+    dptrs = dstrides = None
+    bins = 0
+    if dir_cls is not None:
+        bins = dir_cls[0].shape[4]
+        assert len(dir_cls) == len(box) and all(d.dtype == dt and tuple(d.shape[:4]) == tuple(v.shape[:4]) and d.shape[4] == bins
+                                                for d, v in zip(dir_cls, box))
+        dptrs, dstrides, _ = _segment_args(dir_cls)
+    rc = rt.lib().sec_predict_decode_segments(len(box), ptrs, strides, dptrs, dstrides, dims, bins, b, k, rt.ptr(anchors), rt.ptr(top_idx),
+                                              rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
+                                              rt.dtype_code(dt), rt.stream())
+    rt.check(rc, "sec_predict_decode_segments")
+    return dec, dets, dlab
+
+
 @_traced("predict_select")
 def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     """cls: [B, A, H, W, num_class] view (any strides).  -> (top_idx [B,k] int32 anchor ids sorted by descending
@@ -1652,7 +1729,12 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     rows [0, counts[b]) of frame b (the reference masks by the threshold before its topk); rows behind them are unspecified.
     ``lazy`` = (tile_live [B, tiles] int16 with bit 4 = "tile written", bg = the empty frame's view [1, A, H, W, num_class] with the
     strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg`` (sec_predict_select_lazy).
-    ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry (sec_predict_select_masked)."""
+    ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry (sec_predict_select_masked).
+    A LIST of such views (1 to 4 head tensors of different map size, same dtype / batch / classes): the anchors of view s follow
+    those of the views before it, ``top_idx`` are indices into that concatenation (sec_predict_select_segments; no lazy form, no mask)."""
+    if isinstance(cls, (list, tuple)):
+        assert lazy is None and anchor_mask is None, "the multi-tensor select has no lazy form and no anchor mask"
+        return _predict_select_segments(list(cls), k, score_thr)
     rt.require_gpu(cls)
     b, a, h, w, nc = cls.shape
     k = min(int(k), a * h * w, 1024)
@@ -1687,7 +1769,11 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
 def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=None):
     """box: [B,A,H,W,7] view, dir_cls: [B,A,H,W,bins] view or None, anchors [A*H*W,7] fp32.
     -> (decoded [B,k,7] fp32, dets [B,k,6] fp32 NMS rows, dir_label [B,k] int32).
-    ``lazy`` = (tile_live, (bg_box, bg_dir)): as in :func:`predict_select` (sec_predict_decode_lazy)."""
+    ``lazy`` = (tile_live, (bg_box, bg_dir)): as in :func:`predict_select` (sec_predict_decode_lazy).
+    ``box`` (and ``dir_cls``) LISTS of views: as in :func:`predict_select`, ``anchors`` is the flat list over all of them."""
+    if isinstance(box, (list, tuple)):
+        assert lazy is None, "the multi-tensor decode has no lazy form"
+        return _predict_decode_segments(list(box), None if dir_cls is None else list(dir_cls), anchors, top_idx, top_score, rotate)
     rt.require_gpu(box, anchors, top_idx, top_score)
     b, a, h, w, code = box.shape
     assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)

@@ -42,6 +42,7 @@ SYMBOLS = [
     "sec_kitti_eval_overlaps", "sec_kitti_eval_flags", "sec_kitti_eval_tp_scores", "sec_kitti_eval_thresholds",
     "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr", "sec_kitti_annos_workspace_bytes", "sec_kitti_annos_f64",
     "sec_region_similarity_f32", "sec_assign_targets_sim_f32", "sec_train_metrics_workspace_bytes", "sec_train_metrics_f32",
+    "sec_pfn_radius_fwd", "sec_pfn_radius_fwd_slots", "sec_predict_select_segments", "sec_predict_decode_segments",
 ]
 
 _lib = None
@@ -157,6 +158,8 @@ def lib():
         l.sec_pillar_scatter.argtypes = [vp, vp, ci, ci, vp, vp, sz, i64, i64, i64, i64, ci, vp]
         l.sec_pfn_fwd.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, ci, cf, cf, cf, cf, vp, ci, vp]
         l.sec_pfn_fwd_slots.argtypes = [vp, vp, sz, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, ci, cf, cf, cf, cf, vp, ci, vp]
+        l.sec_pfn_radius_fwd.argtypes = l.sec_pfn_fwd.argtypes
+        l.sec_pfn_radius_fwd_slots.argtypes = l.sec_pfn_fwd_slots.argtypes
         l.sec_pfn_train_workspace_bytes.argtypes = [ci, ci]
         l.sec_pfn_train_fwd.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, cf, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, sz, vp]
         l.sec_pfn_train_bwd.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -234,6 +237,8 @@ def lib():
         l.sec_anchor_area_mask_workspace_bytes.argtypes = [ci, ci, ci]
         l.sec_anchor_area_mask.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, vp, vp, cf, vp, vp, sz, vp]
         l.sec_predict_select_masked.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+        l.sec_predict_select_segments.argtypes = [ci, vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp]
+        l.sec_predict_decode_segments.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp]
         l.sec_assign_targets_masked_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         l.sec_region_similarity_f32.argtypes = [vp, ci, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp]
         l.sec_assign_targets_sim_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]

@@ -141,6 +141,9 @@ class DeviceTrainer:
         (the reference's default training precision); float16 adds dynamic loss scaling (``init_loss_scale``, see
         :meth:`_unscale_and_check`).  Thresholds default to the config's class_settings."""
         from . import models
+        if getattr(det, "heads", None):
+            raise NotImplementedError(f"DeviceTrainer: multi-head network {det.cfg['name']} (RPNNoHead + small_head / large_head) has no device "
+                                      "training step (train such a network through its own module graph)")
         if getattr(det, "encoder", "SimpleVoxel") != "SimpleVoxel":
             # the training forward feeds the voxeliser's SimpleVoxel means straight to the middle; a network whose middle expects
             # another encoder's rows (car.lite, KITTI all.fhd) must not be trained on them
