@@ -749,6 +749,45 @@ int sec_predict_finalize(const float *decoded, const float *top_score, const int
                          int post_max, int use_direction, float dir_offset, float dir_limit_offset,
                          int num_dir_bins, const float *range6, float *boxes, float *scores, int *labels,
                          unsigned char *valid, void *stream);
+/* Multi-class NMS (use_multi_class_nms, voxelnet.py:458-547): the same chain with (frame, class) ITEMS as the unit of work; item
+ * i = frame * num_class + class everywhere below.  Class c selects among the anchors with h_a_begin[c] <= a < h_a_end[c] of the
+ * [B, A, H, W, C] view (target_assigner.anchors_range(c); [0, A) for every class when nms_class_agnostic) by the sigmoid of column
+ * c alone, keeps those with score >= h_score_thr[c] and of them the h_k[c] best.
+ *   select_classes  : ONE launch, a workgroup per item.  top_idx / top_score [B, num_class, k_out] (indices into the FULL anchor
+ *                     list), counts [B, num_class].  Rows [0, counts) of an item equal, bit for bit, what sec_predict_select returns
+ *                     for the one-class strided view (pointer + c channels, the class's a-range, num_class 1, k = h_k[c],
+ *                     score_thr = h_score_thr[c]) with its indices rebased; the rows behind them hold anchor 0 / score 0.
+ *                     The h_* arrays are host arrays of num_class entries, copied into the launch.  Checked before anything is
+ *                     enqueued: SEC_E_UNSUPPORTED for a threshold <= 0, a k above 1024, more than 32 classes or a non-NULL
+ *                     anchor_mask (the reference indexes masked arrays with unmasked ranges there: not reproduced); SEC_E_INVALID
+ *                     for an empty / out-of-range a-range, k <= 0, or k_out below some min(h_k[c], anchors of c).
+ *   decode_classes  : sec_predict_decode of every row of top_idx [B, num_class * k] (rows behind counts decode anchor 0).
+ *   sec_nms_sorted_items_f32 : sec_nms_sorted_f32 with entry i taking thresh_items[i % num_class] and post_max_items[i % num_class]
+ *                     (DEVICE arrays of num_class entries); kind, semantics, SEC_NMS_EXACT_CLIP and workspace
+ *                     (sec_nms_workspace_bytes(items, max_n)) as there.  An item's keep list equals sec_nms_sorted_f32's for that
+ *                     item alone with its own threshold and cap.  At most 65535 items.
+ *   finalize_classes: output row j of a frame, post_offsets[c] <= j < post_offsets[c + 1] (DEVICE array of num_class + 1 ints, the
+ *                     running sum of the classes' post_max, post_offsets[num_class] = post_total), is class c's
+ *                     (j - post_offsets[c])-th survivor: label c, direction fix and range mask as sec_predict_finalize.
+ *                     boxes [B, post_total, 7], scores, labels, valid: the rows with valid set, in row order, are the reference's
+ *                     concatenation class after class.  A frame on which no class keeps anything has no valid row (the reference
+ *                     raises there: torch.cat of an empty list). */
+int sec_predict_select_classes(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
+                               int num_class, const int *h_a_begin, const int *h_a_end, const int *h_k, const float *h_score_thr,
+                               int k_out, int *top_idx, float *top_score, int *counts, int dtype,
+                               const unsigned char *anchor_mask /* must be NULL */, void *stream);
+int sec_predict_decode_classes(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                               int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int num_class, int k,
+                               const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                               float *dets, int *dir_label, int dtype, void *stream);
+int sec_nms_sorted_items_f32(const float *dets, const int *counts, int items, int num_class, int max_n, int stride,
+                             const float *thresh_items, int kind, int semantics, float eps, const int *post_max_items,
+                             int *keep, int *num_keep, void *workspace, size_t workspace_bytes, void *stream);
+int sec_predict_finalize_classes(const float *decoded, const float *top_score, const int *dir_label, const int *keep,
+                                 const int *num_keep, const int *post_offsets, int batch, int num_class, int k, int post_total,
+                                 int use_direction, float dir_offset, float dir_limit_offset, int num_dir_bins,
+                                 const float *range6, float *boxes, float *scores, int *labels, unsigned char *valid,
+                                 void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training side: what the reference computes in DataLoader workers (numpy) and in ~40 torch kernels.

@@ -70,10 +70,14 @@ __global__ __launch_bounds__(kBlock) void k_rotate_iou(const float *__restrict__
 __device__ int g_nms_dbg[4];
 __device__ float g_nms_vals[8 * 32];
 #endif
-template <int ROWS>
+// ITEMS (sec_nms_sorted_items_f32): the batch entries are (frame, class) items and entry b takes the threshold of its class,
+// thr_items[b % num_class], instead of `thresh`.
+template <int ROWS, bool ITEMS = false>
 __global__ __launch_bounds__(kBlock) void k_nms_mask(const float *__restrict__ dets, const int *__restrict__ counts,
                                                     int max_n, int stride, float thresh, int kind, int semantics,
-                                                    float eps, int words, unsigned long long *__restrict__ mask) {
+                                                    float eps, int words, unsigned long long *__restrict__ mask,
+                                                    const float *__restrict__ thr_items = nullptr, int num_class = 1) {
+    if constexpr (ITEMS) thresh = thr_items[blockIdx.y % num_class];
     static_assert(ROWS % 4 == 0 && ROWS <= 64 && 64 % ROWS == 0, "a tile is ROWS rows (a multiple of the 4 waves) x 64 columns");
     // grid (workgroups per frame, batch): a workgroup walks the tiles of ITS frame's live rectangle (ceil(n / ROWS) x ceil(n / 64),
     // n read from the device) with a stride of gridDim.x.  A grid sized for max_n (1000 candidates: 8 000 workgroups at ROWS = 16)
@@ -266,10 +270,14 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
 // Lane w owns removal word w.  Per 64-box block: (1) the intra-block chain is resolved on scalar state
 // with the 64 diagonal words (one per lane, read with v_readlane), (2) each kept row is read once (its words for
 // the later blocks, one per lane) and OR-ed into the owners' removal words.
+// ITEMS: entry b keeps at most post_items[b % num_class] boxes.
+template <bool ITEMS = false>
 __global__ __launch_bounds__(64) void k_nms_reduce(const unsigned long long *__restrict__ mask,
                                                   const int *__restrict__ counts, int max_n, int words, int post_max,
-                                                  int *__restrict__ keep, int *__restrict__ num_keep) {
+                                                  int *__restrict__ keep, int *__restrict__ num_keep,
+                                                  const int *__restrict__ post_items = nullptr, int num_class = 1) {
     int b = blockIdx.x, lane = threadIdx.x;
+    if constexpr (ITEMS) post_max = post_items[b % num_class];
     int n = counts[b];
     if (n > max_n) n = max_n;
     int nwords = (n + 63) >> 6;
@@ -412,7 +420,33 @@ SEC_API int sec_nms_sorted_f32(const float *dets, const int *counts, int batch, 
     int per_frame = 2048 / batch;
     per_frame = per_frame < 32 ? 32 : per_frame > 256 ? 256 : per_frame;
     const dim3 grid(per_frame, batch);
-    hipLaunchKernelGGL(k_nms_mask<16>, grid, dim3(kBlock), 0, st, dets, counts, max_n, stride, thresh, kind, semantics, eps, words, mask);
-    hipLaunchKernelGGL(k_nms_reduce, dim3(batch), dim3(64), 0, st, mask, counts, max_n, words, post_max, keep, num_keep);
+    hipLaunchKernelGGL((k_nms_mask<16, false>), grid, dim3(kBlock), 0, st, dets, counts, max_n, stride, thresh, kind, semantics, eps, words, mask,
+                       (const float *)nullptr, 1);
+    hipLaunchKernelGGL(k_nms_reduce<false>, dim3(batch), dim3(64), 0, st, mask, counts, max_n, words, post_max, keep, num_keep,
+                       (const int *)nullptr, 1);
+    return check_launch();
+}
+
+// sec_nms_sorted_f32 over (frame, class) items: entry i = frame * num_class + class of dets / counts / keep / num_keep takes
+// thresh_items[class] and post_max_items[class] (device arrays of num_class entries; post_max 0 = no cap).  Same kernels, so an
+// item's keep list is what sec_nms_sorted_f32 returns for that item alone with its class's threshold and cap.
+SEC_API int sec_nms_sorted_items_f32(const float *dets, const int *counts, int items, int num_class, int max_n, int stride,
+                                     const float *thresh_items, int kind, int semantics, float eps, const int *post_max_items,
+                                     int *keep, int *num_keep, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!dets || !counts || !keep || !num_keep || !thresh_items || !post_max_items || items <= 0 || num_class <= 0 ||
+        items % num_class != 0 || max_n <= 0 || max_n > 4096 || stride < (kind == 0 ? 5 : 4) || kind < 0 || kind > 1 ||
+        (semantics & ~SEC_NMS_EXACT_CLIP) < 0 || (semantics & ~SEC_NMS_EXACT_CLIP) > 1)
+        return SEC_E_INVALID;
+    if (items > 65535) return SEC_E_UNSUPPORTED;          // one grid row per item
+    if (!workspace || workspace_bytes < sec_nms_workspace_bytes(items, max_n)) return SEC_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    int words = (max_n + 63) / 64;
+    unsigned long long *mask = (unsigned long long *)workspace;
+    int per_item = 2048 / items;                          // as sec_nms_sorted_f32
+    per_item = per_item < 32 ? 32 : per_item > 256 ? 256 : per_item;
+    hipLaunchKernelGGL((k_nms_mask<16, true>), dim3(per_item, items), dim3(kBlock), 0, st, dets, counts, max_n, stride, 0.0f, kind, semantics,
+                       eps, words, mask, thresh_items, num_class);
+    hipLaunchKernelGGL(k_nms_reduce<true>, dim3(items), dim3(64), 0, st, mask, counts, max_n, words, 0, keep, num_keep, post_max_items,
+                       num_class);
     return check_launch();
 }

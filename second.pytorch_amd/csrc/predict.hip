@@ -6,7 +6,9 @@
 //   sec_predict_decode   : gather + second_box_decode (box_torch_ops.py:56-101) of the selected anchors, NMS input
 //                          rows (rotated (x,y,w,l,r,score) or standup (x1,y1,x2,y2,score)), direction argmax;
 //   sec_predict_finalize : gather of the NMS survivors, direction fix (limit_period, voxelnet.py:598-607),
-//                          post_center_range mask (:611-621).
+//                          post_center_range mask (:611-621);
+//   sec_predict_select_classes / _decode_classes / _finalize_classes : the same chain for use_multi_class_nms (voxelnet.py:458-547)
+//                          with (frame, class) items as the unit of work (per-class anchor range, column, threshold, k, post_max).
 // The reference runs ~60 tiny torch kernels plus a GPU->CPU->GPU round trip here; these three launches plus the
 // two NMS launches keep everything on the device with fixed shapes (hipGraph friendly).
 // Tensors are addressed as logit(b, anchor n = (a, y, x), c) = base[b*sb + a*sa + y*sy + x*sx + c*sc] so the RPN head
@@ -927,6 +929,241 @@ __global__ __launch_bounds__(kBlock) void k_predict_finalize(const float *__rest
     valid[t] = ok ? 1 : 0;
 }
 
+// ---- multi-class NMS (voxelnet.py:458-547): (frame, class) items ------------------------------------------------------------
+// Class c of a frame selects among the anchors of ITS a-range [a_begin, a_end) (all anchors when class-agnostic) by the sigmoid of
+// column c alone, with its own threshold and k.  One workgroup per item; gridDim.x = classes, so the workgroups that read a frame's
+// cls rows through different columns are dispatched together and share the rows' cache lines in L2 (a channels-last head keeps the
+// A * C logits of a pixel in one or two lines).
+// The result of an item is what k_predict_select / k_predict_select_reg return for the one-class strided view of the same tensor:
+// entries ordered by (key descending, anchor index ascending), the first min(k, anchors) of them, counts = those whose score reaches
+// the threshold.  Because the threshold is > 0 here (checked on the host), only passing anchors are ever candidates:
+//   common case: at most 1024 anchors pass -- ONE sweep over the head compacts them into LDS, the sort ranks them;
+//   otherwise: the radix select of k_predict_select over the passing anchors (four histogram sweeps, ordered tie ranking), re-reading
+//   the head (L2 resident) instead of a key array.
+constexpr int kMaxSelClasses = 32;
+struct ClassSel {                      // per-class host settings, by value in the kernel argument (read with a uniform index)
+    int a_begin[kMaxSelClasses], a_end[kMaxSelClasses], k[kMaxSelClasses];
+    float thr[kMaxSelClasses];
+};
+
+template <typename T>
+__global__ __launch_bounds__(kSelThreads) void k_predict_select_classes(const T *__restrict__ cls, View5 v, PredGeom g, ClassSel p, int Kout,
+                                                                        int *__restrict__ top_idx, float *__restrict__ top_score,
+                                                                        int *__restrict__ counts) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned ckey[kSelThreads];
+    __shared__ int cidx[kSelThreads];
+    __shared__ int wsum[kSelThreads / 64];
+    __shared__ unsigned s_prefix, s_need;
+    __shared__ int s_cnt, s_eqbase;
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int HW = g.H * g.W;
+    const int first = p.a_begin[c] * HW;                 // the item's anchors: [first, first + N) of the frame's list
+    const int N = (p.a_end[c] - p.a_begin[c]) * HW;
+    const float thr = p.thr[c];
+    int K = p.k[c];
+    if (K > kSelThreads) K = kSelThreads;
+    if (K > N) K = N;
+    const T *frame = cls + (long long)b * v.sb + (long long)c * v.sc;
+    constexpr int UNR = 4;                               // independent logit loads in flight per thread
+    // key of local anchor n (0: past the range, or below the threshold -- never a candidate)
+    auto load_keys = [&](int n0, unsigned (&kk)[UNR]) {
+        float f[UNR];
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+            const int n = n0 + j * kSelThreads + tid;
+            const int m = (n < N ? n : 0) + first;
+            const int x = m % g.W, t = m / g.W, y = t % g.H, a = t / g.H;
+            f[j] = ldf(frame + (long long)a * v.sa + (long long)y * v.sy + (long long)x * v.sx);
+        }
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+            const int n = n0 + j * kSelThreads + tid;
+            kk[j] = (n < N && sigmoidf_(f[j]) >= thr) ? f2key(f[j]) : 0u;
+        }
+    };
+    if (tid == 0) { s_cnt = 0; s_eqbase = 0; }
+    ckey[tid] = 0u;
+    cidx[tid] = 0x7fffffff;
+    __syncthreads();
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    // ---- sweep 1: every passing anchor into the sort buffer (slots in arrival order: the sort ranks them), and their number
+    for (int n0 = 0; n0 < N; n0 += kSelThreads * UNR) {
+        unsigned kk[UNR];
+        load_keys(n0, kk);
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) {
+            const bool hit = kk[j] != 0u;
+            const unsigned long long m = __ballot(hit);
+            if (m) {                                      // one LDS atomic per wave
+                int p0 = 0;
+                if (lane == 0) p0 = atomicAdd(&s_cnt, __popcll(m));
+                p0 = __shfl(p0, 0, 64);
+                const int pos = p0 + __popcll(m & lt);
+                if (hit && pos < kSelThreads) { ckey[pos] = kk[j]; cidx[pos] = n0 + j * kSelThreads + tid; }
+            }
+        }
+    }
+    __syncthreads();
+    const int passing = s_cnt;
+    __syncthreads();
+    if (passing > kSelThreads) {
+        // ---- more candidates than the sort buffer holds: K-th largest key by radix select (8 bits per sweep, MSB first)
+        unsigned prefix = 0, mask = 0, need = K;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (int i = tid; i < 256; i += kSelThreads) hist[i] = 0;
+            __syncthreads();
+            for (int n0 = 0; n0 < N; n0 += kSelThreads * UNR) {
+                unsigned kk[UNR];
+                load_keys(n0, kk);
+#pragma unroll
+                for (int j = 0; j < UNR; ++j) {
+                    const bool act = kk[j] != 0u && (kk[j] & mask) == prefix;
+                    const unsigned d = (kk[j] >> shift) & 255u;
+                    unsigned long long todo = __ballot(act);     // wave-aggregated: the leading bytes take a handful of values
+                    while (todo) {
+                        const int leader = __ffsll((long long)todo) - 1;
+                        const unsigned d0 = __shfl(d, leader, 64);
+                        const unsigned long long same = __ballot(act && d == d0) & todo;
+                        if (lane == leader) atomicAdd(&hist[d0], (unsigned)__popcll(same));
+                        todo &= ~same;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned acc = 0;
+                int bin = 255;
+                for (; bin > 0; --bin) {
+                    if (acc + hist[bin] >= need) break;
+                    acc += hist[bin];
+                }
+                s_prefix = prefix | ((unsigned)bin << shift);
+                s_need = need - acc;                      // how many still to take inside this bin
+            }
+            __syncthreads();
+            prefix = s_prefix;
+            need = s_need;
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        const unsigned T_key = prefix;                    // take all keys > T and the first `need` (by index) equal to T
+        if (tid == 0) { s_cnt = 0; s_eqbase = 0; }
+        ckey[tid] = 0u;
+        cidx[tid] = 0x7fffffff;
+        __syncthreads();
+        for (int n0 = 0; n0 < N; n0 += kSelThreads * UNR) {
+            unsigned kk[UNR];
+            load_keys(n0, kk);
+#pragma unroll
+            for (int j = 0; j < UNR; ++j) {
+                const unsigned key = kk[j];
+                const bool gt = key > T_key;              // (T_key > 0: the K-th of more than K passing keys)
+                bool eq = key == T_key;
+                const unsigned long long em = __ballot(eq);
+                if (__syncthreads_or(eq)) {               // chunks without a tie candidate (almost all) skip the ordered ranking
+                    if (lane == 0) wsum[wv] = __popcll(em);
+                    __syncthreads();
+                    int ebase = s_eqbase;
+                    for (int w2 = 0; w2 < wv; ++w2) ebase += wsum[w2];
+                    const int erank = ebase + __popcll(em & lt);
+                    eq = eq && erank < (int)need;
+                    __syncthreads();
+                    if (tid == 0) {
+                        int tot = 0;
+                        for (int w2 = 0; w2 < kSelThreads / 64; ++w2) tot += wsum[w2];
+                        s_eqbase += tot;
+                    }
+                    __syncthreads();
+                }
+                if (gt || eq) {
+                    const int pos = atomicAdd(&s_cnt, 1);
+                    if (pos < kSelThreads) { ckey[pos] = key; cidx[pos] = n0 + j * kSelThreads + tid; }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- bitonic sort of (key desc, idx asc); strides < 64 stay inside the wave (shuffles), the rest go through LDS.  Unused slots
+    //      hold key 0 / idx INT_MAX and sink to the end.
+    unsigned mk = ckey[tid];
+    int mi = cidx[tid];
+    for (int size = 2; size <= kSelThreads; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            unsigned ok_;
+            int oi;
+            if (stride >= 64) {
+                __syncthreads();
+                ckey[tid] = mk; cidx[tid] = mi;
+                __syncthreads();
+                ok_ = ckey[tid ^ stride]; oi = cidx[tid ^ stride];
+            } else {
+                ok_ = (unsigned)__shfl_xor((int)mk, stride, 64);
+                oi = __shfl_xor(mi, stride, 64);
+            }
+            const bool lower = (tid & stride) == 0;
+            const bool mine_first = mk > ok_ || (mk == ok_ && mi < oi);
+            const bool up = (tid & size) == 0;
+            const bool keep_mine = (lower == up) ? mine_first : !mine_first;
+            if (!keep_mine) { mk = ok_; mi = oi; }
+        }
+    }
+    // ---- outputs: rows [0, counts) are the selection; the rows behind them hold anchor 0 / score 0
+    const bool live = tid < K && mk != 0u;
+    if (tid < Kout) {
+        const size_t o = ((size_t)b * gridDim.x + c) * Kout + tid;
+        top_idx[o] = live ? first + mi : 0;
+        top_score[o] = live ? sigmoidf_(key2f(mk)) : 0.0f;
+    }
+    const unsigned long long m = __ballot(live);
+    __syncthreads();
+    if (lane == 0) wsum[wv] = __popcll(m);
+    __syncthreads();
+    if (tid == 0) {
+        int tot = 0;
+        for (int w2 = 0; w2 < kSelThreads / 64; ++w2) tot += wsum[w2];
+        counts[b * gridDim.x + c] = tot;
+    }
+}
+
+// survivors of the per-item NMS, class after class: output row j of a frame belongs to the class c with post_off[c] <= j < post_off[c + 1]
+// and is that class's (j - post_off[c])-th kept candidate; label = c.  Direction fix and range mask as k_predict_finalize.
+__global__ __launch_bounds__(kBlock) void k_predict_finalize_classes(const float *__restrict__ dec, const float *__restrict__ top_score,
+                                                                    const int *__restrict__ dir_label, const int *__restrict__ keep,
+                                                                    const int *__restrict__ num_keep, const int *__restrict__ post_off,
+                                                                    int batch, int C, int K, int P, int use_dir, float dir_offset,
+                                                                    float dir_limit_offset, float period, const float *__restrict__ range6,
+                                                                    float *__restrict__ boxes, float *__restrict__ scores,
+                                                                    int *__restrict__ labels, unsigned char *__restrict__ valid) {
+    int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= batch * P) return;
+    int b = t / P, j = t - b * P;
+    int c = 0;
+    while (c + 1 < C && j >= post_off[c + 1]) ++c;
+    const int r = j - post_off[c];
+    const size_t item = (size_t)b * C + c;
+    bool ok = r < num_keep[item];
+    int sel = ok ? keep[item * K + r] : 0;
+    const size_t row = item * K + sel;
+    const float *s = dec + row * 7;
+    float o[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) o[q] = s[q];
+    if (use_dir) {   // limit_period(rot - offset, limit_offset, period) + offset + period * dir_label
+        float val = __fsub_rn(o[6], dir_offset);
+        float rot = __fsub_rn(val, __fmul_rn(floorf(__fadd_rn(__fdiv_rn(val, period), dir_limit_offset)), period));
+        o[6] = __fadd_rn(__fadd_rn(rot, dir_offset), __fmul_rn(period, (float)dir_label[row]));
+    }
+    if (range6)
+        ok = ok && o[0] >= range6[0] && o[1] >= range6[1] && o[2] >= range6[2] && o[0] <= range6[3] && o[1] <= range6[4] &&
+             o[2] <= range6[5];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) boxes[(size_t)t * 7 + q] = o[q];
+    scores[t] = top_score[row];
+    labels[t] = c;
+    valid[t] = ok ? 1 : 0;
+}
+
 }  // namespace sec
 
 using namespace sec;
@@ -1216,5 +1453,63 @@ SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box
     else if (dtype == SEC_BF16) SEC_DEC(__hip_bfloat16);
     else SEC_DEC(__half);
 #undef SEC_DEC
+    return check_launch();
+}
+
+// ---- multi-class NMS: (frame, class) items -----------------------------------------------------------------------------------
+SEC_API int sec_predict_select_classes(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
+                                       int num_class, const int *h_a_begin, const int *h_a_end, const int *h_k, const float *h_score_thr,
+                                       int k_out, int *top_idx, float *top_score, int *counts, int dtype,
+                                       const unsigned char *anchor_mask, void *stream) {
+    if (!cls || !h_cls_strides5 || batch <= 0 || anchors_per_loc <= 0 || h <= 0 || w <= 0 || num_class <= 0 || !h_a_begin || !h_a_end ||
+        !h_k || !h_score_thr || k_out <= 0 || k_out > kSelThreads || !top_idx || !top_score || !counts || dtype < SEC_F32 || dtype > SEC_BF16)
+        return SEC_E_INVALID;
+    if (anchor_mask) return SEC_E_UNSUPPORTED;            // the reference indexes masked arrays with unmasked ranges here: not reproduced
+    if (num_class > kMaxSelClasses) return SEC_E_UNSUPPORTED;
+    if ((long long)anchors_per_loc * h * w > 0x7fffffffll || (long long)batch * num_class * k_out > 0x7fffffffll) return SEC_E_UNSUPPORTED;
+    ClassSel p{};
+    for (int c = 0; c < num_class; ++c) {
+        if (h_a_begin[c] < 0 || h_a_end[c] > anchors_per_loc || h_a_begin[c] >= h_a_end[c] || h_k[c] <= 0) return SEC_E_INVALID;
+        if (h_k[c] > kSelThreads) return SEC_E_UNSUPPORTED;                   // the caller takes the torch.topk formulation
+        if (!(h_score_thr[c] > 0.0f)) return SEC_E_UNSUPPORTED;               // a key of 0 stands for "no candidate"
+        const long long n = (long long)(h_a_end[c] - h_a_begin[c]) * h * w;
+        if ((n < h_k[c] ? n : (long long)h_k[c]) > k_out) return SEC_E_INVALID;   // the item's rows do not fit [B, C, k_out]
+        p.a_begin[c] = h_a_begin[c]; p.a_end[c] = h_a_end[c]; p.k[c] = h_k[c]; p.thr[c] = h_score_thr[c];
+    }
+    PredGeom g{batch, anchors_per_loc, h, w, num_class};
+    View5 v = mkview(h_cls_strides5);
+    const dim3 grid(num_class, batch);
+#define SEC_SELC(T) hipLaunchKernelGGL(k_predict_select_classes<T>, grid, dim3(kSelThreads), 0, (hipStream_t)stream, (const T *)cls, v, g, p, \
+                                       k_out, top_idx, top_score, counts)
+    if (dtype == SEC_F32) SEC_SELC(float);
+    else if (dtype == SEC_BF16) SEC_SELC(__hip_bfloat16);
+    else SEC_SELC(__half);
+#undef SEC_SELC
+    return check_launch();
+}
+
+// the rows of all items are one list of num_class * k rows per frame: sec_predict_decode's kernel on [B, num_class * k]
+SEC_API int sec_predict_decode_classes(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                                       int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int num_class, int k,
+                                       const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                       float *dets, int *dir_label, int dtype, void *stream) {
+    if (num_class <= 0 || k <= 0 || (long long)batch * num_class * k > 0x7fffffffll / 7) return SEC_E_INVALID;
+    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, num_class * k, anchors,
+                               top_idx, top_score, rotate, decoded, dets, dir_label, dtype, stream, nullptr, nullptr, nullptr);
+}
+
+SEC_API int sec_predict_finalize_classes(const float *decoded, const float *top_score, const int *dir_label, const int *keep,
+                                         const int *num_keep, const int *post_offsets, int batch, int num_class, int k, int post_total,
+                                         int use_direction, float dir_offset, float dir_limit_offset, int num_dir_bins,
+                                         const float *range6, float *boxes, float *scores, int *labels, unsigned char *valid,
+                                         void *stream) {
+    if (!decoded || !top_score || !keep || !num_keep || !post_offsets || batch <= 0 || num_class <= 0 || k <= 0 || post_total <= 0 ||
+        (long long)batch * post_total > 0x7fffffffll / 7 || !boxes || !scores || !labels || !valid ||
+        (use_direction && (!dir_label || num_dir_bins <= 0)))
+        return SEC_E_INVALID;
+    float period = use_direction ? 6.283185307179586f / (float)num_dir_bins : 0.0f;
+    hipLaunchKernelGGL(k_predict_finalize_classes, dim3(div_up((long long)batch * post_total, kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                       decoded, top_score, dir_label, keep, num_keep, post_offsets, batch, num_class, k, post_total, use_direction, dir_offset,
+                       dir_limit_offset, period, range6, boxes, scores, labels, valid);
     return check_launch();
 }

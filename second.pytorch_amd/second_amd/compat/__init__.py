@@ -296,7 +296,7 @@ def accelerate_nms():
 
 
 def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None,
-                     train_metrics=None):
+                     train_metrics=None, multiclass_nms=None):
     """Serve a reference-built ``VoxelNet``'s ``net(example)`` in eval mode (voxelnet.py:339-375, called by train.py:524) from the
     fused static-capacity, graph-captured pipeline: parameters adopted by state-dict key, same return value
     (voxelnet.py:616-643), fp32 by default and 16-bit after ``net.half()``.  See :mod:`second_amd.dropin`.  Call after the
@@ -311,10 +311,13 @@ def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, trai
     lanes; anything that reads a result gets exactly what the synchronous call returns.  ``train_metrics=True``
     (SEC_TRAIN_METRICS=1): ``net.update_metrics`` (voxelnet.py:654-679, called by train.py:327) writes the network's own metric
     buffers from two launches and returns the same dict after one host read instead of 23 (:mod:`second_amd.train_metrics`);
-    calls outside the kernel's contract go to the reference's method and are counted in the engine's ``stats``."""
+    calls outside the kernel's contract go to the reference's method and are counted in the engine's ``stats``.
+    ``multiclass_nms=True`` (SEC_ACCELERATE_MULTICLASS_NMS=1): a network built with ``use_multi_class_nms`` is served from the
+    per-class device chain instead of being refused; on request because a frame on which no class keeps
+    anything comes back without detections where the reference raises."""
     from ..dropin import accelerate_model as _acc
     return _acc(net, dtype=dtype, graph=graph, static=static, strict=strict, train_dtype=train_dtype, fp32_exact=fp32_exact,
-                deferred=deferred, train_metrics=train_metrics)
+                deferred=deferred, train_metrics=train_metrics, multiclass_nms=multiclass_nms)
 
 
 def rotate_iou_gpu_eval(boxes, query_boxes, criterion=-1, device_id=0):

@@ -94,9 +94,17 @@ def _multi_head_config(net, why):
     return heads
 
 
-def model_config(net):
+def _env_multiclass_nms():
+    import os
+    return os.environ.get("SEC_ACCELERATE_MULTICLASS_NMS", "0") == "1"
+
+
+def model_config(net, multiclass_nms=False):
     """The ``SecondDetector`` configuration of a reference-built VoxelNet (attribute names of voxelnet.py:100-171, rpn.py:202-300,
-    spconv.utils.VoxelGeneratorV2).  Raises :class:`NotAccelerable` for networks outside the fused path."""
+    spconv.utils.VoxelGeneratorV2).  Raises :class:`NotAccelerable` for networks outside the fused path.
+    ``multiclass_nms=True``: a network built with ``use_multi_class_nms`` is taken -- its per-class lists, ``_nms_class_agnostic`` and
+    ``target_assigner.anchors_range`` are read.  Opt-in (as training is): the device path answers a frame on which no class keeps
+    anything with no detections where the reference raises; without it such a network is refused by name, as before."""
     why = []
     vfe, mid, rpn = net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn
     vfe_t, mid_t, rpn_t = type(vfe).__name__, type(mid).__name__, type(rpn).__name__
@@ -112,8 +120,15 @@ def model_config(net):
     if rpn_t not in ("RPNV2", "RPNNoHead") or getattr(rpn, "_use_groupnorm", False) or not getattr(rpn, "_use_norm", True):
         why.append(f"rpn {rpn_t} (BatchNorm RPNV2 / RPNNoHead only)")
     heads = _multi_head_config(net, why) if rpn_t == "RPNNoHead" else None
-    if getattr(net, "_multiclass_nms", False):
-        why.append("multiclass_nms")
+    multiclass = bool(getattr(net, "_multiclass_nms", False))
+    if multiclass and not multiclass_nms:
+        why.append("multiclass_nms (served on request: accelerate_model(net, multiclass_nms=True) or SEC_ACCELERATE_MULTICLASS_NMS=1)")
+    elif multiclass:
+        # (what the device path does not reproduce, each by name; SecondDetector refuses the same configurations)
+        if heads or rpn_t == "RPNNoHead":
+            why.append("multiclass_nms on a multi-head network")
+        if min((float(t) for t in net._nms_score_thresholds), default=1.0) <= 0.0:
+            why.append("multiclass_nms with a score threshold <= 0")
     if not getattr(net, "_use_sigmoid_score", True) or not getattr(net, "_encode_background_as_zeros", True):
         why.append("softmax scores / background class")
     coder = getattr(net, "_box_coder", None) or net.target_assigner.box_coder
@@ -154,6 +169,21 @@ def model_config(net):
         use_rotate_nms=bool(net._use_rotate_nms),
         post_center_range=_seq(net._post_center_range) if len(net._post_center_range) else [-1e30] * 3 + [1e30] * 3,
     )
+    if multiclass:
+        nc = int(net._num_class)
+        lists = {k: list(getattr(net, a)) for k, a in (("nms_score_thresholds", "_nms_score_thresholds"), ("nms_pre_max_sizes", "_nms_pre_max_sizes"),
+                                                        ("nms_post_max_sizes", "_nms_post_max_sizes"), ("nms_iou_thresholds", "_nms_iou_thresholds"))}
+        if any(len(v) != nc for v in lists.values()):
+            raise NotAccelerable(f"accelerate_model: multiclass_nms needs one threshold / size per class ({nc}), got "
+                                 f"{ {k: len(v) for k, v in lists.items()} }")
+        agnostic = bool(getattr(net, "_nms_class_agnostic", False))
+        cfg.update(multiclass_nms=True, nms_class_agnostic=agnostic,
+                   nms_score_thresholds=[float(v) for v in lists["nms_score_thresholds"]],
+                   nms_pre_max_sizes=[int(v) for v in lists["nms_pre_max_sizes"]],
+                   nms_post_max_sizes=[int(v) for v in lists["nms_post_max_sizes"]],
+                   nms_iou_thresholds=[float(v) for v in lists["nms_iou_thresholds"]])
+        if not agnostic:
+            cfg.update(class_anchor_ranges=[tuple(int(v) for v in net.target_assigner.anchors_range(c)) for c in range(nc)])
     if vfe_t == "SimpleVoxelRadius":
         cfg.update(vfe="SimpleVoxelRadius")
     if pillars:
@@ -403,8 +433,8 @@ class FusedVoxelNet:
     ``static=False``: dynamic shapes, eager (what a CPU network under the tests' oracle backend gets)."""
 
     def __init__(self, net, dtype=None, graph=True, static=None, margin=1.25, row_bucket=16384, train_dtype=None, fp32_exact=False,
-                 deferred=False, lanes=3):
-        self.net, self.cfg = net, model_config(net)
+                 deferred=False, lanes=3, multiclass_nms=False):
+        self.net, self.cfg = net, model_config(net, multiclass_nms=multiclass_nms)
         # deferred: eval-mode calls return at once with self-filling dicts (DeferredDetection); consecutive calls alternate between
         # `lanes` sessions on their own streams, so call k + 1's copies and graph overlap call k's tail (see _static_deferred)
         import os
@@ -530,7 +560,10 @@ class FusedVoxelNet:
         above 0 (a masked-out anchor must not pass it).  Anything else keeps the original forward."""
         if "anchors_mask" not in example:
             return True
-        m, anc = example["anchors_mask"], example["anchors"]
+        if self.cfg.get("multiclass_nms"):           # refused by name: the reference indexes the masked arrays with unmasked ranges
+            self.stats["fallback_reason"] = "multiclass_nms with anchors_mask"
+            return False
+        m, anc =example["anchors_mask"], example["anchors"]
         if not isinstance(m, torch.Tensor) or m.dtype not in (torch.bool, torch.uint8) or not m.is_cuda or m.device != anc.device or anc.dim() < 2:
             return False
         batch = anc.shape[0]
@@ -754,8 +787,9 @@ class FusedVoxelNet:
 
 
 def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, train_dtype=None, fp32_exact=False, deferred=None,
-                     train_metrics=None):
-    """Serve ``net(example)`` (eval mode) from the fused pipeline; see the module docstring.  ``train_dtype`` (torch.bfloat16 /
+                     train_metrics=None, multiclass_nms=None):
+    """Serve ``net(example)`` (eval mode) from the fused pipeline; see the module docstring.  ``multiclass_nms=True``
+    (SEC_ACCELERATE_MULTICLASS_NMS=1): networks built with ``use_multi_class_nms`` are served too (:func:`model_config`).  ``train_dtype`` (torch.bfloat16 /
     torch.float16, or SEC_ACCELERATE_TRAIN=bf16|fp16 in the environment): training-mode calls are served too -- loss dict out of one
     graph replay, ``loss.backward()`` a second one that leaves the gradients on the network's own parameters (dropin_train).  Returns ``net`` (its ``forward`` is
     shadowed on the instance; ``net._second_amd_engine`` is the :class:`FusedVoxelNet`, ``net._second_amd_original_forward`` the
@@ -771,7 +805,9 @@ def accelerate_model(net, dtype=None, graph=True, static=None, strict=True, trai
     try:
         import os
         deferred = (os.environ.get("SEC_ACCELERATE_DEFERRED", "0") == "1") if deferred is None else bool(deferred)
-        eng = FusedVoxelNet(net, dtype=dtype, graph=graph, static=static, train_dtype=train_dtype, fp32_exact=fp32_exact, deferred=deferred)
+        multiclass_nms = _env_multiclass_nms() if multiclass_nms is None else bool(multiclass_nms)
+        eng = FusedVoxelNet(net, dtype=dtype, graph=graph, static=static, train_dtype=train_dtype, fp32_exact=fp32_exact, deferred=deferred,
+                            multiclass_nms=multiclass_nms)
     except NotAccelerable:
         if strict:
             raise
@@ -825,7 +861,7 @@ def accelerate_class(cls):
         eng = self.__dict__.get("_second_amd_engine")
         if eng is None and (not self.training or _env_train_dtype() is not None):
             try:
-                eng = FusedVoxelNet(self, train_dtype=_env_train_dtype())
+                eng = FusedVoxelNet(self, train_dtype=_env_train_dtype(), multiclass_nms=_env_multiclass_nms())
             except NotAccelerable:
                 eng = False
             self.__dict__["_second_amd_engine"] = eng

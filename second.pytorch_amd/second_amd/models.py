@@ -225,6 +225,51 @@ def group_feature_map_size(cfg, gi, feature_map_size):
     return [int(v) for v in (sizes[gi] if sizes and sizes[gi] else feature_map_size)]
 
 
+def multiclass_nms_settings(cfg, a_per_loc, feature_map_size):
+    """The per-class settings of ``multiclass_nms`` (the reference's use_multi_class_nms, voxelnet.py:458-547), or None without the key.
+    Keys read: ``nms_class_agnostic`` and the per-class lists ``nms_score_thresholds``, ``nms_pre_max_sizes``, ``nms_post_max_sizes``,
+    ``nms_iou_thresholds`` (each defaults to the scalar setting for every class); the classes' anchor ranges come from
+    ``class_anchor_ranges`` ((begin, end) anchor indices per class: target_assigner.anchors_range) or, with an anchor table in the
+    config, from :func:`anchor_class_ranges`.  -> dict(thr, pre, post, iou, agnostic, a_ranges [(a_begin, a_end)], post_offsets, P)."""
+    if not cfg.get("multiclass_nms"):
+        return None
+    nc = int(cfg["num_class"])
+    if cfg.get("heads"):
+        raise ValueError(f"{cfg.get('name')}: multiclass_nms on a multi-head network is not supported")
+
+    def per_class(key, scalar, conv):
+        v = cfg.get(key)
+        v = [cfg[scalar]] * nc if v is None else list(v)
+        if len(v) != nc:
+            raise ValueError(f"{cfg.get('name')}: {key} has {len(v)} entries for {nc} classes")
+        return [conv(x) for x in v]
+    thr = per_class("nms_score_thresholds", "nms_score_threshold", float)
+    pre = per_class("nms_pre_max_sizes", "nms_pre_max_size", int)
+    post = per_class("nms_post_max_sizes", "nms_post_max_size", int)
+    iou = per_class("nms_iou_thresholds", "nms_iou_threshold", float)
+    if min(thr) <= 0.0:
+        raise ValueError(f"{cfg.get('name')}: multiclass_nms with a score threshold <= 0 is not supported")
+    if min(pre) <= 0 or min(post) <= 0:
+        raise ValueError(f"{cfg.get('name')}: multiclass_nms needs positive nms_pre_max_sizes / nms_post_max_sizes")
+    agnostic = bool(cfg.get("nms_class_agnostic", False))
+    hw = int(feature_map_size[1]) * int(feature_map_size[2])
+    if agnostic:
+        a_ranges = [(0, a_per_loc)] * nc
+    else:
+        rng = cfg.get("class_anchor_ranges")
+        if rng is None:
+            begin = anchor_class_ranges(cfg, feature_map_size)
+            rng = list(zip(begin[:-1], begin[1:]))
+        if len(rng) != nc or any(int(lo) % hw or int(hi) % hw or not 0 <= int(lo) < int(hi) <= a_per_loc * hw for lo, hi in rng):
+            raise ValueError(f"{cfg.get('name')}: multiclass_nms needs one anchor range per class, each whole anchors-per-location "
+                             f"planes of the {feature_map_size[1]} x {feature_map_size[2]} map, got {list(rng)}")
+        a_ranges = [(int(lo) // hw, int(hi) // hw) for lo, hi in rng]
+    offsets = [0]
+    for p in post:
+        offsets.append(offsets[-1] + p)
+    return dict(thr=thr, pre=pre, post=post, iou=iou, agnostic=agnostic, a_ranges=a_ranges, post_offsets=offsets, P=offsets[-1], device={})
+
+
 def anchor_class_ranges(cfg, feature_map_size):
     """Start of every anchor generator's range in the class-major anchor array of generate_anchors (+ the total)."""
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
@@ -1538,6 +1583,7 @@ class SecondDetector(nn.Module):
         self._infer_dtype = None
         self.pfn_slots = True        # PointPillars inference: the PillarFeatureNet walks the voxeliser's point lists (False: pillar tensor)
         self.fused_predict = True
+        self.multiclass = multiclass_nms_settings(cfg, a_per_loc, fm)      # None unless cfg["multiclass_nms"]
         self.rulebook_numbering = os.environ.get("SEC_RULEBOOK_NUMBERING", "sorted")
         bf = cfg.get("block_filtering")
         self.voxel_generator = spconv.utils.VoxelGeneratorV2(cfg["voxel_size"], cfg["point_cloud_range"],
@@ -1689,7 +1735,7 @@ class SecondDetector(nn.Module):
         class _Ctx:
             def __enter__(self_):
                 self_.prev = getattr(det.rpn, "lazy_heads", None)
-                if (self_.prev is not None and det.fused_predict and det.cfg["nms_pre_max_size"] <= 1024
+                if (self_.prev is not None and det.fused_predict and det.cfg["nms_pre_max_size"] <= 1024 and det.multiclass is None
                         and os.environ.get("SEC_RPN_LAZY_HEADS", "1") != "0"):
                     det.rpn.lazy_heads = True
                 return self_
@@ -1918,6 +1964,15 @@ class SecondDetector(nn.Module):
         anchors = self.anchors if anchors is None else anchors
         several = isinstance(preds["cls_preds"], (list, tuple))      # a multi-head network's per-head views (MultiHeadInference)
         on_gpu = (preds["cls_preds"][0] if several else preds["cls_preds"]).is_cuda
+        if self.multiclass is not None:
+            if several:
+                raise ValueError("multiclass_nms on a multi-head network (a list of head views) is not supported")
+            if anchors_mask is not None:
+                raise ValueError("multiclass_nms with anchors_mask is not supported (the reference indexes the masked arrays with "
+                                 "unmasked anchor ranges there)")
+            if on_gpu and self.fused_predict and max(self.multiclass["pre"]) <= 1024:
+                return self._predict_multiclass_fused(preds, batch_size, anchors)
+            return self._predict_multiclass(flat_preds(preds, batch_size), batch_size, anchors)
         if (on_gpu and self.fused_predict and cfg["nms_pre_max_size"] <= 1024 and (several or not self.heads) and not (several and anchors_mask is not None)):
             # (sec_predict_select ranks up to 1024 candidates per frame; larger nms_pre_max_size takes the torch.topk path
             # below, which honours it -- never a silent truncation.  A multi-head network's CONCATENATED predictions -- its module
@@ -1953,6 +2008,89 @@ class SecondDetector(nn.Module):
         r = self.post_center_range
         valid = valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
         return {"boxes": boxes, "scores": scores, "labels": torch.gather(top_labels, 1, sel), "valid": valid}
+
+    def _predict_multiclass(self, preds, batch_size, anchors):
+        """use_multi_class_nms (voxelnet.py:458-547) in plain torch, fixed shapes: per class c its anchor range (all anchors when
+        class-agnostic), sigmoid of column c, threshold, top pre_c, NMS with iou_c, at most post_c survivors in NMS order; classes
+        concatenated in class order (label c), then the direction fix and the range mask.  What runs for CPU tensors and for a pre_c
+        above 1024; P = sum of post_c.  A frame on which no class keeps anything has no valid row (the reference raises there)."""
+        cfg, mc = self.cfg, self.multiclass
+        nc = cfg["num_class"]
+        cls = preds["cls_preds"].reshape(batch_size, -1, nc)
+        box = preds["box_preds"].reshape(batch_size, -1, 7)
+        hw = self.feature_map_size[1] * self.feature_map_size[2]
+        dirs = preds["dir_cls_preds"].reshape(batch_size, -1, cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
+        out_boxes, out_scores, out_labels, out_valid, out_dl = [], [], [], [], []
+        for c in range(nc):
+            lo, hi = mc["a_ranges"][c][0] * hw, mc["a_ranges"][c][1] * hw
+            scores = torch.sigmoid(cls[:, lo:hi, c].float())
+            k = min(mc["pre"][c], hi - lo)
+            masked = torch.where(scores >= mc["thr"][c], scores, torch.full_like(scores, -1.0))
+            top_scores, top_idx = torch.topk(masked, k, dim=1)
+            counts = (top_scores >= mc["thr"][c]).sum(1).to(torch.int32)
+            top_idx = top_idx + lo
+            enc = torch.gather(box, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7)).float()
+            anc = anchors[top_idx] if anchors.dim() == 2 else torch.gather(anchors, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7))
+            dec = decode_boxes(enc, anc)
+            if cfg["use_rotate_nms"]:
+                dets = torch.cat([dec[..., 0:2], dec[..., 3:5], dec[..., 6:7], top_scores.unsqueeze(-1)], -1).contiguous()
+                keep, num_keep = ops.nms_sorted(dets, counts, mc["iou"][c], "rotate", "cpu", post_max=mc["post"][c])
+            else:
+                hx, hy, ang = dec[..., 3] * 0.5, dec[..., 4] * 0.5, dec[..., 6]
+                cs, sn = torch.cos(ang).abs(), torch.sin(ang).abs()
+                ex, ey = hx * cs + hy * sn, hx * sn + hy * cs
+                dets = torch.stack([dec[..., 0] - ex, dec[..., 1] - ey, dec[..., 0] + ex, dec[..., 1] + ey, top_scores], -1).contiguous()
+                keep, num_keep = ops.nms_sorted(dets, counts, mc["iou"][c], "axis_aligned", "numba", post_max=mc["post"][c])
+            p = mc["post"][c]
+            keep = keep.to(top_idx.device)[:, :p]
+            keep = torch.nn.functional.pad(keep, (0, p - keep.shape[1]))              # post_c slots even where fewer were selected
+            valid = torch.arange(p, dtype=torch.int32, device=keep.device).unsqueeze(0) < num_keep.to(keep.device).unsqueeze(1)
+            sel = torch.where(valid, keep, torch.zeros_like(keep)).long()
+            out_boxes.append(torch.gather(dec, 1, sel.unsqueeze(-1).expand(-1, -1, 7)))
+            out_scores.append(torch.gather(top_scores, 1, sel))
+            out_labels.append(torch.full_like(sel, c))
+            out_valid.append(valid)
+            if dirs is not None:
+                d = torch.gather(dirs, 1, top_idx.unsqueeze(-1).expand(-1, -1, cfg["num_direction_bins"]))
+                out_dl.append(torch.gather(torch.max(d, dim=-1)[1], 1, sel))
+        boxes, scores, valid = torch.cat(out_boxes, 1), torch.cat(out_scores, 1), torch.cat(out_valid, 1)
+        if dirs is not None:
+            period = 2 * math.pi / cfg["num_direction_bins"]
+            rot = limit_period(boxes[..., 6] - cfg["direction_offset"], cfg["direction_limit_offset"], period)
+            boxes[..., 6] = rot + cfg["direction_offset"] + period * torch.cat(out_dl, 1).to(boxes.dtype)
+        r = self.post_center_range
+        valid = valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
+        return {"boxes": boxes, "scores": scores, "labels": torch.cat(out_labels, 1), "valid": valid}
+
+    def _predict_multiclass_fused(self, preds, batch_size, anchors):
+        """:meth:`_predict_multiclass` on the device with (frame, class) items: select -> decode -> NMS (two launches) -> finalize from
+        the head tensor in place, no host sync, no torch glue (capturable)."""
+        cfg, mc = self.cfg, self.multiclass
+        a_per_loc = self.num_anchor_per_loc
+        _, h, w = self.feature_map_size
+
+        def view5(t, code):
+            return t if t.dim() == 5 else t.reshape(batch_size, a_per_loc, h, w, code)
+        cls = view5(preds["cls_preds"], cfg["num_class"])
+        box = view5(preds["box_preds"], 7)
+        dirp = view5(preds["dir_cls_preds"], cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
+        if anchors.dim() == 3:
+            anchors = anchors[0]
+        anchors = anchors.float().contiguous()
+        dev = cls.device
+        tab = mc["device"].get(dev)
+        if tab is None:        # the per-class arrays the NMS and finalize kernels index (made once per device, outside any capture)
+            tab = mc["device"][dev] = (torch.tensor(mc["iou"], dtype=torch.float32, device=dev),
+                                       torch.tensor(mc["post"], dtype=torch.int32, device=dev),
+                                       torch.tensor(mc["post_offsets"], dtype=torch.int32, device=dev))
+        iou_t, post_t, off_t = tab
+        top_idx, top_score, counts = ops.predict_select_classes(cls, mc["a_ranges"], mc["pre"], mc["thr"])
+        dec, dets, dlab = ops.predict_decode_classes(box, dirp, anchors, top_idx, top_score, rotate=cfg["use_rotate_nms"])
+        kind, sem = ("rotate", "cpu") if cfg["use_rotate_nms"] else ("axis_aligned", "numba")
+        keep, num_keep = ops.nms_sorted_items(dets, counts, iou_t, post_t, kind, sem)
+        return ops.predict_finalize_classes(dec, top_score, dlab, keep, num_keep, off_t, mc["P"], dirp is not None,
+                                            cfg["direction_offset"], cfg["direction_limit_offset"], cfg["num_direction_bins"],
+                                            self.post_center_range)
 
     def _predict_fused(self, preds, batch_size, anchors, anchors_mask=None):
         """select -> decode -> NMS -> finalize: five launches, no host sync, no torch glue."""

@@ -1823,6 +1823,102 @@ def predict_finalize(dec, top_score, top_label, dir_label, keep, num_keep, post_
     return {"boxes": boxes, "scores": scores, "labels": labels, "valid": valid.view(torch.bool)}
 
 
+# multi-class NMS (use_multi_class_nms, voxelnet.py:458-547): the same chain over (frame, class) items
+def _i_arr(v):
+    import ctypes
+    v = [int(x) for x in v]
+    return (ctypes.c_int * len(v))(*v)
+
+
+@_traced("predict_select_classes")
+def predict_select_classes(cls, a_ranges, k, score_thr, anchor_mask=None):
+    """cls: [B, A, H, W, C] view (any strides).  Class c selects among the anchors with a_ranges[c][0] <= a < a_ranges[c][1] by the
+    sigmoid of column c, threshold score_thr[c] (> 0), the k[c] (<= 1024) best.  -> (top_idx [B, C, K] int32 indices into the full anchor
+    list sorted by descending score, top_score [B, C, K], counts [B, C]) with K = max over c of min(k[c], anchors of c).  Rows
+    [0, counts[b, c]) are the selection (what :func:`predict_select` returns for the one-class strided view); the rows behind them hold
+    anchor 0 / score 0.  One launch.  ``anchor_mask`` is refused (SEC_E_UNSUPPORTED), like a threshold <= 0 or a k above 1024."""
+    rt.require_gpu(cls)
+    b, a, h, w, nc = cls.shape
+    assert len(a_ranges) == nc and len(k) == nc and len(score_thr) == nc, "one a-range, k and threshold per class"
+    kout = max(1, min(1024, max(min(int(kc), max(int(e) - int(s), 0) * h * w) for kc, (s, e) in zip(k, a_ranges))))
+    dev = cls.device
+    top_idx = torch.empty((b, nc, kout), dtype=torch.int32, device=dev)
+    top_score = torch.empty((b, nc, kout), dtype=torch.float32, device=dev)
+    counts = torch.empty((b, nc), dtype=torch.int32, device=dev)
+    rc = rt.lib().sec_predict_select_classes(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, _i_arr(s for s, _ in a_ranges),
+                                             _i_arr(e for _, e in a_ranges), _i_arr(k), rt.f_arr(score_thr), kout, rt.ptr(top_idx),
+                                             rt.ptr(top_score), rt.ptr(counts), rt.dtype_code(cls.dtype), rt.ptr(anchor_mask), rt.stream())
+    rt.check(rc, "sec_predict_select_classes")
+    return top_idx, top_score, counts
+
+
+@_traced("predict_decode_classes")
+def predict_decode_classes(box, dir_cls, anchors, top_idx, top_score, rotate=True):
+    """:func:`predict_decode` of the rows of every item: top_idx / top_score [B, C, K] -> (decoded [B, C, K, 7], dets [B, C, K, 6],
+    dir_label [B, C, K])."""
+    rt.require_gpu(box, anchors, top_idx, top_score)
+    b, a, h, w, code = box.shape
+    assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
+    assert top_idx.dim() == 3 and top_idx.is_contiguous() and top_score.is_contiguous() and top_score.shape == top_idx.shape
+    _, nc, k = top_idx.shape
+    dev = box.device
+    dec = torch.empty((b, nc, k, 7), dtype=torch.float32, device=dev)
+    dets = torch.empty((b, nc, k, 6), dtype=torch.float32, device=dev)
+    dlab = torch.empty((b, nc, k), dtype=torch.int32, device=dev)
+    if dir_cls is not None:
+        assert dir_cls.dtype == box.dtype
+    rc = rt.lib().sec_predict_decode_classes(rt.ptr(box), _strides5(box), rt.ptr(dir_cls), _strides5(dir_cls) if dir_cls is not None else None,
+                                             dir_cls.shape[-1] if dir_cls is not None else 0, b, a, h, w, nc, k, rt.ptr(anchors),
+                                             rt.ptr(top_idx), rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
+                                             rt.dtype_code(box.dtype), rt.stream())
+    rt.check(rc, "sec_predict_decode_classes")
+    return dec, dets, dlab
+
+
+@_traced("nms_sorted_items")
+def nms_sorted_items(dets, counts, thresh_items, post_max_items, kind="rotate", semantics="numba", eps=1.0, exact_clip=False):
+    """:func:`nms_sorted` over (frame, class) items: dets [B, C, max_n, stride] float32, counts [B, C] int32; item (b, c) takes
+    thresh_items[c] (float32 [C], device) and keeps at most post_max_items[c] (int32 [C], device; 0 = no cap).
+    -> (keep [B, C, max_n] int32, num_keep [B, C] int32)."""
+    rt.require_gpu(dets, counts, thresh_items, post_max_items)
+    assert dets.dtype == torch.float32 and dets.dim() == 4 and dets.is_contiguous() and counts.dtype == torch.int32 and counts.is_contiguous()
+    b, nc, max_n, stride = dets.shape
+    assert tuple(counts.shape) == (b, nc)
+    assert thresh_items.dtype == torch.float32 and post_max_items.dtype == torch.int32 and thresh_items.numel() == nc and post_max_items.numel() == nc
+    keep = torch.empty((b, nc, max_n), dtype=torch.int32, device=dets.device)
+    num_keep = torch.empty((b, nc), dtype=torch.int32, device=dets.device)
+    l = rt.lib()
+    ws = rt.workspace(l.sec_nms_workspace_bytes(b * nc, max_n), dets.device)
+    rc = l.sec_nms_sorted_items_f32(rt.ptr(dets), rt.ptr(counts), b * nc, nc, max_n, stride, rt.ptr(thresh_items),
+                                    {"rotate": 0, "axis_aligned": 1}[kind], {"numba": 0, "cpu": 1}[semantics] | (256 if exact_clip else 0),
+                                    float(eps), rt.ptr(post_max_items), rt.ptr(keep), rt.ptr(num_keep), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, "sec_nms_sorted_items_f32")
+    return keep, num_keep
+
+
+@_traced("predict_finalize_classes")
+def predict_finalize_classes(dec, top_score, dir_label, keep, num_keep, post_offsets, post_total, use_direction, dir_offset,
+                             dir_limit_offset, num_dir_bins, range6):
+    """Survivors class after class: dec [B, C, K, 7]; post_offsets int32 [C + 1] (device) = running sum of the classes' post_max,
+    post_total its last entry.  -> dict(boxes [B, P, 7], scores [B, P], labels [B, P] int32, valid [B, P] bool), P = post_total; the
+    valid rows in row order are the reference's order."""
+    rt.require_gpu(dec, keep, num_keep, post_offsets)
+    b, nc, k, _ = dec.shape
+    assert post_offsets.dtype == torch.int32 and post_offsets.numel() == nc + 1
+    p = int(post_total)
+    dev = dec.device
+    boxes = torch.empty((b, p, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, p), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, p), dtype=torch.int32, device=dev)
+    valid = torch.empty((b, p), dtype=torch.uint8, device=dev)
+    rc = rt.lib().sec_predict_finalize_classes(rt.ptr(dec), rt.ptr(top_score), rt.ptr(dir_label), rt.ptr(keep), rt.ptr(num_keep),
+                                               rt.ptr(post_offsets), b, nc, k, p, int(bool(use_direction)), float(dir_offset),
+                                               float(dir_limit_offset), int(num_dir_bins), rt.ptr(range6), rt.ptr(boxes), rt.ptr(scores),
+                                               rt.ptr(labels), rt.ptr(valid), rt.stream())
+    rt.check(rc, "sec_predict_finalize_classes")
+    return {"boxes": boxes, "scores": scores, "labels": labels, "valid": valid.view(torch.bool)}
+
+
 # ----------------------------------------------------------------------------- training: targets + loss (SURVEY 8f item 3)
 SIM_NEAREST_IOU, SIM_DISTANCE = 0, 1         # include/second_hip.h SEC_SIM_*
 

@@ -43,6 +43,7 @@ SYMBOLS = [
     "sec_kitti_eval_pr_workspace_bytes", "sec_kitti_eval_pr", "sec_kitti_annos_workspace_bytes", "sec_kitti_annos_f64",
     "sec_region_similarity_f32", "sec_assign_targets_sim_f32", "sec_train_metrics_workspace_bytes", "sec_train_metrics_f32",
     "sec_pfn_radius_fwd", "sec_pfn_radius_fwd_slots", "sec_predict_select_segments", "sec_predict_decode_segments",
+    "sec_predict_select_classes", "sec_predict_decode_classes", "sec_nms_sorted_items_f32", "sec_predict_finalize_classes",
 ]
 
 _lib = None
@@ -239,6 +240,10 @@ def lib():
         l.sec_predict_select_masked.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
         l.sec_predict_select_segments.argtypes = [ci, vp, vp, vp, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp]
         l.sec_predict_decode_segments.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp]
+        l.sec_predict_select_classes.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp]
+        l.sec_predict_decode_classes.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp]
+        l.sec_nms_sorted_items_f32.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci, cf, vp, vp, vp, vp, sz, vp]
+        l.sec_predict_finalize_classes.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp]
         l.sec_assign_targets_masked_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         l.sec_region_similarity_f32.argtypes = [vp, ci, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp]
         l.sec_assign_targets_sim_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
