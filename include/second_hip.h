@@ -483,6 +483,24 @@ int sec_pfn_train_bwd(const float *voxels, const int *num_points, const int *coo
                       int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
                       float vy, float x_offset, float y_offset, const float *grad_out, const float *out, const signed char *argmax,
                       float *dweight_t, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+/* PillarFeatureNetRadius in TRAINING mode (PillarFeatureNetRadius.forward, pointpillars.py:290-325, with its PFNLayer under train();
+ * config nuscenes/all.pp.mhead.config): the same layer, arguments, limits, status codes and workspace as sec_pfn_train_fwd / _bwd on
+ * the eight-entry row [r, z, f3, x - mean_x, y - mean_y, z - mean_z, x - centre_x, y - centre_y], r = sqrt(x^2 + y^2) in the
+ * arithmetic of sec_pfn_radius_fwd (multiply, multiply, add, square root, each correctly rounded; one device function builds the row
+ * for inference and training).  Cluster mean and pillar centre are taken on the Cartesian coordinates; a padded slot is zero in all
+ * eight entries (the reference masks after decorating, so its centre offsets are zero too).  Linear(8, C, bias=False): weight_t and
+ * dweight_t are [8][C].
+ *   stats f32[C * 10 + 8] = mean[C], invstd[C], M[C][8] = sum x_c * input_j, S1[8] = sum input_j.
+ * num_pillars == 0: fwd is a no-op, bwd zero-fills dweight_t, dgamma and dbeta. */
+int sec_pfn_radius_train_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                             int num_features, const float *weight_t, const float *gamma, const float *beta, float eps, float momentum,
+                             float *running_mean, float *running_var, int channels, float vx, float vy, float x_offset, float y_offset,
+                             float *out, signed char *argmax, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+int sec_pfn_radius_train_bwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                             int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
+                             float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
+                             const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* Block filtering of points_to_voxel_3d_with_filtering (spconv point2voxel.h; enabled by
  * second/configs/nuscenes/all.fhd.config:9-12): keep a voxel iff the z-span of the stored points inside the

@@ -21,6 +21,22 @@ template <> __device__ __forceinline__ float cvt_out(float v) { return v; }
 template <> __device__ __forceinline__ __hip_bfloat16 cvt_out(float v) { return __float2bfloat16(v); }
 template <> __device__ __forceinline__ __half cvt_out(float v) { return __float2half_rn(v); }
 
+// The decorated row of one point, shared by inference (k_pfn_fwd) and the training kernels below, so that both evaluate the very
+// same expressions (the library is built with -ffp-contract=off: the radius is multiply, multiply, add, square root, each correctly
+// rounded).  RADIUS = false: [x, y, z, w, x - mx, y - my, z - mz, x - cx, y - cy] (9); RADIUS = true: [r, z, w, x - mx, y - my,
+// z - mz, x - cx, y - cy] (8) with r = sqrt(x * x + y * y); the cluster mean and the pillar centre are Cartesian in both.
+template <bool RADIUS>
+__device__ __forceinline__ void pfn_row(const float4 q, float mx, float my, float mz, float cx, float cy, float (&f)[RADIUS ? 8 : 9]) {
+    constexpr int IN = RADIUS ? 8 : 9;
+    if constexpr (RADIUS) {
+        f[0] = __fsqrt_rn(__fadd_rn(__fmul_rn(q.x, q.x), __fmul_rn(q.y, q.y)));
+        f[1] = q.z; f[2] = q.w;
+    } else {
+        f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
+    }
+    f[IN - 5] = q.x - mx; f[IN - 4] = q.y - my; f[IN - 3] = q.z - mz; f[IN - 2] = q.x - cx; f[IN - 1] = q.y - cy;
+}
+
 // F = 4 point features (x, y, z, r/dt), IN = 9 decorated features
 // SLOTS: `voxels` is the caller's flat POINT array and `slots` the voxeliser's point lists (slots[p * T + t] = index of pillar p's
 // t-th point, vox_slots_of): the pillar's points are fetched through the list instead of from a [P, T, 4] tensor -- the same
@@ -80,13 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
                 q = SLOTS ? pv[sl[t]] : pv[t];            // wave-uniform address: one broadcast load
             }
             float f[IN];
-            if constexpr (RADIUS) {
-                f[0] = __fsqrt_rn(__fadd_rn(__fmul_rn(q.x, q.x), __fmul_rn(q.y, q.y)));
-                f[1] = q.z; f[2] = q.w;
-            } else {
-                f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
-            }
-            f[IN - 5] = q.x - mx; f[IN - 4] = q.y - my; f[IN - 3] = q.z - mz; f[IN - 2] = q.x - cx; f[IN - 1] = q.y - cy;
+            pfn_row<RADIUS>(q, mx, my, mz, cx, cy, f);
             float y = 0.f;
 #pragma unroll
             for (int j = 0; j < IN; ++j) y = fmaf(f[j], w[j], y);
@@ -111,9 +121,15 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
 //                   xhat * dgamma / N)); summed against the inputs that is closed form in S1 and M:
 //                   dW[c][j] = gamma_c invstd_c (A[c][j] - dbeta_c / N * S1[j] - dgamma_c / N * invstd_c (M[c][j] - mean_c S1[j]))
 // No gradient with respect to the points (they are data).
-constexpr int kPfnIn = 9;
-constexpr int kPfnStatVals = 2 + kPfnIn;          // per channel: sum x, sum x^2, M[c][0..8]
-constexpr int kPfnBwdVals = 2 + kPfnIn;           // per channel: dbeta, dgamma, A[c][0..8]
+// RADIUS (PillarFeatureNetRadius, pointpillars.py:290-325 under train()): the same five kernels on the eight-entry row of pfn_row<true>;
+// a padded slot is zero in all eight entries (the reference masks after decorating), so it is the same x = 0 row as above.
+constexpr int kPfnIn = 9;                         // the wider of the two rows: what the workspace is sized for
+template <bool RADIUS> struct PfnDims {
+    static constexpr int K = RADIUS ? 8 : 9;      // decorated inputs
+    static constexpr int StatVals = 2 + K;        // per channel: sum x, sum x^2, M[c][0..K-1]
+    static constexpr int BwdVals = 2 + K;         // per channel: dbeta, dgamma, A[c][0..K-1]
+};
+constexpr int kPfnStatVals = 2 + kPfnIn;          // the workspace's per-channel pitch (both forms carve it alike)
 constexpr int kPfnMaxBlocks = 1024;
 
 struct PfnPillar {
@@ -137,62 +153,63 @@ __device__ __forceinline__ PfnPillar pfn_pillar(const float4 *__restrict__ pv, i
     r.n = n < T ? n : T;
     return r;
 }
-__device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl, float (&f)[kPfnIn]) {
-    f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
-    f[4] = q.x - pl.mx; f[5] = q.y - pl.my; f[6] = q.z - pl.mz;
-    f[7] = q.x - pl.cx; f[8] = q.y - pl.cy;
+template <bool RADIUS>
+__device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl, float (&f)[RADIUS ? 8 : 9]) {
+    pfn_row<RADIUS>(q, pl.mx, pl.my, pl.mz, pl.cx, pl.cy, f);
 }
 
-// partial[block][c][kPfnStatVals], partial_s1[block][kPfnIn]; C <= 64 (one wave = all channels)
+// partial[block][c][StatVals], partial_s1[block][K]; C <= 64 (one wave = all channels)
+template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                      const int *__restrict__ coords, int P, int T, const float *__restrict__ wt, int C,
                                                      float vx, float vy, float xo, float yo, float *__restrict__ partial,
                                                      float *__restrict__ partial_s1) {
-    __shared__ float red[kBlock / 64][64][kPfnStatVals + 1];
-    __shared__ float red1[kBlock / 64][kPfnIn];
+    constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
+    __shared__ float red[kBlock / 64][64][StatVals + 1];
+    __shared__ float red1[kBlock / 64][K];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool live = lane < C;
-    float w[kPfnIn];
+    float w[K];
 #pragma unroll
-    for (int j = 0; j < kPfnIn; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
-    float acc[kPfnStatVals], s1[kPfnIn];
+    for (int j = 0; j < K; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
+    float acc[StatVals], s1[K];
 #pragma unroll
-    for (int j = 0; j < kPfnStatVals; ++j) acc[j] = 0.f;
+    for (int j = 0; j < StatVals; ++j) acc[j] = 0.f;
 #pragma unroll
-    for (int j = 0; j < kPfnIn; ++j) s1[j] = 0.f;
+    for (int j = 0; j < K; ++j) s1[j] = 0.f;
     for (int p = blockIdx.x * (kBlock / 64) + wv; p < P; p += gridDim.x * (kBlock / 64)) {
         const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
         const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
         for (int t = 0; t < pl.n; ++t) {
-            float f[kPfnIn];
-            pfn_decorate(pv[t], pl, f);
+            float f[K];
+            pfn_decorate<RADIUS>(pv[t], pl, f);
             float x = 0.f;
 #pragma unroll
-            for (int j = 0; j < kPfnIn; ++j) x = fmaf(f[j], w[j], x);
+            for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
             acc[0] += x;
             acc[1] = fmaf(x, x, acc[1]);
 #pragma unroll
-            for (int j = 0; j < kPfnIn; ++j) { acc[2 + j] = fmaf(x, f[j], acc[2 + j]); s1[j] += f[j]; }
+            for (int j = 0; j < K; ++j) { acc[2 + j] = fmaf(x, f[j], acc[2 + j]); s1[j] += f[j]; }
         }
     }
 #pragma unroll
-    for (int j = 0; j < kPfnStatVals; ++j) red[wv][lane][j] = acc[j];
+    for (int j = 0; j < StatVals; ++j) red[wv][lane][j] = acc[j];
     if (lane == 0)
 #pragma unroll
-        for (int j = 0; j < kPfnIn; ++j) red1[wv][j] = s1[j];
+        for (int j = 0; j < K; ++j) red1[wv][j] = s1[j];
     __syncthreads();
     if (wv == 0) {
         if (live)
 #pragma unroll
-            for (int j = 0; j < kPfnStatVals; ++j) {
+            for (int j = 0; j < StatVals; ++j) {
                 float v = 0.f;
                 for (int k = 0; k < kBlock / 64; ++k) v += red[k][lane][j];
-                partial[((size_t)blockIdx.x * C + lane) * kPfnStatVals + j] = v;
+                partial[((size_t)blockIdx.x * C + lane) * StatVals + j] = v;
             }
-        if (lane < kPfnIn) {
+        if (lane < K) {
             float v = 0.f;
             for (int k = 0; k < kBlock / 64; ++k) v += red1[k][lane];
-            partial_s1[(size_t)blockIdx.x * kPfnIn + lane] = v;
+            partial_s1[(size_t)blockIdx.x * K + lane] = v;
         }
     }
 }
@@ -208,26 +225,28 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {   // 256
     return r;
 }
 
-// one block per channel (+ one for S1).  stats[c] layout: mean[C], invstd[C], M[C][9], S1[9]
+// one block per channel (+ one for S1).  stats[c] layout: mean[C], invstd[C], M[C][K], S1[K]
+template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict__ partial, const float *__restrict__ partial_s1,
                                                         int blocks, int C, double rows, float eps, float momentum,
                                                         float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ stats) {
+    constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
     __shared__ double sh[kBlock / 64];
     const int c = blockIdx.x;
     if (c == C) {                                     // S1
-        for (int j = 0; j < kPfnIn; ++j) {
+        for (int j = 0; j < K; ++j) {
             double v = 0.0;
-            for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial_s1[(size_t)b * kPfnIn + j];
+            for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial_s1[(size_t)b * K + j];
             v = block_sum_f64(v, sh);
-            if (threadIdx.x == 0) stats[(size_t)C * (2 + kPfnIn) + j] = (float)v;
+            if (threadIdx.x == 0) stats[(size_t)C * (2 + K) + j] = (float)v;
         }
         return;
     }
-    double tot[kPfnStatVals];
-    for (int j = 0; j < kPfnStatVals; ++j) {
+    double tot[StatVals];
+    for (int j = 0; j < StatVals; ++j) {
         double v = 0.0;
-        for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial[((size_t)b * C + c) * kPfnStatVals + j];
+        for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial[((size_t)b * C + c) * StatVals + j];
         tot[j] = block_sum_f64(v, sh);
     }
     if (threadIdx.x == 0) {
@@ -236,25 +255,27 @@ __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict
         if (var < 0.0) var = 0.0;
         stats[c] = (float)mean;
         stats[C + c] = (float)(1.0 / sqrt(var + (double)eps));
-        for (int j = 0; j < kPfnIn; ++j) stats[(size_t)2 * C + (size_t)c * kPfnIn + j] = (float)tot[2 + j];
+        for (int j = 0; j < K; ++j) stats[(size_t)2 * C + (size_t)c * K + j] = (float)tot[2 + j];
         if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
         if (running_var) running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * var * (rows > 1.0 ? rows / (rows - 1.0) : 1.0));
     }
 }
 
 // normalise with the batch statistics, ReLU, max over the slots; argmax[p][c] = slot of the maximum (first one; -1 = a padded slot)
+template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                          const int *__restrict__ coords, int P, int T, const float *__restrict__ wt,
                                                          const float *__restrict__ gamma, const float *__restrict__ beta,
                                                          const float *__restrict__ stats, int C, float vx, float vy, float xo,
                                                          float yo, float *__restrict__ out, signed char *__restrict__ argmax) {
+    constexpr int K = PfnDims<RADIUS>::K;
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (p >= P) return;
     const bool live = lane < C;
-    float w[kPfnIn];
+    float w[K];
 #pragma unroll
-    for (int j = 0; j < kPfnIn; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
+    for (int j = 0; j < K; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
     const float mean = live ? stats[lane] : 0.f, invstd = live ? stats[C + lane] : 0.f;
     const float ga = live ? gamma[lane] : 0.f, be = live ? beta[lane] : 0.f;
     const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
@@ -262,11 +283,11 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
     float best = -INFINITY;
     int arg = -1;
     for (int t = 0; t < pl.n; ++t) {
-        float f[kPfnIn];
-        pfn_decorate(pv[t], pl, f);
+        float f[K];
+        pfn_decorate<RADIUS>(pv[t], pl, f);
         float x = 0.f;
 #pragma unroll
-        for (int j = 0; j < kPfnIn; ++j) x = fmaf(f[j], w[j], x);
+        for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
         const float y = fmaxf(fmaf((x - mean) * invstd, ga, be), 0.f);
         if (y > best) { best = y; arg = t; }
     }
@@ -280,22 +301,24 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
     }
 }
 
-// partial[block][c][kPfnBwdVals] = (dbeta, dgamma, A[c][0..8])
+// partial[block][c][BwdVals] = (dbeta, dgamma, A[c][0..K-1])
+template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                    const int *__restrict__ coords, int P, int T, const float *__restrict__ wt,
                                                    const float *__restrict__ stats, int C, float vx, float vy, float xo, float yo,
                                                    const float *__restrict__ grad_out, const float *__restrict__ out,
                                                    const signed char *__restrict__ argmax, float *__restrict__ partial) {
-    __shared__ float red[kBlock / 64][64][kPfnBwdVals + 1];
+    constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
+    __shared__ float red[kBlock / 64][64][BwdVals + 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool live = lane < C;
-    float w[kPfnIn];
+    float w[K];
 #pragma unroll
-    for (int j = 0; j < kPfnIn; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
+    for (int j = 0; j < K; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
     const float mean = live ? stats[lane] : 0.f, invstd = live ? stats[C + lane] : 0.f;
-    float acc[kPfnBwdVals];
+    float acc[BwdVals];
 #pragma unroll
-    for (int j = 0; j < kPfnBwdVals; ++j) acc[j] = 0.f;
+    for (int j = 0; j < BwdVals; ++j) acc[j] = 0.f;
     for (int p = blockIdx.x * (kBlock / 64) + wv; p < P; p += gridDim.x * (kBlock / 64)) {
         const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
         const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
@@ -304,42 +327,44 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ vo
         const float dz = out[(size_t)p * C + lane] > 0.f ? g : 0.f;
         const int t = argmax[(size_t)p * C + lane];
         float x = 0.f;
-        float f[kPfnIn];
+        float f[K];
 #pragma unroll
-        for (int j = 0; j < kPfnIn; ++j) f[j] = 0.f;
+        for (int j = 0; j < K; ++j) f[j] = 0.f;
         if (t >= 0) {
-            pfn_decorate(pv[t], pl, f);
+            pfn_decorate<RADIUS>(pv[t], pl, f);
 #pragma unroll
-            for (int j = 0; j < kPfnIn; ++j) x = fmaf(f[j], w[j], x);
+            for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
         }
         acc[0] += dz;
         acc[1] = fmaf(dz, (x - mean) * invstd, acc[1]);
 #pragma unroll
-        for (int j = 0; j < kPfnIn; ++j) acc[2 + j] = fmaf(dz, f[j], acc[2 + j]);
+        for (int j = 0; j < K; ++j) acc[2 + j] = fmaf(dz, f[j], acc[2 + j]);
     }
 #pragma unroll
-    for (int j = 0; j < kPfnBwdVals; ++j) red[wv][lane][j] = acc[j];
+    for (int j = 0; j < BwdVals; ++j) red[wv][lane][j] = acc[j];
     __syncthreads();
     if (wv == 0 && live)
 #pragma unroll
-        for (int j = 0; j < kPfnBwdVals; ++j) {
+        for (int j = 0; j < BwdVals; ++j) {
             float v = 0.f;
             for (int k = 0; k < kBlock / 64; ++k) v += red[k][lane][j];
-            partial[((size_t)blockIdx.x * C + lane) * kPfnBwdVals + j] = v;
+            partial[((size_t)blockIdx.x * C + lane) * BwdVals + j] = v;
         }
 }
 
 // one block per channel: dweight_t[j][c], dgamma[c], dbeta[c]
+template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__restrict__ partial, int blocks, int C, double rows,
                                                             const float *__restrict__ gamma, const float *__restrict__ stats,
                                                             float *__restrict__ dweight_t, float *__restrict__ dgamma,
                                                             float *__restrict__ dbeta) {
+    constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
     __shared__ double sh[kBlock / 64];
     const int c = blockIdx.x;
-    double tot[kPfnBwdVals];
-    for (int j = 0; j < kPfnBwdVals; ++j) {
+    double tot[BwdVals];
+    for (int j = 0; j < BwdVals; ++j) {
         double v = 0.0;
-        for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial[((size_t)b * C + c) * kPfnBwdVals + j];
+        for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial[((size_t)b * C + c) * BwdVals + j];
         tot[j] = block_sum_f64(v, sh);
     }
     if (threadIdx.x == 0) {
@@ -347,8 +372,8 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__rest
         const double db = tot[0], dg = tot[1];
         dbeta[c] = (float)db;
         dgamma[c] = (float)dg;
-        for (int j = 0; j < kPfnIn; ++j) {
-            const double s1 = stats[(size_t)C * (2 + kPfnIn) + j], m = stats[(size_t)2 * C + (size_t)c * kPfnIn + j];
+        for (int j = 0; j < K; ++j) {
+            const double s1 = stats[(size_t)C * (2 + K) + j], m = stats[(size_t)2 * C + (size_t)c * K + j];
             dweight_t[(size_t)j * C + c] = (float)(ga * invstd * (tot[2 + j] - db / rows * s1 - dg / rows * invstd * (m - mean * s1)));
         }
     }
@@ -575,11 +600,12 @@ SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
     return align_up(b * channels * kPfnStatVals * sizeof(float)) + align_up(b * kPfnIn * sizeof(float));
 }
 
-SEC_API int sec_pfn_train_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
-                              int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
-                              float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
-                              float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
-                              size_t workspace_bytes, void *stream) {
+template <bool RADIUS>
+static int pfn_train_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                             int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
+                             float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
+                             float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
+                             size_t workspace_bytes, void *stream) {
     if (num_pillars < 0 || max_points <= 0 || max_points > 127 || channels <= 0 || !weight_t || !gamma || !beta || !out || !argmax || !stats)
         return SEC_E_INVALID;
     if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
@@ -587,23 +613,24 @@ SEC_API int sec_pfn_train_fwd(const float *voxels, const int *num_points, const 
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = pfn_blocks(num_pillars);
-    float *partial = (float *)workspace;
+    float *partial = (float *)workspace;      // the workspace is carved for nine inputs in both forms (eight need less)
     float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * kPfnStatVals * sizeof(float)));
-    hipLaunchKernelGGL(k_pfn_stats, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points, weight_t,
-                       channels, vx, vy, x_offset, y_offset, partial, partial_s1);
+    hipLaunchKernelGGL(k_pfn_stats<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points,
+                       weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1);
     const double rows = (double)num_pillars * (double)max_points;
-    hipLaunchKernelGGL(k_pfn_finalize, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, blocks, channels, rows, eps,
+    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, blocks, channels, rows, eps,
                        momentum, running_mean, running_var, stats);
-    hipLaunchKernelGGL(k_pfn_fwd_train, dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
+    hipLaunchKernelGGL(k_pfn_fwd_train<RADIUS>, dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
                        num_pillars, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);
     return check_launch();
 }
 
-SEC_API int sec_pfn_train_bwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
-                              int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
-                              float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
-                              const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
-                              size_t workspace_bytes, void *stream) {
+template <bool RADIUS>
+static int pfn_train_bwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                             int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
+                             float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
+                             const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
+                             size_t workspace_bytes, void *stream) {
     if (num_pillars < 0 || max_points <= 0 || max_points > 127 || channels <= 0 || !weight_t || !gamma || !stats || !grad_out || !out ||
         !argmax || !dweight_t || !dgamma || !dbeta)
         return SEC_E_INVALID;
@@ -611,19 +638,45 @@ SEC_API int sec_pfn_train_bwd(const float *voxels, const int *num_points, const 
     if (!workspace || workspace_bytes < sec_pfn_train_workspace_bytes(num_pillars, channels)) return SEC_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (num_pillars == 0) {
-        int rc = fill_words(dweight_t, sizeof(float) * kPfnIn * channels, 0u, st);
+        int rc = fill_words(dweight_t, sizeof(float) * PfnDims<RADIUS>::K * channels, 0u, st);
         if (!rc) rc = fill_words(dgamma, sizeof(float) * channels, 0u, st);
         if (!rc) rc = fill_words(dbeta, sizeof(float) * channels, 0u, st);
         return rc;
     }
     const int blocks = pfn_blocks(num_pillars);
     float *partial = (float *)workspace;
-    hipLaunchKernelGGL(k_pfn_bwd, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points, weight_t, stats,
-                       channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
-    hipLaunchKernelGGL(k_pfn_bwd_finalize, dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels,
+    hipLaunchKernelGGL(k_pfn_bwd<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points, weight_t,
+                       stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
+    hipLaunchKernelGGL(k_pfn_bwd_finalize<RADIUS>, dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels,
                        (double)num_pillars * (double)max_points, gamma, stats, dweight_t, dgamma, dbeta);
     return check_launch();
 }
+
+#define SEC_PFN_TRAIN_FWD_ARGS                                                                                                     \
+    const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points, int num_features,             \
+        const float *weight_t, const float *gamma, const float *beta, float eps, float momentum, float *running_mean,             \
+        float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out, signed char *argmax,    \
+        float *stats, void *workspace, size_t workspace_bytes, void *stream
+#define SEC_PFN_TRAIN_FWD_PASS                                                                                                     \
+    voxels, num_points, coords, num_pillars, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
+        running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats, workspace, workspace_bytes, stream
+#define SEC_PFN_TRAIN_BWD_ARGS                                                                                                     \
+    const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points, int num_features,             \
+        const float *weight_t, const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,          \
+        float y_offset, const float *grad_out, const float *out, const signed char *argmax, float *dweight_t, float *dgamma,      \
+        float *dbeta, void *workspace, size_t workspace_bytes, void *stream
+#define SEC_PFN_TRAIN_BWD_PASS                                                                                                     \
+    voxels, num_points, coords, num_pillars, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
+        y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace, workspace_bytes, stream
+SEC_API int sec_pfn_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<false>(SEC_PFN_TRAIN_BWD_PASS); }
+// PillarFeatureNetRadius in training mode (the RADIUS instantiations): the same arguments, weight_t / dweight_t are [8][channels]
+SEC_API int sec_pfn_radius_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<true>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_radius_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<true>(SEC_PFN_TRAIN_BWD_PASS); }
+#undef SEC_PFN_TRAIN_FWD_ARGS
+#undef SEC_PFN_TRAIN_FWD_PASS
+#undef SEC_PFN_TRAIN_BWD_ARGS
+#undef SEC_PFN_TRAIN_BWD_PASS
 
 SEC_API size_t sec_block_filter_workspace_bytes(int rows, int batch, int grid_x, int grid_y, int block_factor) {
     if (rows < 0 || batch <= 0 || block_factor <= 0) return 0;

@@ -407,22 +407,33 @@ class PillarFeatureNet(nn.Module):
         return ops.pfn_forward_slots(points, vox, wt, scale, shift, self.vx, self.vy, self.x_offset, self.y_offset,
                                      out_dtype=out_dtype, num_dev=num_dev)
 
+    train_function = ops.PFNTrainFunction      # the autograd Function of the training kernels for this class's decorated row
+
+    def _forward_train_kernels(self, features, num_voxels, coors):
+        """Training on the device (sec_pfn_train_fwd / _bwd, or their radius forms: batch statistics, argmax backward, no
+        [P, T, C] tensor), or None where the torch formulation has to serve: CPU, eval / frozen or non-affine norm, a linear bias,
+        train_backend = "torch", a shape the kernels do not take, no pillars."""
+        l = self.pfn_layers[0]
+        bn = l.norm
+        if not (features.is_cuda and self.training and bn.training and bn.track_running_stats and bn.affine and l.linear.bias is None
+                and self.train_backend == "hip" and ops.pfn_train_supported(features, bn.num_features)
+                and features.shape[0] > 0):
+            return None
+        mom = bn.momentum if bn.momentum is not None else 0.1
+        out = self.train_function.apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
+                                        bn.running_mean, bn.running_var, bn.eps, mom,
+                                        (self.vx, self.vy, self.x_offset, self.y_offset))
+        ops.bump_bn_counter(bn)
+        return out
+
     def forward(self, features, num_voxels, coors, out_dtype=None, num_dev=None):
         l = self.pfn_layers[0]
         if features.is_cuda and not self.training and not torch.is_grad_enabled():
             wt, scale, shift = self.folded()
             return ops.pfn_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
                                    self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
-        bn = l.norm
-        if (features.is_cuda and self.training and bn.training and bn.track_running_stats and bn.affine and l.linear.bias is None
-                and self.train_backend == "hip" and ops.pfn_train_supported(features, bn.num_features)
-                and features.shape[0] > 0):
-            # training on the device: sec_pfn_train_fwd / _bwd (batch statistics, argmax backward), no [P, T, C] tensor
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            out = ops.PFNTrainFunction.apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
-                                             bn.running_mean, bn.running_var, bn.eps, mom,
-                                             (self.vx, self.vy, self.x_offset, self.y_offset))
-            ops.bump_bn_counter(bn)
+        out = self._forward_train_kernels(features, num_voxels, coors)
+        if out is not None:
             return out
         n = num_voxels.to(features.dtype).view(-1, 1, 1)
         xyz = features[:, :, :3]
@@ -440,8 +451,11 @@ class PillarFeatureNet(nn.Module):
 class PillarFeatureNetRadius(PillarFeatureNet):
     """One-layer PillarFeatureNetRadius (pointpillars.py:240-325; nuscenes/all.pp.mhead): the raw (x, y) of every point give way to
     their radius, so the layer is Linear(num_input_features + 4, C); same keys pfn_layers.0.{linear,norm}.  Inference on the GPU runs
-    sec_pfn_radius_fwd (forward_slots: sec_pfn_radius_fwd_slots); everything else -- CPU, grad mode, training -- the torch
-    formulation below (there is no training kernel for it)."""
+    sec_pfn_radius_fwd (forward_slots: sec_pfn_radius_fwd_slots), training on the GPU sec_pfn_radius_train_fwd / _bwd
+    (ops.PFNRadiusTrainFunction, under the conditions of PillarFeatureNet; train_backend = "torch" selects the formulation below); the
+    torch formulation serves the CPU, eval mode with gradients, and as the autograd reference of the training kernels."""
+
+    train_function = ops.PFNRadiusTrainFunction
 
     def __init__(self, num_input_features=4, num_filters=(64,), voxel_size=(0.2, 0.2, 4), pc_range=(0, -40, -3, 70.4, 40, 1)):
         super().__init__(num_input_features, num_filters, voxel_size, pc_range)
@@ -458,6 +472,9 @@ class PillarFeatureNetRadius(PillarFeatureNet):
             wt, scale, shift = self.folded()
             return ops.pfn_radius_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
                                           self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
+        out = self._forward_train_kernels(features, num_voxels, coors)
+        if out is not None:
+            return out
         n = num_voxels.to(features.dtype).view(-1, 1, 1)
         xyz = features[:, :, :3]
         mean = xyz.sum(1, keepdim=True) / n
@@ -806,6 +823,70 @@ def stage0_crop(height):
 RPN_TRAIN_BACKEND = "hip"
 
 
+def _mixed_block(blk, x, dtype, use_hip):
+    """One block of Conv2d / BatchNorm2d / ReLU modules for :func:`rpn_forward_mixed`: 128-channel stride-1 3x3 triples on the
+    hand-written kernels, everything else on torch under autocast."""
+    mods = list(blk.children())
+    i, pad = 0, 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.ZeroPad2d):
+            pad = m.padding[0]
+            i += 1
+            continue
+        fused = (use_hip and isinstance(m, nn.Conv2d) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d)
+                 and isinstance(mods[i + 2], nn.ReLU) and m.bias is None and m.kernel_size == (3, 3) and m.stride == (1, 1)
+                 and m.padding[0] + pad == 1 and m.padding[1] + pad == 1 and m.dilation == (1, 1) and m.groups == 1
+                 and ops.conv2d_wgrad_supported(m.in_channels, m.out_channels, 3, 1, 1, dtype) and mods[i + 1].training
+                 and mods[i + 1].track_running_stats and mods[i + 1].affine)
+        if fused:
+            bn = mods[i + 1]
+            y = ops.Conv3x3Function.apply(x, m.weight)
+            mom = bn.momentum if bn.momentum is not None else 0.1
+            x = ops.BatchNormReluFunction.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, mom, True)
+            ops.bump_bn_counter(bn)
+            i, pad = i + 3, 0
+            continue
+        with torch.autocast("cuda", dtype=dtype, enabled=x.is_cuda, cache_enabled=False):
+            if pad:
+                x = F.pad(x, (pad, pad, pad, pad))
+                pad = 0
+            x = m(x)
+        i += 1
+    return x
+
+
+def _mixed_deblock(deb, x, dtype, use_hip):
+    """One deblock the same way: the 128 -> 128 1x1 transposed convolution on the hand-written kernels, others on torch."""
+    mods = list(deb.children())
+    m = mods[0]
+    if (use_hip and len(mods) == 3 and isinstance(m, nn.ConvTranspose2d) and isinstance(mods[1], nn.BatchNorm2d)
+            and isinstance(mods[2], nn.ReLU) and m.bias is None and m.kernel_size == (1, 1) and m.stride == (1, 1)
+            and m.padding == (0, 0) and m.output_padding == (0, 0) and m.groups == 1 and m.in_channels == 128
+            and m.out_channels == 128 and dtype in (torch.bfloat16, torch.float16) and mods[1].training
+            and mods[1].track_running_stats and mods[1].affine):
+        bn = mods[1]
+        y = ops.ConvTranspose1x1Function.apply(x, m.weight)
+        mom = bn.momentum if bn.momentum is not None else 0.1
+        z = ops.BatchNormReluFunction.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, mom, True)
+        ops.bump_bn_counter(bn)
+        return z
+    with torch.autocast("cuda", dtype=dtype, enabled=x.is_cuda, cache_enabled=False):
+        return deb(x)
+
+
+def _mixed_trunk(rpn, x, dtype, use_hip):
+    """The walk over ``rpn.blocks`` / ``rpn.deblocks`` shared by :func:`rpn_forward_mixed` and :func:`multihead_forward_mixed`:
+    (every block's output, every deblock's output)."""
+    stages, ups = [], []
+    for i, blk in enumerate(rpn.blocks):
+        x = _mixed_block(blk, x, dtype, use_hip)
+        stages.append(x)
+        if i - rpn._upsample_start_idx >= 0:
+            ups.append(_mixed_deblock(rpn.deblocks[i - rpn._upsample_start_idx], x, dtype, use_hip))
+    return stages, ups
+
+
 def rpn_forward_mixed(rpn, x, dtype, loss_args=None, loss_terms=False):
     """Training forward of an RPNV2 with 16-bit activations over its fp32 master weights (the DeviceTrainer's amp path).  Every
     Conv2d(128, 128, 3, stride 1) + BatchNorm2d + ReLU triple of the blocks runs on the hand-written kernels -- forward and data
@@ -821,57 +902,8 @@ def rpn_forward_mixed(rpn, x, dtype, loss_args=None, loss_terms=False):
     reference's loss dict (voxelnet.py:299-309), from the same launch."""
     use_hip = RPN_TRAIN_BACKEND == "hip" and x.is_cuda
     x = x.to(dtype).contiguous(memory_format=torch.channels_last)
-
-    def run_block(blk, x):
-        mods = list(blk.children())
-        i, pad = 0, 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, nn.ZeroPad2d):
-                pad = m.padding[0]
-                i += 1
-                continue
-            fused = (use_hip and isinstance(m, nn.Conv2d) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d)
-                     and isinstance(mods[i + 2], nn.ReLU) and m.bias is None and m.kernel_size == (3, 3) and m.stride == (1, 1)
-                     and m.padding[0] + pad == 1 and m.padding[1] + pad == 1 and m.dilation == (1, 1) and m.groups == 1
-                     and ops.conv2d_wgrad_supported(m.in_channels, m.out_channels, 3, 1, 1, dtype) and mods[i + 1].training
-                     and mods[i + 1].track_running_stats and mods[i + 1].affine)
-            if fused:
-                bn = mods[i + 1]
-                y = ops.Conv3x3Function.apply(x, m.weight)
-                mom = bn.momentum if bn.momentum is not None else 0.1
-                x = ops.BatchNormReluFunction.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, mom, True)
-                ops.bump_bn_counter(bn)
-                i, pad = i + 3, 0
-                continue
-            with torch.autocast("cuda", dtype=dtype, enabled=x.is_cuda, cache_enabled=False):
-                if pad:
-                    x = F.pad(x, (pad, pad, pad, pad))
-                    pad = 0
-                x = m(x)
-            i += 1
-        return x
-    def run_deblock(deb, x):
-        mods = list(deb.children())
-        m = mods[0]
-        if (use_hip and len(mods) == 3 and isinstance(m, nn.ConvTranspose2d) and isinstance(mods[1], nn.BatchNorm2d)
-                and isinstance(mods[2], nn.ReLU) and m.bias is None and m.kernel_size == (1, 1) and m.stride == (1, 1)
-                and m.padding == (0, 0) and m.output_padding == (0, 0) and m.groups == 1 and m.in_channels == 128
-                and m.out_channels == 128 and dtype in (torch.bfloat16, torch.float16) and mods[1].training
-                and mods[1].track_running_stats and mods[1].affine):
-            bn = mods[1]
-            y = ops.ConvTranspose1x1Function.apply(x, m.weight)
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            z = ops.BatchNormReluFunction.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, mom, True)
-            ops.bump_bn_counter(bn)
-            return z
-        with torch.autocast("cuda", dtype=dtype, enabled=x.is_cuda, cache_enabled=False):
-            return deb(x)
-    ups = []
-    for i, blk in enumerate(rpn.blocks):
-        x = run_block(blk, x)
-        if i - rpn._upsample_start_idx >= 0:
-            ups.append(run_deblock(rpn.deblocks[i - rpn._upsample_start_idx], x))
+    stages, ups = _mixed_trunk(rpn, x, dtype, use_hip)
+    x = stages[-1]
     heads = [(rpn.conv_box, rpn._box_code_size, "box_preds"), (rpn.conv_cls, rpn._num_class, "cls_preds")]
     if rpn._use_direction_classifier:
         heads.append((rpn.conv_dir_cls, rpn._num_direction_bins, "dir_cls_preds"))
@@ -920,6 +952,41 @@ def rpn_forward_mixed(rpn, x, dtype, loss_args=None, loss_terms=False):
         if rpn._use_direction_classifier:
             ret["dir_cls_preds"] = head(rpn.conv_dir_cls, rpn._num_direction_bins)
     return ret
+
+
+def multihead_forward_mixed(det, x, dtype):
+    """Training forward of a multi-head network's dense part (RPNNoHead trunk + large_head on "out" + small_head on the cropped
+    "stage0"; net_multi_head.py:121-176) with ``dtype`` activations over the fp32 master weights: the multi-head sibling of
+    :func:`rpn_forward_mixed`, on the same block walk.  The 128-channel stride-1 3x3 convolutions of the trunk take the hand-written
+    forward / dgrad / wgrad kernels; block 0 and the small head's tower (64-channel 3x3 convolutions, which
+    ops.conv2d_wgrad_supported does not cover; the tower's norms keep torch's eps 1e-5 / momentum 0.1), the strided convolutions,
+    the deblocks and the 1x1 heads run on torch under autocast.  Returns box_preds / cls_preds / dir_cls_preds concatenated large
+    head first, then small, flattened as DefaultHead.forward flattens them.  ``dtype`` = torch.float32 is the module graph's
+    arithmetic (CPU tests)."""
+    rpn = det.rpn
+    use_hip = RPN_TRAIN_BACKEND == "hip" and x.is_cuda
+    x = x.to(dtype)
+    if x.is_cuda:       # the kernels' layout; off the GPU the input keeps its own, so that float32 there IS the module graph's arithmetic
+        x = x.contiguous(memory_format=torch.channels_last)
+    stages, ups = _mixed_trunk(rpn, x, dtype, use_hip)
+    c = stage0_crop(stages[0].shape[2])
+    small_in = stages[0][:, :, c:-c, c:-c]          # a plain slice: autograd pads the gradient
+    tower = _mixed_block(det.small_head.net, small_in, dtype, use_hip)
+    with torch.autocast("cuda", dtype=dtype, enabled=x.is_cuda, cache_enabled=False):
+        out = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
+        parts = []
+        for head, feat in ((det.large_head, out), (det.small_head, tower)):
+            b, a = feat.shape[0], head._num_anchor_per_loc
+
+            def flat(conv, code):
+                y = conv(feat)
+                h, w = y.shape[2:]
+                return y.view(-1, a, code, h, w).permute(0, 1, 3, 4, 2).contiguous().view(b, -1, code)
+            p = {"box_preds": flat(head.conv_box, head._box_code_size), "cls_preds": flat(head.conv_cls, head._num_class)}
+            if head._use_direction_classifier:
+                p["dir_cls_preds"] = flat(head.conv_dir_cls, head._num_direction_bins)
+            parts.append(p)
+    return {k: torch.cat([p[k] for p in parts], dim=1) for k in parts[0]}
 
 
 def fold_conv_bn_(seq):
@@ -1676,12 +1743,8 @@ class SecondDetector(nn.Module):
                 return self.rpn(PillarBEV(voxel_features.to(dt), coors, batch_size, mfe.ny, mfe.nx, num_dev=num_active_dev))
             spatial = mfe(voxel_features if dt is None else voxel_features.to(dt), coors,
                           batch_size, channels_last=dt is not None, num_dev=num_active_dev)
-            if isinstance(self.rpn, RPNNoHead):          # the module graph of the multi-head network (net_multi_head.py:150-176)
-                out = self.rpn(spatial)
-                c = stage0_crop(out["stage0"].shape[2])
-                small = self.small_head(out["stage0"][:, :, c:-c, c:-c])
-                large = self.large_head(out["out"])
-                return {k: torch.cat([large[k], small[k]], dim=1) for k in large}
+            if isinstance(self.rpn, RPNNoHead):
+                return self.multi_head_dense(spatial)
             return self.rpn(spatial)
         if dt is not None:
             spatial = self.middle_feature_extractor(voxel_features.to(dt), coors, batch_size, channels_last=True,
@@ -1691,6 +1754,15 @@ class SecondDetector(nn.Module):
             spatial = self.middle_feature_extractor(voxel_features, coors, batch_size, num_active_dev=num_active_dev,
                                                     site_table=site_table, **pitch)
         return self.rpn(spatial)
+
+    def multi_head_dense(self, spatial):
+        """The module graph of the multi-head network behind the pseudo image (net_multi_head.py:150-176): trunk, small head on the
+        cropped stage 0, large head on the concatenated map; predictions concatenated large first."""
+        out = self.rpn(spatial)
+        c = stage0_crop(out["stage0"].shape[2])
+        small = self.small_head(out["stage0"][:, :, c:-c, c:-c])
+        large = self.large_head(out["out"])
+        return {k: torch.cat([large[k], small[k]], dim=1) for k in large}
 
     def _rpn_takes_rows(self):
         """The RPN consumes the sparse middle's rows + site map (SparseBEV) instead of the dense image: the 16-bit gathered first conv, or

@@ -787,52 +787,79 @@ class PFNTrainFunction(torch.autograd.Function):
     """PFNLayer in training mode (Linear(9, C) -> BatchNorm1d batch statistics -> ReLU -> max over the points; pointpillars.py:51-65)
     on sec_pfn_train_fwd / sec_pfn_train_bwd: the [P, T, C] activation tensor of the torch formulation never exists.  Gradients for
     linear.weight [C, 9], the BatchNorm weight and bias; the points get none (they are data).  running_mean / running_var are
-    updated in place like torch.nn.BatchNorm1d does."""
+    updated in place like torch.nn.BatchNorm1d does.  :class:`PFNRadiusTrainFunction` is the same code on the eight-entry row of
+    PillarFeatureNetRadius (sec_pfn_radius_train_fwd / _bwd, linear.weight [C, 8])."""
+    K = 9
+    FWD, BWD = "sec_pfn_train_fwd", "sec_pfn_train_bwd"
 
-    @staticmethod
-    def forward(ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom):
+    @classmethod
+    def _forward(cls, ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom):
         rt.require_gpu(voxels, num_points, coords, weight, gamma, beta)
         assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
         p, t, f = voxels.shape
-        c = weight.shape[0]
+        c, k = weight.shape[0], cls.K
+        assert weight.shape[1] == k, f"{cls.__name__}: linear.weight is {tuple(weight.shape)}, expected [C, {k}]"
         wt = weight.detach().float().t().contiguous()
         ga, be = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         dev = voxels.device
         out = torch.empty((p, c), dtype=torch.float32, device=dev)
         arg = torch.empty((p, c), dtype=torch.int8, device=dev)
-        stats = torch.empty((c * 11 + 9,), dtype=torch.float32, device=dev)
+        stats = torch.empty((c * (2 + k) + k,), dtype=torch.float32, device=dev)
         l = rt.lib()
         ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
         num_points, coords = num_points.int().contiguous(), coords.contiguous()
         vx, vy, xo, yo = [float(v) for v in geom]
-        rc = l.sec_pfn_train_fwd(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
+        rc = getattr(l, cls.FWD)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
                                  float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c, vx, vy, xo, yo,
                                  rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, "sec_pfn_train_fwd")
+        rt.check(rc, cls.FWD)
         ctx.save_for_backward(voxels, num_points, coords, wt, ga, stats, out, arg)
         ctx.geom = (vx, vy, xo, yo)
         ctx.dtypes = (weight.dtype, gamma.dtype, beta.dtype)
         return out
 
-    @staticmethod
-    def backward(ctx, grad_out):
+    @classmethod
+    def _backward(cls, ctx, grad_out):
         voxels, num_points, coords, wt, ga, stats, out, arg = ctx.saved_tensors
         p, t, f = voxels.shape
         c = wt.shape[1]
         dev = voxels.device
-        dwt = torch.empty((9, c), dtype=torch.float32, device=dev)
+        dwt = torch.empty((cls.K, c), dtype=torch.float32, device=dev)
         dga = torch.empty((c,), dtype=torch.float32, device=dev)
         dbe = torch.empty((c,), dtype=torch.float32, device=dev)
         l = rt.lib()
         ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
         g = grad_out.float().contiguous()
         vx, vy, xo, yo = ctx.geom
-        rc = l.sec_pfn_train_bwd(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
+        rc = getattr(l, cls.BWD)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
                                  vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt), rt.ptr(dga), rt.ptr(dbe),
                                  rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, "sec_pfn_train_bwd")
+        rt.check(rc, cls.BWD)
         wd, gd, bd = ctx.dtypes
         return (None, None, None, dwt.t().contiguous().to(wd), dga.to(gd), dbe.to(bd), None, None, None, None, None)
+
+    @staticmethod
+    def forward(ctx, *args):
+        return PFNTrainFunction._forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return PFNTrainFunction._backward(ctx, grad_out)
+
+
+class PFNRadiusTrainFunction(PFNTrainFunction):
+    """:class:`PFNTrainFunction` for PillarFeatureNetRadius (pointpillars.py:290-325 under train()): the decorated row is
+    [r, z, w, x - mean, y - mean, z - mean, x - centre, y - centre], linear.weight and its gradient are [C, 8]."""
+    K = 8
+    FWD, BWD = "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd"
+
+    @staticmethod
+    def forward(ctx, *args):
+        return PFNRadiusTrainFunction._forward(ctx, *args)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return PFNRadiusTrainFunction._backward(ctx, grad_out)
 
 
 @_traced("pfn_forward")

@@ -44,6 +44,7 @@ SYMBOLS = [
     "sec_region_similarity_f32", "sec_assign_targets_sim_f32", "sec_train_metrics_workspace_bytes", "sec_train_metrics_f32",
     "sec_pfn_radius_fwd", "sec_pfn_radius_fwd_slots", "sec_predict_select_segments", "sec_predict_decode_segments",
     "sec_predict_select_classes", "sec_predict_decode_classes", "sec_nms_sorted_items_f32", "sec_predict_finalize_classes",
+    "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd",
 ]
 
 _lib = None
@@ -164,6 +165,8 @@ def lib():
         l.sec_pfn_train_workspace_bytes.argtypes = [ci, ci]
         l.sec_pfn_train_fwd.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, cf, cf, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, sz, vp]
         l.sec_pfn_train_bwd.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        l.sec_pfn_radius_train_fwd.argtypes = l.sec_pfn_train_fwd.argtypes
+        l.sec_pfn_radius_train_bwd.argtypes = l.sec_pfn_train_bwd.argtypes
         l.sec_block_filter_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
         l.sec_voxel_block_filter_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp, sz, vp]
         l.sec_bias_act_nhwc.argtypes = [vp, vp, sz, ci, ci, ci, vp]

@@ -141,9 +141,7 @@ class DeviceTrainer:
         (the reference's default training precision); float16 adds dynamic loss scaling (``init_loss_scale``, see
         :meth:`_unscale_and_check`).  Thresholds default to the config's class_settings."""
         from . import models
-        if getattr(det, "heads", None):
-            raise NotImplementedError(f"DeviceTrainer: multi-head network {det.cfg['name']} (RPNNoHead + small_head / large_head) has no device "
-                                      "training step (train such a network through its own module graph)")
+        self._check_network(det)
         if getattr(det, "encoder", "SimpleVoxel") != "SimpleVoxel":
             # the training forward feeds the voxeliser's SimpleVoxel means straight to the middle; a network whose middle expects
             # another encoder's rows (car.lite, KITTI all.fhd) must not be trained on them
@@ -196,6 +194,25 @@ class DeviceTrainer:
         self.steps = 0
         self.last = {}
 
+    @staticmethod
+    def _check_network(det):
+        """Refuse what this class's forward cannot train (MultiHeadDeviceTrainer overrides it)."""
+        if getattr(det, "heads", None):
+            raise NotImplementedError(f"DeviceTrainer: multi-head network {det.cfg['name']} (RPNNoHead + small_head / large_head) has no device "
+                                      "training step in this class: use training.MultiHeadDeviceTrainer")
+
+    # the dense part of the network behind the pseudo image / the sparse middle: what MultiHeadDeviceTrainer replaces
+    def _dense_module(self):
+        """The module that owns every parameter and buffer of the dense segment (what _capture_rpn hands to make_graphed_callables)."""
+        return self.det.rpn
+
+    def _dense_forward_fp32(self, spatial):
+        return self.det.rpn(spatial)
+
+    def _dense_forward_mixed(self, mod, x, loss_args=None):
+        from .models import rpn_forward_mixed
+        return rpn_forward_mixed(mod, x, self.amp_dtype, loss_args=loss_args)
+
     def forward_loss(self, points, point_offsets, gt_boxes, gt_offsets, gt_classes=None):
         prev = ops.set_rulebook_numbering(self.det.rulebook_numbering)    # row order of the strided layers is internal here
         try:
@@ -243,7 +260,7 @@ class DeviceTrainer:
                 spatial = det.middle_feature_extractor(feats.float() if self.amp_dtype is None else feats, vox["coordinates"], batch,
                                                        channels_last=mixed)
                 if not mixed:
-                    preds = det.rpn(spatial)
+                    preds = self._dense_forward_fp32(spatial)
             if mixed:
                 # the same captured mixed-precision RPN segment as config 3: the 128 -> 128 3x3 layers of the second block on the
                 # hand-written kernels, the other widths on MIOpen, forward and backward replayed as two hipGraphs
@@ -290,17 +307,15 @@ class DeviceTrainer:
         and the eager step is HOST bound (541 launches at ~14 us each = 7.6 ms for 4.9 ms of kernels, profiles/r03_e_*): its
         forward and backward are therefore captured once as two hipGraphs (torch.cuda.make_graphed_callables over the same
         rpn_forward_mixed) and replayed.  ``self.graph_rpn = False``, a changed input shape or a failed capture fall back to eager."""
-        import os
-        from .models import rpn_forward_mixed
         x = spatial.to(self.amp_dtype).contiguous(memory_format=torch.channels_last)
         if self.static or not self.graph_rpn or not x.is_cuda:
-            return rpn_forward_mixed(self.det.rpn, x, self.amp_dtype, loss_args=loss_args)      # static: the WHOLE step is one graph (capture_step)
+            return self._dense_forward_mixed(self._dense_module(), x, loss_args=loss_args)      # static: the WHOLE step is one graph (capture_step)
         key = (tuple(x.shape), x.dtype)
         if self._graphed_rpn is None or self._graphed_rpn[0] != key:
             self._graphed_rpn = (key, self._capture_rpn(x))
         fn = self._graphed_rpn[1]
         if fn is None:
-            return rpn_forward_mixed(self.det.rpn, x, self.amp_dtype)
+            return self._dense_forward_mixed(self._dense_module(), x)
         if not x.requires_grad:
             x = x.detach().requires_grad_()
         box, cls, dirp = fn(x)
@@ -310,19 +325,18 @@ class DeviceTrainer:
         return out
 
     def _capture_rpn(self, x):
-        from .models import rpn_forward_mixed
-        rpn, dt = self.det.rpn, self.amp_dtype
+        dense, forward_mixed = self._dense_module(), self._dense_forward_mixed
 
         class _Mixed(torch.nn.Module):
             def __init__(self):
                 super().__init__()
-                self.rpn = rpn
+                self.dense = dense          # owns the segment's parameters: make_graphed_callables makes them inputs of the graphs
 
             def forward(self, inp):
-                p = rpn_forward_mixed(self.rpn, inp, dt)
+                p = forward_mixed(self.dense, inp)
                 return p["box_preds"], p["cls_preds"], p.get("dir_cls_preds", p["cls_preds"].new_zeros(0))
         # the warm-up iterations of the capture run BatchNorm in training mode: keep the running statistics out of it
-        saved = {k: v.clone() for k, v in rpn.state_dict().items() if "running_" in k or "num_batches" in k}
+        saved = {k: v.clone() for k, v in dense.state_dict().items() if "running_" in k or "num_batches" in k}
         ops._bn_counter_stack.append([[], False])   # throw-away frame: the three non-capturing warm-up iterations of make_graphed_callables
         try:                                    # must not queue num_batches_tracked increments into the step's deferred list
             sample = x.detach().clone().requires_grad_()
@@ -335,10 +349,10 @@ class DeviceTrainer:
         finally:
             ops._bn_counter_stack.pop()
         with torch.no_grad():
-            sd = rpn.state_dict()
+            sd = dense.state_dict()
             for k, v in saved.items():
                 sd[k].copy_(v)
-        for p in rpn.parameters():
+        for p in dense.parameters():
             p.grad = None
         return fn
 
@@ -515,3 +529,48 @@ class DeviceTrainer:
         names = ("loss", "cls_loss_reduced", "loc_loss_reduced", "dir_loss_reduced", "cls_pos_loss", "cls_neg_loss")
         v = self.last["out6"].tolist()
         return {k: (x if math.isfinite(x) else float("nan")) for k, x in zip(names, v)}
+
+
+class _MultiHeadDense(torch.nn.Module):
+    """The dense segment of a multi-head network as ONE module -- trunk and both heads -- so that a graphed callable built over
+    it takes all their parameters as inputs.  Carries the attributes models.multihead_forward_mixed reads from a detector.  (Not a
+    child of the detector: its parameters are the detector's own.)"""
+
+    def __init__(self, det):
+        super().__init__()
+        self.rpn, self.large_head, self.small_head = det.rpn, det.large_head, det.small_head
+
+
+class MultiHeadDeviceTrainer(DeviceTrainer):
+    """:class:`DeviceTrainer` for the multi-head networks (nuscenes/all.pp.mhead: PillarFeatureNetRadius, PointPillarsScatter,
+    RPNNoHead, large_head on "out" and small_head on the cropped "stage0"; net_multi_head.py:121-176).  The pillar layer trains on
+    sec_pfn_radius_train_fwd / _bwd; fp32 runs the module graph of SecondDetector._network_forward, 16-bit
+    models.multihead_forward_mixed (captured as two hipGraphs like the single-head segment, with the same eager fallbacks); targets
+    per anchor range (ops.assign_targets_per_class over models.anchor_class_ranges), the loss is ops.SecondLossFunction on the
+    concatenated predictions (the fused head loss has no form for these heads); bucket, FlatAdamW, clipping and fp16 loss scaling
+    are inherited."""
+
+    def __init__(self, det, *args, **kwargs):
+        super().__init__(det, *args, **kwargs)
+        self._dense = _MultiHeadDense(det)
+        covered = {id(p) for p in det.parameters()}
+        missing = [n for n, p in self._dense.named_parameters() if id(p) not in covered]
+        assert not missing, f"MultiHeadDeviceTrainer: parameters outside det.parameters(): {missing}"
+
+    @staticmethod
+    def _check_network(det):
+        if not getattr(det, "heads", None):
+            raise NotImplementedError(f"MultiHeadDeviceTrainer: {det.cfg['name']} is a single-head network (no `heads` in its config): "
+                                      "use training.DeviceTrainer")
+        if not det.pillars:
+            raise NotImplementedError(f"MultiHeadDeviceTrainer: {det.cfg['name']}: the multi-head step is built for the PointPillars front end")
+
+    def _dense_module(self):
+        return self._dense
+
+    def _dense_forward_fp32(self, spatial):
+        return self.det.multi_head_dense(spatial)
+
+    def _dense_forward_mixed(self, mod, x, loss_args=None):
+        from .models import multihead_forward_mixed
+        return multihead_forward_mixed(mod, x, self.amp_dtype)
