@@ -228,7 +228,9 @@ def test_bn_relu_on_sparse_rows_vs_torch(ops, c):
 def test_device_trainer_bf16_step_uses_the_hand_written_path_and_tracks_fp32():
     """One bf16 training step (sparse stack + RPN on the hand-written forward / dgrad / wgrad / BatchNorm kernels) next to the
     fp32 step of the same network on the same frames: the six loss scalars within a few percent, every parameter receives a finite
-    gradient, the op trace shows the hand-written RPN convolution (not MIOpen) in the step."""
+    gradient, the op trace shows the hand-written RPN convolution (not MIOpen) in the step.  ("Finite" is all this test asks of the
+    gradients: what they must EQUAL is asserted node by node, against fp64 on each node's own inputs, in
+    tests/test_gpu_train_step_audit.py -- DESIGN.md 9h-a.)"""
     from second_amd import ops, synthetic as syn
     from second_amd.models import SecondDetector, CAR_FHD
     from second_amd.training import DeviceTrainer
