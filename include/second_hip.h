@@ -419,6 +419,39 @@ int sec_conv2d_nhwc_tiles_tail(const void *x, int batch, int h, int w, const voi
                                const void *background_in, const void *packed_w1, const float *bias1, int relu1, const void *packed_w2,
                                const float *bias2, int cout2, void *y_heads, int dtype, void *stream);
 
+/* COVER lists: the live tiles of the fixed 8 x 16 grid are mostly edge tiles of small blobs that straddle a 16-column grid line.  A
+ * tile's origin is only (y0, x0) to the conv kernel, so per conv l, frame and 8-row band ty (rows 8 ty .. 8 ty + 7, clipped to h):
+ *   R = OR over the band's rows of "pixel within Chebyshev distance l + 1 of a site"; walk x from 0: at a set bit of R emit tile
+ *   (ty, x) and advance x by 16, otherwise advance x by 1.  A tile may stick out past the right edge (those columns are never stored).
+ * A band never lists more tiles than the grid has live ones there, so the shapes are those of sec_rpn_tile_live:
+ *   cover_order  [layers][batch][tiles] uint16  entry ty * w + x0; per frame in band, then x order; entries behind the count unspecified
+ *   cover_counts [layers][batch]
+ *   cover_cols   [layers][batch][ceil(h/8)][ceil(w/32)] words  C_l: bit x = some listed tile of the band holds column x (a superset of R)
+ *   cover_halo   [layers][2][batch][tiles][3] words, layers l >= 1 (slot 0 is not written): bit hx of word ry = conv l - 1 wrote pixel
+ *                x0 - 1 + hx of band ty - 1 + ry (from C_{l-1}; a position outside the image counts as written); half 0 follows
+ *                cover_order by rank, half 1 is indexed by GRID tile (x0 = 16 tx: read by a conv in the plain tile order).
+ * tile_order / live_counts (both or neither): the grid lists of sec_rpn_tile_live from the same bitmap.  workspace: as sec_rpn_tile_live.
+ * ceil(h/8) * w > 65535, more than 8 layers or sec_rpn_tile_cover_lds_bytes > 120 KB: SEC_E_UNSUPPORTED -- the caller keeps the grid lists.
+ * The consumers -- sec_conv2d_nhwc_gather_cover (layer 0), sec_conv2d_nhwc_tiles_cover (lazy, writes its listed tiles only),
+ * sec_conv2d_nhwc_tiles_tail_cover and sec_predict_select_cover / sec_predict_decode_cover -- take ONE layer's slices and are the
+ * grid-list entry points otherwise: the K loop, the accumulation order of every output pixel and so every result bit are the same.
+ * Above the list threshold a conv still takes every grid tile in the plain order.  second_amd.RPNInference selects the cover lists on
+ * the single-block lazy chain with lazy heads and the fused tail; SEC_RPN_TILE_COVER=0|1 forces the grid / the cover lists (A/B). */
+size_t sec_rpn_tile_cover_lds_bytes(int h, int w, int layers);
+int sec_rpn_tile_cover(const int *site_map, int batch, int h, int w, int layers, unsigned short *tile_order, int *live_counts,
+                       unsigned short *cover_order, int *cover_counts, unsigned *cover_cols, unsigned *cover_halo, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int sec_conv2d_nhwc_gather_cover(const void *features, long long feature_rows, const int *site_map, int batch, int h, int w,
+                                 const void *packed_weight, const float *bias, int cout, int relu, const unsigned short *cover_order,
+                                 const int *cover_counts, void *y, int dtype, void *stream);
+int sec_conv2d_nhwc_tiles_cover(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int cout,
+                                int relu, const unsigned short *cover_order, const int *cover_counts, const unsigned *cover_halo,
+                                const void *background_in, void *y, int dtype, void *stream);
+int sec_conv2d_nhwc_tiles_tail_cover(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int relu,
+                                     const unsigned short *cover_order, const int *cover_counts, const unsigned *cover_halo,
+                                     const void *background_in, const void *packed_w1, const float *bias1, int relu1,
+                                     const void *packed_w2, const float *bias2, int cout2, void *y_heads, int dtype, void *stream);
+
 /* Adjoint of sec_sparse_to_dense -- rows[i,:] = dense[indices[i]] -- i.e. the backward of
  * SparseConvTensor.dense() (upstream gets it from autograd through scatter_nd, spconv/__init__.py) and of
  * PointPillarsScatter (pointpillars.py:444-476) with stride_z = 0. */
@@ -540,11 +573,11 @@ int sec_conv2d_nhwc(const void *x, int batch, int h, int w, int cin, const void 
  *    SEC_CONV2D_FORM_PLAIN      sec_conv2d_nhwc
  *    SEC_CONV2D_FORM_INTO       sec_conv2d_nhwc_into
  *    SEC_CONV2D_FORM_ROWS       sec_conv2d_nhwc_rows
- *    SEC_CONV2D_FORM_TILES      sec_conv2d_nhwc_tiles, sec_conv2d_nhwc_tiles_lazy
- *    SEC_CONV2D_FORM_TAIL       sec_conv2d_nhwc_tiles_tail
+ *    SEC_CONV2D_FORM_TILES      sec_conv2d_nhwc_tiles, sec_conv2d_nhwc_tiles_lazy, sec_conv2d_nhwc_tiles_cover
+ *    SEC_CONV2D_FORM_TAIL       sec_conv2d_nhwc_tiles_tail, sec_conv2d_nhwc_tiles_tail_cover
  *    SEC_CONV2D_FORM_X3         sec_conv2d_nhwc_x3
  *    SEC_CONV2D_FORM_X3_TILES   sec_conv2d_nhwc_x3_tiles
- *    SEC_CONV2D_FORM_GATHER     sec_conv2d_nhwc_gather
+ *    SEC_CONV2D_FORM_GATHER     sec_conv2d_nhwc_gather, sec_conv2d_nhwc_gather_cover
  * The forms from TILES on exist for one layer (cin 128, 3x3 / stride 1 / pad 1; TAIL: cout 128; X3: SEC_BF16 planes) and answer ""
  * for any other.  Limits on arguments the query does not take (feature_rows, cout2) stay with the entry points.  The answer depends
  * on two switches read once per process: SEC_CONV2D_PATCH=0 (no strided / patch kernel on the plain form) and SEC_CONV2D_MFMA=32
@@ -746,6 +779,19 @@ int sec_predict_decode_lazy(const void *box, const int64_t *h_box_strides5, cons
                             const float *top_score, int rotate, float *decoded, float *dets, int *dir_label,
                             int dtype, const unsigned short *tile_live, const void *box_background,
                             const void *dir_background, void *stream);
+/* The lazy heads behind sec_conv2d_nhwc_tiles_tail_cover: an element (b, y, x) was written when bit x of cover_cols[b][y >> 3] is set
+ * (the LAST conv's slice of sec_rpn_tile_cover's cover_cols, [batch][ceil(h/8)][ceil(w/32)] words); any other element is read from
+ * *_background as above.  anchor_mask as in sec_predict_select_masked (NULL = none). */
+int sec_predict_select_cover(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc,
+                             int h, int w, int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx,
+                             float *top_score, int *top_label, int *counts, int dtype, const unsigned *cover_cols,
+                             const void *cls_background, const unsigned char *anchor_mask /* NULL = none */, void *stream);
+int sec_predict_decode_cover(const void *box, const int64_t *h_box_strides5, const void *dir,
+                             const int64_t *h_dir_strides5, int num_dir_bins, int batch, int anchors_per_loc,
+                             int h, int w, int k, const float *anchors, const int *top_idx,
+                             const float *top_score, int rotate, float *decoded, float *dets, int *dir_label,
+                             int dtype, const unsigned *cover_cols, const void *box_background, const void *dir_background,
+                             void *stream);
 /* Select / decode over SEVERAL head tensors of different map size (multi-head networks: nuscenes/all.pp.mhead predicts 12 anchors
  * per cell on a 100 x 100 map and 8 per cell on a 160 x 160 map).  1 <= num_segments <= 4; segment s has its own device pointer
  * cls[s] (host array of device pointers), strides h_*_strides5[5 s ..] = {sb, sa, sy, sx, sc} and h_dims3[3 s ..] = {A_s, H_s, W_s};

@@ -408,7 +408,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                                                             const T *__restrict__ bg_in = nullptr,
                                                             const T *__restrict__ x_lo = nullptr, T *__restrict__ y_lo = nullptr,
                                                             const T *__restrict__ background_lo = nullptr,
-                                                            const T *__restrict__ bg_in_lo = nullptr, ConvTailArgs tail = ConvTailArgs{}) {
+                                                            const T *__restrict__ bg_in_lo = nullptr, ConvTailArgs tail = ConvTailArgs{},
+                                                            const unsigned *__restrict__ halo3 = nullptr, int cover_w = 0) {
     static_assert(ROLL == 0 || ROLL == 2 || ROLL == 3, "main loops: 0 two-stage, 2 shared-row 32x32x16, 3 row-streamed 16x16x32");
     static_assert(!GATHER || (ROLL >= 2 && CIN == 128), "gather prologue: the shared-row loop on two 64-channel planes");
     static_assert(!TAIL || (ROLL >= 2 && CIN == 128 && TH == 8 && !GATHER && NSPLIT == 1 && !X3), "fused 1x1 tail: the lazy list form of the 128-channel conv");
@@ -439,10 +440,14 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
     const uint4 *x4 = reinterpret_cast<const uint4 *>(x);
     const uint4 *w4 = reinterpret_cast<const uint4 *>(wpk);
     const uint4 *zero16 = w4 + (size_t)9 * cin8 * p.cout;
-    auto issue_halo = [&](int tile) {
-        const int b = tile / (tiles_y * tiles_x);
-        const int trem = tile - b * tiles_y * tiles_x;
-        const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    // Frame and origin of this workgroup's tile (set once, below).  Grid tiles: (trem / tiles_x) * TH, (trem % tiles_x) * TW.  COVER lists
+    // (sec_rpn_tile_cover, cover_w = the map's width): an entry is band * w + x0 -- the tile starts at ANY column of its 8-row band, may
+    // stick out past the right edge (the ragged-edge guards of the loads and stores below) and nothing else in this kernel knows.
+    int tb = 0, ty0 = 0, tx0 = 0;
+    // lazy forms: bit hx of hm0 / hm1 / hm2 = the producer wrote halo pixel x0 - 1 + hx of the row above the tile / its own rows / the row below
+    unsigned hm0 = 0x3ffffu, hm1 = 0x3ffffu, hm2 = 0x3ffffu;
+    auto issue_halo = [&]() {
+        const int b = tb, y0 = ty0, x0 = tx0;
         for (int i = wv; i < (HENT + 63) / 64; i += 4) {
             const int e = i * 64 + lane;
             if (e >= HENT) break;
@@ -460,10 +465,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
     // part.  Here a piece's four halo pixels advance by 16 per step (hx += 16, wrapping at 18 into the next row), the image is a
     // buffer resource whose bounds check zero-fills the rows above and below it, and only the left / right border columns need
     // a select: ~14 VALU per piece, no branches.
-    auto issue_halo2 = [&](int tile, const T *xsrc) {
-        const int b = tile / (tiles_y * tiles_x);
-        const int trem = tile - b * tiles_y * tiles_x;
-        const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    auto issue_halo2 = [&](const T *xsrc) {
+        const int b = tb, y0 = ty0, x0 = tx0;
         const unsigned img_bytes = (unsigned)p.h * (unsigned)p.w * (CIN * 2u);
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(xsrc) + (size_t)b * p.h * p.w * CIN, 0, (int)img_bytes, 0x00020000);
         const int wvs = __builtin_amdgcn_readfirstlane(wv);
@@ -488,15 +491,14 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         }
     };
     // LAZY-BACKGROUND form of issue_halo2 (sec_conv2d_nhwc_tiles_lazy): the layer that produced `x` wrote only ITS live tiles; the
-    // others were never materialised.  `nmask` bit (ry * 3 + rx) says whether the tile holding the halo pixels of row class ry
-    // (0: the row above the tile, 1: its own rows, 2: the row below) and column class rx (left column / own columns / right column)
-    // was live there; pixels of a tile that was not come from `bg_in` = that layer's output for an EMPTY frame ([h][w][CIN]) at the
+    // others were never materialised.  Bit hx of hm0 / hm1 / hm2 (the row above the tile / its own rows / the row below) says whether
+    // the producer wrote halo column hx there -- from the grid lists' nine tile classes (`nmask` bit ry * 3 + rx: left column / own
+    // columns / right column, expanded below) or, per column, from the cover lists' halo masks (a producer's tiles then start at any
+    // x of the band); pixels that were not written come from `bg_in` = that layer's output for an EMPTY frame ([h][w][CIN]) at the
     // same position -- exactly what the producer's copy would have put into `x`.  Both sources share the byte
     // offsets; a lane issues ONE of the two DMAs (the lanes are the LDS slots, an inactive lane writes nothing).
-    auto issue_halo2_lazy = [&](int tile, unsigned nmask, const T *xsrc, const T *bgsrc) {
-        const int b = tile / (tiles_y * tiles_x);
-        const int trem = tile - b * tiles_y * tiles_x;
-        const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    auto issue_halo2_lazy = [&](const T *xsrc, const T *bgsrc) {
+        const int b = tb, y0 = ty0, x0 = tx0;
         const unsigned img_bytes = (unsigned)p.h * (unsigned)p.w * (CIN * 2u);
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(xsrc) + (size_t)b * p.h * p.w * CIN, 0, (int)img_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(bgsrc), 0, (int)img_bytes, 0x00020000);
@@ -513,8 +515,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                 unsigned off = rowoff + ((unsigned)hx << 8) + key;
                 const unsigned ix = (unsigned)(x0 - 1 + hx);
                 off = ix < (unsigned)p.w ? off : 0xfffffff0u;
-                const int ry = hy == 0 ? 0 : (hy == TH + 1 ? 2 : 1), rx = hx == 0 ? 0 : (hx == HW_ - 1 ? 2 : 1);
-                if ((nmask >> (ry * 3 + rx)) & 1u) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)&hal[i * 64], 16, off, 0, 0, 0);
+                const unsigned hm = hy == 0 ? hm0 : (hy == TH + 1 ? hm2 : hm1);
+                if ((hm >> hx) & 1u) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)&hal[i * 64], 16, off, 0, 0, 0);
                 else __builtin_amdgcn_raw_ptr_buffer_load_lds(ers, (lds_ptr_t)&hal[i * 64], 16, off, 0, 0, 0);
             }
             hx += 16;
@@ -527,11 +529,9 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
     // GATHER form of the same pieces: lane (pixel, slot) fetches chunk c = slot ^ key of its halo pixel = 16 bytes at
     // (c & 7) * 16 of the row of plane z = c >> 3; the row comes from the site map (0 = none -> out-of-range offset -> zeros).
     // Returns whether any of this lane's map entries names a row.
-    auto issue_halo_gather = [&](int tile) -> unsigned {
+    auto issue_halo_gather = [&]() -> unsigned {
         constexpr int NP = (HENT / 64 + 3) / 4;
-        const int b = tile / (tiles_y * tiles_x);
-        const int trem = tile - b * tiles_y * tiles_x;
-        const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+        const int b = tb, y0 = ty0, x0 = tx0;
         const unsigned plane = (unsigned)p.h * (unsigned)p.w;
         const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(site_map) + (size_t)b * 2 * plane, 0, (int)(plane * 8u), 0x00020000);
         const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(x), 0, (int)feat_bytes, 0x00020000);
@@ -607,7 +607,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
     // The LIVE tiles of all frames form one list (frame-major) that is cut into eight equal contiguous runs, one per XCD, so that a
     // dense frame does not leave its XCD working while the others idle; the workgroups behind them copy the background tiles.
     unsigned nmask = 0x1ffu;
-    bool listed = false;
+    bool listed = false, placed = false;
+    const bool lazy = nbr_masks != nullptr || halo3 != nullptr;
     {
         int n_live = 0;
         if (tile_order)
@@ -631,8 +632,16 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
             if (is_live) {
                 int f = 0;
                 while (item >= live_counts[f]) item -= live_counts[f++];
-                tile = f * tpf + tile_order[f * tpf + item];
-                if (nbr_masks) nmask = nbr_masks[f * tpf + item];        // rank-indexed half: loaded beside the tile index
+                const int ent = tile_order[f * tpf + item];
+                if (cover_w) {                                            // cover entry: band * w + x0
+                    const int band = ent / cover_w;
+                    tb = f; ty0 = band * TH; tx0 = ent - band * cover_w;
+                    placed = true;
+                    tile = f * tpf + item;                                // (any index below ntile: the origin is all that is used)
+                } else tile = f * tpf + ent;
+                // rank-indexed half of the masks: loaded beside the tile index
+                if (halo3) { const unsigned *m3 = halo3 + (size_t)(f * tpf + item) * 3; hm0 = m3[0]; hm1 = m3[1]; hm2 = m3[2]; }
+                else if (nbr_masks) nmask = nbr_masks[f * tpf + item];
             } else {
                 if (!background) return;                                  // lazy consumers: background tiles are never materialised
                 // A copying workgroup takes kCopyTiles background tiles, two at a time with all their loads in flight: one tile per
@@ -687,12 +696,26 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
         }
     }
     if (tile >= ntile) return;
-    if (nbr_masks && !listed) nmask = nbr_masks[ntile + tile];            // plain order: the tile-indexed half of the masks
+    if (!listed) {                                                        // plain order: the tile-indexed half of the masks
+        if (halo3) { const unsigned *m3 = halo3 + (size_t)(ntile + tile) * 3; hm0 = m3[0]; hm1 = m3[1]; hm2 = m3[2]; }
+        else if (nbr_masks) nmask = nbr_masks[ntile + tile];
+    }
+    if (nbr_masks && !halo3) {       // grid lists: the 3 x 3 tile classes as the same per-column masks (left column, own columns, right column)
+        hm0 = (nmask & 1u) | ((nmask >> 1 & 1u) * 0x1fffeu) | (nmask >> 2 & 1u) << 17;
+        hm1 = (nmask >> 3 & 1u) | ((nmask >> 4 & 1u) * 0x1fffeu) | (nmask >> 5 & 1u) << 17;
+        hm2 = (nmask >> 6 & 1u) | ((nmask >> 7 & 1u) * 0x1fffeu) | (nmask >> 8 & 1u) << 17;
+    }
+    if (!placed) {
+        tb = tile / (tiles_y * tiles_x);
+        const int trem = tile - tb * tiles_y * tiles_x;
+        ty0 = (trem / tiles_x) * TH;
+        tx0 = (trem % tiles_x) * TW;
+    }
 #ifdef SEC_CONV_TIMELINE
     long long *tl = g_timeline2;
     long long tl0 = 0, tl1 = 0, tl2 = 0;
     if (p.stagger == -1) return;                                   // experiment: dispatch cost of the grid alone
-    if (p.stagger == -2) { issue_halo(tile); __syncthreads(); return; }   // ... plus the halo DMA
+    if (p.stagger == -2) { issue_halo(); __syncthreads(); return; }   // ... plus the halo DMA
     if (p.stagger > 0) {       // experiment: desynchronise the three workgroups a CU holds
         const int slot = (blockIdx.x / 256) % 3;
         const long long until = clock64() + (long long)slot * p.stagger;
@@ -710,13 +733,11 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
 #endif
     unsigned gather_live = 1;
     if constexpr (GATHER) {
-        gather_live = issue_halo_gather(tile);
+        gather_live = issue_halo_gather();
         if (!gather_live) {
             // Empty tile (four of five on the KITTI-like clouds): every pixel is act(0 + bias).  Written straight from the bias -- no
             // weight prefetch, no LDS, no further barrier; bit-identical to the full epilogue on zero accumulators.
-            const int b = tile / (tiles_y * tiles_x);
-            const int trem = tile - b * tiles_y * tiles_x;
-            const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+            const int b = tb, y0 = ty0, x0 = tx0;
             const int px = tid >> 4, ch = tid & 15;
             float bv[8];
 #pragma unroll
@@ -735,17 +756,15 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
             return;
         }
     } else if constexpr (ROLL >= 2) {
-        if (nbr_masks) issue_halo2_lazy(tile, nmask, x, bg_in);
-        else issue_halo2(tile, x);
-    } else issue_halo(tile);
+        if (lazy) issue_halo2_lazy(x, bg_in);
+        else issue_halo2(x);
+    } else issue_halo();
 #ifdef SEC_CONV_TIMELINE
     long long tl_issue = 0, tl_eb1 = 0, tl_eb2 = 0;
     if (tl) tl_issue = clock64();
 #endif
     {
-        const int b = tile / (tiles_y * tiles_x);
-        const int trem = tile - b * tiles_y * tiles_x;
-        const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+        const int b = tb, y0 = ty0, x0 = tx0;
         uint4 bq[2][4];
         constexpr int RD = 8;
         uint4 br[RD];                               // ROLL: ring of B fragments, each loaded RD - 1 k-steps ahead of its use
@@ -839,8 +858,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                     if (X3 && pass > 0) {
                         if (pass == 2) {
                             __syncthreads();                    // every wave is done reading x_hi's halo
-                            if (nbr_masks) issue_halo2_lazy(tile, nmask, x_lo, bg_in_lo);
-                            else issue_halo2(tile, x_lo);
+                            if (lazy) issue_halo2_lazy(x_lo, bg_in_lo);
+                            else issue_halo2(x_lo);
                         }
                         prime_w(wp);
                         if (pass == 2) __syncthreads();         // x_lo's halo landed
@@ -915,8 +934,8 @@ __global__ __launch_bounds__(256, CIN == 128 ? 3 : 2) void k_conv2d_halo_reg(con
                     if (X3 && pass > 0) {
                         if (pass == 2) {
                             __syncthreads();                    // every wave is done reading x_hi's halo
-                            if (nbr_masks) issue_halo2_lazy(tile, nmask, x_lo, bg_in_lo);
-                            else issue_halo2(tile, x_lo);
+                            if (lazy) issue_halo2_lazy(x_lo, bg_in_lo);
+                            else issue_halo2(x_lo);
                         }
 #pragma unroll
                         for (int f = 0; f < RD - 1; ++f) br[f] = ld_b(wp + (f % 3) * 48 + (f / 3) * 2);
@@ -1217,6 +1236,8 @@ struct Conv2dExtra {
     void *y_lo = nullptr;
     const void *background_lo = nullptr, *bg_in_lo = nullptr;
     ConvTailArgs tail = ConvTailArgs{};             // tail form: the fused 1x1 pair
+    const unsigned *halo3 = nullptr;                // cover forms: tile_order / live_counts are one layer of sec_rpn_tile_cover (entries band * w + x0),
+    int cover = 0;                                  // ... halo3 its per-column halo masks (lazy consumers; none for the gathered first conv)
 };
 
 template <typename T, int CIN, int TH, int ROLL = 0, bool GATHER = false, int NSPLIT = 1, bool X3 = false, bool TAIL = false>
@@ -1235,7 +1256,7 @@ static int launch_conv2d_halo_reg(const void *x, const void *wpk, const float *b
     const int gx = per_xcd * 8;
     hipLaunchKernelGGL(fn, dim3(gx, p.cout / (128 / NSPLIT)), dim3(256), lds, st, (const T *)x, (const T *)wpk, bias, (T *)y, p, ty, tx, per_xcd,
                        e.site_map, e.feat_bytes, e.tile_order, e.live_counts, (const T *)e.background, e.nbr_masks, (const T *)e.bg_in,
-                       (const T *)e.x_lo, (T *)e.y_lo, (const T *)e.background_lo, (const T *)e.bg_in_lo, e.tail);
+                       (const T *)e.x_lo, (T *)e.y_lo, (const T *)e.background_lo, (const T *)e.bg_in_lo, e.tail, e.halo3, e.cover ? p.w : 0);
     return check_launch();
 }
 
@@ -2079,6 +2100,137 @@ __global__ __launch_bounds__(kTileLiveThreads) void k_rpn_tile_live(const unsign
     if (tid < layers) counts[tid * batch + b] = s_run[tid];
 }
 
+// ---- COVER lists: the reachable pixels of a band covered with tiles at free x ------------------------------------------------------
+// Most live tiles of the fixed grid are edge tiles of small blobs that straddle a 16-column grid line.  A tile's origin is just
+// (y0, x0) to k_conv2d_halo_reg, so per conv l, frame and 8-row band ty (rows 8 ty .. 8 ty + 7, clipped to h):
+//   R    = OR over the band's rows of "pixel within Chebyshev distance l + 1 of a site" (a w-bit row);
+//   walk = x from 0: at a set bit of R emit tile (ty, x) and advance by 16, otherwise advance by 1.
+// A tile may stick out past the right edge (the ragged-edge path of the conv).  Two tiles of a band start >= 16 apart, so their first
+// pixels lie in different grid tiles, each live: a band never lists more tiles than the grid has live ones there, and [B][tiles] holds.
+// Outputs, one workgroup per frame:
+//   order  [l][b][tiles] uint16  entries ty * w + x0, frame-major lists in band, then x order (entries behind the count: unspecified)
+//   counts [l][b]
+//   cols   [l][b][bands][wr] words: C_l = the union of the emitted tiles' columns clipped to w (a superset of R) -- what conv l WRITES
+//   halo   [l][2][b][tiles][3] words (l >= 1; l = 0 unwritten): bit hx of word ry = conv l - 1 wrote pixel x0 - 1 + hx of band
+//          ty - 1 + ry (from C_{l-1}; outside the image counts as written: padding either way).  Half 0 by rank in the list, half 1
+//          for every GRID tile (x0 = 16 tx): what a conv that falls back to the plain tile order reads.
+// LDS: the frame's bitmap [h][wr], then V / C [layers][bands][wr] and R [layers][bands][wr], then count / start [layers][bands].
+__device__ __forceinline__ unsigned cover_halo_bits(const unsigned *crow, int wr, int w, int x0) {
+    // 18 bits: columns x0 - 1 .. x0 + 16 of the row mask `crow` (NULL: a band outside the image), columns outside [0, w) count as set
+    if (!crow) return 0x3ffffu;
+    const int xs = x0 > 0 ? x0 - 1 : 0;                         // first column read; x0 = 0: column -1 is bit 0, set below
+    const int k = xs >> 5;
+    const unsigned long long two = (unsigned long long)crow[k] | (unsigned long long)(k + 1 < wr ? crow[k + 1] : 0u) << 32;
+    unsigned m = (unsigned)(two >> (xs & 31));
+    if (x0 == 0) m = m << 1 | 1u;
+    const int first_out = w - (x0 - 1);                         // halo column of image column w (>= 2: x0 <= w - 1)
+    if (first_out < 18) m |= 0x3ffffu << first_out;
+    return m & 0x3ffffu;
+}
+__global__ __launch_bounds__(kTileLiveThreads) void k_rpn_tile_cover(const unsigned *__restrict__ bits, int h, int w, int layers, int batch,
+                                                                      unsigned short *__restrict__ order, int *__restrict__ counts,
+                                                                      unsigned *__restrict__ cols, unsigned *__restrict__ halo) {
+    extern __shared__ unsigned tl_bits[];
+    constexpr int NT = kTileLiveThreads;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int wr = (w + 31) >> 5, words = h * wr;
+    const int bands = (h + 7) / 8, tx = (w + 15) / 16, tiles = bands * tx;
+    const int nrow = layers * bands;                 // (layer, band) rows
+    unsigned *s_c = tl_bits + words;                 // V (vertical OR), later C: [layers][bands][wr]
+    unsigned *s_r = s_c + nrow * wr;                 // R: [layers][bands][wr]
+    int *s_n = reinterpret_cast<int *>(s_r + nrow * wr);      // tiles of (layer, band), then their first rank
+    for (int i = tid; i < words; i += NT) tl_bits[i] = bits[(long long)b * words + i];
+    __syncthreads();
+    // V[l][ty][k] = OR of the bitmap rows within l + 1 of the band
+    for (int i = tid; i < nrow * wr; i += NT) {
+        const int k = i % wr, row = i / wr, ty = row % bands, K = row / bands + 1;
+        const int ylo = ty * 8 - K > 0 ? ty * 8 - K : 0, yhi = ty * 8 + 7 + K < h - 1 ? ty * 8 + 7 + K : h - 1;
+        unsigned v = 0u;
+        for (int yy = ylo; yy <= yhi; ++yy) v |= tl_bits[yy * wr + k];
+        s_c[i] = v;
+    }
+    __syncthreads();
+    // R = V dilated by l + 1 columns (l + 1 <= 8 < 32: the neighbouring words suffice), clipped to w
+    for (int i = tid; i < nrow * wr; i += NT) {
+        const int k = i % wr, row = i / wr, K = row / bands + 1;
+        const unsigned lo = k > 0 ? s_c[i - 1] : 0u, c = s_c[i], hi = k + 1 < wr ? s_c[i + 1] : 0u;
+        unsigned r = c;
+        for (int s = 1; s <= K; ++s) r |= (c << s) | (lo >> (32 - s)) | (c >> s) | (hi << (32 - s));
+        if (k == wr - 1 && (w & 31)) r &= (1u << (w & 31)) - 1u;
+        s_r[i] = r;
+    }
+    __syncthreads();
+    // the greedy walk of a (layer, band) row: f(x0) per tile, returns the number of tiles
+    auto walk = [&](int row, auto &&f) -> int {
+        const unsigned *r = s_r + row * wr;
+        int n = 0, x = 0;
+        while (x < w) {
+            unsigned wd = r[x >> 5] >> (x & 31);
+            if (!wd) { x = (x | 31) + 1; continue; }          // nothing left in this word
+            x += __ffs((int)wd) - 1;                           // next set bit (inside the same word, so below w: R is clipped)
+            f(x);
+            ++n;
+            x += 16;
+        }
+        return n;
+    };
+    for (int row = tid; row < nrow; row += NT) s_n[row] = walk(row, [](int) {});
+    __syncthreads();
+    if (tid < layers) {                               // exclusive prefix over the bands of a layer
+        int run = 0;
+        for (int ty = 0; ty < bands; ++ty) {
+            const int n = s_n[tid * bands + ty];
+            s_n[tid * bands + ty] = run;
+            run += n;
+        }
+        counts[tid * batch + b] = run;
+    }
+    for (int i = tid; i < nrow * wr; i += NT) s_c[i] = 0u;       // V is spent: C from here on
+    __syncthreads();
+    for (int row = tid; row < nrow; row += NT) {
+        const int l = row / bands, ty = row - l * bands;
+        unsigned short *ord = order + ((long long)l * batch + b) * tiles + s_n[row];
+        unsigned *c = s_c + row * wr;
+        int n = 0;
+        walk(row, [&](int x0) {
+            ord[n++] = (unsigned short)(ty * w + x0);
+            const int x1 = x0 + 15 < w - 1 ? x0 + 15 : w - 1;
+            for (int k = x0 >> 5; k <= x1 >> 5; ++k) {
+                const int a = x0 > 32 * k ? x0 - 32 * k : 0, e = x1 < 32 * k + 31 ? x1 - 32 * k : 31;     // bits a .. e of word k
+                c[k] |= (0xffffffffu >> (31 - e)) & (0xffffffffu << a);
+            }
+        });
+    }
+    __syncthreads();
+    for (int i = tid; i < nrow * wr; i += NT) {
+        const int row = i / wr, l = row / bands;
+        cols[((long long)l * batch + b) * bands * wr + (i - l * bands * wr)] = s_c[i];
+    }
+    // halo masks of the layers l >= 1 from C_{l-1}: per listed tile (the walk again), then per grid tile
+    for (int row = tid + bands; row < nrow; row += NT) {
+        const int l = row / bands, ty = row - l * bands;
+        const unsigned *cp = s_c + (l - 1) * bands * wr;
+        unsigned *hm = halo + ((((long long)l * 2) * batch + b) * tiles + s_n[row]) * 3;
+        int n = 0;
+        walk(row, [&](int x0) {
+            for (int ry = 0; ry < 3; ++ry) {
+                const int yb = ty - 1 + ry;
+                hm[n * 3 + ry] = cover_halo_bits(yb >= 0 && yb < bands ? cp + yb * wr : nullptr, wr, w, x0);
+            }
+            ++n;
+        });
+    }
+    for (int i = tid; i < (layers - 1) * tiles; i += NT) {
+        const int l = 1 + i / tiles, t = i % tiles, ty = t / tx, x0 = (t - ty * tx) * 16;
+        const unsigned *cp = s_c + (l - 1) * bands * wr;
+        unsigned *hm = halo + ((((long long)l * 2 + 1) * batch + b) * tiles + t) * 3;
+        for (int ry = 0; ry < 3; ++ry) {
+            const int yb = ty - 1 + ry;
+            hm[ry] = cover_halo_bits(yb >= 0 && yb < bands ? cp + yb * wr : nullptr, wr, w, x0);
+        }
+    }
+}
+
 }  // namespace sec
 
 using namespace sec;
@@ -2120,15 +2272,54 @@ SEC_API int sec_rpn_tile_live_masks(const int *site_map, int batch, int h, int w
     return rpn_tile_live_impl(site_map, batch, h, w, layers, tile_order, live_counts, nbr_masks, workspace, workspace_bytes, stream);
 }
 
+SEC_API size_t sec_rpn_tile_cover_lds_bytes(int h, int w, int layers) {
+    if (h <= 0 || w <= 0 || layers <= 0) return 0;
+    const size_t wr = (size_t)(w + 31) / 32, bands = (size_t)(h + 7) / 8;
+    return ((size_t)h * wr + 2 * (size_t)layers * bands * wr + (size_t)layers * bands) * 4;
+}
+
+// The cover lists of sec_rpn_tile_cover are usable when an entry band * w + x0 fits 16 bits and the kernel's tables fit the LDS.
+static bool rpn_tile_cover_fits(int h, int w, int layers) {
+    return (long long)((h + 7) / 8) * w <= 65535 && layers <= kTileLiveMaxLayers && sec_rpn_tile_cover_lds_bytes(h, w, layers) <= 120 * 1024;
+}
+
+SEC_API int sec_rpn_tile_cover(const int *site_map, int batch, int h, int w, int layers, unsigned short *tile_order, int *live_counts,
+                               unsigned short *cover_order, int *cover_counts, unsigned *cover_cols, unsigned *cover_halo, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    if (!site_map || !cover_order || !cover_counts || !cover_cols || !cover_halo || !workspace || batch <= 0 || h <= 0 || w <= 0 || layers <= 0 ||
+        ((tile_order != nullptr) != (live_counts != nullptr)))
+        return SEC_E_INVALID;
+    if (!rpn_tile_cover_fits(h, w, layers)) return SEC_E_UNSUPPORTED;       // the caller keeps the grid lists
+    if (tile_order) {       // the grid lists of sec_rpn_tile_live beside them, from the same bitmap
+        const int rc = rpn_tile_live_impl(site_map, batch, h, w, layers, tile_order, live_counts, nullptr, workspace, workspace_bytes, stream);
+        if (rc != SEC_OK) return rc;
+    } else {
+        if (workspace_bytes < sec_rpn_tile_live_workspace_bytes(batch, h, w)) return SEC_E_WORKSPACE;
+        const int words = h * ((w + 31) / 32);
+        hipLaunchKernelGGL(k_bev_bitmap, dim3(div_up((long long)batch * words, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, site_map, h, w, batch,
+                           (unsigned *)workspace);
+    }
+    static bool configured = false;
+    if (!configured) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rpn_tile_cover), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
+        configured = true;
+    }
+    hipLaunchKernelGGL(k_rpn_tile_cover, dim3(batch), dim3(kTileLiveThreads), sec_rpn_tile_cover_lds_bytes(h, w, layers), (hipStream_t)stream,
+                       (const unsigned *)workspace, h, w, layers, batch, cover_order, cover_counts, cover_cols, cover_halo);
+    return check_launch();
+}
+
 static int conv2d_tiles_impl(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int cout, int relu,
                              const unsigned short *tile_order, const int *live_counts, const void *background,
-                             const unsigned short *nbr_masks, const void *background_in, void *y, int dtype, void *stream) {
+                             const unsigned short *nbr_masks, const void *background_in, void *y, int dtype, void *stream,
+                             const unsigned *cover_halo = nullptr) {
     if (!x || !packed_weight || !y || batch <= 0 || h <= 0 || w <= 0 || (tile_order && !live_counts)) return SEC_E_INVALID;
     apply_list_threshold_env();
     Conv2dParams p;
     if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
     Conv2dExtra e;
     e.tile_order = tile_order; e.live_counts = live_counts; e.background = background; e.nbr_masks = nbr_masks; e.bg_in = background_in;
+    e.halo3 = cover_halo; e.cover = cover_halo != nullptr;
     return launch_conv2d_plan(conv2d_fwd_decide(p, kFormTiles, dtype), dtype, x, packed_weight, bias, y, p, cout, e, stream);
 }
 
@@ -2148,12 +2339,48 @@ SEC_API int sec_conv2d_nhwc_tiles_lazy(const void *x, int batch, int h, int w, c
                              dtype, stream);
 }
 
+// sec_conv2d_nhwc_tiles_lazy on one layer (>= 1) of the COVER lists of sec_rpn_tile_cover: cover_order / cover_counts / cover_halo are that
+// layer's slices ([B][tiles], [B], [2][B][tiles][3]).  Writes the listed tiles only (all tiles above the list threshold).
+SEC_API int sec_conv2d_nhwc_tiles_cover(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int cout,
+                                        int relu, const unsigned short *cover_order, const int *cover_counts, const unsigned *cover_halo,
+                                        const void *background_in, void *y, int dtype, void *stream) {
+    if (!cover_order || !cover_halo || !background_in) return SEC_E_INVALID;
+    if ((long long)((h + 7) / 8) * w > 65535) return SEC_E_UNSUPPORTED;
+    return conv2d_tiles_impl(x, batch, h, w, packed_weight, bias, cout, relu, cover_order, cover_counts, nullptr, nullptr, background_in, y, dtype,
+                             stream, cover_halo);
+}
+
+static int conv2d_tiles_tail_impl(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int relu,
+                                  const unsigned short *tile_order, const int *live_counts, const unsigned short *nbr_masks,
+                                  const void *background_in, const void *packed_w1, const float *bias1, int relu1, const void *packed_w2,
+                                  const float *bias2, int cout2, void *y_heads, int dtype, void *stream, const unsigned *cover_halo);
+
+// sec_conv2d_nhwc_tiles_tail on the last layer of the cover lists; the lazy heads behind it read cover_cols (sec_predict_select_cover).
+SEC_API int sec_conv2d_nhwc_tiles_tail_cover(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int relu,
+                                             const unsigned short *cover_order, const int *cover_counts, const unsigned *cover_halo,
+                                             const void *background_in, const void *packed_w1, const float *bias1, int relu1,
+                                             const void *packed_w2, const float *bias2, int cout2, void *y_heads, int dtype, void *stream) {
+    if (!cover_halo) return SEC_E_INVALID;
+    if ((long long)((h + 7) / 8) * w > 65535) return SEC_E_UNSUPPORTED;
+    return conv2d_tiles_tail_impl(x, batch, h, w, packed_weight, bias, relu, cover_order, cover_counts, nullptr, background_in, packed_w1, bias1,
+                                  relu1, packed_w2, bias2, cout2, y_heads, dtype, stream, cover_halo);
+}
+
 // The last 3x3 conv of a single-block RPN with its 1x1 tail (deblock + merged heads) in the epilogue: see k_conv2d_halo_reg<..., TAIL>.
 SEC_API int sec_conv2d_nhwc_tiles_tail(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int relu,
                                        const unsigned short *tile_order, const int *live_counts, const unsigned short *nbr_masks,
                                        const void *background_in, const void *packed_w1, const float *bias1, int relu1, const void *packed_w2,
                                        const float *bias2, int cout2, void *y_heads, int dtype, void *stream) {
-    if (!x || !packed_weight || !tile_order || !live_counts || !nbr_masks || !background_in || !packed_w1 || !bias1 || !packed_w2 || !y_heads ||
+    if (!nbr_masks) return SEC_E_INVALID;
+    return conv2d_tiles_tail_impl(x, batch, h, w, packed_weight, bias, relu, tile_order, live_counts, nbr_masks, background_in, packed_w1, bias1,
+                                  relu1, packed_w2, bias2, cout2, y_heads, dtype, stream, nullptr);
+}
+
+static int conv2d_tiles_tail_impl(const void *x, int batch, int h, int w, const void *packed_weight, const float *bias, int relu,
+                                  const unsigned short *tile_order, const int *live_counts, const unsigned short *nbr_masks,
+                                  const void *background_in, const void *packed_w1, const float *bias1, int relu1, const void *packed_w2,
+                                  const float *bias2, int cout2, void *y_heads, int dtype, void *stream, const unsigned *cover_halo) {
+    if (!x || !packed_weight || !tile_order || !live_counts || (!nbr_masks && !cover_halo) || !background_in || !packed_w1 || !bias1 || !packed_w2 || !y_heads ||
         batch <= 0 || h <= 0 || w <= 0)
         return SEC_E_INVALID;
     if (cout2 != 64) return SEC_E_UNSUPPORTED;
@@ -2162,6 +2389,7 @@ SEC_API int sec_conv2d_nhwc_tiles_tail(const void *x, int batch, int h, int w, c
     if (!conv2d_params(p, batch, h, w, 128, 128, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
     Conv2dExtra e;
     e.tile_order = tile_order; e.live_counts = live_counts; e.nbr_masks = nbr_masks; e.bg_in = background_in;
+    e.halo3 = cover_halo; e.cover = cover_halo != nullptr;
     e.tail = ConvTailArgs{packed_w1, packed_w2, bias1, bias2, y_heads, relu1 & 1};
     // y of the conv itself does not exist: the kernel's `y` is never dereferenced on the TAIL path (background == NULL: lazy form)
     return launch_conv2d_plan(conv2d_fwd_decide(p, kFormTail, dtype), dtype, x, packed_weight, bias, nullptr, p, 128, e, stream);
@@ -2295,6 +2523,24 @@ SEC_API int sec_conv2d_nhwc_gather(const void *features, long long feature_rows,
     Conv2dExtra e;
     e.site_map = site_map; e.feat_bytes = (unsigned)(feature_rows * 128);
     e.tile_order = tile_order; e.live_counts = live_counts; e.background = background;
+    return launch_conv2d_plan(conv2d_fwd_decide(p, kFormGather, dtype), dtype, features, packed_weight, bias, y, p, cout, e, stream);
+}
+
+// sec_conv2d_nhwc_gather on layer 0 of the COVER lists of sec_rpn_tile_cover: the listed tiles only (every consumer is lazy and reads
+// that layer's coverage through its halo masks).
+SEC_API int sec_conv2d_nhwc_gather_cover(const void *features, long long feature_rows, const int *site_map, int batch, int h, int w,
+                                         const void *packed_weight, const float *bias, int cout, int relu, const unsigned short *cover_order,
+                                         const int *cover_counts, void *y, int dtype, void *stream) {
+    if (!site_map || !packed_weight || !y || !cover_order || !cover_counts || batch <= 0 || h <= 0 || w <= 0 || feature_rows < 0 ||
+        (!features && feature_rows > 0))
+        return SEC_E_INVALID;
+    if (feature_rows * 128 >= (1ll << 31) || (long long)((h + 7) / 8) * w > 65535) return SEC_E_UNSUPPORTED;
+    apply_list_threshold_env();
+    Conv2dParams p;
+    if (!conv2d_params(p, batch, h, w, 128, cout, 3, 1, 1, relu & 1)) return SEC_E_INVALID;
+    Conv2dExtra e;
+    e.site_map = site_map; e.feat_bytes = (unsigned)(feature_rows * 128);
+    e.tile_order = cover_order; e.live_counts = cover_counts; e.cover = 1;
     return launch_conv2d_plan(conv2d_fwd_decide(p, kFormGather, dtype), dtype, features, packed_weight, bias, y, p, cout, e, stream);
 }
 

@@ -30,11 +30,18 @@ struct View5 {          // element strides of a [B, A, H, W, C] view
     // anchor-area mask (sec_predict_select_masked): amask[b * A*H*W + n] == 0 takes anchor n of frame b out of the selection -- its key
     // is the smallest one (0: below every logit's, the key of the slots past a frame's end), whose score never reaches a threshold > 0
     const unsigned char *amask;
+    // COVER form of the lazy heads (sec_predict_select_cover / _decode_cover): the producer's tiles start at any column of their 8-row
+    // band (sec_rpn_tile_cover), so "written" is a bit per pixel column and band: `cover` [B][bands][cwr] words, bit x & 31 of word x >> 5
+    const unsigned *cover;
+    int cwr, cbands;
 };
 __device__ __forceinline__ bool anchor_kept(const View5 &v, long long slot) { return !v.amask || v.amask[slot] != 0; }
 // element offset of frame b as seen from pixel (y, x): the frame itself, or the empty frame's map for a tile that was never written
 __device__ __forceinline__ long long frame_off(const View5 &v, int b, int y, int x) {
-    if (v.live) {
+    if (v.cover) {
+        const unsigned m = v.cover[((long long)b * v.cbands + (y >> 3)) * v.cwr + (x >> 5)];
+        if (!((m >> (x & 31)) & 1u)) return v.bg;
+    } else if (v.live) {
         const unsigned m = v.live[(long long)b * v.tpf + (y >> 3) * v.tiles_x + (x >> 4)];
         if (!((m >> 4) & 1u)) return v.bg;
     }
@@ -1168,11 +1175,17 @@ __global__ __launch_bounds__(kBlock) void k_predict_finalize_classes(const float
 
 using namespace sec;
 
-static View5 mkview(const int64_t *s) { return View5{s[0], s[1], s[2], s[3], s[4], 0, nullptr, 0, 0, nullptr}; }
+static View5 mkview(const int64_t *s) { return View5{s[0], s[1], s[2], s[3], s[4], 0, nullptr, 0, 0, nullptr, nullptr, 0, 0}; }
 // the lazy form of a view: `base` is the view's pointer, `background` the same element of the empty frame's map
-static View5 mkview_lazy(const int64_t *s, const void *base, const void *background, const unsigned short *tile_live, int h, int w, int elt) {
+static View5 mkview_lazy(const int64_t *s, const void *base, const void *background, const unsigned short *tile_live, int h, int w, int elt,
+                         const unsigned *cover_cols = nullptr) {
     View5 v = mkview(s);
-    if (tile_live && background) {
+    if (cover_cols && background) {
+        v.bg = (long long)((const char *)background - (const char *)base) / elt;
+        v.cover = cover_cols;
+        v.cwr = (w + 31) / 32;
+        v.cbands = (h + 7) / 8;
+    } else if (tile_live && background) {
         v.bg = (long long)((const char *)background - (const char *)base) / elt;
         v.live = tile_live;
         v.tiles_x = (w + 15) / 16;
@@ -1210,16 +1223,16 @@ static int predict_select_launch(const void *cls, const V &v, const PredGeom &g,
 static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                int *top_label, int *counts, int dtype, void *stream, const unsigned short *tile_live,
-                               const void *cls_background, const unsigned char *anchor_mask) {
+                               const void *cls_background, const unsigned char *anchor_mask, const unsigned *cover_cols = nullptr) {
     if (!key_scratch) return SEC_E_WORKSPACE;
     if (!cls || !h_cls_strides5 || batch <= 0 || anchors_per_loc <= 0 || h <= 0 || w <= 0 || num_class <= 0 || k <= 0 ||
         k > kSelThreads || !top_idx || !top_score || !top_label || !counts)
         return SEC_E_INVALID;
-    if ((tile_live != nullptr) != (cls_background != nullptr) || dtype < SEC_F32 || dtype > SEC_BF16) return SEC_E_INVALID;
+    if ((tile_live != nullptr || cover_cols != nullptr) != (cls_background != nullptr) || (tile_live && cover_cols) || dtype < SEC_F32 || dtype > SEC_BF16) return SEC_E_INVALID;
     // a masked-out anchor's key stands for no score; with a threshold <= 0 (no shipped config has one) it would be counted
     if (anchor_mask && !(score_thr > 0.0f)) return SEC_E_UNSUPPORTED;
     PredGeom g{batch, anchors_per_loc, h, w, num_class};
-    View5 v = mkview_lazy(h_cls_strides5, cls, cls_background, tile_live, h, w, elt_bytes(dtype));
+    View5 v = mkview_lazy(h_cls_strides5, cls, cls_background, tile_live, h, w, elt_bytes(dtype), cover_cols);
     v.amask = anchor_mask;
     return predict_select_launch(cls, v, g, k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, stream);
 }
@@ -1345,13 +1358,15 @@ static int predict_decode_impl(const void *box, const int64_t *h_box_strides5, c
                                int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
                                const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
                                int *dir_label, int dtype, void *stream, const unsigned short *tile_live, const void *box_background,
-                               const void *dir_background) {
+                               const void *dir_background, const unsigned *cover_cols = nullptr) {
     if (!box || !h_box_strides5 || batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label)
         return SEC_E_INVALID;
-    if (dtype < SEC_F32 || dtype > SEC_BF16 || (tile_live && (!box_background || (dir && !dir_background)))) return SEC_E_INVALID;
+    if (dtype < SEC_F32 || dtype > SEC_BF16 || ((tile_live || cover_cols) && (!box_background || (dir && !dir_background))) ||
+        (tile_live && cover_cols))
+        return SEC_E_INVALID;
     PredGeom g{batch, anchors_per_loc, h, w, 1};
-    View5 vb = mkview_lazy(h_box_strides5, box, box_background, tile_live, h, w, elt_bytes(dtype));
-    View5 vd = dir ? mkview_lazy(h_dir_strides5, dir, dir_background, tile_live, h, w, elt_bytes(dtype)) : View5{0, 0, 0, 0, 0, 0, nullptr, 0, 0};
+    View5 vb = mkview_lazy(h_box_strides5, box, box_background, tile_live, h, w, elt_bytes(dtype), cover_cols);
+    View5 vd = dir ? mkview_lazy(h_dir_strides5, dir, dir_background, tile_live, h, w, elt_bytes(dtype), cover_cols) : View5{};
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up((long long)batch * k, kBlock));
 #define SEC_DEC(T) hipLaunchKernelGGL(k_predict_decode<T>, grid, dim3(kBlock), 0, st, (const T *)box, vb, (const T *)dir, vd, \
@@ -1378,6 +1393,27 @@ SEC_API int sec_predict_decode_lazy(const void *box, const int64_t *h_box_stride
     if (!tile_live || !box_background) return SEC_E_INVALID;
     return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, k, anchors, top_idx,
                                top_score, rotate, decoded, dets, dir_label, dtype, stream, tile_live, box_background, dir_background);
+}
+
+// The lazy heads behind a COVER-form producer (sec_conv2d_nhwc_tiles_tail_cover): an element was written when bit x of
+// cover_cols[b][y >> 3] is set (the last conv's coverage masks of sec_rpn_tile_cover, [B][ceil(h / 8)][ceil(w / 32)] words); every other
+// element is read from the empty frame's map.  anchor_mask may be NULL (sec_predict_select_masked otherwise).
+SEC_API int sec_predict_select_cover(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
+                                     int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
+                                     int *top_label, int *counts, int dtype, const unsigned *cover_cols, const void *cls_background,
+                                     const unsigned char *anchor_mask, void *stream) {
+    if (!cover_cols || !cls_background) return SEC_E_INVALID;
+    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
+                               top_label, counts, dtype, stream, nullptr, cls_background, anchor_mask, cover_cols);
+}
+SEC_API int sec_predict_decode_cover(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                                     int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
+                                     const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
+                                     int *dir_label, int dtype, const unsigned *cover_cols, const void *box_background,
+                                     const void *dir_background, void *stream) {
+    if (!cover_cols || !box_background) return SEC_E_INVALID;
+    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, k, anchors, top_idx,
+                               top_score, rotate, decoded, dets, dir_label, dtype, stream, nullptr, box_background, dir_background, cover_cols);
 }
 
 SEC_API int sec_predict_finalize(const float *decoded, const float *top_score, const int *top_label, const int *dir_label,

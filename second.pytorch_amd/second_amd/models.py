@@ -638,12 +638,13 @@ class SparseBEV:
             return ops.sparse_site_map_sorted(tbl[1][1], self.indices.shape[0], self.batch_size, self.spatial_shape, num_dev=self.num_dev)
         return ops.sparse_site_map(self.indices, self.batch_size, self.spatial_shape, num_dev=self.num_dev)
 
-    def tile_lists(self, layers, masks=False):
-        """(order, counts[, nbr_masks]) of ops.rpn_tile_live for the first ``layers`` RPN convs, computed once per tensor: whoever asks
+    def tile_lists(self, layers, masks=False, cover=False):
+        """(order, counts[, nbr_masks | TileCover]) of ops.rpn_tile_live for the first ``layers`` RPN convs, computed once per tensor: whoever asks
         first decides where the launch sits (the sparse segment of a staged capture, so that it stays out of the serialised RPN segment)."""
         t = getattr(self, "_tile_lists", None)
-        if t is None or t[0] != (layers, bool(masks)):
-            t = self._tile_lists = ((layers, bool(masks)), ops.rpn_tile_live(self.site_map(), layers, masks=bool(masks)))
+        key = (layers, bool(masks), bool(cover))
+        if t is None or t[0] != key:
+            t = self._tile_lists = (key, ops.rpn_tile_live(self.site_map(), layers, masks=bool(masks), cover=bool(cover)))
         return t[1]
 
     def dense(self):
@@ -1235,6 +1236,14 @@ class RPNInference(nn.Module):
         self.fused_tail = True
         self.last_live_counts = None       # [convs, B] int32 on the device: live tiles per conv and frame of the last forward (bench / tests)
         self.last_tiles_per_frame = None   # tiles of one frame's map in that forward
+        # tile_cover: the single-block lazy chain with lazy heads and the fused tail follows COVER lists -- per 8-row band the reachable pixels
+        # covered by tiles at free x (sec_rpn_tile_cover: 12 % fewer tiles than the fixed grid has live ones on the KITTI-like clouds);
+        # every other path keeps the grid lists.  preds["lazy_heads"][0] is then the last conv's coverage (int32 words, a bit per pixel
+        # column and band) instead of the per-tile flags, and the head tensor has holes INSIDE grid tiles: off for direct callers, set by
+        # SecondDetector.lazy_heads(cover=True) around forwards whose preds go straight to the fused predict.  SEC_RPN_TILE_COVER=0|1
+        # overrides (A/B, bit-identical detections).  last_live_counts stays the GRID's.
+        self.tile_cover = False
+        self.last_cover_counts = None      # [convs, B] int32: tiles per conv and frame of the cover lists, when the last forward followed them
         self._empty_maps = {}
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._repack())
         # (the fp32 forms: the same live-tile machinery on the split-operand / fp32-MFMA convs, always lazy)
@@ -1419,7 +1428,7 @@ class RPNInference(nn.Module):
                 x = x.dense()
         else:
             pillars = None
-        live = nbr = fused_heads = stage0 = None
+        live = nbr = cover = fused_heads = stage0 = None
         catbuf, coff = None, 0
         for kind, i in self.plan:
             if self.stage0_layer is not None and i == self.stage0_layer + 1:
@@ -1434,16 +1443,34 @@ class RPNInference(nn.Module):
                 if self.background_convs and self.skip_background:
                     empty = self.empty_frame_maps(sm.shape[2], sm.shape[3])
                     lazy = self.lazy_background and self.background_convs >= 2
-                    if lazy:
-                        live, self.last_live_counts, nbr = gather.tile_lists(self.list_layers(), masks=True)
+                    layers_, masks_, cover_ = self.tile_list_request(sm.shape[2], sm.shape[3])
+                    if cover_:
+                        live, self.last_live_counts, cover = gather.tile_lists(layers_, cover=True)
+                        self.last_cover_counts = cover.counts
+                    elif lazy:
+                        live, self.last_live_counts, nbr = gather.tile_lists(layers_, masks=True)
                     else:
-                        (live, self.last_live_counts), nbr = gather.tile_lists(self.background_convs), None
+                        (live, self.last_live_counts), nbr = gather.tile_lists(layers_), None
                     self.last_tiles_per_frame = int(live.shape[-1])
-                    x = ops.conv2d_nhwc_gather(gather.features, sm, self.gather_packed, self.bs[i], self.ws[i].shape[0], relu=True,
-                                               tile_order=live[0], live_counts=self.last_live_counts[0], background=None if lazy else empty[0])
+                    if cover is not None:
+                        x = ops.conv2d_nhwc_gather(gather.features, sm, self.gather_packed, self.bs[i], self.ws[i].shape[0], relu=True,
+                                                   tile_order=cover.order[0], live_counts=cover.counts[0], cover=True)
+                    else:
+                        self.last_cover_counts = None
+                        x = ops.conv2d_nhwc_gather(gather.features, sm, self.gather_packed, self.bs[i], self.ws[i].shape[0], relu=True,
+                                                   tile_order=live[0], live_counts=self.last_live_counts[0], background=None if lazy else empty[0])
                 else:
                     x = ops.conv2d_nhwc_gather(gather.features, sm, self.gather_packed, self.bs[i], self.ws[i].shape[0], relu=True)
                 gather, first = None, False
+            elif kind == "c" and cover is not None and i == self.background_convs - 1:
+                # the cover form of the chain ends in the fused tail (tile_list_request): sec_conv2d_nhwc_tiles_tail_cover
+                fused_heads = ops.conv2d_nhwc_tiles_tail(x, self.packed[i], self.bs[i], cover.order[i], cover.counts[i], None, empty[i - 1],
+                                                         self.packed[-1], self.bs[-1], self.head_packed, self.head_b64, self.head_cout,
+                                                         cover_halo=cover.halo[i])
+                x = None
+            elif kind == "c" and cover is not None:
+                x = ops.conv2d_nhwc_tiles(x, self.packed[i], self.bs[i], 128, cover.order[i], cover.counts[i], None, relu=True,
+                                          cover_halo=cover.halo[i], background_in=empty[i - 1])
             elif kind == "c" and live is not None and nbr is not None and self._tail_in_last_conv(i, x, nbr):
                 # the last conv with the 1x1 tail (deblock + heads) in its epilogue: its output tile never leaves LDS (sec_conv2d_nhwc_tiles_tail)
                 fused_heads = ops.conv2d_nhwc_tiles_tail(x, self.packed[i], self.bs[i], live[i], self.last_live_counts[i], nbr[i], empty[i - 1],
@@ -1473,7 +1500,10 @@ class RPNInference(nn.Module):
             else:
                 ups.append(self._conv(x, i))
         lazy_heads = None
-        if fused_heads is not None:
+        if fused_heads is not None and cover is not None:     # "written" = the last conv's coverage, a bit per pixel column and band
+            y = fused_heads
+            lazy_heads = (cover.cols[self.background_convs - 1], self._split_heads(empty[self.background_convs]))
+        elif fused_heads is not None:
             y = fused_heads
             lazy_heads = (nbr[self.background_convs, 1], self._split_heads(empty[self.background_convs]))
         elif self.chain_tail and live is not None:
@@ -1519,6 +1549,22 @@ class RPNInference(nn.Module):
             self._cat_channels = sum(self.ws[i].shape[0] for i in us)
             self._into_ok = v
         return v
+
+    def tile_list_request(self, h, w):
+        """(layers, masks, cover) a forward on an h x w map passes to SparseBEV.tile_lists -- a staged capture asks for the same lists ahead
+        of the RPN segment.  cover: the single-block lazy chain (128 -> 128 convs, 16-bit) whose last conv runs the fused tail for lazy heads
+        (the condition of :meth:`_tail_in_last_conv`) on a map whose cover entries fit 16 bits; SEC_RPN_TILE_COVER=0|1 forces the grid lists /
+        the cover lists wherever that chain runs."""
+        lazy = self.lazy_background and self.background_convs >= 2
+        env = os.environ.get("SEC_RPN_TILE_COVER", "")
+        want = self.tile_cover if env not in ("0", "1") else env == "1"
+        n = self.background_convs
+        chain = (lazy and self.fused_tail and self.chain_tail and self.lazy_heads and self.head_cout == 64 and n < 8
+                 and sum(1 for kind, _ in self.plan if kind == "c") == n and all(tuple(self.ws[j].shape[:2]) == (128, 128) for j in range(n))
+                 and self.ws[0].dtype in (torch.bfloat16, torch.float16) and os.environ.get("SEC_RPN_FUSED_TAIL", "1") != "0")
+        if want and chain and ops.rpn_tile_cover_supported(h, w, n):
+            return n, False, True
+        return (self.list_layers(), True, False) if lazy else (n, False, False)
 
     def list_layers(self):
         """Layers of live-tile lists / masks a forward asks rpn_tile_live for: one per 3x3 conv, plus one when the heads are lazy (its
@@ -1798,28 +1844,34 @@ class SecondDetector(nn.Module):
         finally:
             ops.set_rulebook_numbering(prev)
 
-    def lazy_heads(self):
+    def lazy_heads(self, cover=False):
         """Context: forwards inside may leave the head tensor's background tiles unwritten (RPNInference.lazy_heads) because their
         preds go straight to :meth:`predict_device`'s fused kernels, which read those tiles from the empty frame's map.  A no-op when
-        the prepared RPN / the predict path cannot do it (or SEC_RPN_LAZY_HEADS=0)."""
+        the prepared RPN / the predict path cannot do it (or SEC_RPN_LAZY_HEADS=0).  ``cover``: the RPN may also follow the cover lists
+        (RPNInference.tile_cover: nobody but the fused predict looks at the head tensor, whose written region is then no union of grid tiles)."""
         det = self
 
         class _Ctx:
             def __enter__(self_):
                 self_.prev = getattr(det.rpn, "lazy_heads", None)
+                self_.prev_cover = getattr(det.rpn, "tile_cover", None)
                 if (self_.prev is not None and det.fused_predict and det.cfg["nms_pre_max_size"] <= 1024 and det.multiclass is None
                         and os.environ.get("SEC_RPN_LAZY_HEADS", "1") != "0"):
                     det.rpn.lazy_heads = True
+                    if cover and self_.prev_cover is not None:
+                        det.rpn.tile_cover = True
                 return self_
 
             def __exit__(self_, *exc):
                 if self_.prev is not None:
                     det.rpn.lazy_heads = self_.prev
+                if self_.prev_cover is not None:
+                    det.rpn.tile_cover = self_.prev_cover
                 return False
         return _Ctx()
 
     def _forward_points(self, points, point_offsets, static=False):
-        with self.lazy_heads():
+        with self.lazy_heads(cover=True):
             return self._forward_points_impl(points, point_offsets, static)
 
     def _forward_points_impl(self, points, point_offsets, static=False):
@@ -1982,12 +2034,11 @@ class SecondDetector(nn.Module):
                                                             bev_sparse=self._rpn_takes_rows(), **pitch)
                     self._branch_overflow = [list(getattr(self.middle_feature_extractor, "last_overflow_checks", []))]
                     if isinstance(spatial, SparseBEV) and getattr(self.rpn, "background_convs", 0) and self.rpn.skip_background:
-                        lazy_ = self.rpn.lazy_background and self.rpn.background_convs >= 2
-                        with self.lazy_heads():
-                            spatial.tile_lists(self.rpn.list_layers() if lazy_ else self.rpn.background_convs,   # the live-tile lists belong to the latency-bound segment
-                                               masks=lazy_)
+                        with self.lazy_heads(cover=True):
+                            layers_, masks_, cover_ = self.rpn.tile_list_request(*spatial.spatial_shape[-2:])
+                            spatial.tile_lists(layers_, masks=masks_, cover=cover_)   # the live-tile lists belong to the latency-bound segment
                 with ops.rt.capture_guard(), torch.cuda.graph(gb, pool=pool, capture_error_mode="thread_local"):
-                    with self.lazy_heads():
+                    with self.lazy_heads(cover=True):
                         preds = self.rpn(spatial)
                 with ops.rt.capture_guard(), torch.cuda.graph(gc, pool=pool, capture_error_mode="thread_local"):
                     out = self.predict_device(preds, batch_size)

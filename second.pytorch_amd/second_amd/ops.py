@@ -9,6 +9,7 @@ import torch
 import ctypes
 import functools
 import os
+from typing import NamedTuple
 
 from . import runtime as rt
 
@@ -1188,10 +1189,12 @@ POISON_LAZY_OUTPUTS = False    # tests: the tiles a lazy conv leaves unwritten a
 
 
 @_traced("conv2d_nhwc_gather")
-def conv2d_nhwc_gather(features, site_map, packed, bias, cout, relu=True, tile_order=None, live_counts=None, background=None):
+def conv2d_nhwc_gather(features, site_map, packed, bias, cout, relu=True, tile_order=None, live_counts=None, background=None, cover=False):
     """3x3 / stride 1 / pad 1 conv + bias + ReLU of ``SparseConvTensor.dense().view(B, 128, H, W)`` read straight from the
     sparse tensor's rows ``features`` [rows, 64] through ``site_map`` [B, 2, H, W] (:func:`sparse_site_map`): no dense image,
-    tiles without sites cost a map lookup.  ``packed`` = conv2d_pack_weight(w[:, gather_channel_perm(64, 2)])."""
+    tiles without sites cost a map lookup.  ``packed`` = conv2d_pack_weight(w[:, gather_channel_perm(64, 2)]).
+    ``cover``: ``tile_order`` / ``live_counts`` are layer 0 of the COVER lists of :func:`rpn_tile_live` (``cover=True``; entries band * W + x0,
+    no background: sec_conv2d_nhwc_gather_cover)."""
     rt.require_gpu(features, site_map, packed)
     assert features.dim() == 2 and features.shape[1] == 64 and features.is_contiguous() and site_map.dtype == torch.int32
     b, d, h, w = site_map.shape
@@ -1207,6 +1210,13 @@ def conv2d_nhwc_gather(features, site_map, packed, bias, cout, relu=True, tile_o
             rt.require_gpu(background)
             assert background.dtype == features.dtype
             assert background.numel() == h * w * int(cout) and background.is_contiguous(memory_format=torch.channels_last)
+    if cover:
+        assert tile_order is not None and background is None, "cover lists: no background copies (every consumer is lazy)"
+        rc = rt.lib().sec_conv2d_nhwc_gather_cover(rt.ptr(features), features.shape[0], rt.ptr(site_map), b, h, w, rt.ptr(packed), rt.ptr(bias),
+                                                   int(cout), int(bool(relu)), rt.ptr(tile_order), rt.ptr(live_counts), rt.ptr(y),
+                                                   rt.dtype_code(features.dtype), rt.stream())
+        rt.check(rc, "sec_conv2d_nhwc_gather_cover")
+        return y
     rc = rt.lib().sec_conv2d_nhwc_gather(rt.ptr(features), features.shape[0], rt.ptr(site_map), b, h, w, rt.ptr(packed), rt.ptr(bias),
                                          int(cout), int(bool(relu)), rt.ptr(tile_order) if tile_order is not None else None,
                                          rt.ptr(live_counts) if tile_order is not None else None,
@@ -1271,12 +1281,29 @@ def conv2d_rows_supported(cin, cout, ksize, stride, pad, dtype):
             and (cout == 64 or cout % 128 == 0))
 
 
+def rpn_tile_cover_supported(h, w, layers):
+    """The cover lists of :func:`rpn_tile_live` exist for this map: an entry band * W + x0 fits 16 bits and the kernel's tables its LDS."""
+    return ((int(h) + 7) // 8) * int(w) <= 65535 and int(layers) <= 8 and rt.lib().sec_rpn_tile_cover_lds_bytes(int(h), int(w), int(layers)) <= 120 * 1024
+
+
+class TileCover(NamedTuple):
+    """The cover lists of sec_rpn_tile_cover: order [layers, B, tiles] int16 (entries band * W + x0), counts [layers, B] int32,
+    cols [layers, B, bands, ceil(W / 32)] int32 (C_l: the columns conv l writes per band), halo [layers, 2, B, tiles, 3] int32
+    (layers >= 1: what conv l - 1 wrote of a tile's 10 x 18 halo; half 0 by rank, half 1 by grid tile)."""
+    order: torch.Tensor
+    counts: torch.Tensor
+    cols: torch.Tensor
+    halo: torch.Tensor
+
+
 @_traced("rpn_tile_live")
-def rpn_tile_live(site_map, layers, masks=False):
+def rpn_tile_live(site_map, layers, masks=False, cover=False):
     """order [layers, B, tiles] int16 + counts [layers, B] int32 for the first ``layers`` 3x3 convs of the RPN (layer 0 = the gathered
     one): per frame the 8 x 16 tiles (row-major indices) that can differ from the layer's background first, the others from the
     end backwards; counts = how many can differ (sec_rpn_tile_live).  ``masks``: also nbr_masks [layers, 2, B, tiles] int16 for the
-    lazy consumers (sec_rpn_tile_live_masks: which of a tile's 3 x 3 neighbours the previous conv really wrote)."""
+    lazy consumers (sec_rpn_tile_live_masks: which of a tile's 3 x 3 neighbours the previous conv really wrote).
+    ``cover`` (without ``masks``): -> (order, counts, TileCover) -- the grid lists and, from the same bitmap, the COVER lists whose tiles start
+    at any column of their 8-row band (sec_rpn_tile_cover); :func:`rpn_tile_cover_supported` says whether the map allows them."""
     rt.require_gpu(site_map)
     assert site_map.dtype == torch.int32 and site_map.dim() == 4 and site_map.shape[1] == 2 and site_map.is_contiguous()
     b, _, h, w = site_map.shape
@@ -1286,6 +1313,15 @@ def rpn_tile_live(site_map, layers, masks=False):
     counts = torch.empty((int(layers), b), dtype=torch.int32, device=site_map.device)
     ws_bytes = rt.lib().sec_rpn_tile_live_workspace_bytes(b, h, w)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=site_map.device)
+    if cover:
+        assert not masks, "the cover lists carry their own halo masks"
+        dev = site_map.device
+        cv = TileCover(torch.empty((int(layers), b, tiles), dtype=torch.int16, device=dev), torch.empty((int(layers), b), dtype=torch.int32, device=dev),
+                       torch.empty((int(layers), b, (h + 7) // 8, (w + 31) // 32), dtype=torch.int32, device=dev),
+                       torch.empty((int(layers), 2, b, tiles, 3), dtype=torch.int32, device=dev))
+        rt.check(rt.lib().sec_rpn_tile_cover(rt.ptr(site_map), b, h, w, int(layers), rt.ptr(order), rt.ptr(counts), rt.ptr(cv.order), rt.ptr(cv.counts),
+                                             rt.ptr(cv.cols), rt.ptr(cv.halo), rt.ptr(ws), ws_bytes, rt.stream()), "sec_rpn_tile_cover")
+        return order, counts, cv
     if masks:
         nbr = torch.empty((int(layers), 2, b, tiles), dtype=torch.int16, device=site_map.device)
         rt.check(rt.lib().sec_rpn_tile_live_masks(rt.ptr(site_map), b, h, w, int(layers), rt.ptr(order), rt.ptr(counts), rt.ptr(nbr), rt.ptr(ws),
@@ -1297,13 +1333,15 @@ def rpn_tile_live(site_map, layers, masks=False):
 
 
 @_traced("conv2d_nhwc_tiles")
-def conv2d_nhwc_tiles(x, packed, bias, cout, tile_order, live_counts, background, relu=True, nbr_masks=None, background_in=None):
+def conv2d_nhwc_tiles(x, packed, bias, cout, tile_order, live_counts, background, relu=True, nbr_masks=None, background_in=None, cover_halo=None):
     """3x3 / stride 1 / pad 1 conv + bias + ReLU on a channels_last [B,128,H,W] tensor; only the live tiles of ``tile_order`` [B, tiles] /
     ``live_counts`` [B] (one layer of :func:`rpn_tile_live`) are convolved, the others are copied from ``background`` = this layer's
     output for an EMPTY frame, channels_last [1, cout, H, W] (sec_conv2d_nhwc_tiles).
     LAZY form (``nbr_masks`` [2, B, tiles] = this layer's slice of rpn_tile_live(masks=True), ``background_in`` = the PRODUCING layer's
     empty-frame output): ``x`` holds only the tiles its producer found live, the halo pixels of the others are read from
-    ``background_in``; ``background`` may then be None -- this layer writes its live tiles only (sec_conv2d_nhwc_tiles_lazy)."""
+    ``background_in``; ``background`` may then be None -- this layer writes its live tiles only (sec_conv2d_nhwc_tiles_lazy).
+    COVER form (``cover_halo`` [2, B, tiles, 3] int32 + ``background_in``, no ``background``): ``tile_order`` / ``live_counts`` / ``cover_halo``
+    are this layer's slices of the TileCover of :func:`rpn_tile_live` (sec_conv2d_nhwc_tiles_cover; lazy, writes its listed tiles only)."""
     rt.require_gpu(x, packed, tile_order, live_counts)
     assert x.dim() == 4 and x.shape[1] == 128 and x.is_contiguous(memory_format=torch.channels_last)
     b, _, h, w = x.shape
@@ -1316,6 +1354,16 @@ def conv2d_nhwc_tiles(x, packed, bias, cout, tile_order, live_counts, background
     y = torch.empty((b, int(cout), h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if POISON_LAZY_OUTPUTS and background is None:
         y.fill_(float("nan"))
+    if cover_halo is not None:
+        rt.require_gpu(cover_halo, background_in)
+        assert background is None and nbr_masks is None, "cover lists: lazy form only"
+        assert cover_halo.dtype == torch.int32 and cover_halo.is_contiguous() and tuple(cover_halo.shape) == (2, b, tiles, 3)
+        assert background_in.dtype == x.dtype and background_in.numel() == h * w * 128 and background_in.is_contiguous(memory_format=torch.channels_last)
+        rc = rt.lib().sec_conv2d_nhwc_tiles_cover(rt.ptr(x), b, h, w, rt.ptr(packed), rt.ptr(bias), int(cout), int(bool(relu)), rt.ptr(tile_order),
+                                                  rt.ptr(live_counts), rt.ptr(cover_halo), rt.ptr(background_in), rt.ptr(y), rt.dtype_code(x.dtype),
+                                                  rt.stream())
+        rt.check(rc, "sec_conv2d_nhwc_tiles_cover")
+        return y
     if nbr_masks is not None:
         rt.require_gpu(nbr_masks, background_in)
         assert nbr_masks.dtype == torch.int16 and nbr_masks.is_contiguous() and tuple(nbr_masks.shape) == (2, b, tiles)
@@ -1335,21 +1383,32 @@ def conv2d_nhwc_tiles(x, packed, bias, cout, tile_order, live_counts, background
 
 @_traced("conv2d_nhwc_tiles_tail")
 def conv2d_nhwc_tiles_tail(x, packed, bias, tile_order, live_counts, nbr_masks, background_in, packed_w1, bias1, packed_w2, bias2, cout2,
-                           relu=True, relu1=True):
+                           relu=True, relu1=True, cover_halo=None):
     """The lazy form of :func:`conv2d_nhwc_tiles` (128 -> 128) with the fused 1x1 tail of :func:`conv1x1_chain` (``x_live_only``, no
     background) in its epilogue -- one launch, the conv's output never reaches memory (sec_conv2d_nhwc_tiles_tail).  Returns the head
-    tensor [B, cout2 = 64, H, W] channels_last; tiles outside the list are unwritten unless the conv took the plain tile order."""
-    rt.require_gpu(x, packed, tile_order, live_counts, nbr_masks, background_in, packed_w1, packed_w2, bias1)
+    tensor [B, cout2 = 64, H, W] channels_last; tiles outside the list are unwritten unless the conv took the plain tile order.
+    COVER form: ``nbr_masks`` None and ``cover_halo`` [2, B, tiles, 3] int32, lists = the last layer of a TileCover (sec_conv2d_nhwc_tiles_tail_cover)."""
+    rt.require_gpu(x, packed, tile_order, live_counts, cover_halo if cover_halo is not None else nbr_masks, background_in, packed_w1, packed_w2, bias1)
     assert x.dim() == 4 and x.shape[1] == 128 and x.is_contiguous(memory_format=torch.channels_last) and int(cout2) == 64
     b, _, h, w = x.shape
     tiles = ((h + 7) // 8) * ((w + 15) // 16)
     assert tile_order.dtype == torch.int16 and tile_order.is_contiguous() and tuple(tile_order.shape) == (b, tiles)
     assert live_counts.dtype == torch.int32 and live_counts.is_contiguous() and live_counts.numel() == b
-    assert nbr_masks.dtype == torch.int16 and nbr_masks.is_contiguous() and tuple(nbr_masks.shape) == (2, b, tiles)
+    if cover_halo is not None:
+        assert nbr_masks is None and cover_halo.dtype == torch.int32 and cover_halo.is_contiguous() and tuple(cover_halo.shape) == (2, b, tiles, 3)
+    else:
+        assert nbr_masks.dtype == torch.int16 and nbr_masks.is_contiguous() and tuple(nbr_masks.shape) == (2, b, tiles)
     assert background_in.dtype == x.dtype and background_in.numel() == h * w * 128 and background_in.is_contiguous(memory_format=torch.channels_last)
     y = torch.empty((b, 64, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if POISON_LAZY_OUTPUTS:
         y.fill_(float("nan"))
+    if cover_halo is not None:
+        rc = rt.lib().sec_conv2d_nhwc_tiles_tail_cover(rt.ptr(x), b, h, w, rt.ptr(packed), rt.ptr(bias), int(bool(relu)), rt.ptr(tile_order),
+                                                       rt.ptr(live_counts), rt.ptr(cover_halo), rt.ptr(background_in), rt.ptr(packed_w1), rt.ptr(bias1),
+                                                       int(bool(relu1)), rt.ptr(packed_w2), rt.ptr(bias2) if bias2 is not None else None, 64, rt.ptr(y),
+                                                       rt.dtype_code(x.dtype), rt.stream())
+        rt.check(rc, "sec_conv2d_nhwc_tiles_tail_cover")
+        return y
     rc = rt.lib().sec_conv2d_nhwc_tiles_tail(rt.ptr(x), b, h, w, rt.ptr(packed), rt.ptr(bias), int(bool(relu)), rt.ptr(tile_order), rt.ptr(live_counts),
                                              rt.ptr(nbr_masks), rt.ptr(background_in), rt.ptr(packed_w1), rt.ptr(bias1), int(bool(relu1)),
                                              rt.ptr(packed_w2), rt.ptr(bias2) if bias2 is not None else None, 64, rt.ptr(y),
@@ -1648,14 +1707,23 @@ def _strides5(t):
 
 
 def _lazy_args(view, lazy, pick):
-    """(tile_live pointer, background pointer of the same view) of a ``lazy=(tile_live [B, tiles] int16, pick-able background)``."""
+    """(tile_live pointer, background pointer of the same view) of a ``lazy=(tile_live [B, tiles] int16, pick-able background)``.
+    COVER form: tile_live is the producer's coverage [B, bands, ceil(W / 32)] int32 (one layer of TileCover.cols) -- see :func:`_lazy_cover`."""
     tile_live, bg = lazy
     b, a, h, w, _ = view.shape
-    assert tile_live.dtype == torch.int16 and tile_live.is_contiguous() and tuple(tile_live.shape) == (b, ((h + 7) // 8) * ((w + 15) // 16))
+    if _lazy_cover(lazy):
+        assert tile_live.is_contiguous() and tuple(tile_live.shape) == (b, (h + 7) // 8, (w + 31) // 32)
+    else:
+        assert tile_live.dtype == torch.int16 and tile_live.is_contiguous() and tuple(tile_live.shape) == (b, ((h + 7) // 8) * ((w + 15) // 16))
     bgv = pick(bg)
     assert bgv.dtype == view.dtype and tuple(bgv.shape[1:]) == tuple(view.shape[1:]) and tuple(bgv.stride()[1:]) == tuple(view.stride()[1:]), \
         "the background view must have the strides of the head view (same channels-last layout)"
     return tile_live, bgv
+
+
+def _lazy_cover(lazy):
+    """The lazy heads' producer followed COVER lists: "written" is a bit per pixel column and band (int32 words), not a flag per grid tile."""
+    return lazy is not None and lazy[0].dtype == torch.int32
 
 
 def _mask_u8(mask, shape, dev, what):
@@ -1771,6 +1839,15 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     top_label = torch.empty((b, k), dtype=torch.int32, device=dev)
     counts = torch.empty((b,), dtype=torch.int32, device=dev)
     keys = torch.empty((b * a * h * w,), dtype=torch.int32, device=dev)
+    if _lazy_cover(lazy):
+        if anchor_mask is not None:
+            anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), dev, "anchor_mask")
+        cols, bgv = _lazy_args(cls, lazy, lambda t: t)
+        rc = rt.lib().sec_predict_select_cover(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
+                                               rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype), rt.ptr(cols),
+                                               rt.ptr(bgv), rt.ptr(anchor_mask) if anchor_mask is not None else None, rt.stream())
+        rt.check(rc, "sec_predict_select_cover")
+        return top_idx, top_score, top_label, counts
     if anchor_mask is not None:
         anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), dev, "anchor_mask")
         tile_live, bgv = _lazy_args(cls, lazy, lambda t: t) if lazy is not None else (None, None)
@@ -1814,11 +1891,12 @@ def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=
     if lazy is not None:
         tile_live, bgb = _lazy_args(box, lazy, lambda t: t[0])
         bgd = _lazy_args(dir_cls, lazy, lambda t: t[1])[1] if dir_cls is not None else None
-        rc = rt.lib().sec_predict_decode_lazy(rt.ptr(box), _strides5(box), rt.ptr(dir_cls), _strides5(dir_cls) if dir_cls is not None else None,
+        entry = "sec_predict_decode_cover" if _lazy_cover(lazy) else "sec_predict_decode_lazy"
+        rc = getattr(rt.lib(), entry)(rt.ptr(box), _strides5(box), rt.ptr(dir_cls), _strides5(dir_cls) if dir_cls is not None else None,
                                               dir_cls.shape[-1] if dir_cls is not None else 0, b, a, h, w, k, rt.ptr(anchors),
                                               rt.ptr(top_idx), rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
                                               rt.dtype_code(box.dtype), rt.ptr(tile_live), rt.ptr(bgb), rt.ptr(bgd), rt.stream())
-        rt.check(rc, "sec_predict_decode_lazy")
+        rt.check(rc, entry)
         return dec, dets, dlab
     rc = rt.lib().sec_predict_decode(rt.ptr(box), _strides5(box), rt.ptr(dir_cls),
                                      _strides5(dir_cls) if dir_cls is not None else None,

@@ -45,6 +45,8 @@ SYMBOLS = [
     "sec_pfn_radius_fwd", "sec_pfn_radius_fwd_slots", "sec_predict_select_segments", "sec_predict_decode_segments",
     "sec_predict_select_classes", "sec_predict_decode_classes", "sec_nms_sorted_items_f32", "sec_predict_finalize_classes",
     "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd",
+    "sec_rpn_tile_cover_lds_bytes", "sec_rpn_tile_cover", "sec_conv2d_nhwc_gather_cover", "sec_conv2d_nhwc_tiles_cover",
+    "sec_conv2d_nhwc_tiles_tail_cover", "sec_predict_select_cover", "sec_predict_decode_cover",
 ]
 
 _lib = None
@@ -200,6 +202,14 @@ def lib():
         l.sec_rpn_tile_live_masks.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]
         l.sec_conv2d_nhwc_tiles_lazy.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]
         l.sec_conv2d_nhwc_tiles_tail.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp]
+        l.sec_rpn_tile_cover_lds_bytes.argtypes = [ci, ci, ci]
+        l.sec_rpn_tile_cover_lds_bytes.restype = sz
+        l.sec_rpn_tile_cover.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        l.sec_conv2d_nhwc_gather_cover.argtypes = [vp, i64, vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, ci, vp]
+        l.sec_conv2d_nhwc_tiles_cover.argtypes = [vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]
+        l.sec_conv2d_nhwc_tiles_tail_cover.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp]
+        l.sec_predict_select_cover.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+        l.sec_predict_decode_cover.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
         l.sec_rotate_iou_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp]
         l.sec_nms_workspace_bytes.argtypes = [ci, ci]
         l.sec_nms_sorted_f32.argtypes = [vp, vp, ci, ci, ci, cf, ci, ci, cf, ci, vp, vp, vp, sz, vp]
