@@ -738,7 +738,9 @@ int sec_nms_sorted_f32(const float *dets, const int *counts, int batch, int max_
  *             counts[b] = entries with sigmoid score >= score_thr (voxelnet.py:545-569, box_torch_ops.py:497-501).
  *             The reference masks by the threshold BEFORE its topk: the result is rows [0, counts[b]) of each frame; what
  *             the rows behind them hold is unspecified (the next-best anchors, or anchor 0 / score 0 when the bf16 path
- *             skipped its bisection because no more than k anchors reach the threshold)
+ *             skipped its bisection because no more than k anchors reach the threshold).  Order: descending logit (+0.0 before
+ *             -0.0), ties by ascending anchor index.  An anchor whose maximum over the classes is NaN (torch.max propagates
+ *             it, `>= thresh` drops it) is no candidate, like a masked-out one: it never lies inside [0, counts[b]).
  *   decode  : second_box_decode (box_torch_ops.py:56-101) of the selected anchors -> decoded [B,k,7];
  *             dets [B,k,6] = NMS rows (rotate: x,y,w,l,r,score ; else standup x1,y1,x2,y2,score,0); direction argmax
  *   finalize: gather of the NMS survivors (keep / num_keep of sec_nms_sorted_f32), direction fix

@@ -96,10 +96,10 @@ __device__ __forceinline__ unsigned anchor_key(const T *cls, const View5 &v, con
     int lab = 0;
     for (int c = 1; c < g.nc; ++c) {
         float f = ldf(p + c * v.sc);
-        if (f > best) { best = f; lab = c; }
+        if (f > best || f != f) { best = f; lab = c; }                 // NaN-propagating maximum (torch.max of voxelnet.py:558)
     }
     if (label) *label = lab;
-    if (!anchor_kept(v, (long long)b * g.A * g.H * g.W + n)) return 0u;
+    if (!anchor_kept(v, (long long)b * g.A * g.H * g.W + n) || best != best) return 0u;   // a NaN score reaches no threshold: key of a masked anchor
     return f2key(best);
 }
 
@@ -171,10 +171,10 @@ __device__ __forceinline__ unsigned anchor_key(const T *, const SegView &v, cons
     int lab = 0;
     for (int c = 1; c < g.nc; ++c) {
         float f = ldf(p + c * sc);
-        if (f > best) { best = f; lab = c; }
+        if (f > best || f != f) { best = f; lab = c; }                 // as the View5 form: NaN propagates and takes key 0
     }
     if (label) *label = lab;
-    return f2key(best);
+    return best != best ? 0u : f2key(best);
 }
 
 constexpr int kSelThreads = 1024;
@@ -301,7 +301,10 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select(const T *__restr
         mask |= 255u << shift;
         __syncthreads();
     }
-    const unsigned T_key = prefix;   // K-th largest key; take all keys > T and the first `need` (by index) equal to T
+    // K-th largest key; take all keys > T and the first `need` (by index) equal to T.  The two KEY16 passes resolved the high half
+    // only: the low half of a bf16 logit's key follows from its sign (0 for a non-negative logit, 0xffff for a negative one, whose
+    // ties would otherwise all compare GREATER than T and overflow the sort buffer in arrival order)
+    const unsigned T_key = (sizeof(T) == 2 && KEY16 && !shortcut && !(prefix & 0x80000000u)) ? (prefix | 0xffffu) : prefix;
     // ---- ordered compaction into LDS
     if (tid == 0) { s_cnt = 0; s_eqbase = 0; }
     ckey[tid] = 0u;
@@ -751,8 +754,10 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
                 else f[j] = ldf(cls + off[j] + (ok[j] ? (long long)c2 * v.sc : 0));
             }
 #pragma unroll
-            for (int j = 0; j < 2 * PB; ++j) if (f[j] > best[j]) best[j] = f[j];
+            for (int j = 0; j < 2 * PB; ++j) if (f[j] > best[j] || f[j] != f[j]) best[j] = f[j];
         }
+#pragma unroll
+        for (int j = 0; j < 2 * PB; ++j) keep[j] = keep[j] && best[j] == best[j];   // as anchor_key(): a NaN maximum holds key 0
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             const unsigned ka = keep[2 * j] ? key16_of<T>(best[2 * j]) : 0u;

@@ -1822,6 +1822,7 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     """cls: [B, A, H, W, num_class] view (any strides).  -> (top_idx [B,k] int32 anchor ids sorted by descending
     score, top_score [B,k] sigmoid scores, top_label [B,k], counts [B] = entries with score >= score_thr).  The selection is
     rows [0, counts[b]) of frame b (the reference masks by the threshold before its topk); rows behind them are unspecified.
+    Order: descending logit (+0.0 before -0.0), ties by ascending anchor index; an anchor whose best logit is NaN is no candidate.
     ``lazy`` = (tile_live [B, tiles] int16 with bit 4 = "tile written", bg = the empty frame's view [1, A, H, W, num_class] with the
     strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg`` (sec_predict_select_lazy).
     ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry (sec_predict_select_masked).
