@@ -19,6 +19,7 @@ __global__ __launch_bounds__(kBlock) void k_rotate_iou(const float *__restrict__
                                                       float *__restrict__ iou) {
     __shared__ float qc[64][9];   // corners of the 64 query boxes of this column tile (+1 pad)
     __shared__ float qa[64];
+    __shared__ bool qthin[64];
     int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int kq = blockIdx.y * 64 + lane;
     if (w == 0 && kq < K) {
@@ -27,14 +28,17 @@ __global__ __launch_bounds__(kBlock) void k_rotate_iou(const float *__restrict__
 #pragma unroll
         for (int i = 0; i < 8; ++i) qc[lane][i] = c[i];
         qa[lane] = qboxes[(size_t)kq * 5 + 2] * qboxes[(size_t)kq * 5 + 3];
+        qthin[lane] = thin_box(qboxes + (size_t)kq * 5);
     }
     __syncthreads();
     float c1[8];
     float a1 = 0.0f;
+    bool thin1 = false;
     if (kq < K) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) c1[i] = qc[lane][i];
         a1 = qa[lane];
+        thin1 = qthin[lane];
     }
     for (int rr = 0; rr < 16; ++rr) {
         int n = blockIdx.x * 64 + w * 16 + rr;
@@ -43,7 +47,8 @@ __global__ __launch_bounds__(kBlock) void k_rotate_iou(const float *__restrict__
         float c2[8];
         box_corners(c2, boxes + (size_t)n * 5);
         float a2 = boxes[(size_t)n * 5 + 2] * boxes[(size_t)n * 5 + 3];
-        float in = far_apart(standup_of(c1), standup_of(c2)) ? 0.0f : quad_inter(c1, c2);
+        const bool skip = !thin1 && !thin_box(boxes + (size_t)n * 5) && far_apart(standup_of(c1), standup_of(c2));
+        float in = skip ? 0.0f : quad_inter(c1, c2);
         float v;
         if (criterion == -1) v = in / (a1 + a2 - in);
         else if (criterion == 0) v = in / a1;
@@ -111,7 +116,9 @@ __global__ __launch_bounds__(kBlock) void k_nms_mask(const float *__restrict__ d
 #pragma unroll
                 for (int i = 0; i < 8; ++i) tile[w][lane][i] = c[i];
                 tile[w][lane][8] = d[2] * d[3];
-                su[w][lane] = standup_of(c);
+                // numba semantics: a thin box (rotated_clip.hpp) is far apart from nothing -- every pair with it runs the clipper, as in
+                // the reference.  The cpu semantics' pre-filter reads the true standup box (and skips far pairs like the reference's own).
+                su[w][lane] = (semantics == 0 && thin_box(d)) ? Standup{-3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f} : standup_of(c);
                 ctr[w][lane][0] = d[0];
                 ctr[w][lane][1] = d[1];
                 ctr[w][lane][2] = 0.5f * fminf(d[2], d[3]);   // radius of the circle inscribed at the centre (any rotation)

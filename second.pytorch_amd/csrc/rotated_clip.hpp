@@ -155,10 +155,16 @@ __device__ __forceinline__ Standup standup_of(const float *c) {
     }
     return s;
 }
-// far apart => the clipper finds no vertex => intersection exactly 0 (margin covers its 1e-6 tolerances)
+// far apart => the clipper finds no vertex => intersection exactly 0 (margin covers its 1e-6 tolerances) -- for boxes that are not
+// thin_box(), see there
 __device__ __forceinline__ bool far_apart(const Standup &a, const Standup &b) {
     const float m = 1e-3f;
     return a.x0 > b.x1 + m || b.x0 > a.x1 + m || a.y0 > b.y1 + m || b.y0 > a.y1 + m;
 }
+// pt_in_quad's tolerance is 1e-6 on DOT PRODUCTS with the edge vectors, i.e. a distance of 1e-6 / side: a box with a side of 1e-4
+// "contains" points 1 cm outside it, and one with a zero side every point of the strip (zero area: of the plane) its other side
+// spans -- the reference then reports the far box's own corners as the intersection and suppresses it (IoU = area / 0).  far_apart's
+// 1 mm margin covers that tolerance down to sides of 2 mm; a thinner box goes through the clipper whatever its distance.
+__device__ __forceinline__ bool thin_box(const float *b) { return !(fminf(fabsf(b[2]), fabsf(b[3])) >= 2e-3f); }
 
 }  // namespace sec
