@@ -504,7 +504,8 @@ int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, siz
  * materialising [P, T, C].  C <= 64, 4 point features, T <= 127.
  *   fwd : out [P, C] f32; argmax [P, C] int8 (slot of the maximum, -1 = a padded slot); stats f32[C * 11 + 9] = mean[C],
  *         invstd[C], M[C][9] = sum x_c * input_j, S1[9] = sum input_j (kept for the backward); running_mean / running_var (may be
- *         NULL) updated with `momentum` (unbiased variance), like torch.nn.BatchNorm1d.
+ *         NULL) updated with `momentum` (unbiased variance), like torch.nn.BatchNorm1d.  The points are expected finite; a
+ *         non-finite one makes mean / invstd of its channels NaN, and then every output of those channels is NaN.
  *   bwd : grad_out [P, C] f32 -> dweight_t [9][C] (the layout of weight_t), dgamma [C], dbeta [C]; no gradient for the points.
  * workspace: sec_pfn_train_workspace_bytes(num_pillars, channels) for either call. */
 size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels);

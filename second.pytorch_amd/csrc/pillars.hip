@@ -112,7 +112,8 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
 // BatchNorm1d over ALL P * T rows (the zero rows of the padded slots included), ReLU, max over the T slots; autograd then runs
 // ~25 kernels over a [P, T, C] tensor (1.1 GB in fp32 at 75 k pillars x 60 points x 64 channels) forward and again backward.
 // Here the [P, T, C] tensor never exists: lane = channel, a wave walks the points of a pillar.
-//   k_pfn_stats     per channel: sum x, sum x^2, M[c][j] = sum x_c * dec_j, and S1[j] = sum dec_j (block partials)
+//   k_pfn_stats     per channel: sum x, sum x^2 (both accumulated in fp64, see there), M[c][j] = sum x_c * dec_j, and
+//                   S1[j] = sum dec_j (block partials)
 //   k_pfn_finalize  mean, 1 / sqrt(var + eps) (biased variance over P * T rows, as BatchNorm does), running statistics
 //   k_pfn_fwd<.., TRAIN>  normalise, ReLU, max over the slots, slot of the maximum (-1: a padded slot won)
 //   k_pfn_bwd       the gradient of the max reaches ONE row per (pillar, channel): dz = g * [out > 0]; block partials of
@@ -158,15 +159,20 @@ __device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl
     pfn_row<RADIUS>(q, pl.mx, pl.my, pl.mz, pl.cx, pl.cy, f);
 }
 
-// partial[block][c][StatVals], partial_s1[block][K]; C <= 64 (one wave = all channels)
+// partial[block][c][StatVals], partial_s1[block][K], partial_d[block][c][2]; C <= 64 (one wave = all channels)
+// sum x and sum x^2 are accumulated and handed on in fp64 (partial_d; slots 0 and 1 of `partial` stay unused): the variance is
+// sum x^2 / N - mean^2, and a channel with |mean| >> std (a cloud offset from the origin, an intensity in 0..255) cancels there: at
+// mean^2 / var = 550 fp32 sums per wave lost 3.8e-6 of invstd where torch's float32 BatchNorm keeps 2.2e-7 (the offset case of
+// tests/test_gpu_pfn_edges.py); in fp64 the kernels keep 7e-8.
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                      const int *__restrict__ coords, int P, int T, const float *__restrict__ wt, int C,
                                                      float vx, float vy, float xo, float yo, float *__restrict__ partial,
-                                                     float *__restrict__ partial_s1) {
+                                                     float *__restrict__ partial_s1, double *__restrict__ partial_d) {
     constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
     __shared__ float red[kBlock / 64][64][StatVals + 1];
     __shared__ float red1[kBlock / 64][K];
+    __shared__ double redd[kBlock / 64][64][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool live = lane < C;
     float w[K];
@@ -177,6 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ 
     for (int j = 0; j < StatVals; ++j) acc[j] = 0.f;
 #pragma unroll
     for (int j = 0; j < K; ++j) s1[j] = 0.f;
+    double sum = 0.0, sq = 0.0;
     for (int p = blockIdx.x * (kBlock / 64) + wv; p < P; p += gridDim.x * (kBlock / 64)) {
         const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
         const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
@@ -186,26 +193,34 @@ __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ 
             float x = 0.f;
 #pragma unroll
             for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
-            acc[0] += x;
-            acc[1] = fmaf(x, x, acc[1]);
+            sum += (double)x;
+            sq = fma((double)x, (double)x, sq);
 #pragma unroll
             for (int j = 0; j < K; ++j) { acc[2 + j] = fmaf(x, f[j], acc[2 + j]); s1[j] += f[j]; }
         }
     }
 #pragma unroll
     for (int j = 0; j < StatVals; ++j) red[wv][lane][j] = acc[j];
+    redd[wv][lane][0] = sum; redd[wv][lane][1] = sq;
     if (lane == 0)
 #pragma unroll
         for (int j = 0; j < K; ++j) red1[wv][j] = s1[j];
     __syncthreads();
     if (wv == 0) {
-        if (live)
+        if (live) {
 #pragma unroll
             for (int j = 0; j < StatVals; ++j) {
                 float v = 0.f;
                 for (int k = 0; k < kBlock / 64; ++k) v += red[k][lane][j];
                 partial[((size_t)blockIdx.x * C + lane) * StatVals + j] = v;
             }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                double v = 0.0;
+                for (int k = 0; k < kBlock / 64; ++k) v += redd[k][lane][j];
+                partial_d[((size_t)blockIdx.x * C + lane) * 2 + j] = v;
+            }
+        }
         if (lane < K) {
             float v = 0.f;
             for (int k = 0; k < kBlock / 64; ++k) v += red1[k][lane];
@@ -228,7 +243,7 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {   // 256
 // one block per channel (+ one for S1).  stats[c] layout: mean[C], invstd[C], M[C][K], S1[K]
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict__ partial, const float *__restrict__ partial_s1,
-                                                        int blocks, int C, double rows, float eps, float momentum,
+                                                        const double *__restrict__ partial_d, int blocks, int C, double rows, float eps, float momentum,
                                                         float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ stats) {
     constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
@@ -246,7 +261,8 @@ __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict
     double tot[StatVals];
     for (int j = 0; j < StatVals; ++j) {
         double v = 0.0;
-        for (int b = threadIdx.x; b < blocks; b += kBlock) v += (double)partial[((size_t)b * C + c) * StatVals + j];
+        for (int b = threadIdx.x; b < blocks; b += kBlock)
+            v += j < 2 ? partial_d[((size_t)b * C + c) * 2 + j] : (double)partial[((size_t)b * C + c) * StatVals + j];
         tot[j] = block_sum_f64(v, sh);
     }
     if (threadIdx.x == 0) {
@@ -295,6 +311,9 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
         const float y = fmaxf(fmaf((0.f - mean) * invstd, ga, be), 0.f);
         if (y > best) { best = y; arg = -1; }
     }
+    // statistics poisoned by a non-finite input (NaN mean or invstd): fmaxf and `y > best` drop the NaN that torch's relu and max
+    // carry, so it is handed on here -- every output of the channel is NaN, as the reference's is
+    if (mean != mean || invstd != invstd) best = __builtin_nanf("");
     if (live) {
         out[(size_t)p * C + lane] = best;
         argmax[(size_t)p * C + lane] = (signed char)arg;
@@ -597,7 +616,8 @@ SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_worksp
 SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
     if (num_pillars < 0 || channels <= 0 || channels > 64) return 0;
     const size_t b = (size_t)pfn_blocks(num_pillars);
-    return align_up(b * channels * kPfnStatVals * sizeof(float)) + align_up(b * kPfnIn * sizeof(float));
+    return align_up(b * channels * kPfnStatVals * sizeof(float)) + align_up(b * kPfnIn * sizeof(float)) +
+           align_up(b * channels * 2 * sizeof(double));
 }
 
 template <bool RADIUS>
@@ -615,10 +635,11 @@ static int pfn_train_fwd_any(const float *voxels, const int *num_points, const i
     const int blocks = pfn_blocks(num_pillars);
     float *partial = (float *)workspace;      // the workspace is carved for nine inputs in both forms (eight need less)
     float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * kPfnStatVals * sizeof(float)));
+    double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * kPfnIn * sizeof(float)));
     hipLaunchKernelGGL(k_pfn_stats<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points,
-                       weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1);
+                       weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
     const double rows = (double)num_pillars * (double)max_points;
-    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, blocks, channels, rows, eps,
+    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels, rows, eps,
                        momentum, running_mean, running_var, stats);
     hipLaunchKernelGGL(k_pfn_fwd_train<RADIUS>, dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
                        num_pillars, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);

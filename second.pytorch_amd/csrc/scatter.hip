@@ -13,7 +13,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter_rows(const T *__restrict__ f
                                                         const int *__restrict__ num_dev, int c, T *__restrict__ out,
                                                         long long sb, long long sc, long long sz, long long sy,
                                                         long long sx) {
-    if (num_dev) n = *num_dev;
+    if (num_dev) { const int live = *num_dev; n = live < n ? (live > 0 ? live : 0) : n; }   // static capacity, as k_gather_rows clamps it
     long long total = (long long)n * c;
     for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < total; g += (long long)gridDim.x * kBlock) {
         int i = (int)(g / c), ch = (int)(g % c);
@@ -86,7 +86,7 @@ static int run_scatter(const void *feat, const int *idx, int n, const int *num_d
 // of a dense image.
 __global__ __launch_bounds__(kBlock) void k_site_map(const int *__restrict__ idx, int n, const int *__restrict__ num_dev, int batch, int d,
                                                     int h, int w, int *__restrict__ map) {
-    if (num_dev) n = *num_dev;
+    if (num_dev) { const int live = *num_dev; n = live < n ? (live > 0 ? live : 0) : n; }
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const int4 q = *reinterpret_cast<const int4 *>(idx + (size_t)i * 4);
         if ((unsigned)q.x < (unsigned)batch && (unsigned)q.y < (unsigned)d && (unsigned)q.z < (unsigned)h && (unsigned)q.w < (unsigned)w)

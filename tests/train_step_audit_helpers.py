@@ -12,7 +12,8 @@ state apply unchanged:
     BatchNorm + ReLU        dense_train_ref_helpers.BnRef  (rows and NHWC; its own rule for mask-ambiguous elements)
     losses                  train_ref_helpers.loss_ref in float64, tolerances of tests/test_gpu_train_edges.py
     AdamW                   train_ref_helpers.adamw_ref, tolerance of tests/test_gpu_train_edges.py::_adam_steps
-    pillar layer            the module's own float64 formulation, bounds of tests/test_gpu_mhead_train.py
+    pillar layer            the module's own float64 formulation, bounds of tests/test_gpu_mhead_train.py; and per element
+                            pfn_ref_helpers.check_train_undecided
     scatter / gather        bit equality
 
 "Every node within its bound on its own inputs" + "every node's inputs are the tensors they should be" (the wiring assertions: weight
@@ -636,7 +637,7 @@ def pfn_factory(node):
 def audit_pfn(node, audit, packers):
     """The float64 formulation of tests/test_gpu_mhead_train.py: the layer's own torch formulation on the CPU in float64; per
     quantity max-abs error over max-abs value within the larger of the project tolerance and four times the error of a float32
-    run of the same formulation."""
+    run of the same formulation.  Then every element against the float64 reference and bounds of tests/pfn_ref_helpers.py."""
     vfe = packers.get("pfn", pfn_factory)(node)                 # fresh module (train mode, torch formulation) for this node's geometry and channel count
     vox, num, coords, weight, gamma, beta, rm0, rv0 = node.args[:8]
     w = None if node.grad_out is None else node.grad_out[0]
@@ -661,6 +662,16 @@ def audit_pfn(node, audit, packers):
         ref = res[torch.float64][k]
         bound = max(PFN_TOL[k], 4 * rel(res[torch.float32][k], ref))
         audit.add(node, k, rel(v.detach().double().cpu(), ref) / bound)
+    # and per element (tests/pfn_ref_helpers.py: float64 written from the reference's formulation, every element inside its own
+    # derived bound; the node kept neither argmax nor statistics, so contested maxima widen the gradient bounds by their spread)
+    import pfn_ref_helpers as P
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    case = P.trim_slots(dict(vox=f32(vox), num=num.detach().cpu().numpy(), coords=coords.detach().cpu().numpy(), geom=tuple(float(g) for g in node.args[10]),
+                             wt=np.ascontiguousarray(f32(weight).T), gamma=f32(gamma), beta=f32(beta), eps=float(node.args[8]),
+                             momentum=float(node.args[9]), rm0=f32(rm0), rv0=f32(rv0), grad_out=None if w is None else f32(w)))
+    per = P.check_train_undecided({k: v.detach().double().cpu() for k, v in got.items()}, case, node.kind == "PFNRadiusTrainFunction")
+    for k, ratio in per.items():
+        audit.add(node, k + " per element", ratio)
 
 
 # ------------------------------------------------------------------------------------------------------------------ voxel means
