@@ -535,6 +535,34 @@ int sec_pfn_radius_train_bwd(const float *voxels, const int *num_points, const i
                              float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
                              const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
                              size_t workspace_bytes, void *stream);
+/* The four training entry points on STATIC-CAPACITY pillars (a captured training step: the arrays keep one size, the voxeliser's
+ * count stays on the device): num_pillars is the capacity of voxels / num_points / coords / out / argmax / grad_out, and
+ * live = min(max(*num_dev, 0), num_pillars) of those rows are pillars.  num_dev is device memory, read by every kernel when it runs
+ * (nothing about it crosses the host; grids are sized by the capacity).  BatchNorm's row count is live * max_points, in double on the
+ * device, wherever the forms above use num_pillars * max_points.  Rows at or past `live` are never read and enter no sum; fwd writes
+ * their `out` as zeros and their `argmax` as -1.  live == 0: stats = (mean 0, invstd 1 / sqrt(eps), M = 0, S1 = 0), the running
+ * statistics keep their values, dweight_t / dgamma / dbeta are zero.  num_dev == NULL: exactly the forms above (which are these
+ * with NULL).  Limits, status codes and workspace (by capacity) as above; a capacity of 0 with a count still writes stats. */
+int sec_pfn_train_fwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                           int max_points, int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
+                           float momentum, float *running_mean, float *running_var, int channels, float vx, float vy, float x_offset,
+                           float y_offset, float *out, signed char *argmax, float *stats, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int sec_pfn_train_bwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                           int max_points, int num_features, const float *weight_t, const float *gamma, const float *stats,
+                           int channels, float vx, float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
+                           const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int sec_pfn_radius_train_fwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                                  int max_points, int num_features, const float *weight_t, const float *gamma, const float *beta,
+                                  float eps, float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
+                                  float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+int sec_pfn_radius_train_bwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                                  int max_points, int num_features, const float *weight_t, const float *gamma, const float *stats,
+                                  int channels, float vx, float vy, float x_offset, float y_offset, const float *grad_out,
+                                  const float *out, const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* Block filtering of points_to_voxel_3d_with_filtering (spconv point2voxel.h; enabled by
  * second/configs/nuscenes/all.fhd.config:9-12): keep a voxel iff the z-span of the stored points inside the

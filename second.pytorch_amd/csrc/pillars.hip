@@ -137,6 +137,15 @@ struct PfnPillar {
     float mx, my, mz, cx, cy;
     int n;
 };
+// Static capacity (the *_live entry points): the arrays hold P rows, of which the first min(max(*num_dev, 0), P) are pillars; the
+// count lives in device memory, so a captured graph replays on whatever the voxeliser counted.  One wave-uniform load, kept in a
+// scalar register; num_dev == NULL: all P rows are pillars.  Rows at or past the count are never read by any kernel below.
+__device__ __forceinline__ int pfn_live(const int *__restrict__ num_dev, int P) {
+    if (!num_dev) return P;
+    int v = __builtin_amdgcn_readfirstlane(*num_dev);
+    v = v > 0 ? v : 0;
+    return v < P ? v : P;
+}
 // the pillar constants exactly as k_pfn_fwd derives them (mean over all T slots / n, pillar centre from its coordinates)
 __device__ __forceinline__ PfnPillar pfn_pillar(const float4 *__restrict__ pv, int T, int n, const int *__restrict__ coords, int p,
                                                 float vx, float vy, float xo, float yo, int lane) {
@@ -166,10 +175,12 @@ __device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl
 // tests/test_gpu_pfn_edges.py); in fp64 the kernels keep 7e-8.
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ voxels, const int *__restrict__ num_points,
-                                                     const int *__restrict__ coords, int P, int T, const float *__restrict__ wt, int C,
-                                                     float vx, float vy, float xo, float yo, float *__restrict__ partial,
-                                                     float *__restrict__ partial_s1, double *__restrict__ partial_d) {
+                                                     const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
+                                                     const float *__restrict__ wt, int C, float vx, float vy, float xo, float yo,
+                                                     float *__restrict__ partial, float *__restrict__ partial_s1,
+                                                     double *__restrict__ partial_d) {
     constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
+    P = pfn_live(num_dev, P);
     __shared__ float red[kBlock / 64][64][StatVals + 1];
     __shared__ float red1[kBlock / 64][K];
     __shared__ double redd[kBlock / 64][64][2];
@@ -243,10 +254,12 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {   // 256
 // one block per channel (+ one for S1).  stats[c] layout: mean[C], invstd[C], M[C][K], S1[K]
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict__ partial, const float *__restrict__ partial_s1,
-                                                        const double *__restrict__ partial_d, int blocks, int C, double rows, float eps, float momentum,
+                                                        const double *__restrict__ partial_d, int blocks, int C, int P,
+                                                        const int *__restrict__ num_dev, int T, float eps, float momentum,
                                                         float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ stats) {
     constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
+    const double rows = (double)pfn_live(num_dev, P) * (double)T;      // BatchNorm's N: the live pillars' slots
     __shared__ double sh[kBlock / 64];
     const int c = blockIdx.x;
     if (c == C) {                                     // S1
@@ -266,21 +279,23 @@ __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict
         tot[j] = block_sum_f64(v, sh);
     }
     if (threadIdx.x == 0) {
-        const double mean = tot[0] / rows;
-        double var = tot[1] / rows - mean * mean;
+        // no live pillar (rows == 0, every sum is zero): mean 0, variance 0, the running statistics keep their values
+        const double mean = rows > 0.0 ? tot[0] / rows : 0.0;
+        double var = rows > 0.0 ? tot[1] / rows - mean * mean : 0.0;
         if (var < 0.0) var = 0.0;
         stats[c] = (float)mean;
         stats[C + c] = (float)(1.0 / sqrt(var + (double)eps));
         for (int j = 0; j < K; ++j) stats[(size_t)2 * C + (size_t)c * K + j] = (float)tot[2 + j];
-        if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
-        if (running_var) running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * var * (rows > 1.0 ? rows / (rows - 1.0) : 1.0));
+        if (rows > 0.0 && running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);
+        if (rows > 0.0 && running_var) running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * var * (rows > 1.0 ? rows / (rows - 1.0) : 1.0));
     }
 }
 
 // normalise with the batch statistics, ReLU, max over the slots; argmax[p][c] = slot of the maximum (first one; -1 = a padded slot)
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restrict__ voxels, const int *__restrict__ num_points,
-                                                         const int *__restrict__ coords, int P, int T, const float *__restrict__ wt,
+                                                         const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
+                                                         const float *__restrict__ wt,
                                                          const float *__restrict__ gamma, const float *__restrict__ beta,
                                                          const float *__restrict__ stats, int C, float vx, float vy, float xo,
                                                          float yo, float *__restrict__ out, signed char *__restrict__ argmax) {
@@ -289,6 +304,13 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
     const int p = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (p >= P) return;
     const bool live = lane < C;
+    if (p >= pfn_live(num_dev, P)) {                  // a row of the capacity past the count: defined, and nothing of it is read
+        if (live) {
+            out[(size_t)p * C + lane] = 0.f;
+            argmax[(size_t)p * C + lane] = (signed char)-1;
+        }
+        return;
+    }
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = live ? wt[(size_t)j * C + lane] : 0.f;
@@ -323,11 +345,13 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
 // partial[block][c][BwdVals] = (dbeta, dgamma, A[c][0..K-1])
 template <bool RADIUS>
 __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ voxels, const int *__restrict__ num_points,
-                                                   const int *__restrict__ coords, int P, int T, const float *__restrict__ wt,
-                                                   const float *__restrict__ stats, int C, float vx, float vy, float xo, float yo,
+                                                   const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
+                                                   const float *__restrict__ wt, const float *__restrict__ stats, int C, float vx,
+                                                   float vy, float xo, float yo,
                                                    const float *__restrict__ grad_out, const float *__restrict__ out,
                                                    const signed char *__restrict__ argmax, float *__restrict__ partial) {
     constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
+    P = pfn_live(num_dev, P);
     __shared__ float red[kBlock / 64][64][BwdVals + 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const bool live = lane < C;
@@ -373,12 +397,14 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ vo
 
 // one block per channel: dweight_t[j][c], dgamma[c], dbeta[c]
 template <bool RADIUS>
-__global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__restrict__ partial, int blocks, int C, double rows,
+__global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__restrict__ partial, int blocks, int C, int P,
+                                                            const int *__restrict__ num_dev, int T,
                                                             const float *__restrict__ gamma, const float *__restrict__ stats,
                                                             float *__restrict__ dweight_t, float *__restrict__ dgamma,
                                                             float *__restrict__ dbeta) {
     constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
     __shared__ double sh[kBlock / 64];
+    const double rows = (double)pfn_live(num_dev, P) * (double)T;
     const int c = blockIdx.x;
     double tot[BwdVals];
     for (int j = 0; j < BwdVals; ++j) {
@@ -393,7 +419,9 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__rest
         dgamma[c] = (float)dg;
         for (int j = 0; j < K; ++j) {
             const double s1 = stats[(size_t)C * (2 + K) + j], m = stats[(size_t)2 * C + (size_t)c * K + j];
-            dweight_t[(size_t)j * C + c] = (float)(ga * invstd * (tot[2 + j] - db / rows * s1 - dg / rows * invstd * (m - mean * s1)));
+            // no live pillar: every sum is zero and so is the gradient (0 / 0 is not evaluated)
+            dweight_t[(size_t)j * C + c] =
+                rows > 0.0 ? (float)(ga * invstd * (tot[2 + j] - db / rows * s1 - dg / rows * invstd * (m - mean * s1))) : 0.f;
         }
     }
 }
@@ -621,7 +649,7 @@ SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
 }
 
 template <bool RADIUS>
-static int pfn_train_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+static int pfn_train_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
                              int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
                              float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
                              float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
@@ -630,24 +658,24 @@ static int pfn_train_fwd_any(const float *voxels, const int *num_points, const i
         return SEC_E_INVALID;
     if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < sec_pfn_train_workspace_bytes(num_pillars, channels)) return SEC_E_WORKSPACE;
-    if (num_pillars == 0) return SEC_OK;
+    if (num_pillars == 0 && !num_dev) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int blocks = pfn_blocks(num_pillars);
+    const int blocks = pfn_blocks(num_pillars);      // grids by capacity; every kernel reads the count itself (pfn_live)
     float *partial = (float *)workspace;      // the workspace is carved for nine inputs in both forms (eight need less)
     float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * kPfnStatVals * sizeof(float)));
     double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * kPfnIn * sizeof(float)));
-    hipLaunchKernelGGL(k_pfn_stats<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points,
-                       weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
-    const double rows = (double)num_pillars * (double)max_points;
-    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels, rows, eps,
-                       momentum, running_mean, running_var, stats);
+    hipLaunchKernelGGL(k_pfn_stats<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
+                       max_points, weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
+    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels,
+                       num_pillars, num_dev, max_points, eps, momentum, running_mean, running_var, stats);
+    if (num_pillars == 0) return check_launch();    // a capacity of zero: the statistics of no pillar, nothing else to write
     hipLaunchKernelGGL(k_pfn_fwd_train<RADIUS>, dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
-                       num_pillars, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);
+                       num_pillars, num_dev, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);
     return check_launch();
 }
 
 template <bool RADIUS>
-static int pfn_train_bwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+static int pfn_train_bwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
                              int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
                              float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
                              const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
@@ -666,34 +694,48 @@ static int pfn_train_bwd_any(const float *voxels, const int *num_points, const i
     }
     const int blocks = pfn_blocks(num_pillars);
     float *partial = (float *)workspace;
-    hipLaunchKernelGGL(k_pfn_bwd<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, max_points, weight_t,
-                       stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
-    hipLaunchKernelGGL(k_pfn_bwd_finalize<RADIUS>, dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels,
-                       (double)num_pillars * (double)max_points, gamma, stats, dweight_t, dgamma, dbeta);
+    hipLaunchKernelGGL(k_pfn_bwd<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev, max_points,
+                       weight_t, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
+    hipLaunchKernelGGL(k_pfn_bwd_finalize<RADIUS>, dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels, num_pillars, num_dev,
+                       max_points, gamma, stats, dweight_t, dgamma, dbeta);
     return check_launch();
 }
 
 #define SEC_PFN_TRAIN_FWD_ARGS                                                                                                     \
-    const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points, int num_features,             \
-        const float *weight_t, const float *gamma, const float *beta, float eps, float momentum, float *running_mean,             \
+    const float *voxels, const int *num_points, const int *coords, int num_pillars, SEC_PFN_NUM_DEV_ARG int max_points,           \
+        int num_features, const float *weight_t, const float *gamma, const float *beta, float eps, float momentum, float *running_mean,             \
         float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out, signed char *argmax,    \
         float *stats, void *workspace, size_t workspace_bytes, void *stream
 #define SEC_PFN_TRAIN_FWD_PASS                                                                                                     \
-    voxels, num_points, coords, num_pillars, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
+    voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
         running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats, workspace, workspace_bytes, stream
 #define SEC_PFN_TRAIN_BWD_ARGS                                                                                                     \
-    const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points, int num_features,             \
-        const float *weight_t, const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,          \
+    const float *voxels, const int *num_points, const int *coords, int num_pillars, SEC_PFN_NUM_DEV_ARG int max_points,           \
+        int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,          \
         float y_offset, const float *grad_out, const float *out, const signed char *argmax, float *dweight_t, float *dgamma,      \
         float *dbeta, void *workspace, size_t workspace_bytes, void *stream
 #define SEC_PFN_TRAIN_BWD_PASS                                                                                                     \
-    voxels, num_points, coords, num_pillars, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
+    voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
         y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace, workspace_bytes, stream
+// the entry points of before are the live-count forms with no count (num_dev = NULL: every row is a pillar)
+#define SEC_PFN_NUM_DEV_ARG
+#define SEC_PFN_NUM_DEV nullptr
 SEC_API int sec_pfn_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<false>(SEC_PFN_TRAIN_FWD_PASS); }
 SEC_API int sec_pfn_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<false>(SEC_PFN_TRAIN_BWD_PASS); }
 // PillarFeatureNetRadius in training mode (the RADIUS instantiations): the same arguments, weight_t / dweight_t are [8][channels]
 SEC_API int sec_pfn_radius_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<true>(SEC_PFN_TRAIN_FWD_PASS); }
 SEC_API int sec_pfn_radius_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<true>(SEC_PFN_TRAIN_BWD_PASS); }
+// static capacity: num_pillars rows, the first min(max(*num_dev, 0), num_pillars) of them pillars (device memory, read by the kernels)
+#undef SEC_PFN_NUM_DEV_ARG
+#undef SEC_PFN_NUM_DEV
+#define SEC_PFN_NUM_DEV_ARG const int *num_dev,
+#define SEC_PFN_NUM_DEV num_dev
+SEC_API int sec_pfn_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<false>(SEC_PFN_TRAIN_BWD_PASS); }
+SEC_API int sec_pfn_radius_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<true>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_radius_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<true>(SEC_PFN_TRAIN_BWD_PASS); }
+#undef SEC_PFN_NUM_DEV_ARG
+#undef SEC_PFN_NUM_DEV
 #undef SEC_PFN_TRAIN_FWD_ARGS
 #undef SEC_PFN_TRAIN_FWD_PASS
 #undef SEC_PFN_TRAIN_BWD_ARGS

@@ -409,20 +409,24 @@ class PillarFeatureNet(nn.Module):
 
     train_function = ops.PFNTrainFunction      # the autograd Function of the training kernels for this class's decorated row
 
-    def _forward_train_kernels(self, features, num_voxels, coors):
+    def _forward_train_kernels(self, features, num_voxels, coors, num_dev=None):
         """Training on the device (sec_pfn_train_fwd / _bwd, or their radius forms: batch statistics, argmax backward, no
         [P, T, C] tensor), or None where the torch formulation has to serve: CPU, eval / frozen or non-affine norm, a linear bias,
-        train_backend = "torch", a shape the kernels do not take, no pillars."""
+        train_backend = "torch", a shape the kernels do not take, no pillars.  ``num_dev``: static-capacity pillars with the count
+        on the device (the _live entry points); the torch formulation cannot serve those, so falling through is an error."""
         l = self.pfn_layers[0]
         bn = l.norm
         if not (features.is_cuda and self.training and bn.training and bn.track_running_stats and bn.affine and l.linear.bias is None
                 and self.train_backend == "hip" and ops.pfn_train_supported(features, bn.num_features)
                 and features.shape[0] > 0):
+            if num_dev is not None:
+                raise RuntimeError(f"{type(self).__name__}: a device-side pillar count (num_dev) in training mode needs the HIP "
+                                   "training kernels (GPU, train_backend = 'hip', affine tracked BatchNorm, T <= 127, C <= 64)")
             return None
         mom = bn.momentum if bn.momentum is not None else 0.1
         out = self.train_function.apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
                                         bn.running_mean, bn.running_var, bn.eps, mom,
-                                        (self.vx, self.vy, self.x_offset, self.y_offset))
+                                        (self.vx, self.vy, self.x_offset, self.y_offset), *(() if num_dev is None else (num_dev,)))
         ops.bump_bn_counter(bn)
         return out
 
@@ -432,7 +436,7 @@ class PillarFeatureNet(nn.Module):
             wt, scale, shift = self.folded()
             return ops.pfn_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
                                    self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
-        out = self._forward_train_kernels(features, num_voxels, coors)
+        out = self._forward_train_kernels(features, num_voxels, coors, num_dev)
         if out is not None:
             return out
         n = num_voxels.to(features.dtype).view(-1, 1, 1)
@@ -472,7 +476,7 @@ class PillarFeatureNetRadius(PillarFeatureNet):
             wt, scale, shift = self.folded()
             return ops.pfn_radius_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
                                           self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
-        out = self._forward_train_kernels(features, num_voxels, coors)
+        out = self._forward_train_kernels(features, num_voxels, coors, num_dev)
         if out is not None:
             return out
         n = num_voxels.to(features.dtype).view(-1, 1, 1)
@@ -501,7 +505,7 @@ class PointPillarsScatter(nn.Module):
         if torch.is_grad_enabled() and voxel_features.requires_grad:   # training: differentiable scatter
             from spconv.functional import PillarScatterFunction
             return PillarScatterFunction.apply(voxel_features.contiguous(), coords.int().contiguous(), batch_size,
-                                               self.ny, self.nx, channels_last)
+                                               self.ny, self.nx, channels_last, *(() if num_dev is None else (num_dev,)))
         return ops.pillar_scatter(voxel_features.contiguous(), coords.int().contiguous(), batch_size, self.ny, self.nx,
                                   channels_last=channels_last, num_dev=num_dev)
 

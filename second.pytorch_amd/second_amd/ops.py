@@ -668,11 +668,11 @@ def sparse_to_dense(features, indices, batch_size, spatial_shape, channels_last_
     return out
 
 
-def dense_to_sparse(dense, indices, num_dev=None, depth=0):
+def dense_to_sparse(dense, indices, num_dev=None, depth=0, zero_fill=False):
     """rows[i,:] = dense[b_i, :, (z_i,) y_i, x_i]: the adjoint of :func:`sparse_to_dense` ([B,C,D,H,W]; with ``depth`` = D > 0 of its
     ``channels_last_2d`` form [B, C*D, H, W], channel = c * D + z, in any strides) and of :func:`pillar_scatter` ([B,C,H,W], z
     ignored) -- what autograd needs for their backward.  ``num_dev``: static capacity -- only the first num_dev[0] rows are gathered
-    (the others stay unwritten)."""
+    (the others stay unwritten, or are zero with ``zero_fill``)."""
     rt.require_gpu(dense, indices)
     n = indices.shape[0]
     c = dense.shape[1]
@@ -685,7 +685,7 @@ def dense_to_sparse(dense, indices, num_dev=None, depth=0):
         sb, sc, sz, sy, sx = st[0], st[1] * depth, st[1], st[2], st[3]
     else:
         (sb, sc, sy, sx), sz = st, 0
-    rows = torch.empty((n, c), dtype=dense.dtype, device=dense.device)
+    rows = (torch.zeros if zero_fill else torch.empty)((n, c), dtype=dense.dtype, device=dense.device)
     rc = rt.lib().sec_dense_to_sparse(rt.ptr(dense), rt.ptr(indices.contiguous()), n, c, rt.ptr(num_dev), rt.ptr(rows), sb, sc, sz, sy, sx,
                                       rt.dtype_code(dense.dtype), rt.stream())
     rt.check(rc, "sec_dense_to_sparse")
@@ -789,13 +789,22 @@ class PFNTrainFunction(torch.autograd.Function):
     on sec_pfn_train_fwd / sec_pfn_train_bwd: the [P, T, C] activation tensor of the torch formulation never exists.  Gradients for
     linear.weight [C, 9], the BatchNorm weight and bias; the points get none (they are data).  running_mean / running_var are
     updated in place like torch.nn.BatchNorm1d does.  :class:`PFNRadiusTrainFunction` is the same code on the eight-entry row of
-    PillarFeatureNetRadius (sec_pfn_radius_train_fwd / _bwd, linear.weight [C, 8])."""
+    PillarFeatureNetRadius (sec_pfn_radius_train_fwd / _bwd, linear.weight [C, 8]).
+    ``num_dev`` (optional last argument, int32 [1] on the device): static capacity -- the first min(max(num_dev[0], 0), P) rows are
+    pillars, read by the kernels when they run (sec_pfn_train_fwd_live / _bwd_live and their radius forms), so a captured step
+    replays on any count; the rows past it are never read, their ``out`` rows are zero and they enter no statistic or gradient."""
     K = 9
     FWD, BWD = "sec_pfn_train_fwd", "sec_pfn_train_bwd"
 
     @classmethod
-    def _forward(cls, ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom):
+    def _forward(cls, ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom,
+                 num_dev=None):
         rt.require_gpu(voxels, num_points, coords, weight, gamma, beta)
+        if num_dev is not None:
+            rt.require_gpu(num_dev)
+            assert num_dev.dtype == torch.int32 and num_dev.numel() >= 1
+        live = () if num_dev is None else (rt.ptr(num_dev),)
+        fwd = cls.FWD if num_dev is None else cls.FWD + "_live"
         assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
         p, t, f = voxels.shape
         c, k = weight.shape[0], cls.K
@@ -810,11 +819,12 @@ class PFNTrainFunction(torch.autograd.Function):
         ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
         num_points, coords = num_points.int().contiguous(), coords.contiguous()
         vx, vy, xo, yo = [float(v) for v in geom]
-        rc = getattr(l, cls.FWD)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
-                                 float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c, vx, vy, xo, yo,
-                                 rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, cls.FWD)
+        rc = getattr(l, fwd)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
+                             float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c, vx, vy, xo, yo,
+                             rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
+        rt.check(rc, fwd)
         ctx.save_for_backward(voxels, num_points, coords, wt, ga, stats, out, arg)
+        ctx.num_dev = num_dev
         ctx.geom = (vx, vy, xo, yo)
         ctx.dtypes = (weight.dtype, gamma.dtype, beta.dtype)
         return out
@@ -832,12 +842,14 @@ class PFNTrainFunction(torch.autograd.Function):
         ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
         g = grad_out.float().contiguous()
         vx, vy, xo, yo = ctx.geom
-        rc = getattr(l, cls.BWD)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
-                                 vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt), rt.ptr(dga), rt.ptr(dbe),
-                                 rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, cls.BWD)
+        live = () if ctx.num_dev is None else (rt.ptr(ctx.num_dev),)
+        bwd = cls.BWD if ctx.num_dev is None else cls.BWD + "_live"
+        rc = getattr(l, bwd)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
+                             vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt), rt.ptr(dga), rt.ptr(dbe),
+                             rt.ptr(ws), ws.numel(), rt.stream())
+        rt.check(rc, bwd)
         wd, gd, bd = ctx.dtypes
-        return (None, None, None, dwt.t().contiguous().to(wd), dga.to(gd), dbe.to(bd), None, None, None, None, None)
+        return (None, None, None, dwt.t().contiguous().to(wd), dga.to(gd), dbe.to(bd), None, None, None, None, None, None)
 
     @staticmethod
     def forward(ctx, *args):

@@ -45,6 +45,7 @@ SYMBOLS = [
     "sec_pfn_radius_fwd", "sec_pfn_radius_fwd_slots", "sec_predict_select_segments", "sec_predict_decode_segments",
     "sec_predict_select_classes", "sec_predict_decode_classes", "sec_nms_sorted_items_f32", "sec_predict_finalize_classes",
     "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd",
+    "sec_pfn_train_fwd_live", "sec_pfn_train_bwd_live", "sec_pfn_radius_train_fwd_live", "sec_pfn_radius_train_bwd_live",
     "sec_rpn_tile_cover_lds_bytes", "sec_rpn_tile_cover", "sec_conv2d_nhwc_gather_cover", "sec_conv2d_nhwc_tiles_cover",
     "sec_conv2d_nhwc_tiles_tail_cover", "sec_predict_select_cover", "sec_predict_decode_cover",
 ]
@@ -169,6 +170,9 @@ def lib():
         l.sec_pfn_train_bwd.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, cf, cf, cf, cf, vp, vp, vp, vp, vp, vp, vp, sz, vp]
         l.sec_pfn_radius_train_fwd.argtypes = l.sec_pfn_train_fwd.argtypes
         l.sec_pfn_radius_train_bwd.argtypes = l.sec_pfn_train_bwd.argtypes
+        for name in ("sec_pfn_train_fwd", "sec_pfn_train_bwd", "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd"):
+            at = getattr(l, name).argtypes               # the live-count forms: num_dev after num_pillars
+            getattr(l, name + "_live").argtypes = at[:4] + [vp] + at[4:]
         l.sec_block_filter_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
         l.sec_voxel_block_filter_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp, sz, vp]
         l.sec_bias_act_nhwc.argtypes = [vp, vp, sz, ci, ci, ci, vp]

@@ -84,14 +84,18 @@ class SparseToDenseFunction(torch.autograd.Function):
 
 
 class PillarScatterFunction(torch.autograd.Function):
-    """PointPillarsScatter with a gradient (pointpillars.py:444-476 relies on index assignment under autograd)."""
+    """PointPillarsScatter with a gradient (pointpillars.py:444-476 relies on index assignment under autograd).  ``num_dev`` (int32
+    [1] on the device): static-capacity rows -- only the first num_dev[0] land, and only they get a gradient (the others: zero)."""
 
     @staticmethod
-    def forward(ctx, features, coords, batch_size, ny, nx, channels_last=False):
+    def forward(ctx, features, coords, batch_size, ny, nx, channels_last=False, num_dev=None):
         ctx.save_for_backward(coords)
-        return _ops.pillar_scatter(features, coords, batch_size, ny, nx, channels_last=channels_last)
+        ctx.num_dev = num_dev
+        return _ops.pillar_scatter(features, coords, batch_size, ny, nx, channels_last=channels_last, num_dev=num_dev)
 
     @staticmethod
     def backward(ctx, grad):
         (coords,) = ctx.saved_tensors
-        return _ops.dense_to_sparse(grad, coords), None, None, None, None, None
+        # with a count the rows past it are not gathered: zero-initialised, so that the gradient is defined at capacity
+        rows = _ops.dense_to_sparse(grad, coords, num_dev=ctx.num_dev, zero_fill=ctx.num_dev is not None)
+        return rows, None, None, None, None, None, None
