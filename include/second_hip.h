@@ -564,6 +564,51 @@ int sec_pfn_radius_train_bwd_live(const float *voxels, const int *num_points, co
                                   const float *out, const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* The PillarFeatureNet FAMILY by row kind (the four encoders of pointpillars.py, each with its with_distance option).  One device
+ * function builds the decorated row for every entry point of this section.  m = cluster mean (sum over all T slots / num_points, on
+ * the raw x, y, z), c = pillar centre (coords * voxel size + offset), r = sqrt(x^2 + y^2), h = max_t z - min_t z over ALL T slots
+ * of the pillar (the zero z of a padded slot takes part; lanes beyond T do not), a per-pillar constant:
+ *   SEC_PFN_PLAIN          [x, y, z, w, x-mx, y-my, z-mz, x-cx, y-cy]        9   PillarFeatureNet
+ *   SEC_PFN_RADIUS         [r, z, w, x-mx, y-my, z-mz, x-cx, y-cy]           8   PillarFeatureNetRadius
+ *   SEC_PFN_OLD            [x-cx, y-cy, z, w, x-mx, y-my, z-mz, x-cx, y-cy]  9   PillarFeatureNetOld (the centre offsets stand in
+ *                          the raw x, y columns; the mean is taken before, on raw x, y).  The reference writes them into the
+ *                          caller's tensor; these entry points never write their input
+ *   SEC_PFN_RADIUS_HEIGHT  [r, z, w, x-mx, y-my, z-mz, x-cx, y-cy, h]        9   PillarFeatureNetRadiusHeight
+ * with_distance = 1 appends sqrt(a^2 + b^2 + z^2) as the LAST entry (after h), a, b = raw x, y (OLD: x-cx, y-cy): three products,
+ * two adds left to right, a square root, each correctly rounded.  Every entry of a padded slot is zero.
+ * sec_pfn_row_width = K, the entries per row (0 for an unknown kind or with_distance outside {0, 1}); weight_t / dweight_t are
+ * [K][C], stats is f32[C * (2 + K) + K] laid out as above.  The argument lists are those of sec_pfn_fwd / sec_pfn_fwd_slots and of
+ * the _live training forms (num_dev may be NULL) with (kind, with_distance) in front; workspace by
+ * sec_pfn_kind_train_workspace_bytes (its per-channel pitch follows K).  Decided on the host before any launch: unknown kind or
+ * with_distance outside {0, 1}: SEC_E_INVALID; num_features != 4, and in training max_points > 127 or channels > 64:
+ * SEC_E_UNSUPPORTED; a workspace below the query: SEC_E_WORKSPACE.  PLAIN / RADIUS without distance run the very kernels of
+ * sec_pfn_fwd / sec_pfn_radius_* (bit-identical results). */
+#define SEC_PFN_PLAIN 0
+#define SEC_PFN_RADIUS 1
+#define SEC_PFN_OLD 2
+#define SEC_PFN_RADIUS_HEIGHT 3
+int sec_pfn_row_width(int kind, int with_distance);
+int sec_pfn_kind_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords, int num_pillars,
+                     const int *num_dev, int max_points, int num_features, const float *weight_t, const float *scale,
+                     const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
+                     int out_dtype, void *stream);
+int sec_pfn_kind_fwd_slots(int kind, int with_distance, const float *points, const void *vox_workspace, size_t vox_workspace_bytes,
+                           int vox_num_points, int vox_batch, int vox_max_voxels, int max_points, int num_features,
+                           const int *num_points_per_voxel, const int *coords, int num_pillars, const int *num_dev,
+                           const float *weight_t, const float *scale, const float *shift, int channels, float vx, float vy,
+                           float x_offset, float y_offset, void *out, int out_dtype, void *stream);
+size_t sec_pfn_kind_train_workspace_bytes(int kind, int with_distance, int num_pillars, int channels);
+int sec_pfn_kind_train_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                           int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                           const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
+                           float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out,
+                           signed char *argmax, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+int sec_pfn_kind_train_bwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                           int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                           const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,
+                           float y_offset, const float *grad_out, const float *out, const signed char *argmax, float *dweight_t,
+                           float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Block filtering of points_to_voxel_3d_with_filtering (spconv point2voxel.h; enabled by
  * second/configs/nuscenes/all.fhd.config:9-12): keep a voxel iff the z-span of the stored points inside the
  * block_size x block_size block window around it lies in (height_threshold, height_high_threshold); the

@@ -23,18 +23,46 @@ template <> __device__ __forceinline__ __half cvt_out(float v) { return __float2
 
 // The decorated row of one point, shared by inference (k_pfn_fwd) and the training kernels below, so that both evaluate the very
 // same expressions (the library is built with -ffp-contract=off: the radius is multiply, multiply, add, square root, each correctly
-// rounded).  RADIUS = false: [x, y, z, w, x - mx, y - my, z - mz, x - cx, y - cy] (9); RADIUS = true: [r, z, w, x - mx, y - my,
-// z - mz, x - cx, y - cy] (8) with r = sqrt(x * x + y * y); the cluster mean and the pillar centre are Cartesian in both.
-template <bool RADIUS>
-__device__ __forceinline__ void pfn_row(const float4 q, float mx, float my, float mz, float cx, float cy, float (&f)[RADIUS ? 8 : 9]) {
-    constexpr int IN = RADIUS ? 8 : 9;
-    if constexpr (RADIUS) {
+// rounded).  The four encoders of pointpillars.py by KIND (SEC_PFN_*), m = cluster mean, c = pillar centre, both Cartesian in all:
+//   kPfnPlain         [x, y, z, w, x - mx, y - my, z - mz, x - cx, y - cy]            (9)
+//   kPfnRadius        [r, z, w, x - mx, y - my, z - mz, x - cx, y - cy]               (8)  r = sqrt(x * x + y * y)
+//   kPfnOld           [x - cx, y - cy, z, w, x - mx, y - my, z - mz, x - cx, y - cy]  (9)  the reference writes the centre offsets
+//                     through a view into the raw x, y columns AFTER it took the mean: columns 0, 1 repeat columns 7, 8 bit for bit
+//   kPfnRadiusHeight  [r, z, w, x - mx, y - my, z - mz, x - cx, y - cy, h]            (9)  h = max z - min z over the pillar's T slots
+// DIST (with_distance) appends sqrt(a * a + b * b + z * z) over the first three feature columns as the reference holds them at that
+// point: raw x, y, z, and for kPfnOld the centred x - cx, y - cy with raw z; it comes last (after h): three products, the adds left
+// to right, the square root.
+enum { kPfnPlain = SEC_PFN_PLAIN, kPfnRadius = SEC_PFN_RADIUS, kPfnOld = SEC_PFN_OLD, kPfnRadiusHeight = SEC_PFN_RADIUS_HEIGHT };
+constexpr int pfn_width(int kind, bool dist) { return (kind == kPfnRadius ? 8 : 9) + (dist ? 1 : 0); }
+template <int KIND, bool DIST>
+__device__ __forceinline__ void pfn_row(const float4 q, float mx, float my, float mz, float cx, float cy, float h,
+                                        float (&f)[pfn_width(KIND, DIST)]) {
+    constexpr bool POLAR = KIND == kPfnRadius || KIND == kPfnRadiusHeight;
+    constexpr int B = POLAR ? 3 : 4;                  // the raw part's width
+    if constexpr (POLAR) {
         f[0] = __fsqrt_rn(__fadd_rn(__fmul_rn(q.x, q.x), __fmul_rn(q.y, q.y)));
         f[1] = q.z; f[2] = q.w;
     } else {
         f[0] = q.x; f[1] = q.y; f[2] = q.z; f[3] = q.w;
     }
-    f[IN - 5] = q.x - mx; f[IN - 4] = q.y - my; f[IN - 3] = q.z - mz; f[IN - 2] = q.x - cx; f[IN - 1] = q.y - cy;
+    f[B] = q.x - mx; f[B + 1] = q.y - my; f[B + 2] = q.z - mz; f[B + 3] = q.x - cx; f[B + 4] = q.y - cy;
+    if constexpr (KIND == kPfnOld) { f[0] = f[B + 3]; f[1] = f[B + 4]; }       // the centred columns stand where raw x, y stood
+    if constexpr (KIND == kPfnRadiusHeight) f[B + 5] = h;
+    if constexpr (DIST) {
+        const float a = KIND == kPfnOld ? f[0] : q.x, b = KIND == kPfnOld ? f[1] : q.y;
+        f[pfn_width(KIND, DIST) - 1] =
+            __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)), __fmul_rn(q.z, q.z)));
+    }
+}
+// h of kPfnRadiusHeight: the wave's max z - min z.  A lane holds the extrema of the slots it read (a padded slot's zero z among them,
+// as the reference's min / max over the whole tensor has it) or the identities +inf / -inf when it read none (lanes >= T).
+__device__ __forceinline__ float wave_span(float lo, float hi) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, d, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, d, 64));
+    }
+    return __fsub_rn(hi, lo);
 }
 
 // F = 4 point features (x, y, z, r/dt), IN = 9 decorated features
@@ -42,10 +70,10 @@ __device__ __forceinline__ void pfn_row(const float4 q, float mx, float my, floa
 // t-th point, vox_slots_of): the pillar's points are fetched through the list instead of from a [P, T, 4] tensor -- the same
 // values in the same positions (slots >= n read as zero), so the result is bit-identical, and the voxeliser need not write (nor
 // this kernel re-read) that tensor: 98 MB each way at 100 k pillars x 60 slots.
-// RADIUS: PillarFeatureNetRadius (pointpillars.py:290-325): the decorated row is [hypot(x, y), z, w, x - mx, y - my, z - mz, x - cx,
-// y - cy] (IN = 8; the raw x, y give way to their radius, in the arithmetic store_radius_row4 pins to torch.norm); the cluster mean
-// and the pillar centre stay Cartesian, as above.
-template <typename OT, bool SLOTS = false, bool RADIUS = false>
+// KIND / DIST: the decorated row of pfn_row (kPfnRadius: the raw x, y give way to their radius, in the arithmetic store_radius_row4
+// pins to torch.norm); the cluster mean and the pillar centre stay Cartesian, as above.  kPfnRadiusHeight takes min / max z in the
+// mean pass, over the same T slots (SLOTS: the slots >= n read as zero there too).
+template <typename OT, bool SLOTS = false, int KIND = kPfnPlain, bool DIST = false>
 __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                    const int *__restrict__ coords, int P, const int *__restrict__ num_dev,
                                                    int T, const float *__restrict__ wt, const float *__restrict__ scale,
@@ -63,21 +91,25 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
     // pillar mean over all T slots (padded slots are zero) / n
     float sx = 0.f, sy = 0.f, sz = 0.f;
     float4 mine = make_float4(0, 0, 0, 0);            // T <= 64: lane t keeps point t for the channel loop below
+    float zlo = INFINITY, zhi = -INFINITY;
     for (int t0 = 0; t0 < T; t0 += 64) {
         float4 q = make_float4(0, 0, 0, 0);
         if (t0 + lane < T) {
             if (SLOTS) { if (t0 + lane < n) q = pv[sl[t0 + lane]]; }
             else q = pv[t0 + lane];
+            if constexpr (KIND == kPfnRadiusHeight) { zlo = fminf(zlo, q.z); zhi = fmaxf(zhi, q.z); }
         }
         if (t0 == 0) mine = q;
         sx += q.x; sy += q.y; sz += q.z;
     }
     const float inv = (float)n;
     const float mx = wave_sum(sx) / inv, my = wave_sum(sy) / inv, mz = wave_sum(sz) / inv;
+    float h = 0.f;
+    if constexpr (KIND == kPfnRadiusHeight) h = wave_span(zlo, zhi);
     for (int c0 = 0; c0 < C; c0 += 64) {
         const int c = c0 + lane;
         const bool live = c < C;
-        constexpr int IN = RADIUS ? 8 : 9;
+        constexpr int IN = pfn_width(KIND, DIST);
         float w[IN];
 #pragma unroll
         for (int j = 0; j < IN; ++j) w[j] = live ? wt[(size_t)j * C + c] : 0.f;
@@ -96,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
                 q = SLOTS ? pv[sl[t]] : pv[t];            // wave-uniform address: one broadcast load
             }
             float f[IN];
-            pfn_row<RADIUS>(q, mx, my, mz, cx, cy, f);
+            pfn_row<KIND, DIST>(q, mx, my, mz, cx, cy, h, f);
             float y = 0.f;
 #pragma unroll
             for (int j = 0; j < IN; ++j) y = fmaf(f[j], w[j], y);
@@ -122,19 +154,19 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
 //                   xhat * dgamma / N)); summed against the inputs that is closed form in S1 and M:
 //                   dW[c][j] = gamma_c invstd_c (A[c][j] - dbeta_c / N * S1[j] - dgamma_c / N * invstd_c (M[c][j] - mean_c S1[j]))
 // No gradient with respect to the points (they are data).
-// RADIUS (PillarFeatureNetRadius, pointpillars.py:290-325 under train()): the same five kernels on the eight-entry row of pfn_row<true>;
-// a padded slot is zero in all eight entries (the reference masks after decorating), so it is the same x = 0 row as above.
-constexpr int kPfnIn = 9;                         // the wider of the two rows: what the workspace is sized for
-template <bool RADIUS> struct PfnDims {
-    static constexpr int K = RADIUS ? 8 : 9;      // decorated inputs
+// KIND / DIST (the other encoders of pointpillars.py under train()): the same five kernels on the K-entry row of pfn_row<KIND, DIST>;
+// a padded slot is zero in all K entries (the reference masks after decorating, h and the distance included), so it is the same
+// x = 0 row as above.
+constexpr int kPfnIn = 9;                         // sec_pfn_train_workspace_bytes' row width (the entry points of before carve by it)
+template <int KIND, bool DIST> struct PfnDims {
+    static constexpr int K = pfn_width(KIND, DIST);   // decorated inputs
     static constexpr int StatVals = 2 + K;        // per channel: sum x, sum x^2, M[c][0..K-1]
     static constexpr int BwdVals = 2 + K;         // per channel: dbeta, dgamma, A[c][0..K-1]
 };
-constexpr int kPfnStatVals = 2 + kPfnIn;          // the workspace's per-channel pitch (both forms carve it alike)
 constexpr int kPfnMaxBlocks = 1024;
 
 struct PfnPillar {
-    float mx, my, mz, cx, cy;
+    float mx, my, mz, cx, cy, h;
     int n;
 };
 // Static capacity (the *_live entry points): the arrays hold P rows, of which the first min(max(*num_dev, 0), P) are pillars; the
@@ -146,7 +178,9 @@ __device__ __forceinline__ int pfn_live(const int *__restrict__ num_dev, int P) 
     v = v > 0 ? v : 0;
     return v < P ? v : P;
 }
-// the pillar constants exactly as k_pfn_fwd derives them (mean over all T slots / n, pillar centre from its coordinates)
+// the pillar constants exactly as k_pfn_fwd derives them (mean over all T slots / n, pillar centre from its coordinates, and for
+// kPfnRadiusHeight max z - min z over the T slots; h = 0 and no work for it otherwise)
+template <int KIND>
 __device__ __forceinline__ PfnPillar pfn_pillar(const float4 *__restrict__ pv, int T, int n, const int *__restrict__ coords, int p,
                                                 float vx, float vy, float xo, float yo, int lane) {
     const int4 co = *reinterpret_cast<const int4 *>(coords + (size_t)p * 4);
@@ -154,18 +188,23 @@ __device__ __forceinline__ PfnPillar pfn_pillar(const float4 *__restrict__ pv, i
     r.cx = __fadd_rn(__fmul_rn((float)co.w, vx), xo);
     r.cy = __fadd_rn(__fmul_rn((float)co.z, vy), yo);
     float sx = 0.f, sy = 0.f, sz = 0.f;
+    float zlo = INFINITY, zhi = -INFINITY;
     for (int t0 = 0; t0 < T; t0 += 64) {
         float4 q = (t0 + lane < T) ? pv[t0 + lane] : make_float4(0, 0, 0, 0);
         sx += q.x; sy += q.y; sz += q.z;
+        if constexpr (KIND == kPfnRadiusHeight)
+            if (t0 + lane < T) { zlo = fminf(zlo, q.z); zhi = fmaxf(zhi, q.z); }
     }
     const float inv = (float)n;
     r.mx = wave_sum(sx) / inv; r.my = wave_sum(sy) / inv; r.mz = wave_sum(sz) / inv;
+    r.h = 0.f;
+    if constexpr (KIND == kPfnRadiusHeight) r.h = wave_span(zlo, zhi);
     r.n = n < T ? n : T;
     return r;
 }
-template <bool RADIUS>
-__device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl, float (&f)[RADIUS ? 8 : 9]) {
-    pfn_row<RADIUS>(q, pl.mx, pl.my, pl.mz, pl.cx, pl.cy, f);
+template <int KIND, bool DIST>
+__device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl, float (&f)[pfn_width(KIND, DIST)]) {
+    pfn_row<KIND, DIST>(q, pl.mx, pl.my, pl.mz, pl.cx, pl.cy, pl.h, f);
 }
 
 // partial[block][c][StatVals], partial_s1[block][K], partial_d[block][c][2]; C <= 64 (one wave = all channels)
@@ -173,13 +212,13 @@ __device__ __forceinline__ void pfn_decorate(const float4 q, const PfnPillar &pl
 // sum x^2 / N - mean^2, and a channel with |mean| >> std (a cloud offset from the origin, an intensity in 0..255) cancels there: at
 // mean^2 / var = 550 fp32 sums per wave lost 3.8e-6 of invstd where torch's float32 BatchNorm keeps 2.2e-7 (the offset case of
 // tests/test_gpu_pfn_edges.py); in fp64 the kernels keep 7e-8.
-template <bool RADIUS>
+template <int KIND, bool DIST>
 __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                      const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
                                                      const float *__restrict__ wt, int C, float vx, float vy, float xo, float yo,
                                                      float *__restrict__ partial, float *__restrict__ partial_s1,
                                                      double *__restrict__ partial_d) {
-    constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
+    constexpr int K = PfnDims<KIND, DIST>::K, StatVals = PfnDims<KIND, DIST>::StatVals;
     P = pfn_live(num_dev, P);
     __shared__ float red[kBlock / 64][64][StatVals + 1];
     __shared__ float red1[kBlock / 64][K];
@@ -197,10 +236,10 @@ __global__ __launch_bounds__(kBlock) void k_pfn_stats(const float *__restrict__ 
     double sum = 0.0, sq = 0.0;
     for (int p = blockIdx.x * (kBlock / 64) + wv; p < P; p += gridDim.x * (kBlock / 64)) {
         const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
-        const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
+        const PfnPillar pl = pfn_pillar<KIND>(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
         for (int t = 0; t < pl.n; ++t) {
             float f[K];
-            pfn_decorate<RADIUS>(pv[t], pl, f);
+            pfn_decorate<KIND, DIST>(pv[t], pl, f);
             float x = 0.f;
 #pragma unroll
             for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
@@ -252,13 +291,13 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {   // 256
 }
 
 // one block per channel (+ one for S1).  stats[c] layout: mean[C], invstd[C], M[C][K], S1[K]
-template <bool RADIUS>
+template <int KIND, bool DIST>
 __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict__ partial, const float *__restrict__ partial_s1,
                                                         const double *__restrict__ partial_d, int blocks, int C, int P,
                                                         const int *__restrict__ num_dev, int T, float eps, float momentum,
                                                         float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ stats) {
-    constexpr int K = PfnDims<RADIUS>::K, StatVals = PfnDims<RADIUS>::StatVals;
+    constexpr int K = PfnDims<KIND, DIST>::K, StatVals = PfnDims<KIND, DIST>::StatVals;
     const double rows = (double)pfn_live(num_dev, P) * (double)T;      // BatchNorm's N: the live pillars' slots
     __shared__ double sh[kBlock / 64];
     const int c = blockIdx.x;
@@ -292,14 +331,14 @@ __global__ __launch_bounds__(kBlock) void k_pfn_finalize(const float *__restrict
 }
 
 // normalise with the batch statistics, ReLU, max over the slots; argmax[p][c] = slot of the maximum (first one; -1 = a padded slot)
-template <bool RADIUS>
+template <int KIND, bool DIST>
 __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                          const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
                                                          const float *__restrict__ wt,
                                                          const float *__restrict__ gamma, const float *__restrict__ beta,
                                                          const float *__restrict__ stats, int C, float vx, float vy, float xo,
                                                          float yo, float *__restrict__ out, signed char *__restrict__ argmax) {
-    constexpr int K = PfnDims<RADIUS>::K;
+    constexpr int K = PfnDims<KIND, DIST>::K;
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (p >= P) return;
@@ -317,12 +356,12 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
     const float mean = live ? stats[lane] : 0.f, invstd = live ? stats[C + lane] : 0.f;
     const float ga = live ? gamma[lane] : 0.f, be = live ? beta[lane] : 0.f;
     const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
-    const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
+    const PfnPillar pl = pfn_pillar<KIND>(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
     float best = -INFINITY;
     int arg = -1;
     for (int t = 0; t < pl.n; ++t) {
         float f[K];
-        pfn_decorate<RADIUS>(pv[t], pl, f);
+        pfn_decorate<KIND, DIST>(pv[t], pl, f);
         float x = 0.f;
 #pragma unroll
         for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
@@ -343,14 +382,14 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd_train(const float *__restric
 }
 
 // partial[block][c][BwdVals] = (dbeta, dgamma, A[c][0..K-1])
-template <bool RADIUS>
+template <int KIND, bool DIST>
 __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ voxels, const int *__restrict__ num_points,
                                                    const int *__restrict__ coords, int P, const int *__restrict__ num_dev, int T,
                                                    const float *__restrict__ wt, const float *__restrict__ stats, int C, float vx,
                                                    float vy, float xo, float yo,
                                                    const float *__restrict__ grad_out, const float *__restrict__ out,
                                                    const signed char *__restrict__ argmax, float *__restrict__ partial) {
-    constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
+    constexpr int K = PfnDims<KIND, DIST>::K, BwdVals = PfnDims<KIND, DIST>::BwdVals;
     P = pfn_live(num_dev, P);
     __shared__ float red[kBlock / 64][64][BwdVals + 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -364,7 +403,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ vo
     for (int j = 0; j < BwdVals; ++j) acc[j] = 0.f;
     for (int p = blockIdx.x * (kBlock / 64) + wv; p < P; p += gridDim.x * (kBlock / 64)) {
         const float4 *pv = reinterpret_cast<const float4 *>(voxels) + (size_t)p * T;
-        const PfnPillar pl = pfn_pillar(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
+        const PfnPillar pl = pfn_pillar<KIND>(pv, T, num_points[p], coords, p, vx, vy, xo, yo, lane);
         if (!live) continue;
         const float g = grad_out[(size_t)p * C + lane];
         const float dz = out[(size_t)p * C + lane] > 0.f ? g : 0.f;
@@ -374,7 +413,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ vo
 #pragma unroll
         for (int j = 0; j < K; ++j) f[j] = 0.f;
         if (t >= 0) {
-            pfn_decorate<RADIUS>(pv[t], pl, f);
+            pfn_decorate<KIND, DIST>(pv[t], pl, f);
 #pragma unroll
             for (int j = 0; j < K; ++j) x = fmaf(f[j], w[j], x);
         }
@@ -396,13 +435,13 @@ __global__ __launch_bounds__(kBlock) void k_pfn_bwd(const float *__restrict__ vo
 }
 
 // one block per channel: dweight_t[j][c], dgamma[c], dbeta[c]
-template <bool RADIUS>
+template <int KIND, bool DIST>
 __global__ __launch_bounds__(kBlock) void k_pfn_bwd_finalize(const float *__restrict__ partial, int blocks, int C, int P,
                                                             const int *__restrict__ num_dev, int T,
                                                             const float *__restrict__ gamma, const float *__restrict__ stats,
                                                             float *__restrict__ dweight_t, float *__restrict__ dgamma,
                                                             float *__restrict__ dbeta) {
-    constexpr int K = PfnDims<RADIUS>::K, BwdVals = PfnDims<RADIUS>::BwdVals;
+    constexpr int K = PfnDims<KIND, DIST>::K, BwdVals = PfnDims<KIND, DIST>::BwdVals;
     __shared__ double sh[kBlock / 64];
     const double rows = (double)pfn_live(num_dev, P) * (double)T;
     const int c = blockIdx.x;
@@ -560,7 +599,7 @@ static BfWorkspace carve_bf(void *ws, size_t cap, int rows, int batch, int bx, i
 
 using namespace sec;
 
-template <bool RADIUS>
+template <int KIND, bool DIST>
 static int pfn_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
                         int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
                         int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
@@ -570,7 +609,7 @@ static int pfn_fwd_any(const float *voxels, const int *num_points, const int *co
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, false, RADIUS>), grid, block, 0, st, voxels, num_points, coords, num_pillars, num_dev, \
+#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, false, KIND, DIST>), grid, block, 0, st, voxels, num_points, coords, num_pillars, num_dev, \
                                        max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out)
     if (out_dtype == SEC_F32) SEC_PFN(float);
     else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
@@ -580,7 +619,7 @@ static int pfn_fwd_any(const float *voxels, const int *num_points, const int *co
     return check_launch();
 }
 
-template <bool RADIUS>
+template <int KIND, bool DIST>
 static int pfn_fwd_slots_any(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
                               int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
                               const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
@@ -597,7 +636,7 @@ static int pfn_fwd_slots_any(const float *points, const void *vox_workspace, siz
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, true, RADIUS>), grid, block, 0, st, points, num_points_per_voxel, coords, num_pillars, num_dev, \
+#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, true, KIND, DIST>), grid, block, 0, st, points, num_points_per_voxel, coords, num_pillars, num_dev, \
                                        max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out, slots)
     if (out_dtype == SEC_F32) SEC_PFN(float);
     else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
@@ -611,7 +650,7 @@ SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *c
                         int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
                         int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
                         void *stream) {
-    return pfn_fwd_any<false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
+    return pfn_fwd_any<kPfnPlain, false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
                                vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
 SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
@@ -619,16 +658,16 @@ SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, si
                               const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
                               const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
                               int out_dtype, void *stream) {
-    return pfn_fwd_slots_any<false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
+    return pfn_fwd_slots_any<kPfnPlain, false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
                                      num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
                                      vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
-// PillarFeatureNetRadius (k_pfn_fwd<.., RADIUS>): the same arguments, weight_t is [num_features + 4][channels]
+// PillarFeatureNetRadius (k_pfn_fwd<.., kPfnRadius>): the same arguments, weight_t is [num_features + 4][channels]
 SEC_API int sec_pfn_radius_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
                         int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
                         int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
                         void *stream) {
-    return pfn_fwd_any<true>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
+    return pfn_fwd_any<kPfnRadius, false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
                                vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
 SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
@@ -636,20 +675,26 @@ SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_worksp
                               const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
                               const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
                               int out_dtype, void *stream) {
-    return pfn_fwd_slots_any<true>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
+    return pfn_fwd_slots_any<kPfnRadius, false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
                                      num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
                                      vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
 
-SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
+// the training workspace for rows of `width` entries: partial[blocks][C][2 + width], partial_s1[blocks][width], partial_d[blocks][C][2]
+static size_t pfn_train_ws_bytes(int width, int num_pillars, int channels) {
     if (num_pillars < 0 || channels <= 0 || channels > 64) return 0;
     const size_t b = (size_t)pfn_blocks(num_pillars);
-    return align_up(b * channels * kPfnStatVals * sizeof(float)) + align_up(b * kPfnIn * sizeof(float)) +
+    return align_up(b * channels * (2 + width) * sizeof(float)) + align_up(b * width * sizeof(float)) +
            align_up(b * channels * 2 * sizeof(double));
 }
+SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
+    return pfn_train_ws_bytes(kPfnIn, num_pillars, channels);
+}
 
-template <bool RADIUS>
-static int pfn_train_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
+// `width`: the row width the caller's workspace was sized and is carved for (>= the kind's K; the per-block partials themselves are
+// pitched by the kind's own K): kPfnIn from the entry points of before, the kind's K from sec_pfn_kind_train_*
+template <int KIND, bool DIST>
+static int pfn_train_fwd_any(int width, const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
                              int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
                              float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
                              float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
@@ -657,25 +702,25 @@ static int pfn_train_fwd_any(const float *voxels, const int *num_points, const i
     if (num_pillars < 0 || max_points <= 0 || max_points > 127 || channels <= 0 || !weight_t || !gamma || !beta || !out || !argmax || !stats)
         return SEC_E_INVALID;
     if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
-    if (!workspace || workspace_bytes < sec_pfn_train_workspace_bytes(num_pillars, channels)) return SEC_E_WORKSPACE;
+    if (!workspace || workspace_bytes < pfn_train_ws_bytes(width, num_pillars, channels)) return SEC_E_WORKSPACE;
     if (num_pillars == 0 && !num_dev) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = pfn_blocks(num_pillars);      // grids by capacity; every kernel reads the count itself (pfn_live)
-    float *partial = (float *)workspace;      // the workspace is carved for nine inputs in both forms (eight need less)
-    float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * kPfnStatVals * sizeof(float)));
-    double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * kPfnIn * sizeof(float)));
-    hipLaunchKernelGGL(k_pfn_stats<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
+    float *partial = (float *)workspace;      // carved for `width` inputs (the radius form of before: for nine, eight need less)
+    float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * (2 + width) * sizeof(float)));
+    double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * width * sizeof(float)));
+    hipLaunchKernelGGL((k_pfn_stats<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
                        max_points, weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
-    hipLaunchKernelGGL(k_pfn_finalize<RADIUS>, dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels,
+    hipLaunchKernelGGL((k_pfn_finalize<KIND, DIST>), dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels,
                        num_pillars, num_dev, max_points, eps, momentum, running_mean, running_var, stats);
     if (num_pillars == 0) return check_launch();    // a capacity of zero: the statistics of no pillar, nothing else to write
-    hipLaunchKernelGGL(k_pfn_fwd_train<RADIUS>, dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
+    hipLaunchKernelGGL((k_pfn_fwd_train<KIND, DIST>), dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
                        num_pillars, num_dev, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);
     return check_launch();
 }
 
-template <bool RADIUS>
-static int pfn_train_bwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
+template <int KIND, bool DIST>
+static int pfn_train_bwd_any(int width, const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
                              int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
                              float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
                              const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
@@ -684,19 +729,19 @@ static int pfn_train_bwd_any(const float *voxels, const int *num_points, const i
         !argmax || !dweight_t || !dgamma || !dbeta)
         return SEC_E_INVALID;
     if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
-    if (!workspace || workspace_bytes < sec_pfn_train_workspace_bytes(num_pillars, channels)) return SEC_E_WORKSPACE;
+    if (!workspace || workspace_bytes < pfn_train_ws_bytes(width, num_pillars, channels)) return SEC_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (num_pillars == 0) {
-        int rc = fill_words(dweight_t, sizeof(float) * PfnDims<RADIUS>::K * channels, 0u, st);
+        int rc = fill_words(dweight_t, sizeof(float) * PfnDims<KIND, DIST>::K * channels, 0u, st);
         if (!rc) rc = fill_words(dgamma, sizeof(float) * channels, 0u, st);
         if (!rc) rc = fill_words(dbeta, sizeof(float) * channels, 0u, st);
         return rc;
     }
     const int blocks = pfn_blocks(num_pillars);
     float *partial = (float *)workspace;
-    hipLaunchKernelGGL(k_pfn_bwd<RADIUS>, dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev, max_points,
+    hipLaunchKernelGGL((k_pfn_bwd<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev, max_points,
                        weight_t, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
-    hipLaunchKernelGGL(k_pfn_bwd_finalize<RADIUS>, dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels, num_pillars, num_dev,
+    hipLaunchKernelGGL((k_pfn_bwd_finalize<KIND, DIST>), dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels, num_pillars, num_dev,
                        max_points, gamma, stats, dweight_t, dgamma, dbeta);
     return check_launch();
 }
@@ -707,7 +752,7 @@ static int pfn_train_bwd_any(const float *voxels, const int *num_points, const i
         float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out, signed char *argmax,    \
         float *stats, void *workspace, size_t workspace_bytes, void *stream
 #define SEC_PFN_TRAIN_FWD_PASS                                                                                                     \
-    voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
+    kPfnIn, voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
         running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats, workspace, workspace_bytes, stream
 #define SEC_PFN_TRAIN_BWD_ARGS                                                                                                     \
     const float *voxels, const int *num_points, const int *coords, int num_pillars, SEC_PFN_NUM_DEV_ARG int max_points,           \
@@ -715,31 +760,108 @@ static int pfn_train_bwd_any(const float *voxels, const int *num_points, const i
         float y_offset, const float *grad_out, const float *out, const signed char *argmax, float *dweight_t, float *dgamma,      \
         float *dbeta, void *workspace, size_t workspace_bytes, void *stream
 #define SEC_PFN_TRAIN_BWD_PASS                                                                                                     \
-    voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
+    kPfnIn, voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
         y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace, workspace_bytes, stream
 // the entry points of before are the live-count forms with no count (num_dev = NULL: every row is a pillar)
 #define SEC_PFN_NUM_DEV_ARG
 #define SEC_PFN_NUM_DEV nullptr
-SEC_API int sec_pfn_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<false>(SEC_PFN_TRAIN_BWD_PASS); }
-// PillarFeatureNetRadius in training mode (the RADIUS instantiations): the same arguments, weight_t / dweight_t are [8][channels]
-SEC_API int sec_pfn_radius_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<true>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_radius_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<true>(SEC_PFN_TRAIN_BWD_PASS); }
+SEC_API int sec_pfn_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_BWD_PASS); }
+// PillarFeatureNetRadius in training mode (the kPfnRadius instantiations): the same arguments, weight_t / dweight_t are [8][channels]
+SEC_API int sec_pfn_radius_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_radius_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_BWD_PASS); }
 // static capacity: num_pillars rows, the first min(max(*num_dev, 0), num_pillars) of them pillars (device memory, read by the kernels)
 #undef SEC_PFN_NUM_DEV_ARG
 #undef SEC_PFN_NUM_DEV
 #define SEC_PFN_NUM_DEV_ARG const int *num_dev,
 #define SEC_PFN_NUM_DEV num_dev
-SEC_API int sec_pfn_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<false>(SEC_PFN_TRAIN_BWD_PASS); }
-SEC_API int sec_pfn_radius_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<true>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_radius_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<true>(SEC_PFN_TRAIN_BWD_PASS); }
+SEC_API int sec_pfn_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_BWD_PASS); }
+SEC_API int sec_pfn_radius_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_FWD_PASS); }
+SEC_API int sec_pfn_radius_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_BWD_PASS); }
 #undef SEC_PFN_NUM_DEV_ARG
 #undef SEC_PFN_NUM_DEV
 #undef SEC_PFN_TRAIN_FWD_ARGS
 #undef SEC_PFN_TRAIN_FWD_PASS
 #undef SEC_PFN_TRAIN_BWD_ARGS
 #undef SEC_PFN_TRAIN_BWD_PASS
+
+// ---- the family by row kind: one switch from (kind, with_distance) to the instantiation ------------------------------------------
+SEC_API int sec_pfn_row_width(int kind, int with_distance) {
+    if (kind < kPfnPlain || kind > kPfnRadiusHeight || (with_distance != 0 && with_distance != 1)) return 0;
+    return pfn_width(kind, with_distance != 0);
+}
+// CALL(KIND, DIST) for the pair the caller named; kPfnPlain / kPfnRadius without distance are the instantiations behind sec_pfn_fwd /
+// sec_pfn_radius_* themselves
+#define SEC_PFN_BY_KIND(CALL)                                                                  \
+    switch (kind * 2 + with_distance) {                                                        \
+    case kPfnPlain * 2: return CALL(kPfnPlain, false);                                         \
+    case kPfnPlain * 2 + 1: return CALL(kPfnPlain, true);                                      \
+    case kPfnRadius * 2: return CALL(kPfnRadius, false);                                       \
+    case kPfnRadius * 2 + 1: return CALL(kPfnRadius, true);                                    \
+    case kPfnOld * 2: return CALL(kPfnOld, false);                                             \
+    case kPfnOld * 2 + 1: return CALL(kPfnOld, true);                                          \
+    case kPfnRadiusHeight * 2: return CALL(kPfnRadiusHeight, false);                           \
+    default: return CALL(kPfnRadiusHeight, true);                                              \
+    }
+SEC_API int sec_pfn_kind_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                             int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                             const float *scale, const float *shift, int channels, float vx, float vy, float x_offset,
+                             float y_offset, void *out, int out_dtype, void *stream) {
+    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
+#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
+    pfn_fwd_any<KIND, DIST>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift,     \
+                            channels, vx, vy, x_offset, y_offset, out, out_dtype, stream)
+    SEC_PFN_BY_KIND(SEC_PFN_CALL)
+#undef SEC_PFN_CALL
+}
+SEC_API int sec_pfn_kind_fwd_slots(int kind, int with_distance, const float *points, const void *vox_workspace,
+                                   size_t vox_workspace_bytes, int vox_num_points, int vox_batch, int vox_max_voxels, int max_points,
+                                   int num_features, const int *num_points_per_voxel, const int *coords, int num_pillars,
+                                   const int *num_dev, const float *weight_t, const float *scale, const float *shift, int channels,
+                                   float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype, void *stream) {
+    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
+#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
+    pfn_fwd_slots_any<KIND, DIST>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points, \
+                                  num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels, \
+                                  vx, vy, x_offset, y_offset, out, out_dtype, stream)
+    SEC_PFN_BY_KIND(SEC_PFN_CALL)
+#undef SEC_PFN_CALL
+}
+SEC_API size_t sec_pfn_kind_train_workspace_bytes(int kind, int with_distance, int num_pillars, int channels) {
+    const int width = sec_pfn_row_width(kind, with_distance);
+    return width ? pfn_train_ws_bytes(width, num_pillars, channels) : 0;
+}
+SEC_API int sec_pfn_kind_train_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                                   int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                                   const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
+                                   float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out,
+                                   signed char *argmax, float *stats, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
+    if (max_points > 127) return SEC_E_UNSUPPORTED;       // the int8 argmax; (the entry points of before answer SEC_E_INVALID)
+#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
+    pfn_train_fwd_any<KIND, DIST>(pfn_width(KIND, DIST), voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, \
+                                  weight_t, gamma, beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset,      \
+                                  y_offset, out, argmax, stats, workspace, workspace_bytes, stream)
+    SEC_PFN_BY_KIND(SEC_PFN_CALL)
+#undef SEC_PFN_CALL
+}
+SEC_API int sec_pfn_kind_train_bwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                                   int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                                   const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,
+                                   float y_offset, const float *grad_out, const float *out, const signed char *argmax,
+                                   float *dweight_t, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
+    if (max_points > 127) return SEC_E_UNSUPPORTED;       // the int8 argmax; (the entry points of before answer SEC_E_INVALID)
+#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
+    pfn_train_bwd_any<KIND, DIST>(pfn_width(KIND, DIST), voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, \
+                                  weight_t, gamma, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t,   \
+                                  dgamma, dbeta, workspace, workspace_bytes, stream)
+    SEC_PFN_BY_KIND(SEC_PFN_CALL)
+#undef SEC_PFN_CALL
+}
+#undef SEC_PFN_BY_KIND
 
 SEC_API size_t sec_block_filter_workspace_bytes(int rows, int batch, int grid_x, int grid_y, int block_factor) {
     if (rows < 0 || batch <= 0 || block_factor <= 0) return 0;

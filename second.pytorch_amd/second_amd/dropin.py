@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .models import SecondDetector
+from .models import PILLAR_VFES, VFES, SecondDetector
 
 
 class NotAccelerable(NotImplementedError):
@@ -108,7 +108,7 @@ def model_config(net, multiclass_nms=False):
     why = []
     vfe, mid, rpn = net.voxel_feature_extractor, net.middle_feature_extractor, net.rpn
     vfe_t, mid_t, rpn_t = type(vfe).__name__, type(mid).__name__, type(rpn).__name__
-    pillar_vfes = ("PillarFeatureNet", "PillarFeatureNetRadius")
+    pillar_vfes = PILLAR_VFES
     if vfe_t not in ("SimpleVoxel", "SimpleVoxelRadius") + pillar_vfes:
         why.append(f"voxel feature extractor {vfe_t}")
     if mid_t not in SPARSE_MIDDLE_STRIDE and mid_t != "PointPillarsScatter":
@@ -188,10 +188,13 @@ def model_config(net, multiclass_nms=False):
         cfg.update(vfe="SimpleVoxelRadius")
     if pillars:
         lin = vfe.pfn_layers[0].linear
-        extra = 5 if vfe_t == "PillarFeatureNet" else 4          # PillarFeatureNetRadius: (x, y) -> r
+        # the decorated row of the module's kind beyond the four point features (PillarFeatureNetRadius: (x, y) -> r; RadiusHeight:
+        # + h; with_distance: one more).  PillarFeatureNetOld centres the caller's voxels in place; the device path never writes them
+        with_distance = bool(getattr(vfe, "_with_distance", False))
+        extra = ops.pfn_row_width(VFES[vfe_t].kind, with_distance) - 4
         if len(vfe.pfn_layers) != 1 or lin.in_features != int(net._num_input_features) + extra:
             raise NotAccelerable(f"accelerate_model: {vfe_t} other than one layer on (x, y, z, r) + {extra} decorations")
-        cfg.update(vfe=vfe_t, vfe_filters=[int(lin.out_features)])
+        cfg.update(vfe=vfe_t, vfe_filters=[int(lin.out_features)], vfe_with_distance=with_distance)
     if heads:
         cfg.update(rpn_class="RPNNoHead", heads=heads)
     if not use_dir:

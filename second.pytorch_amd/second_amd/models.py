@@ -206,6 +206,36 @@ ALL_PP_MHEAD = dict(
 )  # second/configs/nuscenes/all.pp.mhead.config (VoxelNetNuscenesMultiHead: 120 000 + 204 800 anchors)
 
 
+ALL_PP_MIDA = dict(
+    name="nuscenes/all.pp.mida",
+    point_cloud_range=[-50, -50, -5, 50, 50, 3], voxel_size=[0.25, 0.25, 8], max_points_per_voxel=60,
+    max_voxels=30000, num_point_features=4,
+    # PillarFeatureNetOld: the centre offsets stand in the raw x, y columns too (models.PillarFeatureNetOld); with_distance: false
+    vfe="PillarFeatureNetOld", vfe_filters=[64], vfe_with_distance=False, middle="PointPillarsScatter", middle_in=64,
+    rpn=dict(layer_nums=[3, 5, 5], layer_strides=[2, 2, 2], num_filters=[64, 128, 256],
+             upsample_strides=[0.5, 1, 2], num_upsample_filters=[128, 128, 128], num_input_features=64),
+    downsample_factor=4,       # 400 x 400 pillars -> one 100 x 100 map, 20 anchors per cell
+    # car, bicycle, bus, construction_vehicle, motorcycle, pedestrian, traffic_cone, trailer (2 sizes), truck, barrier
+    anchor_sizes=[[1.95017717, 4.60718145, 1.72270761], [0.60058911, 1.68452161, 1.27192197], [2.94046906, 11.1885991, 3.47030982],
+                  [2.73050468, 6.38352896, 3.13312415], [0.76279481, 2.09973778, 1.44403034], [0.66344886, 0.7256437, 1.75748069],
+                  [0.39694519, 0.40359262, 1.06232151], [3, 15, 3.8], [2, 3, 3.8], [2.4560939, 6.73778078, 2.73004906],
+                  [2.49008838, 0.48578221, 0.98297065]],
+    anchor_ranges=[[-50, -50, z, 50, 50, z] for z in
+                   (-0.93897414, -1.03743013, -0.0715754, -0.08168083, -0.99194854, -0.73911038, -1.27868911,
+                    0.22228277, 0.22228277, -0.37937912, -1.27247968)],
+    anchor_groups=[[0], [1], [2], [3], [4], [5], [6], [7, 8], [9], [10]],
+    rotations=[0, 1.57], group_rotations={5: [0], 6: [0]},   # pedestrian / traffic_cone: one rotation
+    group_class_ids=[1, 2, 3, 4, 5, 6, 7, 8, 9, 10], matched_thresholds=[0.25, 0.2, 0.5, 0.4, 0.2, 0.5, 0.5, 0.5, 0.5, 0.3],
+    unmatched_thresholds=[0.2, 0.15, 0.35, 0.3, 0.15, 0.35, 0.35, 0.35, 0.35, 0.2], assign_per_class=True,
+    # pedestrian / traffic_cone: distance_similarity { distance_norm: 1.414, with_rotation: false, rotation_alpha: 0.0 }
+    group_similarity=[None if gi not in (5, 6) else dict(kind="distance", distance_norm=1.414, with_rotation=False, rotation_alpha=0.0)
+                      for gi in range(10)],
+    num_class=10, num_direction_bins=2, direction_offset=0.0, direction_limit_offset=0.0,   # no direction_offset in the config
+    nms_score_threshold=0.05, nms_pre_max_size=1000, nms_post_max_size=300, nms_iou_threshold=0.5,
+    use_rotate_nms=False, post_center_range=[-59.6, -59.6, -10, 59.6, 59.6, 10],
+)  # second/configs/nuscenes/all.pp.mida.config (VoxelNet, one head: 100 x 100 x 20 = 200 000 anchors)
+
+
 def anchor_area_threshold_of(cfg):
     """The config's ``anchor_area_threshold`` when it asks for the anchor-area mask (>= 0), else None."""
     thr = cfg.get("anchor_area_threshold", -1)
@@ -376,14 +406,25 @@ class PillarFeatureNet(nn.Module):
     backward through the argmax; train_backend = "torch" selects the formulation below); the torch formulation serves CPU
     tests and as the autograd reference of the training kernels."""
 
-    def __init__(self, num_input_features=4, num_filters=(64,), voxel_size=(0.2, 0.2, 4), pc_range=(0, -40, -3, 70.4, 40, 1)):
+    kind = ops.PFN_PLAIN        # the decorated row (ops.PFN_*; include/second_hip.h); the subclasses differ in nothing else
+
+    def __init__(self, num_input_features=4, num_filters=(64,), voxel_size=(0.2, 0.2, 4), pc_range=(0, -40, -3, 70.4, 40, 1),
+                 with_distance=False):
         super().__init__()
         assert len(num_filters) == 1, "the shipped PointPillars configs use a single PFN layer"
-        self.pfn_layers = nn.ModuleList([PFNLayer(num_input_features + 5, num_filters[0])])
+        self.with_distance = bool(with_distance)      # one more entry per row: the point's distance (see decorate)
+        self._with_distance = self.with_distance      # (the reference's attribute name: what dropin.model_config reads)
+        self.pfn_layers = nn.ModuleList([PFNLayer(num_input_features - 4 + ops.pfn_row_width(self.kind, self.with_distance),
+                                                  num_filters[0])])
         self.vx, self.vy = voxel_size[0], voxel_size[1]
         self.x_offset, self.y_offset = self.vx / 2 + pc_range[0], self.vy / 2 + pc_range[1]
 
     train_backend = "hip"       # "torch": the reference's materialised [P, T, C] formulation in training (A/B, tests)
+
+    @property
+    def _family(self):
+        """True where the row is not one of the two the entry points of before build (sec_pfn_* / sec_pfn_radius_*)."""
+        return self.with_distance or self.kind not in (ops.PFN_PLAIN, ops.PFN_RADIUS)
 
     def folded(self):
         """(W^T, scale, shift) of Linear + BatchNorm1d in eval mode; cached until one of the five tensors changes (in-place updates
@@ -405,9 +446,12 @@ class PillarFeatureNet(nn.Module):
         [P, T, 4] pillar tensor is neither written nor read; bit-identical to :meth:`forward` on the materialised pillars."""
         wt, scale, shift = self.folded()
         return ops.pfn_forward_slots(points, vox, wt, scale, shift, self.vx, self.vy, self.x_offset, self.y_offset,
-                                     out_dtype=out_dtype, num_dev=num_dev)
+                                     out_dtype=out_dtype, num_dev=num_dev, kind=self.kind, with_distance=self.with_distance)
 
     train_function = ops.PFNTrainFunction      # the autograd Function of the training kernels for this class's decorated row
+
+    def _train_function(self):
+        return ops.pfn_kind_train_function(self.kind, self.with_distance) if self._family else self.train_function
 
     def _forward_train_kernels(self, features, num_voxels, coors, num_dev=None):
         """Training on the device (sec_pfn_train_fwd / _bwd, or their radius forms: batch statistics, argmax backward, no
@@ -424,30 +468,55 @@ class PillarFeatureNet(nn.Module):
                                    "training kernels (GPU, train_backend = 'hip', affine tracked BatchNorm, T <= 127, C <= 64)")
             return None
         mom = bn.momentum if bn.momentum is not None else 0.1
-        out = self.train_function.apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
+        out = self._train_function().apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
                                         bn.running_mean, bn.running_var, bn.eps, mom,
                                         (self.vx, self.vy, self.x_offset, self.y_offset), *(() if num_dev is None else (num_dev,)))
         ops.bump_bn_counter(bn)
         return out
 
     def forward(self, features, num_voxels, coors, out_dtype=None, num_dev=None):
-        l = self.pfn_layers[0]
         if features.is_cuda and not self.training and not torch.is_grad_enabled():
             wt, scale, shift = self.folded()
             return ops.pfn_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
-                                   self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
+                                   self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev, kind=self.kind,
+                                   with_distance=self.with_distance)
         out = self._forward_train_kernels(features, num_voxels, coors, num_dev)
         if out is not None:
             return out
+        return self._forward_torch(features, num_voxels, coors)
+
+    def decorate(self, features, num_voxels, coors):
+        """The decorated, masked rows [P, T, K] of this class's kind in torch -- the formulation for the CPU, for autograd through eval
+        mode and for train_backend = "torch"; the table of include/second_hip.h (SEC_PFN_*).  ``features`` is only read: the
+        reference's PillarFeatureNetOld writes the centre offsets into the caller's x, y columns (a second call on the same example
+        centres twice there); here the centred columns are new tensors."""
         n = num_voxels.to(features.dtype).view(-1, 1, 1)
         xyz = features[:, :, :3]
         mean = xyz.sum(1, keepdim=True) / n
         cx = coors[:, 3].to(features.dtype).view(-1, 1) * self.vx + self.x_offset
         cy = coors[:, 2].to(features.dtype).view(-1, 1) * self.vy + self.y_offset
-        dec = torch.cat([features, xyz - mean, (features[:, :, 0] - cx).unsqueeze(-1), (features[:, :, 1] - cy).unsqueeze(-1)], -1)
+        centre = torch.stack([features[:, :, 0] - cx, features[:, :, 1] - cy], -1)
+        if self.kind in (ops.PFN_RADIUS, ops.PFN_RADIUS_HEIGHT):
+            raw = torch.cat([torch.linalg.vector_norm(features[:, :, :2], ord=2, dim=2, keepdim=True), features[:, :, 2:]], -1)
+        elif self.kind == ops.PFN_OLD:
+            raw = torch.cat([centre, features[:, :, 2:]], -1)
+        else:
+            raw = features
+        parts = [raw, xyz - mean, centre]
+        if self.kind == ops.PFN_RADIUS_HEIGHT:        # max z - min z over ALL slots of the tensor, the padded zeros among them
+            z = features[:, :, 2:3]
+            parts.append((z.max(dim=1, keepdim=True)[0] - z.min(dim=1, keepdim=True)[0]).expand_as(z))
+        if self.with_distance:                        # over the first three columns as the reference holds them: Old's are centred
+            first3 = raw[:, :, :3] if self.kind == ops.PFN_OLD else xyz
+            parts.append(torch.linalg.vector_norm(first3, ord=2, dim=2, keepdim=True))
+        dec = torch.cat(parts, -1)
         t = features.shape[1]
         mask = (torch.arange(t, device=features.device).view(1, -1) < num_voxels.view(-1, 1)).to(features.dtype)
-        x = l.linear(dec * mask.unsqueeze(-1))
+        return dec * mask.unsqueeze(-1)
+
+    def _forward_torch(self, features, num_voxels, coors):
+        l = self.pfn_layers[0]
+        x = l.linear(self.decorate(features, num_voxels, coors))
         x = F.relu(l.norm(x.permute(0, 2, 1)).permute(0, 2, 1))
         return x.max(dim=1)[0]
 
@@ -461,17 +530,11 @@ class PillarFeatureNetRadius(PillarFeatureNet):
 
     train_function = ops.PFNRadiusTrainFunction
 
-    def __init__(self, num_input_features=4, num_filters=(64,), voxel_size=(0.2, 0.2, 4), pc_range=(0, -40, -3, 70.4, 40, 1)):
-        super().__init__(num_input_features, num_filters, voxel_size, pc_range)
-        self.pfn_layers = nn.ModuleList([PFNLayer(num_input_features + 4, num_filters[0])])
-
-    def forward_slots(self, points, vox, out_dtype=None, num_dev=None):
-        wt, scale, shift = self.folded()
-        return ops.pfn_forward_slots(points, vox, wt, scale, shift, self.vx, self.vy, self.x_offset, self.y_offset,
-                                     out_dtype=out_dtype, num_dev=num_dev, radius=True)
+    kind = ops.PFN_RADIUS
 
     def forward(self, features, num_voxels, coors, out_dtype=None, num_dev=None):
-        l = self.pfn_layers[0]
+        if self.with_distance:
+            return super().forward(features, num_voxels, coors, out_dtype=out_dtype, num_dev=num_dev)
         if features.is_cuda and not self.training and not torch.is_grad_enabled():
             wt, scale, shift = self.folded()
             return ops.pfn_radius_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
@@ -479,19 +542,24 @@ class PillarFeatureNetRadius(PillarFeatureNet):
         out = self._forward_train_kernels(features, num_voxels, coors, num_dev)
         if out is not None:
             return out
-        n = num_voxels.to(features.dtype).view(-1, 1, 1)
-        xyz = features[:, :, :3]
-        mean = xyz.sum(1, keepdim=True) / n
-        cx = coors[:, 3].to(features.dtype).view(-1, 1) * self.vx + self.x_offset
-        cy = coors[:, 2].to(features.dtype).view(-1, 1) * self.vy + self.y_offset
-        radius = torch.linalg.vector_norm(features[:, :, :2], ord=2, dim=2, keepdim=True)
-        dec = torch.cat([radius, features[:, :, 2:], xyz - mean, (features[:, :, 0] - cx).unsqueeze(-1),
-                         (features[:, :, 1] - cy).unsqueeze(-1)], -1)
-        t = features.shape[1]
-        mask = (torch.arange(t, device=features.device).view(1, -1) < num_voxels.view(-1, 1)).to(features.dtype)
-        x = l.linear(dec * mask.unsqueeze(-1))
-        x = F.relu(l.norm(x.permute(0, 2, 1)).permute(0, 2, 1))
-        return x.max(dim=1)[0]
+        return self._forward_torch(features, num_voxels, coors)
+
+
+class PillarFeatureNetOld(PillarFeatureNet):
+    """One-layer PillarFeatureNetOld (pointpillars.py:68-151; nuscenes/all.pp.mida, all.pp.deprecated): the centre offsets stand in
+    the raw x, y columns as well -- [x - cx, y - cy, z, w, x - mx, y - my, z - mz, x - cx, y - cy] -- because the reference writes
+    them through a view of its input, after it took the cluster mean on the raw x, y.  Linear(num_input_features + 5, C), keys
+    pfn_layers.0.{linear,norm}; sec_pfn_kind_fwd / _fwd_slots / _train_fwd / _train_bwd with SEC_PFN_OLD.  The reference's side
+    effect is NOT reproduced: the caller's ``voxels`` are never written (there a second call on the same example centres twice)."""
+    kind = ops.PFN_OLD
+
+
+class PillarFeatureNetRadiusHeight(PillarFeatureNet):
+    """One-layer PillarFeatureNetRadiusHeight (pointpillars.py:328-417): PillarFeatureNetRadius' row with the pillar's height h =
+    max z - min z appended, taken over all T slots of the pillar tensor (the zero z of a padded slot takes part, as in the
+    reference's min / max over dim 1) and masked to zero on padded slots like every entry.  Linear(num_input_features + 5, C);
+    sec_pfn_kind_* with SEC_PFN_RADIUS_HEIGHT."""
+    kind = ops.PFN_RADIUS_HEIGHT
 
 
 class PointPillarsScatter(nn.Module):
@@ -616,8 +684,9 @@ class SpMiddleFHDPeople(SpMiddlePlanned):
 
 
 VFES = {"SimpleVoxel": SimpleVoxel, "SimpleVoxelRadius": SimpleVoxelRadius, "PillarFeatureNet": PillarFeatureNet,
-        "PillarFeatureNetRadius": PillarFeatureNetRadius}
-PILLAR_VFES = ("PillarFeatureNet", "PillarFeatureNetRadius")
+        "PillarFeatureNetRadius": PillarFeatureNetRadius, "PillarFeatureNetOld": PillarFeatureNetOld,
+        "PillarFeatureNetRadiusHeight": PillarFeatureNetRadiusHeight}
+PILLAR_VFES = ("PillarFeatureNet", "PillarFeatureNetRadius", "PillarFeatureNetOld", "PillarFeatureNetRadiusHeight")
 MIDDLES = {"SpMiddleFHD": SpMiddleFHD, "SpMiddleFHDLite": SpMiddleFHDLite, "SpMiddleFHDPeople": SpMiddleFHDPeople}
 
 
@@ -1663,7 +1732,8 @@ class SecondDetector(nn.Module):
         self.encoder = "SimpleVoxelRadius" if cfg.get("vfe") == "SimpleVoxelRadius" else "SimpleVoxel"
         if self.pillars:
             self.voxel_feature_extractor = VFES[cfg["vfe"]](cfg["num_point_features"], cfg["vfe_filters"], cfg["voxel_size"],
-                                                            cfg["point_cloud_range"])
+                                                            cfg["point_cloud_range"],
+                                                            with_distance=bool(cfg.get("vfe_with_distance", False)))
             self.middle_feature_extractor = PointPillarsScatter(dense_shape, cfg["middle_in"])
         else:
             self.voxel_feature_extractor = VFES[cfg.get("vfe", "SimpleVoxel")](cfg["num_point_features"])

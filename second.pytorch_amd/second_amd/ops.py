@@ -707,23 +707,38 @@ def pillar_scatter(features, coords, batch_size, ny, nx, channels_last=False, nu
     return out
 
 
+PFN_PLAIN, PFN_RADIUS, PFN_OLD, PFN_RADIUS_HEIGHT = rt.SEC_PFN_PLAIN, rt.SEC_PFN_RADIUS, rt.SEC_PFN_OLD, rt.SEC_PFN_RADIUS_HEIGHT
+
+
+def pfn_row_width(kind, with_distance=False):
+    """Entries of the decorated row of a PillarFeatureNet ``kind`` (PFN_*; include/second_hip.h): 9 / 8 / 9 / 9, one more with the
+    distance.  Arithmetic on the two arguments (as sec_pfn_row_width answers it): needs no library."""
+    if kind not in (PFN_PLAIN, PFN_RADIUS, PFN_OLD, PFN_RADIUS_HEIGHT):
+        raise ValueError(f"unknown PillarFeatureNet row kind {kind!r}")
+    return (8 if kind == PFN_RADIUS else 9) + (1 if with_distance else 0)
+
+
 @_traced("pfn_forward")
 def pfn_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None,
-                num_dev=None):
+                num_dev=None, kind=PFN_PLAIN, with_distance=False):
     """Fused PillarFeatureNet (one PFNLayer, eval): decorate -> Linear(9,C) -> folded BN -> ReLU -> max over points
     (second/pytorch/models/pointpillars.py:203-237,51-65).  voxels [P,T,4] fp32, coords [P,4] (b,z,y,x),
-    weight_t [9,C] = linear.weight.T, scale/shift fp32 [C]."""
+    weight_t [9,C] = linear.weight.T, scale/shift fp32 [C].
+    ``kind`` / ``with_distance``: the other encoders of the family on sec_pfn_kind_fwd (PFN_RADIUS, PFN_OLD, PFN_RADIUS_HEIGHT, each
+    with the optional distance entry; weight_t is [pfn_row_width(kind, with_distance), C]).  The defaults make the sec_pfn_fwd call
+    of before.  The input is never written (the reference's PillarFeatureNetOld centres the caller's x, y columns in place)."""
     rt.require_gpu(voxels, num_points, coords, weight_t, scale, shift)
     assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
     p, t, f = voxels.shape
     c = weight_t.shape[1]
-    assert weight_t.shape[0] == f + 5 and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
+    assert weight_t.shape[0] == f - 4 + pfn_row_width(kind, with_distance) and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
     out_dtype = out_dtype or torch.float32
     out = torch.empty((p, c), dtype=out_dtype, device=voxels.device)
-    rc = rt.lib().sec_pfn_fwd(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p, rt.ptr(num_dev), t, f,
-                              rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset),
-                              float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
-    rt.check(rc, "sec_pfn_fwd")
+    name, lead = ("sec_pfn_fwd", ()) if kind == PFN_PLAIN and not with_distance else ("sec_pfn_kind_fwd", (int(kind), int(bool(with_distance))))
+    rc = getattr(rt.lib(), name)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p, rt.ptr(num_dev), t, f,
+                                 rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset),
+                                 float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
+    rt.check(rc, name)
     return out
 
 
@@ -797,14 +812,23 @@ class PFNTrainFunction(torch.autograd.Function):
     FWD, BWD = "sec_pfn_train_fwd", "sec_pfn_train_bwd"
 
     @classmethod
+    def _entry(cls, which, num_dev):
+        """(entry point, leading arguments, the num_dev argument if the form takes one) of ``which`` = "fwd" / "bwd"."""
+        name = cls.FWD if which == "fwd" else cls.BWD
+        return (name, (), ()) if num_dev is None else (name + "_live", (), (rt.ptr(num_dev),))
+
+    @classmethod
+    def _workspace_bytes(cls, p, c):
+        return rt.lib().sec_pfn_train_workspace_bytes(p, c)
+
+    @classmethod
     def _forward(cls, ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom,
                  num_dev=None):
         rt.require_gpu(voxels, num_points, coords, weight, gamma, beta)
         if num_dev is not None:
             rt.require_gpu(num_dev)
             assert num_dev.dtype == torch.int32 and num_dev.numel() >= 1
-        live = () if num_dev is None else (rt.ptr(num_dev),)
-        fwd = cls.FWD if num_dev is None else cls.FWD + "_live"
+        fwd, lead, live = cls._entry("fwd", num_dev)
         assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
         p, t, f = voxels.shape
         c, k = weight.shape[0], cls.K
@@ -816,10 +840,10 @@ class PFNTrainFunction(torch.autograd.Function):
         arg = torch.empty((p, c), dtype=torch.int8, device=dev)
         stats = torch.empty((c * (2 + k) + k,), dtype=torch.float32, device=dev)
         l = rt.lib()
-        ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
+        ws = rt.workspace(cls._workspace_bytes(p, c), dev)
         num_points, coords = num_points.int().contiguous(), coords.contiguous()
         vx, vy, xo, yo = [float(v) for v in geom]
-        rc = getattr(l, fwd)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
+        rc = getattr(l, fwd)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
                              float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c, vx, vy, xo, yo,
                              rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
         rt.check(rc, fwd)
@@ -839,12 +863,11 @@ class PFNTrainFunction(torch.autograd.Function):
         dga = torch.empty((c,), dtype=torch.float32, device=dev)
         dbe = torch.empty((c,), dtype=torch.float32, device=dev)
         l = rt.lib()
-        ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), dev)
+        ws = rt.workspace(cls._workspace_bytes(p, c), dev)
         g = grad_out.float().contiguous()
         vx, vy, xo, yo = ctx.geom
-        live = () if ctx.num_dev is None else (rt.ptr(ctx.num_dev),)
-        bwd = cls.BWD if ctx.num_dev is None else cls.BWD + "_live"
-        rc = getattr(l, bwd)(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
+        bwd, lead, live = cls._entry("bwd", ctx.num_dev)
+        rc = getattr(l, bwd)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
                              vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt), rt.ptr(dga), rt.ptr(dbe),
                              rt.ptr(ws), ws.numel(), rt.stream())
         rt.check(rc, bwd)
@@ -858,6 +881,47 @@ class PFNTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         return PFNTrainFunction._backward(ctx, grad_out)
+
+
+class PFNKindTrainFunction(PFNTrainFunction):
+    """:class:`PFNTrainFunction` for any encoder of the family on sec_pfn_kind_train_fwd / _bwd: a subclass sets ``KIND`` (PFN_*) and
+    ``WITH_DISTANCE``, from which the row width K follows (linear.weight and its gradient are [C, K], stats f32[C * (2 + K) + K]);
+    :func:`pfn_kind_train_function` makes them.  ``num_dev`` as in the base class (the entry points take NULL for "every row")."""
+    KIND, WITH_DISTANCE = PFN_PLAIN, False
+    K = 9
+
+    @classmethod
+    def _entry(cls, which, num_dev):
+        lead = (int(cls.KIND), int(bool(cls.WITH_DISTANCE)))
+        return "sec_pfn_kind_train_" + which, lead, (rt.ptr(num_dev),)
+
+    @classmethod
+    def _workspace_bytes(cls, p, c):
+        return rt.lib().sec_pfn_kind_train_workspace_bytes(int(cls.KIND), int(bool(cls.WITH_DISTANCE)), p, c)
+
+    @staticmethod
+    def forward(ctx, *args):
+        raise NotImplementedError("use a subclass made by pfn_kind_train_function(kind, with_distance)")
+
+
+_pfn_kind_functions = {}
+
+
+def pfn_kind_train_function(kind, with_distance=False):
+    """The :class:`PFNKindTrainFunction` subclass of one (kind, with_distance) pair; one class per pair, made on first use."""
+    key = (int(kind), bool(with_distance))
+    fn = _pfn_kind_functions.get(key)
+    if fn is None:
+        def forward(ctx, *args):
+            return fn._forward(ctx, *args)
+
+        def backward(ctx, grad_out):
+            return fn._backward(ctx, grad_out)
+
+        fn = _pfn_kind_functions[key] = type(
+            f"PFNKind{key[0]}{'Dist' if key[1] else ''}TrainFunction", (PFNKindTrainFunction,),
+            dict(KIND=key[0], WITH_DISTANCE=key[1], K=pfn_row_width(*key), forward=staticmethod(forward), backward=staticmethod(backward)))
+    return fn
 
 
 class PFNRadiusTrainFunction(PFNTrainFunction):
@@ -876,21 +940,31 @@ class PFNRadiusTrainFunction(PFNTrainFunction):
 
 
 @_traced("pfn_forward")
-def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None, num_dev=None, radius=False):
+def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None, num_dev=None, radius=False,
+                      kind=None, with_distance=False):
     """:func:`pfn_forward` straight from the voxeliser's point lists: ``vox`` = the result of ``voxelize(points, ..., fill=False)``
     (or with fill), ``points`` the array it was called on.  Bit-identical to the tensor form; no [P, T, 4] tensor is read.
-    ``radius``: :func:`pfn_radius_forward` the same way (sec_pfn_radius_fwd_slots)."""
+    ``radius``: :func:`pfn_radius_forward` the same way (sec_pfn_radius_fwd_slots).  ``kind`` / ``with_distance``: any encoder of the
+    family (sec_pfn_kind_fwd_slots); PFN_PLAIN / PFN_RADIUS without distance make the calls of before."""
     rt.require_gpu(points, weight_t, scale, shift)
-    assert weight_t.shape[0] == points.shape[1] + (4 if radius else 5) and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
-    kind, ws, n, max_voxels, max_points, _ = vox["site_table"]
-    assert kind == "vox" and points.shape[0] == n and points.dtype == torch.float32 and points.is_contiguous()
+    if kind is None:
+        kind = PFN_RADIUS if radius else PFN_PLAIN
+    assert not radius or kind == PFN_RADIUS, "radius=True names PFN_RADIUS"
+    assert (weight_t.shape[0] == points.shape[1] - 4 + pfn_row_width(kind, with_distance) and weight_t.dtype == torch.float32
+            and weight_t.is_contiguous())
+    table, ws, n, max_voxels, max_points, _ = vox["site_table"]
+    assert table == "vox" and points.shape[0] == n and points.dtype == torch.float32 and points.is_contiguous()
     npv, coords = vox["num_points_per_voxel"], vox["coordinates"].contiguous()
     p, c = coords.shape[0], weight_t.shape[1]
     batch = vox["voxel_offsets"].numel() - 1
     out_dtype = out_dtype or torch.float32
     out = torch.empty((p, c), dtype=out_dtype, device=points.device)
-    name = "sec_pfn_radius_fwd_slots" if radius else "sec_pfn_fwd_slots"
-    rc = getattr(rt.lib(), name)(rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels, max_points, points.shape[1],
+    lead = ()
+    if with_distance or kind not in (PFN_PLAIN, PFN_RADIUS):
+        name, lead = "sec_pfn_kind_fwd_slots", (int(kind), int(bool(with_distance)))
+    else:
+        name = "sec_pfn_radius_fwd_slots" if kind == PFN_RADIUS else "sec_pfn_fwd_slots"
+    rc = getattr(rt.lib(), name)(*lead, rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels, max_points, points.shape[1],
                                  rt.ptr(npv), rt.ptr(coords), p, rt.ptr(num_dev), rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c,
                                  float(vx), float(vy), float(x_offset), float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype),
                                  rt.stream())

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libsecond_hip.so")
 LIB_PATH = os.environ.get("SEC_HIP_LIB", LIB_PATH)   # A/B builds: point at another libsecond_hip.so
 
 SEC_F32, SEC_F16, SEC_BF16 = 0, 1, 2
+SEC_PFN_PLAIN, SEC_PFN_RADIUS, SEC_PFN_OLD, SEC_PFN_RADIUS_HEIGHT = 0, 1, 2, 3      # row kinds of the sec_pfn_kind_* entry points
 ABI_VERSION = 9          # include/second_hip.h SEC_ABI_VERSION the argtypes in lib() were written for
 _DTYPES = {torch.float32: SEC_F32, torch.float16: SEC_F16, torch.bfloat16: SEC_BF16}
 _ERRORS = {-1: "SEC_E_INVALID (bad argument)", -2: "SEC_E_WORKSPACE (workspace too small)",
@@ -46,6 +47,8 @@ SYMBOLS = [
     "sec_predict_select_classes", "sec_predict_decode_classes", "sec_nms_sorted_items_f32", "sec_predict_finalize_classes",
     "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd",
     "sec_pfn_train_fwd_live", "sec_pfn_train_bwd_live", "sec_pfn_radius_train_fwd_live", "sec_pfn_radius_train_bwd_live",
+    "sec_pfn_row_width", "sec_pfn_kind_fwd", "sec_pfn_kind_fwd_slots", "sec_pfn_kind_train_workspace_bytes", "sec_pfn_kind_train_fwd",
+    "sec_pfn_kind_train_bwd",
     "sec_rpn_tile_cover_lds_bytes", "sec_rpn_tile_cover", "sec_conv2d_nhwc_gather_cover", "sec_conv2d_nhwc_tiles_cover",
     "sec_conv2d_nhwc_tiles_tail_cover", "sec_predict_select_cover", "sec_predict_decode_cover",
 ]
@@ -117,6 +120,7 @@ def lib():
                      "sec_conv2d_packed_weight_bytes", "sec_indice_conv_bwd_workspace_bytes",
                      "sec_assign_targets_workspace_bytes", "sec_second_loss_workspace_bytes", "sec_heads_loss_workspace_bytes",
                      "sec_conv2d_wgrad_workspace_bytes", "sec_bn_train_workspace_bytes", "sec_pfn_train_workspace_bytes",
+                     "sec_pfn_kind_train_workspace_bytes",
                      "sec_flat_adamw_workspace_bytes", "sec_db_sample_merge_points_workspace_bytes",
                      "sec_anchor_area_mask_workspace_bytes", "sec_kitti_eval_pr_workspace_bytes",
                      "sec_kitti_annos_workspace_bytes", "sec_train_metrics_workspace_bytes"):
@@ -173,6 +177,13 @@ def lib():
         for name in ("sec_pfn_train_fwd", "sec_pfn_train_bwd", "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd"):
             at = getattr(l, name).argtypes               # the live-count forms: num_dev after num_pillars
             getattr(l, name + "_live").argtypes = at[:4] + [vp] + at[4:]
+        # the family by row kind: (kind, with_distance) in front of the argument lists above
+        l.sec_pfn_row_width.argtypes = [ci, ci]
+        l.sec_pfn_kind_fwd.argtypes = [ci, ci] + l.sec_pfn_fwd.argtypes
+        l.sec_pfn_kind_fwd_slots.argtypes = [ci, ci] + l.sec_pfn_fwd_slots.argtypes
+        l.sec_pfn_kind_train_workspace_bytes.argtypes = [ci, ci, ci, ci]
+        l.sec_pfn_kind_train_fwd.argtypes = [ci, ci] + l.sec_pfn_train_fwd_live.argtypes
+        l.sec_pfn_kind_train_bwd.argtypes = [ci, ci] + l.sec_pfn_train_bwd_live.argtypes
         l.sec_block_filter_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]
         l.sec_voxel_block_filter_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp, sz, vp]
         l.sec_bias_act_nhwc.argtypes = [vp, vp, sz, ci, ci, ci, vp]
