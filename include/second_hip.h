@@ -147,7 +147,13 @@ int sec_rulebook_subm3d_after_conv(const int *indices, int n_in, const int *n_in
 /* SubMConv3d on the voxels of a sec_voxelize_f32 call whose workspace is still intact (the first layer of SpMiddleFHD,
  * middle.py:146): the voxeliser's hash table (cell -> voxel row) is this layer's site lookup, no re-hash.  `indices` must be
  * that call's coors (all rows, unfiltered), vox_* its num_points / max_voxels / max_points arguments, h_vox_grid3_zyx its
- * grid in (z, y, x) order (<= h_shape3 per dim).  Same nbr_out as sec_rulebook_subm3d. */
+ * grid in (z, y, x) order (<= h_shape3 per dim).  Same nbr_out as sec_rulebook_subm3d.
+ * CONTRACT: that call must have written its hash keys.  Every call with a `voxels` tensor does, whatever its path (fused or
+ * unfused scan, with or without the peek, voxel cap hit: slots of voxels past the cap read as absent).  A call with voxels == NULL
+ * and max_points > 8 whose batch * cells fits its table (1 024 slots up to 512 points, else the next power of two at or above
+ * twice the points) numbers its slots by cell and leaves the key array UNWRITTEN: this function cannot tell and would probe
+ * whatever an earlier call left there.  The caller has to know which call it made; second_amd.ops marks such a result
+ * (site_table[0] == "vox_slots", ops.voxelize_keeps_keys) and refuses it in rulebook_subm / rulebook_chain before any launch. */
 int sec_rulebook_subm3d_after_voxelize(const int *indices, int n_in, const int *n_in_dev, int batch,
                                        const int *h_shape3, const int *h_ksize3, const int *h_dilation3,
                                        int *nbr_out, const void *vox_workspace, size_t vox_workspace_bytes,

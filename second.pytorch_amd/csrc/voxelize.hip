@@ -647,7 +647,9 @@ __global__ __launch_bounds__(kBlock) void k_vox_fill(const float *__restrict__ p
 // the 4-channel kernels, its weight padded 3 -> 4 input channels with a zero row.
 template <typename OT>
 __device__ __forceinline__ void store_radius_row4(OT *__restrict__ out, size_t row, float mx, float my, float mz, float mw) {
-    const float r = __fsqrt_rn(__fadd_rn(__fmul_rn(mx, mx), __fmul_rn(my, my)));
+    // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the intrinsic is the native v_sqrt_f32 (1 ulp), the library call is
+    // the correctly rounded root the comment above promises (tests/test_gpu_voxel_edges.py: test_radius_rows_on_both_routes)
+    const float r = sqrtf(__fadd_rn(__fmul_rn(mx, mx), __fmul_rn(my, my)));
     if constexpr (std::is_same<OT, float>::value) {
         *reinterpret_cast<float4 *>(out + row * 4) = make_float4(r, mz, mw, 0.0f);
     } else {

@@ -46,6 +46,17 @@ def _traced(name):
 ENCODERS = {"SimpleVoxel": 0, "SimpleVoxelRadius": 1}      # `encoder` of sec_voxelize_encode_f32
 
 
+def voxelize_keeps_keys(num_points, batch, max_points, fill, cells):
+    """Whether a sec_voxelize_f32 call of these arguments leaves the hash keys (cell -> slot) in its workspace.  The pillar form --
+    no voxel tensor, more than 8 points per voxel, ``batch * cells`` within the table carve_vox sizes (1 024 slots up to 512 points,
+    the next power of two at or above twice the points beyond) -- numbers its slots by cell and never writes the key array
+    (csrc/voxelize.hip: ``dense`` of voxelize_impl); what the key array holds then is whatever an earlier call left there."""
+    n = int(num_points)
+    table = 1024 if n <= 512 else 1 << (2 * n - 1).bit_length()
+    dense = (not fill) and int(max_points) > 8 and n > 0 and int(batch) * int(cells) <= table and int(batch) * int(cells) < 0x7fffffff
+    return not dense
+
+
 @_traced("voxelize")
 def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, max_voxels,
              cap_mode="break", mean_features=0, sync=True, mean_dtype=None, fill=True, encoder="SimpleVoxel"):
@@ -57,6 +68,9 @@ def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, m
     with ``sync=False`` they keep capacity B*max_voxels and only rows < voxel_offsets[B] are defined.
     ``fill=False``: no ``voxels`` tensor (None in the result); the per-voxel point lists stay in the workspace behind
     ``site_table`` for :func:`pfn_forward_slots` (``points`` must stay alive and unchanged until then).
+    ``site_table[0]`` is ``"vox"`` when the workspace also holds the call's hash keys -- the site lookup of the first SubM rulebook
+    (:func:`rulebook_subm`, :func:`rulebook_chain`) -- and ``"vox_slots"`` when it holds the point lists only
+    (:func:`voxelize_keeps_keys`): the rulebook builders refuse that table by name.
     ``encoder="SimpleVoxelRadius"`` (voxel_encoder.py:246-255; ``mean_features`` must be 4): ``mean`` holds the rows
     ``[sqrt(mx^2 + my^2), mz, mw, 0]`` -- pitch 4, channel 3 zero -- instead of the means (sec_voxelize_encode_f32).
     """
@@ -93,7 +107,8 @@ def voxelize(points, point_offsets, point_cloud_range, voxel_size, max_points, m
     # the hash table this call leaves in its workspace (cell -> voxel row) is the site lookup of the first SubM rulebook
     r6, v3 = np.asarray(point_cloud_range, np.float32), np.asarray(voxel_size, np.float32)
     grid_zyx = [int(v) for v in np.round((r6[3:] - r6[:3]) / v3).astype(np.int64)[::-1]]
-    out["site_table"] = ("vox", ws, int(n), int(max_voxels), int(max_points), grid_zyx)
+    tag = "vox" if voxelize_keeps_keys(n, batch, max_points, fill, int(np.prod(grid_zyx, dtype=np.int64))) else "vox_slots"
+    out["site_table"] = (tag, ws, int(n), int(max_voxels), int(max_points), grid_zyx)
     if mean is not None:
         out["mean"] = mean
     if sync:
@@ -117,14 +132,23 @@ def _kvol(ksize):
     return int(np.prod([int(k) for k in ((ksize,) * 3 if isinstance(ksize, int) else ksize)]))
 
 
+def _refuse_keyless_table(site_table, who):
+    if site_table is not None and isinstance(site_table[0], str) and site_table[0] == "vox_slots":
+        raise rt.SecondHipError(f"{who}: site_table comes from a voxelize(fill=False) call that numbered its slots by cell and wrote no "
+                                "hash keys (site_table[0] == 'vox_slots'): there is nothing to look sites up in; build the rulebook "
+                                "without site_table")
+
+
 @_traced("rulebook_subm")
 def rulebook_subm(indices, batch_size, spatial_shape, ksize=3, dilation=1, want_pairs=False, n_dev=None, site_table=None):
     """SubMConv3d rulebook (spconv.ops.get_indice_pairs(subm=True)).  indices [N,4] int32 (b,z,y,x).
     ``n_dev`` (device int32[1]) switches to static-capacity mode: only the first n_dev rows are live.
     ``site_table``: the ``site_table`` entry of the :func:`rulebook_conv` result whose out_indices these are -- its
-    hash table is reused instead of re-hashing the sites."""
+    hash table is reused instead of re-hashing the sites.  A voxeliser table without keys (``"vox_slots"``, see
+    :func:`voxelize`) is refused before anything is launched: its key array was never written."""
     rt.require_gpu(indices)
     assert indices.dtype == torch.int32 and indices.is_contiguous()
+    _refuse_keyless_table(site_table, "rulebook_subm")
     n = indices.shape[0]
     k = _kvol(ksize)
     dev = indices.device
@@ -324,7 +348,9 @@ def rulebook_chain(indices0, batch_size, shape0, convs, n_dev=None, site_table=N
         shapes.append(conv_output_shape(shapes[-1], ks3, st3, pd3, 1))
         ks_all += ks3; st_all += st3; pd_all += pd3
         caps.append(int(cap))
-    vox = site_table if (site_table is not None and isinstance(site_table[0], str) and site_table[0] == "vox") else None
+    if want_subm[0]:      # (the levels above never read the voxeliser's table)
+        _refuse_keyless_table(site_table, "rulebook_chain")
+    vox =site_table if (site_table is not None and isinstance(site_table[0], str) and site_table[0] == "vox") else None
     if want_subm[0] and vox is None:
         return None
     ia = lambda v: (ctypes.c_int * len(v))(*[int(x) for x in v])
@@ -953,7 +979,7 @@ def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_o
     assert (weight_t.shape[0] == points.shape[1] - 4 + pfn_row_width(kind, with_distance) and weight_t.dtype == torch.float32
             and weight_t.is_contiguous())
     table, ws, n, max_voxels, max_points, _ = vox["site_table"]
-    assert table == "vox" and points.shape[0] == n and points.dtype == torch.float32 and points.is_contiguous()
+    assert table in ("vox", "vox_slots") and points.shape[0] == n and points.dtype == torch.float32 and points.is_contiguous()
     npv, coords = vox["num_points_per_voxel"], vox["coordinates"].contiguous()
     p, c = coords.shape[0], weight_t.shape[1]
     batch = vox["voxel_offsets"].numel() - 1
