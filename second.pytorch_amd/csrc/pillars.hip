@@ -1,8 +1,15 @@
 // PointPillars front end + NuScenes block filter on gfx950.
-//   sec_pfn_fwd                : PillarFeatureNet.forward with one PFNLayer, eval mode
+//   sec_pfn_kind_fwd           : PillarFeatureNet.forward with one PFNLayer, eval mode
 //                                (second/pytorch/models/pointpillars.py:203-237 + :51-65): ~15 torch kernels on a
 //                                [P,60,9] tensor in the reference, ONE launch here.  One wave64 per pillar, lane =
 //                                output channel (64 channels == one wave), points broadcast with v_readlane.
+//                                (kind, with_distance) name one of the four encoders of that file, each with the
+//                                optional distance entry (pfn_row).
+//   sec_pfn_kind_fwd_slots     : the same from the voxeliser's point lists, no [P,T,4] tensor
+//   sec_pfn_kind_train_fwd/bwd : the layer under train() (batch statistics, backward through the argmax), five kernels;
+//                                num_dev: static capacity with the pillar count on the device
+//   sec_pfn_fwd, sec_pfn_radius_*, their _slots, _train_ and _live forms: the same launchers with the kind fixed by the
+//                                name (PLAIN / RADIUS without distance); see "host side" below
 //   sec_voxel_block_filter_f32 : height-span filter of points_to_voxel_3d_with_filtering (SURVEY A.2,
 //                                enabled by second/configs/nuscenes/all.fhd.config:9-12) + order-preserving
 //                                compaction of the voxel arrays (flag + exclusive scan).
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_pfn_fwd(const float *__restrict__ vo
 // KIND / DIST (the other encoders of pointpillars.py under train()): the same five kernels on the K-entry row of pfn_row<KIND, DIST>;
 // a padded slot is zero in all K entries (the reference masks after decorating, h and the distance included), so it is the same
 // x = 0 row as above.
-constexpr int kPfnIn = 9;                         // sec_pfn_train_workspace_bytes' row width (the entry points of before carve by it)
+constexpr int kPfnIn = 9;                         // sec_pfn_train_workspace_bytes' row width (see pfn_train_ws_width)
 template <int KIND, bool DIST> struct PfnDims {
     static constexpr int K = pfn_width(KIND, DIST);   // decorated inputs
     static constexpr int StatVals = 2 + K;        // per channel: sum x, sum x^2, M[c][0..K-1]
@@ -502,31 +509,9 @@ __global__ __launch_bounds__(kBlock) void k_bf_minmax(const float *__restrict__ 
     atomicMax(&maxs[cell], f2ord(z));
 }
 
-__global__ __launch_bounds__(kBlock) void k_bf_mask(const int *__restrict__ coors, const int *__restrict__ voff, BfParams p,
-                                                   const int *__restrict__ mins, const int *__restrict__ maxs, int rows,
-                                                   int *__restrict__ keep) {
-    int v = blockIdx.x * kBlock + threadIdx.x;
-    if (v >= rows) return;
-    if (v >= voff[p.batch]) { keep[v] = 0; return; }
-    int4 c = *reinterpret_cast<const int4 *>(coors + (size_t)v * 4);
-    int cy = c.z / p.block_factor, cx = c.w / p.block_factor;
-    int y0 = max(cy - p.block_size / 2, 0), y1 = min(cy + p.block_size - p.block_size / 2, p.by);
-    int x0 = max(cx - p.block_size / 2, 0), x1 = min(cx + p.block_size - p.block_size / 2, p.bx);
-    float hmin = 99999999.0f, hmax = -99999999.0f;
-    for (int y = y0; y < y1; ++y)
-        for (int x = x0; x < x1; ++x) {
-            int cell = (c.x * p.by + y) * p.bx + x;
-            hmin = fminf(hmin, ord2f(mins[cell]));
-            hmax = fmaxf(hmax, ord2f(maxs[cell]));
-        }
-    float span = __fsub_rn(hmax, hmin);
-    keep[v] = (span > p.thr && span < p.high) ? 1 : 0;
-}
-
-// The same test with one WAVE per voxel: lane l takes cell l of the (block_size x block_size <= 64-cell) window, the wave reduces
-// min / max with shuffles.  The thread-per-voxel form above walks its 64 cells x 2 arrays itself -- 128 loads on one thread's
-// dependency chain: 214 us for the 360 k voxels of a nuscenes/all.fhd batch; min and max do not depend on the order, so the result
-// is bit-identical.
+// The height-span test with one WAVE per voxel: lane l takes cell l of the (block_size x block_size <= 64-cell) window, the wave
+// reduces min / max with shuffles.  (One thread per voxel walks its 64 cells x 2 arrays itself -- 128 loads on one thread's
+// dependency chain: 214 us for the 360 k voxels of a nuscenes/all.fhd batch.)
 __global__ __launch_bounds__(kBlock) void k_bf_mask_wave(const int *__restrict__ coors, const int *__restrict__ voff, BfParams p,
                                                         const int *__restrict__ mins, const int *__restrict__ maxs, int rows,
                                                         int *__restrict__ keep) {
@@ -599,44 +584,42 @@ static BfWorkspace carve_bf(void *ws, size_t cap, int rows, int batch, int bx, i
 
 using namespace sec;
 
-template <int KIND, bool DIST>
-static int pfn_fwd_any(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
-                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
-                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
-                        void *stream) {
-    if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !weight_t || !scale || !shift || !out) return SEC_E_INVALID;
-    if (num_features != 4) return SEC_E_UNSUPPORTED;  // x, y, z + one extra (reflectance / dt): every shipped config
-    if (num_pillars == 0) return SEC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, false, KIND, DIST>), grid, block, 0, st, voxels, num_points, coords, num_pillars, num_dev, \
-                                       max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out)
-    if (out_dtype == SEC_F32) SEC_PFN(float);
-    else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
-    else if (out_dtype == SEC_F16) SEC_PFN(__half);
-    else return SEC_E_UNSUPPORTED;
-#undef SEC_PFN
-    return check_launch();
+// ---- PillarFeatureNet, host side: one path from the nineteen entry points to the kernels -------------------------------------------
+// pfn_by_kind names the <KIND, DIST> instantiation; pfn_fwd, pfn_fwd_slots, pfn_train_fwd and pfn_train_bwd validate once and
+// enqueue; every public function below them is one forwarding statement.
+SEC_API int sec_pfn_row_width(int kind, int with_distance) {
+    if (kind < kPfnPlain || kind > kPfnRadiusHeight || (with_distance != 0 && with_distance != 1)) return 0;
+    return pfn_width(kind, with_distance != 0);
 }
 
-template <int KIND, bool DIST>
-static int pfn_fwd_slots_any(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
-                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
-                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
-                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
-                              int out_dtype, void *stream) {
-    if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !points || !vox_workspace || !num_points_per_voxel || !coords ||
-        !weight_t || !scale || !shift || !out)
-        return SEC_E_INVALID;
-    if (num_features != 4) return SEC_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(points) & 15) != 0) return SEC_E_UNSUPPORTED;      // float4 gathers
-    const int *count, *slots;
-    if (!vox_slots_of(vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points, &count, &slots))
-        return SEC_E_WORKSPACE;
+template <int KIND, bool DIST> struct PfnRow {
+    static constexpr int kind = KIND;
+    static constexpr bool dist = DIST;
+};
+// f(PfnRow<KIND, DIST>{}) for the pair the caller named, SEC_E_INVALID for a pair that names no row
+template <class F> static int pfn_by_kind(int kind, int with_distance, F &&f) {
+    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
+    switch (kind * 2 + with_distance) {
+    case kPfnPlain * 2: return f(PfnRow<kPfnPlain, false>{});
+    case kPfnPlain * 2 + 1: return f(PfnRow<kPfnPlain, true>{});
+    case kPfnRadius * 2: return f(PfnRow<kPfnRadius, false>{});
+    case kPfnRadius * 2 + 1: return f(PfnRow<kPfnRadius, true>{});
+    case kPfnOld * 2: return f(PfnRow<kPfnOld, false>{});
+    case kPfnOld * 2 + 1: return f(PfnRow<kPfnOld, true>{});
+    case kPfnRadiusHeight * 2: return f(PfnRow<kPfnRadiusHeight, false>{});
+    default: return f(PfnRow<kPfnRadiusHeight, true>{});
+    }
+}
+
+// k_pfn_fwd in the output type asked for.  `src`: the [P, T, 4] pillar tensor, or with SLOTS the flat point array behind `slots`.
+template <bool SLOTS, int KIND, bool DIST>
+static int pfn_fwd_launch(const float *src, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                          int max_points, const float *weight_t, const float *scale, const float *shift, int channels, float vx,
+                          float vy, float x_offset, float y_offset, void *out, int out_dtype, const int *slots, void *stream) {
     if (num_pillars == 0) return SEC_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(div_up(num_pillars, kBlock / 64)), block(kBlock);
-#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, true, KIND, DIST>), grid, block, 0, st, points, num_points_per_voxel, coords, num_pillars, num_dev, \
+#define SEC_PFN(OT) hipLaunchKernelGGL((k_pfn_fwd<OT, SLOTS, KIND, DIST>), grid, block, 0, st, src, num_points, coords, num_pillars, num_dev, \
                                        max_points, weight_t, scale, shift, channels, vx, vy, x_offset, y_offset, (OT *)out, slots)
     if (out_dtype == SEC_F32) SEC_PFN(float);
     else if (out_dtype == SEC_BF16) SEC_PFN(__hip_bfloat16);
@@ -646,38 +629,37 @@ static int pfn_fwd_slots_any(const float *points, const void *vox_workspace, siz
     return check_launch();
 }
 
-SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
-                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
-                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
-                        void *stream) {
-    return pfn_fwd_any<kPfnPlain, false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
-                               vx, vy, x_offset, y_offset, out, out_dtype, stream);
+static int pfn_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords, int num_pillars,
+                   const int *num_dev, int max_points, int num_features, const float *weight_t, const float *scale,
+                   const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
+                   void *stream) {
+    return pfn_by_kind(kind, with_distance, [&](auto row) -> int {
+        if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !weight_t || !scale || !shift || !out) return SEC_E_INVALID;
+        if (num_features != 4) return SEC_E_UNSUPPORTED;  // x, y, z + one extra (reflectance / dt): every shipped config
+        return pfn_fwd_launch<false, decltype(row)::kind, decltype(row)::dist>(voxels, num_points, coords, num_pillars, num_dev, max_points,
+                                                                               weight_t, scale, shift, channels, vx, vy, x_offset,
+                                                                               y_offset, out, out_dtype, nullptr, stream);
+    });
 }
-SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
-                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
-                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
-                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
-                              int out_dtype, void *stream) {
-    return pfn_fwd_slots_any<kPfnPlain, false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
-                                     num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
-                                     vx, vy, x_offset, y_offset, out, out_dtype, stream);
-}
-// PillarFeatureNetRadius (k_pfn_fwd<.., kPfnRadius>): the same arguments, weight_t is [num_features + 4][channels]
-SEC_API int sec_pfn_radius_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
-                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
-                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
-                        void *stream) {
-    return pfn_fwd_any<kPfnRadius, false>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift, channels,
-                               vx, vy, x_offset, y_offset, out, out_dtype, stream);
-}
-SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
-                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
-                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
-                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
-                              int out_dtype, void *stream) {
-    return pfn_fwd_slots_any<kPfnRadius, false>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points,
-                                     num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
-                                     vx, vy, x_offset, y_offset, out, out_dtype, stream);
+
+static int pfn_fwd_slots(int kind, int with_distance, const float *points, const void *vox_workspace, size_t vox_workspace_bytes,
+                         int vox_num_points, int vox_batch, int vox_max_voxels, int max_points, int num_features,
+                         const int *num_points_per_voxel, const int *coords, int num_pillars, const int *num_dev,
+                         const float *weight_t, const float *scale, const float *shift, int channels, float vx, float vy,
+                         float x_offset, float y_offset, void *out, int out_dtype, void *stream) {
+    return pfn_by_kind(kind, with_distance, [&](auto row) -> int {
+        if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !points || !vox_workspace || !num_points_per_voxel || !coords ||
+            !weight_t || !scale || !shift || !out)
+            return SEC_E_INVALID;
+        if (num_features != 4) return SEC_E_UNSUPPORTED;
+        if ((reinterpret_cast<uintptr_t>(points) & 15) != 0) return SEC_E_UNSUPPORTED;      // float4 gathers
+        const int *count, *slots;
+        if (!vox_slots_of(vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points, &count, &slots))
+            return SEC_E_WORKSPACE;
+        return pfn_fwd_launch<true, decltype(row)::kind, decltype(row)::dist>(points, num_points_per_voxel, coords, num_pillars, num_dev,
+                                                                              max_points, weight_t, scale, shift, channels, vx, vy,
+                                                                              x_offset, y_offset, out, out_dtype, slots, stream);
+    });
 }
 
 // the training workspace for rows of `width` entries: partial[blocks][C][2 + width], partial_s1[blocks][width], partial_d[blocks][C][2]
@@ -687,181 +669,243 @@ static size_t pfn_train_ws_bytes(int width, int num_pillars, int channels) {
     return align_up(b * channels * (2 + width) * sizeof(float)) + align_up(b * width * sizeof(float)) +
            align_up(b * channels * 2 * sizeof(double));
 }
-SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
-    return pfn_train_ws_bytes(kPfnIn, num_pillars, channels);
+
+// `before`: the call came through one of the training entry points older than sec_pfn_kind_*.  Their callers hold two answers of
+// theirs, which the two functions below keep; nothing else tells the older symbols from the kind forms.
+// (1) The row width a training workspace is sized and carved for.  sec_pfn_train_workspace_bytes takes no kind, so what its callers
+// allocate is for nine entries, the radius row's eight included, and the older forms carve by it; the kind forms by the kind's own
+// K.  Only the offsets of the three arrays move: the per-block partials inside them are pitched by K either way.
+template <int KIND, bool DIST> static constexpr int pfn_train_ws_width(bool before) {
+    return before ? kPfnIn : PfnDims<KIND, DIST>::K;
+}
+// (2) The status of max_points > 127 (the int8 argmax cannot name the slot).  The older forms list T <= 127 with their argument checks
+// (SEC_E_INVALID); sec_pfn_kind_* document it with the shape limits (SEC_E_UNSUPPORTED) and answer it ahead of the other checks.
+static int pfn_train_long_pillar_status(bool before) { return before ? SEC_E_INVALID : SEC_E_UNSUPPORTED; }
+
+static int pfn_train_fwd(bool before, int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                         int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                         const float *gamma, const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                         int channels, float vx, float vy, float x_offset, float y_offset, float *out, signed char *argmax,
+                         float *stats, void *workspace, size_t workspace_bytes, void *stream) {
+    return pfn_by_kind(kind, with_distance, [&](auto row) -> int {
+        constexpr int KIND = decltype(row)::kind;
+        constexpr bool DIST = decltype(row)::dist;
+        if (max_points > 127) return pfn_train_long_pillar_status(before);
+        if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !weight_t || !gamma || !beta || !out || !argmax || !stats)
+            return SEC_E_INVALID;
+        if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
+        const int width = pfn_train_ws_width<KIND, DIST>(before);
+        if (!workspace || workspace_bytes < pfn_train_ws_bytes(width, num_pillars, channels)) return SEC_E_WORKSPACE;
+        if (num_pillars == 0 && !num_dev) return SEC_OK;
+        hipStream_t st = (hipStream_t)stream;
+        const int blocks = pfn_blocks(num_pillars);      // grids by capacity; every kernel reads the count itself (pfn_live)
+        float *partial = (float *)workspace;
+        float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * (2 + width) * sizeof(float)));
+        double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * width * sizeof(float)));
+        hipLaunchKernelGGL((k_pfn_stats<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
+                           max_points, weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
+        hipLaunchKernelGGL((k_pfn_finalize<KIND, DIST>), dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks,
+                           channels, num_pillars, num_dev, max_points, eps, momentum, running_mean, running_var, stats);
+        if (num_pillars == 0) return check_launch();    // a capacity of zero: the statistics of no pillar, nothing else to write
+        hipLaunchKernelGGL((k_pfn_fwd_train<KIND, DIST>), dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points,
+                           coords, num_pillars, num_dev, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out,
+                           argmax);
+        return check_launch();
+    });
 }
 
-// `width`: the row width the caller's workspace was sized and is carved for (>= the kind's K; the per-block partials themselves are
-// pitched by the kind's own K): kPfnIn from the entry points of before, the kind's K from sec_pfn_kind_train_*
-template <int KIND, bool DIST>
-static int pfn_train_fwd_any(int width, const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
-                             int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
-                             float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
-                             float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
-                             size_t workspace_bytes, void *stream) {
-    if (num_pillars < 0 || max_points <= 0 || max_points > 127 || channels <= 0 || !weight_t || !gamma || !beta || !out || !argmax || !stats)
-        return SEC_E_INVALID;
-    if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
-    if (!workspace || workspace_bytes < pfn_train_ws_bytes(width, num_pillars, channels)) return SEC_E_WORKSPACE;
-    if (num_pillars == 0 && !num_dev) return SEC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int blocks = pfn_blocks(num_pillars);      // grids by capacity; every kernel reads the count itself (pfn_live)
-    float *partial = (float *)workspace;      // carved for `width` inputs (the radius form of before: for nine, eight need less)
-    float *partial_s1 = (float *)((char *)workspace + align_up((size_t)blocks * channels * (2 + width) * sizeof(float)));
-    double *partial_d = (double *)((char *)partial_s1 + align_up((size_t)blocks * width * sizeof(float)));
-    hipLaunchKernelGGL((k_pfn_stats<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
-                       max_points, weight_t, channels, vx, vy, x_offset, y_offset, partial, partial_s1, partial_d);
-    hipLaunchKernelGGL((k_pfn_finalize<KIND, DIST>), dim3(channels + 1), dim3(kBlock), 0, st, partial, partial_s1, partial_d, blocks, channels,
-                       num_pillars, num_dev, max_points, eps, momentum, running_mean, running_var, stats);
-    if (num_pillars == 0) return check_launch();    // a capacity of zero: the statistics of no pillar, nothing else to write
-    hipLaunchKernelGGL((k_pfn_fwd_train<KIND, DIST>), dim3(div_up(num_pillars, kBlock / 64)), dim3(kBlock), 0, st, voxels, num_points, coords,
-                       num_pillars, num_dev, max_points, weight_t, gamma, beta, stats, channels, vx, vy, x_offset, y_offset, out, argmax);
-    return check_launch();
+static int pfn_train_bwd(bool before, int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
+                         int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
+                         const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset, float y_offset,
+                         const float *grad_out, const float *out, const signed char *argmax, float *dweight_t, float *dgamma,
+                         float *dbeta, void *workspace, size_t workspace_bytes, void *stream) {
+    return pfn_by_kind(kind, with_distance, [&](auto row) -> int {
+        constexpr int KIND = decltype(row)::kind;
+        constexpr bool DIST = decltype(row)::dist;
+        if (max_points > 127) return pfn_train_long_pillar_status(before);
+        if (num_pillars < 0 || max_points <= 0 || channels <= 0 || !weight_t || !gamma || !stats || !grad_out || !out || !argmax ||
+            !dweight_t || !dgamma || !dbeta)
+            return SEC_E_INVALID;
+        if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
+        if (!workspace || workspace_bytes < pfn_train_ws_bytes(pfn_train_ws_width<KIND, DIST>(before), num_pillars, channels))
+            return SEC_E_WORKSPACE;
+        hipStream_t st = (hipStream_t)stream;
+        if (num_pillars == 0) {
+            int rc = fill_words(dweight_t, sizeof(float) * PfnDims<KIND, DIST>::K * channels, 0u, st);
+            if (!rc) rc = fill_words(dgamma, sizeof(float) * channels, 0u, st);
+            if (!rc) rc = fill_words(dbeta, sizeof(float) * channels, 0u, st);
+            return rc;
+        }
+        const int blocks = pfn_blocks(num_pillars);
+        float *partial = (float *)workspace;
+        hipLaunchKernelGGL((k_pfn_bwd<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev,
+                           max_points, weight_t, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
+        hipLaunchKernelGGL((k_pfn_bwd_finalize<KIND, DIST>), dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels, num_pillars,
+                           num_dev, max_points, gamma, stats, dweight_t, dgamma, dbeta);
+        return check_launch();
+    });
 }
 
-template <int KIND, bool DIST>
-static int pfn_train_bwd_any(int width, const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev, int max_points,
-                             int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
-                             float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
-                             const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
-                             size_t workspace_bytes, void *stream) {
-    if (num_pillars < 0 || max_points <= 0 || max_points > 127 || channels <= 0 || !weight_t || !gamma || !stats || !grad_out || !out ||
-        !argmax || !dweight_t || !dgamma || !dbeta)
-        return SEC_E_INVALID;
-    if (num_features != 4 || channels > 64) return SEC_E_UNSUPPORTED;
-    if (!workspace || workspace_bytes < pfn_train_ws_bytes(width, num_pillars, channels)) return SEC_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (num_pillars == 0) {
-        int rc = fill_words(dweight_t, sizeof(float) * PfnDims<KIND, DIST>::K * channels, 0u, st);
-        if (!rc) rc = fill_words(dgamma, sizeof(float) * channels, 0u, st);
-        if (!rc) rc = fill_words(dbeta, sizeof(float) * channels, 0u, st);
-        return rc;
-    }
-    const int blocks = pfn_blocks(num_pillars);
-    float *partial = (float *)workspace;
-    hipLaunchKernelGGL((k_pfn_bwd<KIND, DIST>), dim3(blocks), dim3(kBlock), 0, st, voxels, num_points, coords, num_pillars, num_dev, max_points,
-                       weight_t, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, partial);
-    hipLaunchKernelGGL((k_pfn_bwd_finalize<KIND, DIST>), dim3(channels), dim3(kBlock), 0, st, partial, blocks, channels, num_pillars, num_dev,
-                       max_points, gamma, stats, dweight_t, dgamma, dbeta);
-    return check_launch();
-}
-
-#define SEC_PFN_TRAIN_FWD_ARGS                                                                                                     \
-    const float *voxels, const int *num_points, const int *coords, int num_pillars, SEC_PFN_NUM_DEV_ARG int max_points,           \
-        int num_features, const float *weight_t, const float *gamma, const float *beta, float eps, float momentum, float *running_mean,             \
-        float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out, signed char *argmax,    \
-        float *stats, void *workspace, size_t workspace_bytes, void *stream
-#define SEC_PFN_TRAIN_FWD_PASS                                                                                                     \
-    kPfnIn, voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, beta, eps, momentum, running_mean,        \
-        running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats, workspace, workspace_bytes, stream
-#define SEC_PFN_TRAIN_BWD_ARGS                                                                                                     \
-    const float *voxels, const int *num_points, const int *coords, int num_pillars, SEC_PFN_NUM_DEV_ARG int max_points,           \
-        int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,          \
-        float y_offset, const float *grad_out, const float *out, const signed char *argmax, float *dweight_t, float *dgamma,      \
-        float *dbeta, void *workspace, size_t workspace_bytes, void *stream
-#define SEC_PFN_TRAIN_BWD_PASS                                                                                                     \
-    kPfnIn, voxels, num_points, coords, num_pillars, SEC_PFN_NUM_DEV, max_points, num_features, weight_t, gamma, stats, channels, vx, vy, x_offset,        \
-        y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace, workspace_bytes, stream
-// the entry points of before are the live-count forms with no count (num_dev = NULL: every row is a pillar)
-#define SEC_PFN_NUM_DEV_ARG
-#define SEC_PFN_NUM_DEV nullptr
-SEC_API int sec_pfn_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_BWD_PASS); }
-// PillarFeatureNetRadius in training mode (the kPfnRadius instantiations): the same arguments, weight_t / dweight_t are [8][channels]
-SEC_API int sec_pfn_radius_train_fwd(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_radius_train_bwd(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_BWD_PASS); }
-// static capacity: num_pillars rows, the first min(max(*num_dev, 0), num_pillars) of them pillars (device memory, read by the kernels)
-#undef SEC_PFN_NUM_DEV_ARG
-#undef SEC_PFN_NUM_DEV
-#define SEC_PFN_NUM_DEV_ARG const int *num_dev,
-#define SEC_PFN_NUM_DEV num_dev
-SEC_API int sec_pfn_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnPlain, false>(SEC_PFN_TRAIN_BWD_PASS); }
-SEC_API int sec_pfn_radius_train_fwd_live(SEC_PFN_TRAIN_FWD_ARGS) { return pfn_train_fwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_FWD_PASS); }
-SEC_API int sec_pfn_radius_train_bwd_live(SEC_PFN_TRAIN_BWD_ARGS) { return pfn_train_bwd_any<kPfnRadius, false>(SEC_PFN_TRAIN_BWD_PASS); }
-#undef SEC_PFN_NUM_DEV_ARG
-#undef SEC_PFN_NUM_DEV
-#undef SEC_PFN_TRAIN_FWD_ARGS
-#undef SEC_PFN_TRAIN_FWD_PASS
-#undef SEC_PFN_TRAIN_BWD_ARGS
-#undef SEC_PFN_TRAIN_BWD_PASS
-
-// ---- the family by row kind: one switch from (kind, with_distance) to the instantiation ------------------------------------------
-SEC_API int sec_pfn_row_width(int kind, int with_distance) {
-    if (kind < kPfnPlain || kind > kPfnRadiusHeight || (with_distance != 0 && with_distance != 1)) return 0;
-    return pfn_width(kind, with_distance != 0);
-}
-// CALL(KIND, DIST) for the pair the caller named; kPfnPlain / kPfnRadius without distance are the instantiations behind sec_pfn_fwd /
-// sec_pfn_radius_* themselves
-#define SEC_PFN_BY_KIND(CALL)                                                                  \
-    switch (kind * 2 + with_distance) {                                                        \
-    case kPfnPlain * 2: return CALL(kPfnPlain, false);                                         \
-    case kPfnPlain * 2 + 1: return CALL(kPfnPlain, true);                                      \
-    case kPfnRadius * 2: return CALL(kPfnRadius, false);                                       \
-    case kPfnRadius * 2 + 1: return CALL(kPfnRadius, true);                                    \
-    case kPfnOld * 2: return CALL(kPfnOld, false);                                             \
-    case kPfnOld * 2 + 1: return CALL(kPfnOld, true);                                          \
-    case kPfnRadiusHeight * 2: return CALL(kPfnRadiusHeight, false);                           \
-    default: return CALL(kPfnRadiusHeight, true);                                              \
-    }
+// -- the public functions: (kind, with_distance) from the caller, or fixed by the symbol's name; num_dev from the caller (the _live
+// forms: static capacity, the first min(max(*num_dev, 0), num_pillars) rows are pillars), or NULL: every row is a pillar
 SEC_API int sec_pfn_kind_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
                              int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
                              const float *scale, const float *shift, int channels, float vx, float vy, float x_offset,
                              float y_offset, void *out, int out_dtype, void *stream) {
-    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
-#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
-    pfn_fwd_any<KIND, DIST>(voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift,     \
-                            channels, vx, vy, x_offset, y_offset, out, out_dtype, stream)
-    SEC_PFN_BY_KIND(SEC_PFN_CALL)
-#undef SEC_PFN_CALL
+    return pfn_fwd(kind, with_distance, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift,
+                   channels, vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
+SEC_API int sec_pfn_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                        int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
+                        int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
+                        void *stream) {
+    return pfn_fwd(kPfnPlain, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift,
+                   channels, vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+// PillarFeatureNetRadius: the same arguments, weight_t is [num_features + 4][channels]
+SEC_API int sec_pfn_radius_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                               int max_points, int num_features, const float *weight_t, const float *scale, const float *shift,
+                               int channels, float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype,
+                               void *stream) {
+    return pfn_fwd(kPfnRadius, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, scale, shift,
+                   channels, vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+
 SEC_API int sec_pfn_kind_fwd_slots(int kind, int with_distance, const float *points, const void *vox_workspace,
                                    size_t vox_workspace_bytes, int vox_num_points, int vox_batch, int vox_max_voxels, int max_points,
                                    int num_features, const int *num_points_per_voxel, const int *coords, int num_pillars,
                                    const int *num_dev, const float *weight_t, const float *scale, const float *shift, int channels,
                                    float vx, float vy, float x_offset, float y_offset, void *out, int out_dtype, void *stream) {
-    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
-#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
-    pfn_fwd_slots_any<KIND, DIST>(points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels, max_points, \
-                                  num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels, \
-                                  vx, vy, x_offset, y_offset, out, out_dtype, stream)
-    SEC_PFN_BY_KIND(SEC_PFN_CALL)
-#undef SEC_PFN_CALL
+    return pfn_fwd_slots(kind, with_distance, points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels,
+                         max_points, num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
+                         vx, vy, x_offset, y_offset, out, out_dtype, stream);
 }
+SEC_API int sec_pfn_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+                              int vox_batch, int vox_max_voxels, int max_points, int num_features, const int *num_points_per_voxel,
+                              const int *coords, int num_pillars, const int *num_dev, const float *weight_t, const float *scale,
+                              const float *shift, int channels, float vx, float vy, float x_offset, float y_offset, void *out,
+                              int out_dtype, void *stream) {
+    return pfn_fwd_slots(kPfnPlain, 0, points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels,
+                         max_points, num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
+                         vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+SEC_API int sec_pfn_radius_fwd_slots(const float *points, const void *vox_workspace, size_t vox_workspace_bytes, int vox_num_points,
+                                     int vox_batch, int vox_max_voxels, int max_points, int num_features,
+                                     const int *num_points_per_voxel, const int *coords, int num_pillars, const int *num_dev,
+                                     const float *weight_t, const float *scale, const float *shift, int channels, float vx, float vy,
+                                     float x_offset, float y_offset, void *out, int out_dtype, void *stream) {
+    return pfn_fwd_slots(kPfnRadius, 0, points, vox_workspace, vox_workspace_bytes, vox_num_points, vox_batch, vox_max_voxels,
+                         max_points, num_features, num_points_per_voxel, coords, num_pillars, num_dev, weight_t, scale, shift, channels,
+                         vx, vy, x_offset, y_offset, out, out_dtype, stream);
+}
+
 SEC_API size_t sec_pfn_kind_train_workspace_bytes(int kind, int with_distance, int num_pillars, int channels) {
-    const int width = sec_pfn_row_width(kind, with_distance);
-    return width ? pfn_train_ws_bytes(width, num_pillars, channels) : 0;
+    size_t bytes = 0;      // stays zero for a pair that names no row
+    pfn_by_kind(kind, with_distance, [&](auto row) -> int {
+        bytes = pfn_train_ws_bytes(pfn_train_ws_width<decltype(row)::kind, decltype(row)::dist>(false), num_pillars, channels);
+        return SEC_OK;
+    });
+    return bytes;
 }
+SEC_API size_t sec_pfn_train_workspace_bytes(int num_pillars, int channels) {
+    return pfn_train_ws_bytes(pfn_train_ws_width<kPfnPlain, false>(true), num_pillars, channels);
+}
+
 SEC_API int sec_pfn_kind_train_fwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
                                    int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
                                    const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
                                    float *running_var, int channels, float vx, float vy, float x_offset, float y_offset, float *out,
                                    signed char *argmax, float *stats, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
-    if (max_points > 127) return SEC_E_UNSUPPORTED;       // the int8 argmax; (the entry points of before answer SEC_E_INVALID)
-#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
-    pfn_train_fwd_any<KIND, DIST>(pfn_width(KIND, DIST), voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, \
-                                  weight_t, gamma, beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset,      \
-                                  y_offset, out, argmax, stats, workspace, workspace_bytes, stream)
-    SEC_PFN_BY_KIND(SEC_PFN_CALL)
-#undef SEC_PFN_CALL
+    return pfn_train_fwd(false, kind, with_distance, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t,
+                         gamma, beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats,
+                         workspace, workspace_bytes, stream);
 }
+SEC_API int sec_pfn_train_fwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                                   int max_points, int num_features, const float *weight_t, const float *gamma, const float *beta,
+                                   float eps, float momentum, float *running_mean, float *running_var, int channels, float vx,
+                                   float vy, float x_offset, float y_offset, float *out, signed char *argmax, float *stats,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return pfn_train_fwd(true, kPfnPlain, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, gamma,
+                         beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats,
+                         workspace, workspace_bytes, stream);
+}
+// PillarFeatureNetRadius in training mode: the same arguments, weight_t / dweight_t are [8][channels]
+SEC_API int sec_pfn_radius_train_fwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars,
+                                          const int *num_dev, int max_points, int num_features, const float *weight_t,
+                                          const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
+                                          float *running_var, int channels, float vx, float vy, float x_offset, float y_offset,
+                                          float *out, signed char *argmax, float *stats, void *workspace, size_t workspace_bytes,
+                                          void *stream) {
+    return pfn_train_fwd(true, kPfnRadius, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, gamma,
+                         beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats,
+                         workspace, workspace_bytes, stream);
+}
+SEC_API int sec_pfn_train_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                              int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
+                              float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
+                              float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+    return pfn_train_fwd(true, kPfnPlain, 0, voxels, num_points, coords, num_pillars, nullptr, max_points, num_features, weight_t, gamma,
+                         beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats,
+                         workspace, workspace_bytes, stream);
+}
+SEC_API int sec_pfn_radius_train_fwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                                     int num_features, const float *weight_t, const float *gamma, const float *beta, float eps,
+                                     float momentum, float *running_mean, float *running_var, int channels, float vx, float vy,
+                                     float x_offset, float y_offset, float *out, signed char *argmax, float *stats, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    return pfn_train_fwd(true, kPfnRadius, 0, voxels, num_points, coords, num_pillars, nullptr, max_points, num_features, weight_t, gamma,
+                         beta, eps, momentum, running_mean, running_var, channels, vx, vy, x_offset, y_offset, out, argmax, stats,
+                         workspace, workspace_bytes, stream);
+}
+
 SEC_API int sec_pfn_kind_train_bwd(int kind, int with_distance, const float *voxels, const int *num_points, const int *coords,
                                    int num_pillars, const int *num_dev, int max_points, int num_features, const float *weight_t,
                                    const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,
                                    float y_offset, const float *grad_out, const float *out, const signed char *argmax,
                                    float *dweight_t, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
                                    void *stream) {
-    if (!sec_pfn_row_width(kind, with_distance)) return SEC_E_INVALID;
-    if (max_points > 127) return SEC_E_UNSUPPORTED;       // the int8 argmax; (the entry points of before answer SEC_E_INVALID)
-#define SEC_PFN_CALL(KIND, DIST)                                                                                                  \
-    pfn_train_bwd_any<KIND, DIST>(pfn_width(KIND, DIST), voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, \
-                                  weight_t, gamma, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t,   \
-                                  dgamma, dbeta, workspace, workspace_bytes, stream)
-    SEC_PFN_BY_KIND(SEC_PFN_CALL)
-#undef SEC_PFN_CALL
+    return pfn_train_bwd(false, kind, with_distance, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t,
+                         gamma, stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
 }
-#undef SEC_PFN_BY_KIND
+SEC_API int sec_pfn_train_bwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars, const int *num_dev,
+                                   int max_points, int num_features, const float *weight_t, const float *gamma, const float *stats,
+                                   int channels, float vx, float vy, float x_offset, float y_offset, const float *grad_out,
+                                   const float *out, const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return pfn_train_bwd(true, kPfnPlain, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, gamma,
+                         stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
+}
+SEC_API int sec_pfn_radius_train_bwd_live(const float *voxels, const int *num_points, const int *coords, int num_pillars,
+                                          const int *num_dev, int max_points, int num_features, const float *weight_t,
+                                          const float *gamma, const float *stats, int channels, float vx, float vy, float x_offset,
+                                          float y_offset, const float *grad_out, const float *out, const signed char *argmax,
+                                          float *dweight_t, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                          void *stream) {
+    return pfn_train_bwd(true, kPfnRadius, 0, voxels, num_points, coords, num_pillars, num_dev, max_points, num_features, weight_t, gamma,
+                         stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
+}
+SEC_API int sec_pfn_train_bwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                              int num_features, const float *weight_t, const float *gamma, const float *stats, int channels, float vx,
+                              float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
+                              const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+    return pfn_train_bwd(true, kPfnPlain, 0, voxels, num_points, coords, num_pillars, nullptr, max_points, num_features, weight_t, gamma,
+                         stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
+}
+SEC_API int sec_pfn_radius_train_bwd(const float *voxels, const int *num_points, const int *coords, int num_pillars, int max_points,
+                                     int num_features, const float *weight_t, const float *gamma, const float *stats, int channels,
+                                     float vx, float vy, float x_offset, float y_offset, const float *grad_out, const float *out,
+                                     const signed char *argmax, float *dweight_t, float *dgamma, float *dbeta, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
+    return pfn_train_bwd(true, kPfnRadius, 0, voxels, num_points, coords, num_pillars, nullptr, max_points, num_features, weight_t, gamma,
+                         stats, channels, vx, vy, x_offset, y_offset, grad_out, out, argmax, dweight_t, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
+}
 
 SEC_API size_t sec_block_filter_workspace_bytes(int rows, int batch, int grid_x, int grid_y, int block_factor) {
     if (rows < 0 || batch <= 0 || block_factor <= 0) return 0;
@@ -888,15 +932,8 @@ SEC_API int sec_voxel_block_filter_f32(const float *voxels, const int *coors, co
     if (rows > 0) {
         hipLaunchKernelGGL(k_bf_minmax, dim3(div_up((long long)rows * max_points, kBlock)), dim3(kBlock), 0, st, voxels,
                            coors, num_points, voxel_offsets, p, w.mins, w.maxs);
-        // one wave per voxel (wave_form 0: one thread per voxel, the round-2 form)
-        static int wave_form = -1;
-        if (wave_form < 0) wave_form = 1;
-        if (wave_form)
-            hipLaunchKernelGGL(k_bf_mask_wave, dim3(div_up(rows, kBlock / 64)), dim3(kBlock), 0, st, coors, voxel_offsets, p, w.mins,
-                               w.maxs, rows, w.keep);
-        else
-            hipLaunchKernelGGL(k_bf_mask, dim3(div_up(rows, kBlock)), dim3(kBlock), 0, st, coors, voxel_offsets, p, w.mins,
-                               w.maxs, rows, w.keep);
+        hipLaunchKernelGGL(k_bf_mask_wave, dim3(div_up(rows, kBlock / 64)), dim3(kBlock), 0, st, coors, voxel_offsets, p, w.mins,
+                           w.maxs, rows, w.keep);
     }
     if ((rc = exclusive_scan_i32(w.keep, w.pos, rows, w.total, w.scan, st))) return rc;
     long long work = (long long)(rows > 0 ? rows : 1) * max_points * num_features;

@@ -402,9 +402,9 @@ class PFNLayer(nn.Module):
 
 class PillarFeatureNet(nn.Module):
     """One-layer PillarFeatureNet (pointpillars.py:150-237); keys pfn_layers.0.{linear,norm}.  Inference on the
-    GPU runs the fused sec_pfn_fwd kernel, training on the GPU sec_pfn_train_fwd / _bwd (ops.PFNTrainFunction: batch statistics,
-    backward through the argmax; train_backend = "torch" selects the formulation below); the torch formulation serves CPU
-    tests and as the autograd reference of the training kernels."""
+    GPU runs the fused sec_pfn_kind_fwd kernel, training on the GPU sec_pfn_kind_train_fwd / _bwd (ops.PFNTrainFunction: batch
+    statistics, backward through the argmax; train_backend = "torch" selects the formulation below); the torch formulation serves
+    CPU tests and as the autograd reference of the training kernels."""
 
     kind = ops.PFN_PLAIN        # the decorated row (ops.PFN_*; include/second_hip.h); the subclasses differ in nothing else
 
@@ -420,11 +420,6 @@ class PillarFeatureNet(nn.Module):
         self.x_offset, self.y_offset = self.vx / 2 + pc_range[0], self.vy / 2 + pc_range[1]
 
     train_backend = "hip"       # "torch": the reference's materialised [P, T, C] formulation in training (A/B, tests)
-
-    @property
-    def _family(self):
-        """True where the row is not one of the two the entry points of before build (sec_pfn_* / sec_pfn_radius_*)."""
-        return self.with_distance or self.kind not in (ops.PFN_PLAIN, ops.PFN_RADIUS)
 
     def folded(self):
         """(W^T, scale, shift) of Linear + BatchNorm1d in eval mode; cached until one of the five tensors changes (in-place updates
@@ -448,16 +443,11 @@ class PillarFeatureNet(nn.Module):
         return ops.pfn_forward_slots(points, vox, wt, scale, shift, self.vx, self.vy, self.x_offset, self.y_offset,
                                      out_dtype=out_dtype, num_dev=num_dev, kind=self.kind, with_distance=self.with_distance)
 
-    train_function = ops.PFNTrainFunction      # the autograd Function of the training kernels for this class's decorated row
-
-    def _train_function(self):
-        return ops.pfn_kind_train_function(self.kind, self.with_distance) if self._family else self.train_function
-
     def _forward_train_kernels(self, features, num_voxels, coors, num_dev=None):
-        """Training on the device (sec_pfn_train_fwd / _bwd, or their radius forms: batch statistics, argmax backward, no
+        """Training on the device (sec_pfn_kind_train_fwd / _bwd on this class's row: batch statistics, argmax backward, no
         [P, T, C] tensor), or None where the torch formulation has to serve: CPU, eval / frozen or non-affine norm, a linear bias,
         train_backend = "torch", a shape the kernels do not take, no pillars.  ``num_dev``: static-capacity pillars with the count
-        on the device (the _live entry points); the torch formulation cannot serve those, so falling through is an error."""
+        on the device; the torch formulation cannot serve those, so falling through is an error."""
         l = self.pfn_layers[0]
         bn = l.norm
         if not (features.is_cuda and self.training and bn.training and bn.track_running_stats and bn.affine and l.linear.bias is None
@@ -468,9 +458,10 @@ class PillarFeatureNet(nn.Module):
                                    "training kernels (GPU, train_backend = 'hip', affine tracked BatchNorm, T <= 127, C <= 64)")
             return None
         mom = bn.momentum if bn.momentum is not None else 0.1
-        out = self._train_function().apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias,
-                                        bn.running_mean, bn.running_var, bn.eps, mom,
-                                        (self.vx, self.vy, self.x_offset, self.y_offset), *(() if num_dev is None else (num_dev,)))
+        fn = ops.pfn_kind_train_function(self.kind, self.with_distance)
+        out = fn.apply(features.contiguous(), num_voxels, coors.int(), l.linear.weight, bn.weight, bn.bias, bn.running_mean,
+                       bn.running_var, bn.eps, mom, (self.vx, self.vy, self.x_offset, self.y_offset),
+                       *(() if num_dev is None else (num_dev,)))
         ops.bump_bn_counter(bn)
         return out
 
@@ -523,26 +514,9 @@ class PillarFeatureNet(nn.Module):
 
 class PillarFeatureNetRadius(PillarFeatureNet):
     """One-layer PillarFeatureNetRadius (pointpillars.py:240-325; nuscenes/all.pp.mhead): the raw (x, y) of every point give way to
-    their radius, so the layer is Linear(num_input_features + 4, C); same keys pfn_layers.0.{linear,norm}.  Inference on the GPU runs
-    sec_pfn_radius_fwd (forward_slots: sec_pfn_radius_fwd_slots), training on the GPU sec_pfn_radius_train_fwd / _bwd
-    (ops.PFNRadiusTrainFunction, under the conditions of PillarFeatureNet; train_backend = "torch" selects the formulation below); the
-    torch formulation serves the CPU, eval mode with gradients, and as the autograd reference of the training kernels."""
-
-    train_function = ops.PFNRadiusTrainFunction
-
+    their radius, so the layer is Linear(num_input_features + 4, C); same keys pfn_layers.0.{linear,norm}.  sec_pfn_kind_* with
+    SEC_PFN_RADIUS (in training ops.PFNRadiusTrainFunction), under the conditions of PillarFeatureNet."""
     kind = ops.PFN_RADIUS
-
-    def forward(self, features, num_voxels, coors, out_dtype=None, num_dev=None):
-        if self.with_distance:
-            return super().forward(features, num_voxels, coors, out_dtype=out_dtype, num_dev=num_dev)
-        if features.is_cuda and not self.training and not torch.is_grad_enabled():
-            wt, scale, shift = self.folded()
-            return ops.pfn_radius_forward(features.float().contiguous(), num_voxels.int(), coors.int(), wt, scale, shift, self.vx,
-                                          self.vy, self.x_offset, self.y_offset, out_dtype=out_dtype, num_dev=num_dev)
-        out = self._forward_train_kernels(features, num_voxels, coors, num_dev)
-        if out is not None:
-            return out
-        return self._forward_torch(features, num_voxels, coors)
 
 
 class PillarFeatureNetOld(PillarFeatureNet):

@@ -750,9 +750,9 @@ def pfn_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_of
     """Fused PillarFeatureNet (one PFNLayer, eval): decorate -> Linear(9,C) -> folded BN -> ReLU -> max over points
     (second/pytorch/models/pointpillars.py:203-237,51-65).  voxels [P,T,4] fp32, coords [P,4] (b,z,y,x),
     weight_t [9,C] = linear.weight.T, scale/shift fp32 [C].
-    ``kind`` / ``with_distance``: the other encoders of the family on sec_pfn_kind_fwd (PFN_RADIUS, PFN_OLD, PFN_RADIUS_HEIGHT, each
-    with the optional distance entry; weight_t is [pfn_row_width(kind, with_distance), C]).  The defaults make the sec_pfn_fwd call
-    of before.  The input is never written (the reference's PillarFeatureNetOld centres the caller's x, y columns in place)."""
+    ``kind`` / ``with_distance``: the encoder of the family (sec_pfn_kind_fwd: PFN_PLAIN, PFN_RADIUS, PFN_OLD, PFN_RADIUS_HEIGHT, each
+    with the optional distance entry; weight_t is [pfn_row_width(kind, with_distance), C]).  The input is never written (the
+    reference's PillarFeatureNetOld centres the caller's x, y columns in place)."""
     rt.require_gpu(voxels, num_points, coords, weight_t, scale, shift)
     assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
     p, t, f = voxels.shape
@@ -760,31 +760,19 @@ def pfn_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_of
     assert weight_t.shape[0] == f - 4 + pfn_row_width(kind, with_distance) and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
     out_dtype = out_dtype or torch.float32
     out = torch.empty((p, c), dtype=out_dtype, device=voxels.device)
-    name, lead = ("sec_pfn_fwd", ()) if kind == PFN_PLAIN and not with_distance else ("sec_pfn_kind_fwd", (int(kind), int(bool(with_distance))))
-    rc = getattr(rt.lib(), name)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p, rt.ptr(num_dev), t, f,
-                                 rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset),
-                                 float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
-    rt.check(rc, name)
+    rc = rt.lib().sec_pfn_kind_fwd(int(kind), int(bool(with_distance)), rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p,
+                                   rt.ptr(num_dev), t, f, rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy),
+                                   float(x_offset), float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
+    rt.check(rc, "sec_pfn_kind_fwd")
     return out
 
 
-@_traced("pfn_radius_forward")
 def pfn_radius_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=None,
                        num_dev=None):
     """Fused PillarFeatureNetRadius (one PFNLayer, eval; pointpillars.py:290-325): :func:`pfn_forward` with the decorated row
     [hypot(x, y), z, w, x - mean, y - mean, z - mean, x - centre, y - centre], so weight_t is [8, C] = linear.weight.T."""
-    rt.require_gpu(voxels, num_points, coords, weight_t, scale, shift)
-    assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
-    p, t, f = voxels.shape
-    c = weight_t.shape[1]
-    assert weight_t.shape[0] == f + 4 and weight_t.dtype == torch.float32 and weight_t.is_contiguous()
-    out_dtype = out_dtype or torch.float32
-    out = torch.empty((p, c), dtype=out_dtype, device=voxels.device)
-    rc = rt.lib().sec_pfn_radius_fwd(rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords.contiguous()), p, rt.ptr(num_dev), t, f,
-                                     rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset),
-                                     float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
-    rt.check(rc, "sec_pfn_radius_fwd")
-    return out
+    return pfn_forward(voxels, num_points, coords, weight_t, scale, shift, vx, vy, x_offset, y_offset, out_dtype=out_dtype,
+                       num_dev=num_dev, kind=PFN_RADIUS)
 
 
 # ---- BatchNorm step counters of the fused training paths ----------------------------------------------------------------------
@@ -826,26 +814,16 @@ def pfn_train_supported(voxels, channels):
 
 
 class PFNTrainFunction(torch.autograd.Function):
-    """PFNLayer in training mode (Linear(9, C) -> BatchNorm1d batch statistics -> ReLU -> max over the points; pointpillars.py:51-65)
-    on sec_pfn_train_fwd / sec_pfn_train_bwd: the [P, T, C] activation tensor of the torch formulation never exists.  Gradients for
-    linear.weight [C, 9], the BatchNorm weight and bias; the points get none (they are data).  running_mean / running_var are
-    updated in place like torch.nn.BatchNorm1d does.  :class:`PFNRadiusTrainFunction` is the same code on the eight-entry row of
-    PillarFeatureNetRadius (sec_pfn_radius_train_fwd / _bwd, linear.weight [C, 8]).
+    """PFNLayer in training mode (Linear(K, C) -> BatchNorm1d batch statistics -> ReLU -> max over the points; pointpillars.py:51-65)
+    on sec_pfn_kind_train_fwd / _bwd: the [P, T, C] activation tensor of the torch formulation never exists.  Gradients for
+    linear.weight [C, K], the BatchNorm weight and bias; the points get none (they are data).  running_mean / running_var are
+    updated in place like torch.nn.BatchNorm1d does.  The class names the decorated row: ``KIND`` (PFN_*), ``WITH_DISTANCE`` and the
+    row width ``K`` that follows from them (stats is f32[C * (2 + K) + K]); this one is PillarFeatureNet's nine-entry row, the
+    subclasses of :func:`pfn_kind_train_function` are the same code on the other rows of the family.
     ``num_dev`` (optional last argument, int32 [1] on the device): static capacity -- the first min(max(num_dev[0], 0), P) rows are
-    pillars, read by the kernels when they run (sec_pfn_train_fwd_live / _bwd_live and their radius forms), so a captured step
-    replays on any count; the rows past it are never read, their ``out`` rows are zero and they enter no statistic or gradient."""
-    K = 9
-    FWD, BWD = "sec_pfn_train_fwd", "sec_pfn_train_bwd"
-
-    @classmethod
-    def _entry(cls, which, num_dev):
-        """(entry point, leading arguments, the num_dev argument if the form takes one) of ``which`` = "fwd" / "bwd"."""
-        name = cls.FWD if which == "fwd" else cls.BWD
-        return (name, (), ()) if num_dev is None else (name + "_live", (), (rt.ptr(num_dev),))
-
-    @classmethod
-    def _workspace_bytes(cls, p, c):
-        return rt.lib().sec_pfn_train_workspace_bytes(p, c)
+    pillars, read by the kernels when they run, so a captured step replays on any count; the rows past it are never read, their
+    ``out`` rows are zero and they enter no statistic or gradient."""
+    KIND, WITH_DISTANCE, K = PFN_PLAIN, False, 9
 
     @classmethod
     def _forward(cls, ctx, voxels, num_points, coords, weight, gamma, beta, running_mean, running_var, eps, momentum, geom,
@@ -854,7 +832,6 @@ class PFNTrainFunction(torch.autograd.Function):
         if num_dev is not None:
             rt.require_gpu(num_dev)
             assert num_dev.dtype == torch.int32 and num_dev.numel() >= 1
-        fwd, lead, live = cls._entry("fwd", num_dev)
         assert voxels.dtype == torch.float32 and voxels.is_contiguous() and coords.dtype == torch.int32
         p, t, f = voxels.shape
         c, k = weight.shape[0], cls.K
@@ -866,13 +843,14 @@ class PFNTrainFunction(torch.autograd.Function):
         arg = torch.empty((p, c), dtype=torch.int8, device=dev)
         stats = torch.empty((c * (2 + k) + k,), dtype=torch.float32, device=dev)
         l = rt.lib()
-        ws = rt.workspace(cls._workspace_bytes(p, c), dev)
+        row = (int(cls.KIND), int(cls.WITH_DISTANCE))
+        ws = rt.workspace(l.sec_pfn_kind_train_workspace_bytes(*row, p, c), dev)
         num_points, coords = num_points.int().contiguous(), coords.contiguous()
         vx, vy, xo, yo = [float(v) for v in geom]
-        rc = getattr(l, fwd)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(be),
-                             float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c, vx, vy, xo, yo,
-                             rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, fwd)
+        rc = l.sec_pfn_kind_train_fwd(*row, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, rt.ptr(num_dev), t, f, rt.ptr(wt),
+                                      rt.ptr(ga), rt.ptr(be), float(eps), float(momentum), rt.ptr(running_mean), rt.ptr(running_var), c,
+                                      vx, vy, xo, yo, rt.ptr(out), rt.ptr(arg), rt.ptr(stats), rt.ptr(ws), ws.numel(), rt.stream())
+        rt.check(rc, "sec_pfn_kind_train_fwd")
         ctx.save_for_backward(voxels, num_points, coords, wt, ga, stats, out, arg)
         ctx.num_dev = num_dev
         ctx.geom = (vx, vy, xo, yo)
@@ -889,14 +867,14 @@ class PFNTrainFunction(torch.autograd.Function):
         dga = torch.empty((c,), dtype=torch.float32, device=dev)
         dbe = torch.empty((c,), dtype=torch.float32, device=dev)
         l = rt.lib()
-        ws = rt.workspace(cls._workspace_bytes(p, c), dev)
+        row = (int(cls.KIND), int(cls.WITH_DISTANCE))
+        ws = rt.workspace(l.sec_pfn_kind_train_workspace_bytes(*row, p, c), dev)
         g = grad_out.float().contiguous()
         vx, vy, xo, yo = ctx.geom
-        bwd, lead, live = cls._entry("bwd", ctx.num_dev)
-        rc = getattr(l, bwd)(*lead, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, *live, t, f, rt.ptr(wt), rt.ptr(ga), rt.ptr(stats), c,
-                             vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt), rt.ptr(dga), rt.ptr(dbe),
-                             rt.ptr(ws), ws.numel(), rt.stream())
-        rt.check(rc, bwd)
+        rc = l.sec_pfn_kind_train_bwd(*row, rt.ptr(voxels), rt.ptr(num_points), rt.ptr(coords), p, rt.ptr(ctx.num_dev), t, f, rt.ptr(wt),
+                                      rt.ptr(ga), rt.ptr(stats), c, vx, vy, xo, yo, rt.ptr(g), rt.ptr(out), rt.ptr(arg), rt.ptr(dwt),
+                                      rt.ptr(dga), rt.ptr(dbe), rt.ptr(ws), ws.numel(), rt.stream())
+        rt.check(rc, "sec_pfn_kind_train_bwd")
         wd, gd, bd = ctx.dtypes
         return (None, None, None, dwt.t().contiguous().to(wd), dga.to(gd), dbe.to(bd), None, None, None, None, None, None)
 
@@ -909,60 +887,40 @@ class PFNTrainFunction(torch.autograd.Function):
         return PFNTrainFunction._backward(ctx, grad_out)
 
 
-class PFNKindTrainFunction(PFNTrainFunction):
-    """:class:`PFNTrainFunction` for any encoder of the family on sec_pfn_kind_train_fwd / _bwd: a subclass sets ``KIND`` (PFN_*) and
-    ``WITH_DISTANCE``, from which the row width K follows (linear.weight and its gradient are [C, K], stats f32[C * (2 + K) + K]);
-    :func:`pfn_kind_train_function` makes them.  ``num_dev`` as in the base class (the entry points take NULL for "every row")."""
-    KIND, WITH_DISTANCE = PFN_PLAIN, False
-    K = 9
+PFNKindTrainFunction = PFNTrainFunction     # the name callers of the kind family tested their classes against: the same base now
 
-    @classmethod
-    def _entry(cls, which, num_dev):
-        lead = (int(cls.KIND), int(bool(cls.WITH_DISTANCE)))
-        return "sec_pfn_kind_train_" + which, lead, (rt.ptr(num_dev),)
 
-    @classmethod
-    def _workspace_bytes(cls, p, c):
-        return rt.lib().sec_pfn_kind_train_workspace_bytes(int(cls.KIND), int(bool(cls.WITH_DISTANCE)), p, c)
-
-    @staticmethod
+def _pfn_train_subclass(name, kind, with_distance, doc):
+    """:class:`PFNTrainFunction` on another row: a class of its own (an autograd Function's forward / backward are static, so each
+    names its class), whose name is the autograd node's."""
     def forward(ctx, *args):
-        raise NotImplementedError("use a subclass made by pfn_kind_train_function(kind, with_distance)")
+        return fn._forward(ctx, *args)
 
+    def backward(ctx, grad_out):
+        return fn._backward(ctx, grad_out)
 
-_pfn_kind_functions = {}
-
-
-def pfn_kind_train_function(kind, with_distance=False):
-    """The :class:`PFNKindTrainFunction` subclass of one (kind, with_distance) pair; one class per pair, made on first use."""
-    key = (int(kind), bool(with_distance))
-    fn = _pfn_kind_functions.get(key)
-    if fn is None:
-        def forward(ctx, *args):
-            return fn._forward(ctx, *args)
-
-        def backward(ctx, grad_out):
-            return fn._backward(ctx, grad_out)
-
-        fn = _pfn_kind_functions[key] = type(
-            f"PFNKind{key[0]}{'Dist' if key[1] else ''}TrainFunction", (PFNKindTrainFunction,),
-            dict(KIND=key[0], WITH_DISTANCE=key[1], K=pfn_row_width(*key), forward=staticmethod(forward), backward=staticmethod(backward)))
+    fn = type(name, (PFNTrainFunction,), dict(KIND=kind, WITH_DISTANCE=with_distance, K=pfn_row_width(kind, with_distance), __doc__=doc,
+                                              forward=staticmethod(forward), backward=staticmethod(backward)))
     return fn
 
 
-class PFNRadiusTrainFunction(PFNTrainFunction):
+PFNRadiusTrainFunction = _pfn_train_subclass(
+    "PFNRadiusTrainFunction", PFN_RADIUS, False,
     """:class:`PFNTrainFunction` for PillarFeatureNetRadius (pointpillars.py:290-325 under train()): the decorated row is
-    [r, z, w, x - mean, y - mean, z - mean, x - centre, y - centre], linear.weight and its gradient are [C, 8]."""
-    K = 8
-    FWD, BWD = "sec_pfn_radius_train_fwd", "sec_pfn_radius_train_bwd"
+    [r, z, w, x - mean, y - mean, z - mean, x - centre, y - centre], linear.weight and its gradient are [C, 8].""")
 
-    @staticmethod
-    def forward(ctx, *args):
-        return PFNRadiusTrainFunction._forward(ctx, *args)
+_pfn_kind_functions = {(PFN_PLAIN, False): PFNTrainFunction, (PFN_RADIUS, False): PFNRadiusTrainFunction}
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        return PFNRadiusTrainFunction._backward(ctx, grad_out)
+
+def pfn_kind_train_function(kind, with_distance=False):
+    """The training Function of one (kind, with_distance) pair: :class:`PFNTrainFunction` / :class:`PFNRadiusTrainFunction` for the
+    rows they name, for the others a subclass of :class:`PFNTrainFunction` made on first use; one class per pair."""
+    key = (int(kind), bool(with_distance))
+    fn = _pfn_kind_functions.get(key)
+    if fn is None:
+        name = f"PFNKind{key[0]}{'Dist' if key[1] else ''}TrainFunction"
+        fn = _pfn_kind_functions[key] = _pfn_train_subclass(name, *key, f":class:`PFNTrainFunction` on the row {key} of the family.")
+    return fn
 
 
 @_traced("pfn_forward")
@@ -970,8 +928,7 @@ def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_o
                       kind=None, with_distance=False):
     """:func:`pfn_forward` straight from the voxeliser's point lists: ``vox`` = the result of ``voxelize(points, ..., fill=False)``
     (or with fill), ``points`` the array it was called on.  Bit-identical to the tensor form; no [P, T, 4] tensor is read.
-    ``radius``: :func:`pfn_radius_forward` the same way (sec_pfn_radius_fwd_slots).  ``kind`` / ``with_distance``: any encoder of the
-    family (sec_pfn_kind_fwd_slots); PFN_PLAIN / PFN_RADIUS without distance make the calls of before."""
+    ``kind`` / ``with_distance``: the encoder of the family (sec_pfn_kind_fwd_slots); ``radius=True`` is short for kind=PFN_RADIUS."""
     rt.require_gpu(points, weight_t, scale, shift)
     if kind is None:
         kind = PFN_RADIUS if radius else PFN_PLAIN
@@ -985,16 +942,11 @@ def pfn_forward_slots(points, vox, weight_t, scale, shift, vx, vy, x_offset, y_o
     batch = vox["voxel_offsets"].numel() - 1
     out_dtype = out_dtype or torch.float32
     out = torch.empty((p, c), dtype=out_dtype, device=points.device)
-    lead = ()
-    if with_distance or kind not in (PFN_PLAIN, PFN_RADIUS):
-        name, lead = "sec_pfn_kind_fwd_slots", (int(kind), int(bool(with_distance)))
-    else:
-        name = "sec_pfn_radius_fwd_slots" if kind == PFN_RADIUS else "sec_pfn_fwd_slots"
-    rc = getattr(rt.lib(), name)(*lead, rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels, max_points, points.shape[1],
-                                 rt.ptr(npv), rt.ptr(coords), p, rt.ptr(num_dev), rt.ptr(weight_t), rt.ptr(scale), rt.ptr(shift), c,
-                                 float(vx), float(vy), float(x_offset), float(y_offset), rt.ptr(out), rt.dtype_code(out_dtype),
-                                 rt.stream())
-    rt.check(rc, name)
+    rc = rt.lib().sec_pfn_kind_fwd_slots(int(kind), int(bool(with_distance)), rt.ptr(points), rt.ptr(ws), ws.numel(), n, batch, max_voxels,
+                                         max_points, points.shape[1], rt.ptr(npv), rt.ptr(coords), p, rt.ptr(num_dev), rt.ptr(weight_t),
+                                         rt.ptr(scale), rt.ptr(shift), c, float(vx), float(vy), float(x_offset), float(y_offset),
+                                         rt.ptr(out), rt.dtype_code(out_dtype), rt.stream())
+    rt.check(rc, "sec_pfn_kind_fwd_slots")
     return out
 
 

@@ -248,7 +248,7 @@ class DeviceTrainer:
                 labels, reg_targets, importance = ops.assign_targets_per_class(det.anchors, gt_boxes, gt_offsets, gt_classes,
                                                                                begin, ids, mts, uts, anchors_mask=amask, **sim)
         if det.pillars:
-            # PointPillars (nuscenes/all.pp.largea): PillarFeatureNet on sec_pfn_train_fwd / _bwd (batch statistics; the [P, T, C]
+            # PointPillars (nuscenes/all.pp.largea): PillarFeatureNet on sec_pfn_kind_train_fwd / _bwd (batch statistics; the [P, T, C]
             # tensor of the reference formulation is never built), differentiable pillar scatter (sec_pillar_scatter / sec_dense_to_sparse),
             # the three-block RPN through _rpn_mixed (16-bit) or torch convolutions (fp32)
             with torch.autocast("cuda", dtype=self.amp_dtype or torch.float32, enabled=self.amp_dtype is not None):
@@ -544,7 +544,7 @@ class _MultiHeadDense(torch.nn.Module):
 class MultiHeadDeviceTrainer(DeviceTrainer):
     """:class:`DeviceTrainer` for the multi-head networks (nuscenes/all.pp.mhead: PillarFeatureNetRadius, PointPillarsScatter,
     RPNNoHead, large_head on "out" and small_head on the cropped "stage0"; net_multi_head.py:121-176).  The pillar layer trains on
-    sec_pfn_radius_train_fwd / _bwd; fp32 runs the module graph of SecondDetector._network_forward, 16-bit
+    sec_pfn_kind_train_fwd / _bwd (SEC_PFN_RADIUS); fp32 runs the module graph of SecondDetector._network_forward, 16-bit
     models.multihead_forward_mixed (captured as two hipGraphs like the single-head segment, with the same eager fallbacks); targets
     per anchor range (ops.assign_targets_per_class over models.anchor_class_ranges), the loss is ops.SecondLossFunction on the
     concatenated predictions (the fused head loss has no form for these heads); bucket, FlatAdamW, clipping and fp16 loss scaling

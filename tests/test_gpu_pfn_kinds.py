@@ -86,10 +86,23 @@ def test_inference_live_count_through_the_c_entry_point(live, row):
             assert K.check_eval(out[:n], head, *row, kind) <= 1.0
 
 
-@pytest.mark.parametrize("radius", [False, True], ids=["plain", "radius"])
-def test_existing_rows_through_the_kind_entry_are_bit_equal(radius):
-    """Kinds 0 / 1 without distance through sec_pfn_kind_fwd run the instantiations of sec_pfn_fwd / sec_pfn_radius_fwd."""
+SLOTS_RANGE, SLOTS_VOXEL, SLOTS_GEOM = [0, 0, -3, 1, 1, 1], [0.25, 0.25, 4], (0.25, 0.25, 0.125, 0.125)
+
+
+def _slots_cloud(rng):
+    """The cloud of tests/test_gpu_pfn_edges.py: 300 points in one pillar (it overflows every T), 400 spread over the others; every
+    z below zero.  -> points [700, 4], the offsets of its two frames."""
+    pts = rng.uniform([0, 0, -3, 0], [1, 1, -0.25, 1], (700, 4)).astype(np.float32)
+    pts[:300, :2] = rng.uniform(0.51, 0.74, (300, 2))                                # all in pillar (2, 2) of the first cloud
+    pts[:380] = pts[rng.permutation(380)]
+    return pts, np.array([0, 380, 700], np.int32)
+
+
+def _older_forward(radius):
+    """sec_pfn_fwd / sec_pfn_radius_fwd through ctypes against ops.pfn_forward (T > 64: the second pass of the slot loop; C > 64: the
+    second pass of the channel loop; a negative BN scale)."""
     from second_amd import ops, runtime as rt
+    fn = rt.lib().sec_pfn_radius_fwd if radius else rt.lib().sec_pfn_fwd
     for case_id in ((33, 65, 65, "far", "plain"), (5, 9, 128, "axis", "negative_scale")):
         case = H.eval_case(*case_id)
         p, t, _ = case["vox"].shape
@@ -99,27 +112,108 @@ def test_existing_rows_through_the_kind_entry_are_bit_equal(radius):
         for dt in H.KINDS.values():
             want = (ops.pfn_radius_forward if radius else ops.pfn_forward)(*a, *case["geom"], out_dtype=dt)
             got = torch.empty_like(want)
-            rc = rt.lib().sec_pfn_kind_fwd(int(radius), 0, rt.ptr(a[0]), rt.ptr(a[1]), rt.ptr(a[2]), p, None, t, 4, rt.ptr(a[3]), rt.ptr(a[4]),
-                                           rt.ptr(a[5]), c, *[ctypes.c_float(v) for v in case["geom"]], rt.ptr(got), rt.dtype_code(dt), rt.stream())
+            rc = fn(rt.ptr(a[0]), rt.ptr(a[1]), rt.ptr(a[2]), p, None, t, 4, rt.ptr(a[3]), rt.ptr(a[4]), rt.ptr(a[5]), c,
+                    *[ctypes.c_float(v) for v in case["geom"]], rt.ptr(got), rt.dtype_code(dt), rt.stream())
             assert rc == 0
             assert torch.equal(got, want), (case_id, dt)
+
+
+def _older_forward_slots(radius):
+    """sec_pfn_fwd_slots / sec_pfn_radius_fwd_slots through ctypes against ops.pfn_forward_slots on the voxeliser's point lists
+    (fill=False), on both sides of the 64-slot pass."""
+    from second_amd import ops, runtime as rt
+    fn = rt.lib().sec_pfn_radius_fwd_slots if radius else rt.lib().sec_pfn_fwd_slots
+    for t in (5, 65):
+        rng = np.random.default_rng(t)
+        pts, offs = _slots_cloud(rng)
+        c = 65
+        wt = dev((rng.standard_normal((8 if radius else 9, c)) / 3).astype(np.float32))
+        sc, sh = dev(rng.uniform(0.5, 1.5, c).astype(np.float32)), dev(rng.uniform(-0.3, 0.3, c).astype(np.float32))
+        dpts = dev(pts)
+        v = ops.voxelize(dpts, dev(offs), SLOTS_RANGE, SLOTS_VOXEL, t, 32, "break", fill=False)
+        table, ws, n, max_voxels, max_points, _ = v["site_table"]
+        npv, coords = v["num_points_per_voxel"], v["coordinates"].contiguous()
+        assert int(npv.max()) == t and int(npv.min()) < t and (n, max_points) == (700, t)
+        p = coords.shape[0]
+        for dt in H.KINDS.values():
+            want = ops.pfn_forward_slots(dpts, v, wt, sc, sh, *SLOTS_GEOM, out_dtype=dt, radius=radius)
+            got = torch.empty_like(want)
+            rc = fn(rt.ptr(dpts), rt.ptr(ws), ws.numel(), n, 2, max_voxels, max_points, 4, rt.ptr(npv), rt.ptr(coords), p, None, rt.ptr(wt),
+                    rt.ptr(sc), rt.ptr(sh), c, *[ctypes.c_float(g) for g in SLOTS_GEOM], rt.ptr(got), rt.dtype_code(dt), rt.stream())
+            assert rc == 0
+            assert torch.equal(got, want), (t, dt)
+
+
+def _older_training(radius):
+    """sec_pfn_train_fwd / _bwd (or their radius forms; no count, the workspace of sec_pfn_train_workspace_bytes) through ctypes
+    against ops.PFNTrainFunction / PFNRadiusTrainFunction: out, argmax, stats, running statistics and the three gradients, bit for
+    bit.  T = 127: the int8 argmax sits at its last slot."""
+    from second_amd import ops, runtime as rt
+    l = rt.lib()
+    fwd = l.sec_pfn_radius_train_fwd if radius else l.sec_pfn_train_fwd
+    bwd = l.sec_pfn_radius_train_bwd if radius else l.sec_pfn_train_bwd
+    cls = ops.PFNRadiusTrainFunction if radius else ops.PFNTrainFunction
+    assert (3, 127, 64, "plain", (-0.3, 0.3)) in H.TRAIN_CASES
+    for p, t, c in ((33, 5, 16), (3, 127, 64)):
+        case = H.train_case(p, t, c, "plain")
+        wt = H._wt(case, radius)
+        k = wt.shape[0]
+        a = {n: dev(case[n]) for n in ("vox", "num", "coords", "gamma", "beta", "grad_out")}
+        geom = [ctypes.c_float(v) for v in case["geom"]]
+        # through ops
+        w, ga, be = dev(wt.T.copy()).requires_grad_(), a["gamma"].clone().requires_grad_(), a["beta"].clone().requires_grad_()
+        rm, rv = dev(np.asarray(case["rm0"], np.float32)), dev(np.asarray(case["rv0"], np.float32))
+        out = cls.apply(a["vox"], a["num"], a["coords"], w, ga, be, rm, rv, case["eps"], case["momentum"], case["geom"])
+        assert type(out.grad_fn).__name__ == cls.__name__ + "Backward"
+        saved = out.grad_fn.saved_tensors                          # voxels, num_points, coords, wt, gamma, stats, out, argmax
+        out.backward(a["grad_out"])
+        want = dict(out=out.detach(), argmax=saved[7], stats=saved[5], running_mean=rm, running_var=rv, d_linear_weight=w.grad,
+                    d_norm_weight=ga.grad, d_norm_bias=be.grad)
+        if t == 127:
+            assert bool((want["argmax"] == 126).any())
+        # the older symbols
+        dwt = dev(wt)
+        rm2, rv2 = dev(np.asarray(case["rm0"], np.float32)), dev(np.asarray(case["rv0"], np.float32))
+        out2, arg2 = torch.empty((p, c), device="cuda"), torch.empty((p, c), dtype=torch.int8, device="cuda")
+        stats2 = torch.empty((c * (2 + k) + k,), device="cuda")
+        dw, dg, db = torch.empty((k, c), device="cuda"), torch.empty((c,), device="cuda"), torch.empty((c,), device="cuda")
+        ws = rt.workspace(l.sec_pfn_train_workspace_bytes(p, c), "cuda")
+        rc = fwd(rt.ptr(a["vox"]), rt.ptr(a["num"]), rt.ptr(a["coords"]), p, t, 4, rt.ptr(dwt), rt.ptr(a["gamma"]), rt.ptr(a["beta"]),
+                 float(case["eps"]), float(case["momentum"]), rt.ptr(rm2), rt.ptr(rv2), c, *geom, rt.ptr(out2), rt.ptr(arg2), rt.ptr(stats2),
+                 rt.ptr(ws), ws.numel(), rt.stream())
+        assert rc == 0
+        rc = bwd(rt.ptr(a["vox"]), rt.ptr(a["num"]), rt.ptr(a["coords"]), p, t, 4, rt.ptr(dwt), rt.ptr(a["gamma"]), rt.ptr(stats2), c, *geom,
+                 rt.ptr(a["grad_out"]), rt.ptr(out2), rt.ptr(arg2), rt.ptr(dw), rt.ptr(dg), rt.ptr(db), rt.ptr(ws), ws.numel(), rt.stream())
+        assert rc == 0
+        got = dict(out=out2, argmax=arg2, stats=stats2, running_mean=rm2, running_var=rv2, d_linear_weight=dw.t(), d_norm_weight=dg,
+                   d_norm_bias=db)
+        for name in want:
+            assert torch.equal(got[name], want[name]), ((p, t, c), name)
+
+
+@pytest.mark.parametrize("radius", [False, True], ids=["plain", "radius"])
+def test_existing_rows_through_the_kind_entry_are_bit_equal(radius):
+    """The eight older C symbols without a count -- sec_pfn_fwd, sec_pfn_fwd_slots, sec_pfn_train_fwd / _bwd and their radius forms
+    -- forward to the launchers of sec_pfn_kind_* with kinds 0 / 1 and no distance.  The Python side calls the kind entry points
+    only, so here the older symbols are called through ctypes and must reproduce ops bit for bit (the four _live forms:
+    tests/test_gpu_pfn_live.py)."""
+    _older_forward(radius)
+    _older_forward_slots(radius)
+    _older_training(radius)
 
 
 # ---- slots forms ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("row", K.NEW_ROWS, ids=K.row_id)
 @pytest.mark.parametrize("t", [5, 64, 65, 200])
 def test_slots_form_is_bit_equal_to_the_tensor_form(t, row):
-    """The cloud of tests/test_gpu_pfn_edges.py: 300 points in one pillar (it overflows every T), 400 spread over the others; every
-    z below zero, so a ragged pillar's h has the padded zero as its maximum in both forms (the slots form reads slots >= n as zero)."""
+    """The cloud of _slots_cloud; every z below zero, so a ragged pillar's h has the padded zero as its maximum in both forms (the
+    slots form reads slots >= n as zero)."""
     from second_amd import ops
     kind, dist = row
     rng = np.random.default_rng(t)
-    pts = rng.uniform([0, 0, -3, 0], [1, 1, -0.25, 1], (700, 4)).astype(np.float32)
-    pts[:300, :2] = rng.uniform(0.51, 0.74, (300, 2))                                # all in pillar (2, 2) of the first cloud
-    pts[:380] = pts[rng.permutation(380)]
-    offs = np.array([0, 380, 700], np.int32)
-    rg, vs = [0, 0, -3, 1, 1, 1], [0.25, 0.25, 4]
-    geom = (0.25, 0.25, 0.125, 0.125)
+    pts, offs = _slots_cloud(rng)
+    rg, vs = SLOTS_RANGE, SLOTS_VOXEL
+    geom = SLOTS_GEOM
     c = 65
     wt = (rng.standard_normal((K.width(kind, dist), c)) / 3).astype(np.float32)
     sc, sh = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.uniform(-0.3, 0.3, c).astype(np.float32)
@@ -144,7 +238,7 @@ def _train(case, row, backward=True, num_dev=None):
     from second_amd import ops
     kind, dist = row
     cls = ops.pfn_kind_train_function(kind, dist)
-    assert issubclass(cls, ops.PFNKindTrainFunction) and (cls.KIND, cls.WITH_DISTANCE, cls.K) == (kind, dist, K.width(kind, dist))
+    assert issubclass(cls, ops.PFNTrainFunction) and (cls.KIND, cls.WITH_DISTANCE, cls.K) == (kind, dist, K.width(kind, dist))
     wt = K.wt_of(case, kind, dist)
     c = wt.shape[1]
     w, ga, be = dev(wt.T.copy()).requires_grad_(), dev(case["gamma"]).requires_grad_(), dev(case["beta"]).requires_grad_()
@@ -201,7 +295,7 @@ def test_training_live_count_behind_a_garbage_tail(row):
 @pytest.mark.parametrize("row", K.NEW_ROWS, ids=K.row_id)
 def test_module_runs_the_kernels_and_matches_the_fixture(row):
     """models.PillarFeatureNet* on the GPU against what the reference's module computed (tests/golden/pfn_kinds.npz): eval through
-    forward, training through PFNKindTrainFunction, input untouched."""
+    forward, training through the row's class of ops.pfn_kind_train_function, input untouched."""
     from second_amd import models, ops
     kind, dist = row
     g = K.load_fixture()

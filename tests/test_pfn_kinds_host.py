@@ -196,6 +196,23 @@ def test_kind_entry_points_validate_before_any_launch():
     assert tf(K.OLD, 0, t=128) == -3 and tb(K.OLD, 0, t=128) == -3                   # T > 127: the int8 argmax ends at slot 126
 
 
+def test_one_training_function_per_row_of_the_family():
+    """ops.pfn_kind_train_function (no library call): one cached class per (kind, with_distance), the two named classes for the rows
+    they name, every class a PFNTrainFunction that carries its row and the row's width."""
+    from second_amd import ops
+    assert len(K.ALL_ROWS) == 8
+    classes = {row: ops.pfn_kind_train_function(*row) for row in K.ALL_ROWS}
+    assert classes[(K.PLAIN, False)] is ops.PFNTrainFunction and classes[(K.RADIUS, False)] is ops.PFNRadiusTrainFunction
+    assert ops.PFNKindTrainFunction is ops.PFNTrainFunction            # the earlier base's name: callers' issubclass checks hold
+    assert len(set(classes.values())) == 8 and len({cls.__name__ for cls in classes.values()}) == 8
+    for (kind, dist), cls in classes.items():
+        assert ops.pfn_kind_train_function(kind, dist) is cls and ops.pfn_kind_train_function(int(kind), int(dist)) is cls
+        assert issubclass(cls, ops.PFNTrainFunction)
+        assert (cls.KIND, cls.WITH_DISTANCE, cls.K) == (kind, dist, K.width(kind, dist))
+    with pytest.raises(ValueError):
+        ops.pfn_kind_train_function(4, False)
+
+
 # ---- the models' torch formulations ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("row", K.ALL_ROWS, ids=K.row_id)
 def test_torch_formulation_matches_the_fixture_and_leaves_its_input(fixture, row):

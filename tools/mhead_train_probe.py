@@ -5,7 +5,7 @@ synthetic clouds of 60 000 points, 40 boxes per frame spread over both heads' cl
       once outside the loop, as the reference's data loader does it on the host);
   (b) ``training.MultiHeadDeviceTrainer`` in fp32 and (c) in bf16: voxelisation and target assignment included;
   (d) the PillarFeatureNetRadius layer alone at 4 x 30 000 pillars x 60 slots: forward + backward of the torch formulation against
-      sec_pfn_radius_train_fwd / _bwd, with the peak memory of each (torch.cuda.max_memory_allocated above the resident inputs);
+      sec_pfn_kind_train_fwd / _bwd (SEC_PFN_RADIUS), with the peak memory of each (torch.cuda.max_memory_allocated above the resident inputs);
   (e) the 64-channel 3x3 convolutions that stay on torch in (c) -- block 0 and the small head's tower -- forward + backward alone,
       and their share of the bf16 step (the follow-up DESIGN.md section 9h names).
 Medians of three windows of >= 0.5 s after warm-up.  No figure here is a pass criterion.

@@ -1,6 +1,6 @@
 """Probe: the PillarFeatureNet family (plain, radius, old, radius_height; each also with_distance) at nuScenes size.
   (a) the layer alone at 4 x 30 000 pillars x 60 slots, 64 channels: forward (eval) and forward + backward (train) of every kind on the
-      kernels (sec_pfn_fwd / sec_pfn_radius_fwd / sec_pfn_kind_*) against the module's torch formulation (the reference's
+      kernels (sec_pfn_kind_*) against the module's torch formulation (the reference's
       materialised [P, T, C] tensor), with the peak memory of each above the resident inputs;
   (b) ``SecondDetector.forward_points`` at models.ALL_PP_MIDA (PillarFeatureNetOld, 400 x 400 pillars, 200 000 anchors), batch 8, bf16.
 Medians of three windows of >= 0.5 s after warm-up.  No figure here is a pass criterion.
