@@ -835,6 +835,16 @@ int sec_predict_decode(const void *box, const int64_t *h_box_strides5, const voi
                        int h, int w, int k, const float *anchors, const int *top_idx,
                        const float *top_score, int rotate, float *decoded, float *dets, int *dir_label,
                        int dtype, void *stream);
+/* Which form every select entry point below takes for a head (or a list of heads) of anchors_per_frame anchors per frame: a pure
+ * function of its arguments, nothing is launched.  *chunks (may be NULL) receives the first-stage chunk count of a chunked form, else 0.
+ *   "radix32"          fp32 heads: radix select on 32-bit keys
+ *   "direct"           16-bit heads of up to 8 192 anchors (one chunk): one workgroup per frame on 16-bit keys held in registers
+ *   "chunk4+kpN"       16-bit heads of up to 589 824 anchors: top-k of every 8192-anchor chunk, then one workgroup per frame over the
+ *                      candidates with N = 5 / 10 / 20 / 36 key pairs per thread
+ *   "chunk36+kpN"      ... of up to 5 308 416 anchors: chunks of 73 728 anchors
+ *   "radix16"          larger 16-bit heads: the radix select again (on 32-bit keys of the 16-bit logits)
+ *   ""                 a dtype the select refuses */
+const char *sec_predict_select_plan_name(long long anchors_per_frame, int dtype, int *chunks);
 /* LAZY heads: the producer of the head tensor (sec_conv1x1_chain_nhwc_tiles with background == NULL and SEC_CHAIN_X_LIVE_ONLY) wrote
  * only the 8 x 16 tiles its live list names -- the copy of the other ~60 % of the map (22 MB per batch of 8 for car.fhd) never
  * happens.  tile_live [batch][ceil(h/8) * ceil(w/16)] (row-major tiles): bit 4 set = the tile was written (the tile-indexed half of

@@ -22,6 +22,15 @@ void set_last_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)))
 template <typename T> inline const char *dtype_name() { return "float"; }
 template <> inline const char *dtype_name<__hip_bfloat16>() { return "__hip_bfloat16"; }
 template <> inline const char *dtype_name<__half>() { return "__half"; }
+// Host-side type dispatch: f(TypeTag<element type>) for a dtype code, f a generic lambda (`typename decltype(t)::type` inside it).
+template <typename T> struct TypeTag { using type = T; };
+// a 16-bit dtype code (the caller has refused every other code)
+template <typename F> inline int by_dtype16(int dtype, F &&f) { return dtype == SEC_BF16 ? f(TypeTag<__hip_bfloat16>{}) : f(TypeTag<__half>{}); }
+// SEC_F32 / SEC_BF16 / SEC_F16; any other code is refused
+template <typename F> inline int by_dtype(int dtype, F &&f) {
+    if (dtype == SEC_F32) return f(TypeTag<float>{});
+    return dtype == SEC_BF16 || dtype == SEC_F16 ? by_dtype16(dtype, f) : SEC_E_UNSUPPORTED;
+}
 inline int check_launch() {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error(e); return SEC_E_LAUNCH; }

@@ -1926,10 +1926,6 @@ static int launch_conv2d_plan_t(const Conv2dPlan &d, const void *x, const void *
     return SEC_E_UNSUPPORTED;       // not taken, or a plan without an instantiation
 }
 
-template <typename T> struct TypeTag { using type = T; };
-// f(TypeTag<element type>) for a 16-bit dtype code (the caller has refused every other code)
-template <typename F> static int by_dtype16(int dtype, F &&f) { return dtype == SEC_BF16 ? f(TypeTag<__hip_bfloat16>{}) : f(TypeTag<__half>{}); }
-
 // `ldc`: channel pitch of y in elements (sec_conv2d_nhwc_into; p.cout everywhere else)
 static int launch_conv2d_plan(const Conv2dPlan &d, int dtype, const void *x, const void *wpk, const float *bias, void *y, const Conv2dParams &p,
                               int ldc, const Conv2dExtra &e, void *stream) {

@@ -413,13 +413,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
     const unsigned *fk2 = reinterpret_cast<const unsigned *>(keys + (size_t)b * ns);   // ns is even: dword aligned
     if (K > kSelThreads) K = kSelThreads;
     if (K > N) K = N;
-#ifdef SEC_SELECT_TIMING
-    long long tstamp[8]; int tsi = 0;
-#define SEC_TS() do { __syncthreads(); tstamp[tsi++] = clock64(); } while (0)
-#else
-#define SEC_TS() do {} while (0)
-#endif
-    SEC_TS();
     const int n_base = wv * (KP * 128) + lane * 2;    // pair i of this thread = anchors n_base + 128 i and + 1
     unsigned k2[KP];                                  // low half: even anchor's key, high half: the odd one's
 #pragma unroll
@@ -427,7 +420,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
         const int n = n_base + i * 128;
         k2[i] = ld_sel(fk2, n >> 1, n < ns, 0u);
     }
-    SEC_TS();
     // K-th largest 16-bit key by bisection on its bits, MSB first (no histogram, no atomics).  Counting sweeps run over
     // all registers only while more than CAND_CAP keys lie at or above the current lower bound; then those few are
     // compacted into LDS (two per thread) and the remaining bits are resolved on them.  Out-of-range slots hold key 0
@@ -538,7 +530,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
         }
     }
     const unsigned prefix = cand;
-    SEC_TS();
     if (!sorted_ready) {
     const unsigned need = cand == 0xffffu ? (unsigned)K : (unsigned)(K - count_ge(cand + 1, it));
     const unsigned T_key = prefix;   // K-th largest (16-bit) key; take all keys > T and the first `need` (by index) equal to T
@@ -578,7 +569,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
     }
     }   // !sorted_ready
     __syncthreads();
-    SEC_TS();
     // ---- bitonic sort of (key desc, idx asc); strides < 64 stay inside the wave (shuffles), the rest go through LDS
     unsigned mk = ckey[tid];
     int mi = cidx[tid];
@@ -602,7 +592,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
             if (!keep_mine) { mk = ok_; mi = oi; }
         }
     }
-    SEC_TS();
     // ---- outputs
     if (INDIRECT) {                                   // slot -> anchor id (empty candidate slots carry 0x7fffffff)
         const int a_ = (mi < N) ? slot_anchor[(size_t)b * N + mi] : 0x7fffffff;
@@ -627,13 +616,6 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_reg(const T *__r
         for (int w2 = 0; w2 < kSelThreads / 64; ++w2) tot += wsum[w2];
         counts[b] = tot;
     }
-#ifdef SEC_SELECT_TIMING
-    SEC_TS();
-    if (b == 0 && tid == 0)
-        printf("[select_reg] load %lld  bisect %lld  compact %lld  sort %lld  out %lld  (clock64 ticks)\n", tstamp[1] - tstamp[0],
-               tstamp[2] - tstamp[1], tstamp[3] - tstamp[2], tstamp[4] - tstamp[3], tstamp[5] - tstamp[4]);
-#endif
-#undef SEC_TS
 }
 
 // ---- chunked select, stage 1 (whole chip) -------------------------------------------------------------------------------
@@ -1180,26 +1162,41 @@ __global__ __launch_bounds__(kBlock) void k_predict_finalize_classes(const float
 
 using namespace sec;
 
+// ---- host side: head forms, the select decision, one launcher per stage, thin entry points ----------------------------------
 static View5 mkview(const int64_t *s) { return View5{s[0], s[1], s[2], s[3], s[4], 0, nullptr, 0, 0, nullptr, nullptr, 0, 0}; }
-// the lazy form of a view: `base` is the view's pointer, `background` the same element of the empty frame's map
-static View5 mkview_lazy(const int64_t *s, const void *base, const void *background, const unsigned short *tile_live, int h, int w, int elt,
-                         const unsigned *cover_cols = nullptr) {
-    View5 v = mkview(s);
-    if (cover_cols && background) {
-        v.bg = (long long)((const char *)background - (const char *)base) / elt;
-        v.cover = cover_cols;
-        v.cwr = (w + 31) / 32;
-        v.cbands = (h + 7) / 8;
-    } else if (tile_live && background) {
-        v.bg = (long long)((const char *)background - (const char *)base) / elt;
-        v.live = tile_live;
-        v.tiles_x = (w + 15) / 16;
-        v.tpf = ((h + 7) / 8) * v.tiles_x;
-    }
-    return v;
-}
 static int elt_bytes(int dtype) { return dtype == SEC_F32 ? 4 : 2; }
+static bool dtype_ok(int dtype) { return dtype >= SEC_F32 && dtype <= SEC_BF16; }
 
+// How the producer left a head tensor, and which anchors take part.  All NULL: an EAGER head.  tile_live: TILE-LAZY (bit 4 of
+// tile_live[b][tile] = the 8 x 16 tile was written).  cover_cols: COVER-LAZY (a bit per pixel column and 8-row band).  A lazy head
+// reads every unwritten element from the empty frame's map: `background` for the cls (select) / box (decode) view, `dir_background`
+// for the decode's direction view.  anchor_mask: the MASKED select (on any of the three).
+struct HeadForm {
+    const unsigned short *tile_live; const unsigned *cover_cols; const void *background, *dir_background; const unsigned char *anchor_mask;
+};
+// the View5 of one view of such a head (`base` its pointer, `background` the same element of the empty frame's map); SEC_E_INVALID
+// for both lazy forms at once, a lazy form without its background or a background without a lazy form
+static int head_view(const HeadForm &f, const int64_t *strides5, const void *base, const void *background, int h, int w, int dtype, View5 *out) {
+    if ((f.tile_live && f.cover_cols) || (f.tile_live != nullptr || f.cover_cols != nullptr) != (background != nullptr)) return SEC_E_INVALID;
+    View5 v = mkview(strides5);
+    if (background) v.bg = (long long)((const char *)background - (const char *)base) / elt_bytes(dtype);
+    if (f.cover_cols) { v.cover = f.cover_cols; v.cwr = (w + 31) / 32; v.cbands = (h + 7) / 8; }
+    else if (f.tile_live) { v.live = f.tile_live; v.tiles_x = (w + 15) / 16; v.tpf = ((h + 7) / 8) * v.tiles_x; }
+    v.amask = f.anchor_mask;
+    *out = v;
+    return SEC_OK;
+}
+
+static unsigned ordered_key(float x) {               // f2key() on the host
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// 32-bit key of a logit safely below the score threshold's (k_predict_select's shortcut; 0: none)
+static unsigned conservative_thr32(float thr) {
+    if (!(thr > 0.0f) || !(thr < 1.0f)) return 0u;
+    const float x = logf(thr / (1.0f - thr));
+    return ordered_key(x - (fabsf(x) * 1e-4f + 1e-5f));
+}
 // a 16-bit key no larger than the key of any bf16 logit whose sigmoid reaches `thr` (0 = no such bound): the logit of thr, lowered
 // by more than bf16's and sigmoidf's rounding, mapped like f2key() >> 16, minus one key step (truncation of a negative value's
 // bits rounds it UP)
@@ -1207,146 +1204,128 @@ static unsigned conservative_thr16(float thr, int dtype) {
     if (!(thr > 0.0f) || !(thr < 1.0f)) return 0u;
     float x = logf(thr / (1.0f - thr));
     x -= fabsf(x) / 64.0f + 0.01f;
-    unsigned k16;
+    unsigned k16 = ordered_key(x) >> 16;
     if (dtype == SEC_F16) {                          // key16_of<__half>: the sign trick on the half's own bits
         if (!(fabsf(x) < 60000.0f)) return 0u;
         const unsigned u = __half_as_ushort(__float2half_rn(x));
         k16 = (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
-    } else {
-        unsigned u;
-        __builtin_memcpy(&u, &x, 4);
-        const unsigned key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        k16 = key >> 16;
     }
     return k16 > 2u ? k16 - 2u : 0u;                 // two key steps down: covers the rounding of the conversions above
 }
 
-template <typename V>
-static int predict_select_launch(const void *cls, const V &v, const PredGeom &g, int k, float score_thr, unsigned *key_scratch, int *top_idx,
-                                 float *top_score, int *top_label, int *counts, int dtype, void *stream);
+// ---- the select decision, by anchors per frame and dtype; the names are those of sec_predict_select_plan_name ---------------------
+//   radix32        fp32 heads: k_predict_keys + k_predict_select<float, false>, an 8-bit radix select on 32-bit keys
+//   direct         16-bit heads of up to kSelChunk = 8192 anchors: k_predict_keys16 + one k_predict_select_reg<T, 36> workgroup per frame
+//   chunkKP+kpKP2  larger ones: per-chunk top-K on the whole chip (k_predict_select_chunk<T, KP>: chunks of 8192 anchors, KP 4, while their
+//                  candidate lists fit the second stage; of 73 728 anchors, KP 36, up to 5.3 M anchors per frame), then one workgroup per
+//                  frame over the chunks * 1024 candidates (k_predict_select_reg<T, KP2, INDIRECT>, KP2 = 5 / 10 / 20 / 36 key pairs per thread)
+//   radix16        16-bit heads above that: the radix select OF A 16-BIT HEAD.  Its kernels are the 32-bit-key ones of radix32:
+//                  k_predict_select<bf16, true> (two passes, over the high half of the key) and k_predict_select<__half, false>
+enum class SelectForm { kRefused, kRadix32, kRadix16, kDirect, kChunked };
+struct SelectPlan { SelectForm form; int kp, chunks, kp2; };   // of kChunked only: first-stage KP (4 / 36), its chunk count, second-stage KP2
+constexpr long long kSelRegCap = (long long)kSelThreads * 72;   // keys one workgroup of k_predict_select_reg holds (KP 36)
 
-static int predict_select_impl(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
-                               int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
-                               int *top_label, int *counts, int dtype, void *stream, const unsigned short *tile_live,
-                               const void *cls_background, const unsigned char *anchor_mask, const unsigned *cover_cols = nullptr) {
-    if (!key_scratch) return SEC_E_WORKSPACE;
-    if (!cls || !h_cls_strides5 || batch <= 0 || anchors_per_loc <= 0 || h <= 0 || w <= 0 || num_class <= 0 || k <= 0 ||
-        k > kSelThreads || !top_idx || !top_score || !top_label || !counts)
-        return SEC_E_INVALID;
-    if ((tile_live != nullptr || cover_cols != nullptr) != (cls_background != nullptr) || (tile_live && cover_cols) || dtype < SEC_F32 || dtype > SEC_BF16) return SEC_E_INVALID;
-    // a masked-out anchor's key stands for no score; with a threshold <= 0 (no shipped config has one) it would be counted
-    if (anchor_mask && !(score_thr > 0.0f)) return SEC_E_UNSUPPORTED;
-    PredGeom g{batch, anchors_per_loc, h, w, num_class};
-    View5 v = mkview_lazy(h_cls_strides5, cls, cls_background, tile_live, h, w, elt_bytes(dtype), cover_cols);
-    v.amask = anchor_mask;
-    return predict_select_launch(cls, v, g, k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, stream);
+static SelectPlan predict_select_decide(long long n /* anchors per frame */, int dtype) {
+    if (dtype == SEC_F32) return {SelectForm::kRadix32, 0, 0, 0};
+    if (dtype != SEC_BF16 && dtype != SEC_F16) return {SelectForm::kRefused, 0, 0, 0};
+    const long long c4 = (n + kSelChunk - 1) / kSelChunk, c36 = (n + kSelRegCap - 1) / kSelRegCap;
+    SelectPlan p{SelectForm::kChunked, 0, 0, 0};
+    if (c4 >= 2 && c4 * kSelThreads <= kSelRegCap) { p.kp = 4; p.chunks = (int)c4; }
+    else if (n > kSelRegCap && c36 * kSelThreads <= kSelRegCap) { p.kp = 36; p.chunks = (int)c36; }
+    else return {n <= kSelRegCap ? SelectForm::kDirect : SelectForm::kRadix16, 0, 0, 0};
+    const int pairs = (p.chunks + 1) / 2;            // key pairs per second-stage thread: chunks * 1024 candidates / 2 / 1024 threads
+    p.kp2 = pairs <= 5 ? 5 : pairs <= 10 ? 10 : pairs <= 20 ? 20 : 36;
+    return p;
 }
+
+SEC_API const char *sec_predict_select_plan_name(long long anchors_per_frame, int dtype, int *chunks) {
+    static const char *const plain[] = {"", "radix32", "radix16", "direct"};          // indexed by SelectForm
+    static const char *const chunked[2][4] = {{"chunk4+kp5", "chunk4+kp10", "chunk4+kp20", "chunk4+kp36"},
+                                              {"chunk36+kp5", "chunk36+kp10", "chunk36+kp20", "chunk36+kp36"}};
+    const SelectPlan p = predict_select_decide(anchors_per_frame, dtype);
+    if (chunks) *chunks = p.chunks;
+    return p.form == SelectForm::kChunked ? chunked[p.kp == 36][p.kp2 == 5 ? 0 : p.kp2 == 10 ? 1 : p.kp2 == 20 ? 2 : 3] : plain[(int)p.form];
+}
+
+struct SelectArgs {                                  // what every select entry point takes besides its head(s)
+    int k; float score_thr; unsigned *key_scratch; int *top_idx; float *top_score; int *top_label, *counts; int dtype; hipStream_t st;
+};
+template <int N> using Int = std::integral_constant<int, N>;
 
 // the select of a validated call; V = View5 (one head tensor, g = its geometry) or SegView (cls unused, g.A * g.H * g.W = all anchors)
 template <typename V>
-static int predict_select_launch(const void *cls, const V &v, const PredGeom &g, int k, float score_thr, unsigned *key_scratch, int *top_idx,
-                                 float *top_score, int *top_label, int *counts, int dtype, void *stream) {
-    const int batch = g.batch;
-    hipStream_t st = (hipStream_t)stream;
+static int predict_select_launch(const void *cls, const V &v, const PredGeom &g, const SelectArgs &a) {
     const long long nfr = (long long)g.A * g.H * g.W;
-    const long long total = (long long)batch * nfr;
-#define SEC_SEL(T, K16)                                                                                                         \
-    do {                                                                                                                        \
-        hipLaunchKernelGGL((k_predict_keys<T, V>), dim3(div_up(total, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, key_scratch); \
-            hipLaunchKernelGGL((k_predict_select<T, K16, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k,        \
-                               score_thr, key_scratch, top_idx, top_score, top_label, counts, thr_key32);                        \
-    } while (0)
-    // 32-bit key of a logit safely below the score threshold's (k_predict_select's shortcut; 0: none)
-    unsigned thr_key32 = 0u;
-    if (score_thr > 0.0f && score_thr < 1.0f) {
-        float x = logf(score_thr / (1.0f - score_thr));
-        x -= fabsf(x) * 1e-4f + 1e-5f;
-        unsigned u;
-        __builtin_memcpy(&u, &x, 4);
-        thr_key32 = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    // 16-bit heads (bf16 / fp16): register-resident select on 16-bit keys
-    static int use_thr = -1, chunked = -1;
-    if (use_thr < 0) use_thr = 1;
-    if (chunked < 0) chunked = 1;
-    const bool h16 = dtype == SEC_BF16 || dtype == SEC_F16;
-    const unsigned thr16 = (use_thr && h16) ? conservative_thr16(score_thr, dtype) : 0u;
-    const long long reg_cap = (long long)kSelThreads * 72;           // keys one workgroup of k_predict_select_reg holds
-    // chunked form: per-chunk top-K on the whole chip, then one workgroup per frame over the candidates.  Chunks of 8192 anchors
-    // (KP 4) while their candidate lists fit the second stage, of 73 728 anchors (KP 36) for larger heads (up to 5.3 M anchors per
-    // frame).  The candidate arrays live in key_scratch (4 bytes per anchor; they need 6 bytes per candidate slot).
-    int kp = 0;
-    if (h16 && chunked) {
-        const long long c4 = (nfr + kSelChunk - 1) / kSelChunk, c36 = (nfr + reg_cap - 1) / reg_cap;
-        if (c4 >= 2 && c4 * kSelThreads <= reg_cap) kp = 4;
-        else if (nfr > reg_cap && c36 * kSelThreads <= reg_cap) kp = 36;
-    }
-    if (kp) {
-        const long long per = (long long)kSelThreads * 2 * kp;
-        const int chunks = (int)((nfr + per - 1) / per);
-        const long long n2 = (long long)chunks * kSelThreads;
-        if ((size_t)batch * n2 * 6 <= (size_t)total * 4) {
-            unsigned short *ck = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(key_scratch) + (size_t)batch * n2 * 4);
-            int *ci = reinterpret_cast<int *>(key_scratch);
-            const int pairs = (int)((n2 / 2 + kSelThreads - 1) / kSelThreads);
-#define SEC_SEL2(T, KP2) hipLaunchKernelGGL((k_predict_select_reg<T, KP2, true, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, \
-                                            score_thr, ck, (int)n2, top_idx, top_score, top_label, counts, (int)n2, ci, thr16)
-#define SEC_CHUNKED(T)                                                                                                                      \
-    do {                                                                                                                                    \
-        if (kp == 4)                                                                                                                        \
-            hipLaunchKernelGGL((k_predict_select_chunk<T, 4, V>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
-                               chunks, thr16, ck, ci);                                                                                      \
-        else                                                                                                                                \
-            hipLaunchKernelGGL((k_predict_select_chunk<T, 36, V>), dim3(chunks, batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, (int)nfr, k, \
-                               chunks, thr16, ck, ci);                                                                                      \
-        if (pairs <= 5) SEC_SEL2(T, 5);                                                                                                     \
-        else if (pairs <= 10) SEC_SEL2(T, 10);                                                                                              \
-        else if (pairs <= 20) SEC_SEL2(T, 20);                                                                                              \
-        else SEC_SEL2(T, 36);                                                                                                               \
-    } while (0)
-            if (dtype == SEC_BF16) SEC_CHUNKED(__hip_bfloat16);
-            else SEC_CHUNKED(__half);
-#undef SEC_CHUNKED
-#undef SEC_SEL2
-            return check_launch();
+    const SelectPlan plan = predict_select_decide(nfr, a.dtype);
+    if (plan.form == SelectForm::kRefused) return SEC_E_UNSUPPORTED;
+    const dim3 frames(g.batch), wg(kSelThreads);
+    return by_dtype(a.dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *c = (const T *)cls;
+        if (plan.form == SelectForm::kRadix32 || plan.form == SelectForm::kRadix16) {
+            constexpr bool kKey16 = std::is_same<T, __hip_bfloat16>::value;
+            hipLaunchKernelGGL((k_predict_keys<T, V>), dim3(div_up((long long)g.batch * nfr, kBlock)), dim3(kBlock), 0, a.st, c, v, g, a.key_scratch);
+            hipLaunchKernelGGL((k_predict_select<T, kKey16, V>), frames, wg, 0, a.st, c, v, g, a.k, a.score_thr, a.key_scratch, a.top_idx,
+                               a.top_score, a.top_label, a.counts, conservative_thr32(a.score_thr));
+        } else if constexpr (!std::is_same<T, float>::value) {      // (the 16-bit forms have no fp32 instantiation)
+            const unsigned thr16 = conservative_thr16(a.score_thr, a.dtype);
+            if (plan.form == SelectForm::kDirect) {
+                const int ns = (int)((nfr + 1) & ~1ll);
+                unsigned short *keys16 = reinterpret_cast<unsigned short *>(a.key_scratch);
+                hipLaunchKernelGGL((k_predict_keys16<T, V>), dim3(div_up((long long)g.batch * ns, kBlock)), dim3(kBlock), 0, a.st, c, v, g, ns, keys16);
+                hipLaunchKernelGGL((k_predict_select_reg<T, 36, false, V>), frames, wg, 0, a.st, c, v, g, a.k, a.score_thr, keys16, ns, a.top_idx,
+                                   a.top_score, a.top_label, a.counts, 0, (const int *)nullptr, thr16);
+            } else {
+                // The candidate arrays live in key_scratch: n2 = chunks * 1024 slots per frame, 4 bytes of anchor id then 2 bytes of key
+                // each, inside the 4 bytes per anchor the caller provides.  They always fit: both chunked forms have c >= 2 chunks of
+                // P = 8192 or 73 728 anchors, so a frame has more than (c - 1) P anchors, and 6144 c <= 4 ((c - 1) P + 1) holds for every
+                // c >= 2 at either P (at c = 2 and P = 8192: 12 288 <= 32 772; the right side grows faster in c).
+                const int n2 = plan.chunks * kSelThreads;
+                int *ci = reinterpret_cast<int *>(a.key_scratch);
+                unsigned short *ck = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(a.key_scratch) + (size_t)g.batch * n2 * 4);
+                auto stage1 = [&](auto kp) {
+                    hipLaunchKernelGGL((k_predict_select_chunk<T, decltype(kp)::value, V>), dim3(plan.chunks, g.batch), wg, 0, a.st, c, v, g,
+                                       (int)nfr, a.k, plan.chunks, thr16, ck, ci);
+                };
+                auto stage2 = [&](auto kp2) {
+                    hipLaunchKernelGGL((k_predict_select_reg<T, decltype(kp2)::value, true, V>), frames, wg, 0, a.st, c, v, g, a.k, a.score_thr, ck,
+                                       n2, a.top_idx, a.top_score, a.top_label, a.counts, n2, ci, thr16);
+                };
+                plan.kp == 4 ? stage1(Int<4>{}) : stage1(Int<36>{});
+                plan.kp2 == 5 ? stage2(Int<5>{}) : plan.kp2 == 10 ? stage2(Int<10>{}) : plan.kp2 == 20 ? stage2(Int<20>{}) : stage2(Int<36>{});
+            }
         }
-    }
-    if (h16 && nfr <= reg_cap) {                                     // one workgroup per frame over a compact 16-bit key array
-        const int ns = (int)((nfr + 1) & ~1ll);
-#define SEC_REG(T)                                                                                                                          \
-    do {                                                                                                                                    \
-        hipLaunchKernelGGL((k_predict_keys16<T, V>), dim3(div_up((long long)batch * ns, kBlock)), dim3(kBlock), 0, st, (const T *)cls, v, g, ns, \
-                           reinterpret_cast<unsigned short *>(key_scratch));                                                                \
-        hipLaunchKernelGGL((k_predict_select_reg<T, 36, false, V>), dim3(batch), dim3(kSelThreads), 0, st, (const T *)cls, v, g, k, score_thr,       \
-                           reinterpret_cast<const unsigned short *>(key_scratch), ns, top_idx, top_score, top_label, counts, 0,            \
-                           (const int *)nullptr, thr16);                                                                                    \
-    } while (0)
-        if (dtype == SEC_BF16) SEC_REG(__hip_bfloat16);
-        else SEC_REG(__half);
-#undef SEC_REG
         return check_launch();
-    }
-    if (dtype == SEC_F32) SEC_SEL(float, false);
-    else if (dtype == SEC_BF16) SEC_SEL(__hip_bfloat16, true);
-    else if (dtype == SEC_F16) SEC_SEL(__half, false);
-    else return SEC_E_UNSUPPORTED;
-#undef SEC_SEL
-    return check_launch();
+    });
+}
+
+// the select over one head tensor of any form
+static int predict_select_head(const void *cls, const int64_t *h_cls_strides5, const PredGeom &g, const SelectArgs &a, const HeadForm &f) {
+    if (!a.key_scratch) return SEC_E_WORKSPACE;
+    if (!cls || !h_cls_strides5 || g.batch <= 0 || g.A <= 0 || g.H <= 0 || g.W <= 0 || g.nc <= 0 || a.k <= 0 || a.k > kSelThreads || !a.top_idx ||
+        !a.top_score || !a.top_label || !a.counts || !dtype_ok(a.dtype))
+        return SEC_E_INVALID;
+    View5 v;
+    if (int rc = head_view(f, h_cls_strides5, cls, f.background, g.H, g.W, a.dtype, &v)) return rc;
+    // a masked-out anchor's key stands for no score; with a threshold <= 0 (no shipped config has one) it would be counted
+    if (f.anchor_mask && !(a.score_thr > 0.0f)) return SEC_E_UNSUPPORTED;
+    return predict_select_launch(cls, v, g, a);
 }
 
 SEC_API int sec_predict_select(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                int *top_label, int *counts, int dtype, void *stream) {
-    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, nullptr, nullptr, nullptr);
+    return predict_select_head(cls, h_cls_strides5, {batch, anchors_per_loc, h, w, num_class},
+                               {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream}, HeadForm{});
 }
 SEC_API int sec_predict_select_lazy(const void *cls, const int64_t *h_cls_strides5, int batch, int anchors_per_loc, int h, int w,
                                     int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                     int *top_label, int *counts, int dtype, const unsigned short *tile_live, const void *cls_background,
                                     void *stream) {
     if (!tile_live || !cls_background) return SEC_E_INVALID;
-    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, tile_live, cls_background, nullptr);
+    return predict_select_head(cls, h_cls_strides5, {batch, anchors_per_loc, h, w, num_class},
+                               {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream},
+                               {tile_live, nullptr, cls_background, nullptr, nullptr});
 }
 // sec_predict_select / _lazy with the anchor-area mask of sec_anchor_area_mask: frame b keeps the anchors with anchor_mask[b][n] != 0
 // (voxelnet.py:429-439 indexes the frame's head rows by the mask before the score threshold); indices stay indices into the full
@@ -1355,51 +1334,10 @@ SEC_API int sec_predict_select_masked(const void *cls, const int64_t *h_cls_stri
                                       int num_class, int k, float score_thr, unsigned *key_scratch, int *top_idx, float *top_score,
                                       int *top_label, int *counts, int dtype, const unsigned short *tile_live, const void *cls_background,
                                       const unsigned char *anchor_mask, void *stream) {
-    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, tile_live, cls_background, anchor_mask);
+    return predict_select_head(cls, h_cls_strides5, {batch, anchors_per_loc, h, w, num_class},
+                               {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream},
+                               {tile_live, nullptr, cls_background, nullptr, anchor_mask});
 }
-
-static int predict_decode_impl(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
-                               int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
-                               const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
-                               int *dir_label, int dtype, void *stream, const unsigned short *tile_live, const void *box_background,
-                               const void *dir_background, const unsigned *cover_cols = nullptr) {
-    if (!box || !h_box_strides5 || batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label)
-        return SEC_E_INVALID;
-    if (dtype < SEC_F32 || dtype > SEC_BF16 || ((tile_live || cover_cols) && (!box_background || (dir && !dir_background))) ||
-        (tile_live && cover_cols))
-        return SEC_E_INVALID;
-    PredGeom g{batch, anchors_per_loc, h, w, 1};
-    View5 vb = mkview_lazy(h_box_strides5, box, box_background, tile_live, h, w, elt_bytes(dtype), cover_cols);
-    View5 vd = dir ? mkview_lazy(h_dir_strides5, dir, dir_background, tile_live, h, w, elt_bytes(dtype), cover_cols) : View5{};
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(div_up((long long)batch * k, kBlock));
-#define SEC_DEC(T) hipLaunchKernelGGL(k_predict_decode<T>, grid, dim3(kBlock), 0, st, (const T *)box, vb, (const T *)dir, vd, \
-                                      num_dir_bins, g, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label)
-    if (dtype == SEC_F32) SEC_DEC(float);
-    else if (dtype == SEC_BF16) SEC_DEC(__hip_bfloat16);
-    else if (dtype == SEC_F16) SEC_DEC(__half);
-    else return SEC_E_UNSUPPORTED;
-#undef SEC_DEC
-    return check_launch();
-}
-SEC_API int sec_predict_decode(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
-                               int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
-                               const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
-                               int *dir_label, int dtype, void *stream) {
-    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, k, anchors, top_idx,
-                               top_score, rotate, decoded, dets, dir_label, dtype, stream, nullptr, nullptr, nullptr);
-}
-SEC_API int sec_predict_decode_lazy(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
-                                    int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
-                                    const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
-                                    int *dir_label, int dtype, const unsigned short *tile_live, const void *box_background,
-                                    const void *dir_background, void *stream) {
-    if (!tile_live || !box_background) return SEC_E_INVALID;
-    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, k, anchors, top_idx,
-                               top_score, rotate, decoded, dets, dir_label, dtype, stream, tile_live, box_background, dir_background);
-}
-
 // The lazy heads behind a COVER-form producer (sec_conv2d_nhwc_tiles_tail_cover): an element was written when bit x of
 // cover_cols[b][y >> 3] is set (the last conv's coverage masks of sec_rpn_tile_cover, [B][ceil(h / 8)][ceil(w / 32)] words); every other
 // element is read from the empty frame's map.  anchor_mask may be NULL (sec_predict_select_masked otherwise).
@@ -1408,8 +1346,56 @@ SEC_API int sec_predict_select_cover(const void *cls, const int64_t *h_cls_strid
                                      int *top_label, int *counts, int dtype, const unsigned *cover_cols, const void *cls_background,
                                      const unsigned char *anchor_mask, void *stream) {
     if (!cover_cols || !cls_background) return SEC_E_INVALID;
-    return predict_select_impl(cls, h_cls_strides5, batch, anchors_per_loc, h, w, num_class, k, score_thr, key_scratch, top_idx, top_score,
-                               top_label, counts, dtype, stream, nullptr, cls_background, anchor_mask, cover_cols);
+    return predict_select_head(cls, h_cls_strides5, {batch, anchors_per_loc, h, w, num_class},
+                               {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream},
+                               {nullptr, cover_cols, cls_background, nullptr, anchor_mask});
+}
+
+// ---- decode -------------------------------------------------------------------------------------------------------------------
+struct DecodeArgs {                                  // what every decode entry point takes besides its head(s)
+    int num_dir_bins, k; const float *anchors; const int *top_idx; const float *top_score; int rotate; float *decoded, *dets; int *dir_label;
+    int dtype; hipStream_t st;
+};
+// the decode of a validated call; V as in predict_select_launch.  `dir` of the kernel says whether there is a direction head (with
+// a SegView that is all it says: the addresses come from vb / vd)
+template <typename V>
+static int predict_decode_launch(const void *box, const V &vb, const void *dir, const V &vd, const PredGeom &g, const DecodeArgs &a) {
+    return by_dtype(a.dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((k_predict_decode<T, V>), dim3(div_up((long long)g.batch * a.k, kBlock)), dim3(kBlock), 0, a.st, (const T *)box, vb,
+                           (const T *)dir, vd, a.num_dir_bins, g, a.k, a.anchors, a.top_idx, a.top_score, a.rotate, a.decoded, a.dets, a.dir_label);
+        return check_launch();
+    });
+}
+
+// the decode over one head tensor of any form (g.nc unused)
+static int predict_decode_head(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5, const PredGeom &g,
+                               const DecodeArgs &a, const HeadForm &f) {
+    if (!box || !h_box_strides5 || g.batch <= 0 || a.k <= 0 || !a.anchors || !a.top_idx || !a.top_score || !a.decoded || !a.dets || !a.dir_label ||
+        !dtype_ok(a.dtype))
+        return SEC_E_INVALID;
+    View5 vb, vd{};
+    int rc = head_view(f, h_box_strides5, box, f.background, g.H, g.W, a.dtype, &vb);
+    if (!rc && dir) rc = head_view(f, h_dir_strides5, dir, f.dir_background, g.H, g.W, a.dtype, &vd);
+    return rc ? rc : predict_decode_launch(box, vb, dir, vd, g, a);
+}
+
+SEC_API int sec_predict_decode(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                               int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
+                               const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
+                               int *dir_label, int dtype, void *stream) {
+    return predict_decode_head(box, h_box_strides5, dir, h_dir_strides5, {batch, anchors_per_loc, h, w, 1},
+                               {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream}, HeadForm{});
+}
+SEC_API int sec_predict_decode_lazy(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                                    int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
+                                    const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
+                                    int *dir_label, int dtype, const unsigned short *tile_live, const void *box_background,
+                                    const void *dir_background, void *stream) {
+    if (!tile_live || !box_background) return SEC_E_INVALID;
+    return predict_decode_head(box, h_box_strides5, dir, h_dir_strides5, {batch, anchors_per_loc, h, w, 1},
+                               {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream},
+                               {tile_live, nullptr, box_background, dir_background, nullptr});
 }
 SEC_API int sec_predict_decode_cover(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
                                      int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
@@ -1417,8 +1403,9 @@ SEC_API int sec_predict_decode_cover(const void *box, const int64_t *h_box_strid
                                      int *dir_label, int dtype, const unsigned *cover_cols, const void *box_background,
                                      const void *dir_background, void *stream) {
     if (!cover_cols || !box_background) return SEC_E_INVALID;
-    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, k, anchors, top_idx,
-                               top_score, rotate, decoded, dets, dir_label, dtype, stream, nullptr, box_background, dir_background, cover_cols);
+    return predict_decode_head(box, h_box_strides5, dir, h_dir_strides5, {batch, anchors_per_loc, h, w, 1},
+                               {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream},
+                               {nullptr, cover_cols, box_background, dir_background, nullptr});
 }
 
 SEC_API int sec_predict_finalize(const float *decoded, const float *top_score, const int *top_label, const int *dir_label,
@@ -1462,12 +1449,12 @@ SEC_API int sec_predict_select_segments(int num_segments, const void *const *cls
     long long n;
     if (int rc = mksegs(num_segments, cls, h_cls_strides5, h_dims3, &v, &n)) return rc;
     if (k > kSelThreads) return SEC_E_UNSUPPORTED;
-    if (batch <= 0 || num_class <= 0 || k <= 0 || !top_idx || !top_score || !top_label || !counts || dtype < SEC_F32 || dtype > SEC_BF16)
-        return SEC_E_INVALID;
+    if (batch <= 0 || num_class <= 0 || k <= 0 || !top_idx || !top_score || !top_label || !counts || !dtype_ok(dtype)) return SEC_E_INVALID;
     if ((long long)batch * n > 0x7fffffffll) return SEC_E_UNSUPPORTED;
     if (!key_scratch) return SEC_E_WORKSPACE;
-    PredGeom g{batch, 1, 1, (int)n, num_class};                  // the kernels take N = A * H * W from it; addresses come from the segments
-    return predict_select_launch((const void *)nullptr, v, g, k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, stream);
+    // the kernels take N = A * H * W from the geometry; addresses come from the segments
+    return predict_select_launch((const void *)nullptr, v, PredGeom{batch, 1, 1, (int)n, num_class},
+                                 {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream});
 }
 
 SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
@@ -1480,21 +1467,11 @@ SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box
     if (dir)
         if (int rc = mksegs(num_segments, dir, h_dir_strides5, h_dims3, &vd, &n)) return rc;
     if (k > kSelThreads) return SEC_E_UNSUPPORTED;
-    if (batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label || dtype < SEC_F32 || dtype > SEC_BF16 ||
+    if (batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label || !dtype_ok(dtype) ||
         (dir && num_dir_bins <= 0))
         return SEC_E_INVALID;
-    PredGeom g{batch, 1, 1, (int)n, 1};
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(div_up((long long)batch * k, kBlock));
-    // `dir` of the kernel only says whether there is a direction head; its address comes from vd
-#define SEC_DEC(T) hipLaunchKernelGGL((k_predict_decode<T, SegView>), grid, dim3(kBlock), 0, st, (const T *)nullptr, vb,                    \
-                                      (const T *)(dir ? dir[0] : nullptr), vd, num_dir_bins, g, k, anchors, top_idx, top_score, rotate, decoded, \
-                                      dets, dir_label)
-    if (dtype == SEC_F32) SEC_DEC(float);
-    else if (dtype == SEC_BF16) SEC_DEC(__hip_bfloat16);
-    else SEC_DEC(__half);
-#undef SEC_DEC
-    return check_launch();
+    return predict_decode_launch((const void *)nullptr, vb, dir ? dir[0] : nullptr, vd, PredGeom{batch, 1, 1, (int)n, 1},
+                                 {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream});
 }
 
 // ---- multi-class NMS: (frame, class) items -----------------------------------------------------------------------------------
@@ -1503,7 +1480,7 @@ SEC_API int sec_predict_select_classes(const void *cls, const int64_t *h_cls_str
                                        int k_out, int *top_idx, float *top_score, int *counts, int dtype,
                                        const unsigned char *anchor_mask, void *stream) {
     if (!cls || !h_cls_strides5 || batch <= 0 || anchors_per_loc <= 0 || h <= 0 || w <= 0 || num_class <= 0 || !h_a_begin || !h_a_end ||
-        !h_k || !h_score_thr || k_out <= 0 || k_out > kSelThreads || !top_idx || !top_score || !counts || dtype < SEC_F32 || dtype > SEC_BF16)
+        !h_k || !h_score_thr || k_out <= 0 || k_out > kSelThreads || !top_idx || !top_score || !counts || !dtype_ok(dtype))
         return SEC_E_INVALID;
     if (anchor_mask) return SEC_E_UNSUPPORTED;            // the reference indexes masked arrays with unmasked ranges here: not reproduced
     if (num_class > kMaxSelClasses) return SEC_E_UNSUPPORTED;
@@ -1517,16 +1494,14 @@ SEC_API int sec_predict_select_classes(const void *cls, const int64_t *h_cls_str
         if ((n < h_k[c] ? n : (long long)h_k[c]) > k_out) return SEC_E_INVALID;   // the item's rows do not fit [B, C, k_out]
         p.a_begin[c] = h_a_begin[c]; p.a_end[c] = h_a_end[c]; p.k[c] = h_k[c]; p.thr[c] = h_score_thr[c];
     }
-    PredGeom g{batch, anchors_per_loc, h, w, num_class};
-    View5 v = mkview(h_cls_strides5);
-    const dim3 grid(num_class, batch);
-#define SEC_SELC(T) hipLaunchKernelGGL(k_predict_select_classes<T>, grid, dim3(kSelThreads), 0, (hipStream_t)stream, (const T *)cls, v, g, p, \
-                                       k_out, top_idx, top_score, counts)
-    if (dtype == SEC_F32) SEC_SELC(float);
-    else if (dtype == SEC_BF16) SEC_SELC(__hip_bfloat16);
-    else SEC_SELC(__half);
-#undef SEC_SELC
-    return check_launch();
+    const PredGeom g{batch, anchors_per_loc, h, w, num_class};
+    const View5 v = mkview(h_cls_strides5);
+    return by_dtype(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(k_predict_select_classes<T>, dim3(num_class, batch), dim3(kSelThreads), 0, (hipStream_t)stream, (const T *)cls, v, g,
+                           p, k_out, top_idx, top_score, counts);
+        return check_launch();
+    });
 }
 
 // the rows of all items are one list of num_class * k rows per frame: sec_predict_decode's kernel on [B, num_class * k]
@@ -1535,8 +1510,9 @@ SEC_API int sec_predict_decode_classes(const void *box, const int64_t *h_box_str
                                        const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
                                        float *dets, int *dir_label, int dtype, void *stream) {
     if (num_class <= 0 || k <= 0 || (long long)batch * num_class * k > 0x7fffffffll / 7) return SEC_E_INVALID;
-    return predict_decode_impl(box, h_box_strides5, dir, h_dir_strides5, num_dir_bins, batch, anchors_per_loc, h, w, num_class * k, anchors,
-                               top_idx, top_score, rotate, decoded, dets, dir_label, dtype, stream, nullptr, nullptr, nullptr);
+    return predict_decode_head(box, h_box_strides5, dir, h_dir_strides5, {batch, anchors_per_loc, h, w, 1},
+                               {num_dir_bins, num_class * k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream},
+                               HeadForm{});
 }
 
 SEC_API int sec_predict_finalize_classes(const float *decoded, const float *top_score, const int *dir_label, const int *keep,

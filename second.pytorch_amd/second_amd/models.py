@@ -2128,6 +2128,37 @@ class SecondDetector(nn.Module):
         top_labels = torch.gather(labels, 1, top_idx) if labels is not None else torch.zeros_like(top_idx)
         return dec, top_scores, counts, dir_labels, top_labels
 
+    def _nms_kind(self):
+        """(kind, semantics) of ops.nms_sorted for this config: nms.py's rotated NMS, or spconv's axis-aligned one on the standup boxes."""
+        return ("rotate", "cpu") if self.cfg["use_rotate_nms"] else ("axis_aligned", "numba")
+
+    def _nms_rows(self, dec, top_scores):
+        """The NMS input rows of decoded boxes ``dec`` [B, k, 7] and their scores [B, k], plus :meth:`_nms_kind`."""
+        if self.cfg["use_rotate_nms"]:
+            # (x, y, w, l, r, score): boxes_for_nms = box[:, [0, 1, 3, 4, 6]] (voxelnet.py:570); slices, not index
+            # lists, so that nothing is staged from the host (hipGraph capture)
+            dets = torch.cat([dec[..., 0:2], dec[..., 3:5], dec[..., 6:7], top_scores.unsqueeze(-1)], -1).contiguous()
+        else:
+            # standup boxes of the rotated BEV rectangles (voxelnet.py:571-576 -> center_to_corner_box2d +
+            # corner_to_standup_nd), then nms -> nms_gpu_cc -> spconv non_max_suppression ('+1', IoU > thr)
+            hx, hy, ang = dec[..., 3] * 0.5, dec[..., 4] * 0.5, dec[..., 6]
+            cs, sn = torch.cos(ang).abs(), torch.sin(ang).abs()
+            ex, ey = hx * cs + hy * sn, hx * sn + hy * cs
+            dets = torch.stack([dec[..., 0] - ex, dec[..., 1] - ey, dec[..., 0] + ex, dec[..., 1] + ey, top_scores], -1).contiguous()
+        return (dets, *self._nms_kind())
+
+    def _fix_direction_and_range(self, boxes, valid, dir_labels):
+        """The direction fix of ``boxes`` [B, P, 7] in place (voxelnet.py:598-607; ``dir_labels`` [B, P], a list of per-class [B, P_c]
+        to concatenate, or None) -> ``valid`` and the post_center_range mask (:611-621)."""
+        cfg = self.cfg
+        if dir_labels is not None:
+            period = 2 * math.pi / cfg["num_direction_bins"]
+            rot = limit_period(boxes[..., 6] - cfg["direction_offset"], cfg["direction_limit_offset"], period)
+            boxes[..., 6] = rot + cfg["direction_offset"] + period * (torch.cat(dir_labels, 1) if isinstance(dir_labels, list)
+                                                                      else dir_labels).to(boxes.dtype)
+        r = self.post_center_range
+        return valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
+
     def predict_device(self, preds, batch_size, anchors=None, anchors_mask=None):
         """-> dict of padded device tensors: boxes [B,P,7], scores [B,P], labels [B,P], valid [B,P] (bool).
         ``anchors_mask`` [B, A] bool / uint8 (the example's, or :meth:`anchor_area_mask`): frame b keeps the anchors with a non-zero entry."""
@@ -2151,33 +2182,14 @@ class SecondDetector(nn.Module):
             return self._predict_fused(preds, batch_size, anchors, anchors_mask)
         preds = flat_preds(preds, batch_size)
         dec, top_scores, counts, dir_labels, top_labels = self._select(preds, batch_size, anchors, anchors_mask)
-        if cfg["use_rotate_nms"]:
-            # (x, y, w, l, r, score): boxes_for_nms = box[:, [0, 1, 3, 4, 6]] (voxelnet.py:570); slices, not index
-            # lists, so that nothing is staged from the host (hipGraph capture)
-            dets = torch.cat([dec[..., 0:2], dec[..., 3:5], dec[..., 6:7], top_scores.unsqueeze(-1)], -1).contiguous()
-            keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], "rotate", "cpu",
-                                            post_max=cfg["nms_post_max_size"])
-        else:
-            # standup boxes of the rotated BEV rectangles (voxelnet.py:571-576 -> center_to_corner_box2d +
-            # corner_to_standup_nd), then nms -> nms_gpu_cc -> spconv non_max_suppression ('+1', IoU > thr)
-            hx, hy, ang = dec[..., 3] * 0.5, dec[..., 4] * 0.5, dec[..., 6]
-            cs, sn = torch.cos(ang).abs(), torch.sin(ang).abs()
-            ex, ey = hx * cs + hy * sn, hx * sn + hy * cs
-            dets = torch.stack([dec[..., 0] - ex, dec[..., 1] - ey, dec[..., 0] + ex, dec[..., 1] + ey, top_scores], -1).contiguous()
-            keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], "axis_aligned", "numba",
-                                            post_max=cfg["nms_post_max_size"])
+        dets, kind, sem = self._nms_rows(dec, top_scores)
+        keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], kind, sem, post_max=cfg["nms_post_max_size"])
         p = min(cfg["nms_post_max_size"], keep.shape[1])
         valid = self._arange_p[:p].unsqueeze(0) < num_keep.unsqueeze(1)
         sel = torch.where(valid, keep[:, :p], torch.zeros_like(keep[:, :p])).long()   # slots past num_keep are undefined
         boxes = torch.gather(dec, 1, sel.unsqueeze(-1).expand(-1, -1, 7))
         scores = torch.gather(top_scores, 1, sel)
-        if dir_labels is not None:
-            dl = torch.gather(dir_labels, 1, sel)
-            period = 2 * math.pi / cfg["num_direction_bins"]
-            rot = limit_period(boxes[..., 6] - cfg["direction_offset"], cfg["direction_limit_offset"], period)
-            boxes[..., 6] = rot + cfg["direction_offset"] + period * dl.to(boxes.dtype)
-        r = self.post_center_range
-        valid = valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
+        valid = self._fix_direction_and_range(boxes, valid, None if dir_labels is None else torch.gather(dir_labels, 1, sel))
         return {"boxes": boxes, "scores": scores, "labels": torch.gather(top_labels, 1, sel), "valid": valid}
 
     def _predict_multiclass(self, preds, batch_size, anchors):
@@ -2203,15 +2215,8 @@ class SecondDetector(nn.Module):
             enc = torch.gather(box, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7)).float()
             anc = anchors[top_idx] if anchors.dim() == 2 else torch.gather(anchors, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7))
             dec = decode_boxes(enc, anc)
-            if cfg["use_rotate_nms"]:
-                dets = torch.cat([dec[..., 0:2], dec[..., 3:5], dec[..., 6:7], top_scores.unsqueeze(-1)], -1).contiguous()
-                keep, num_keep = ops.nms_sorted(dets, counts, mc["iou"][c], "rotate", "cpu", post_max=mc["post"][c])
-            else:
-                hx, hy, ang = dec[..., 3] * 0.5, dec[..., 4] * 0.5, dec[..., 6]
-                cs, sn = torch.cos(ang).abs(), torch.sin(ang).abs()
-                ex, ey = hx * cs + hy * sn, hx * sn + hy * cs
-                dets = torch.stack([dec[..., 0] - ex, dec[..., 1] - ey, dec[..., 0] + ex, dec[..., 1] + ey, top_scores], -1).contiguous()
-                keep, num_keep = ops.nms_sorted(dets, counts, mc["iou"][c], "axis_aligned", "numba", post_max=mc["post"][c])
+            dets, kind, sem = self._nms_rows(dec, top_scores)
+            keep, num_keep = ops.nms_sorted(dets, counts, mc["iou"][c], kind, sem, post_max=mc["post"][c])
             p = mc["post"][c]
             keep = keep.to(top_idx.device)[:, :p]
             keep = torch.nn.functional.pad(keep, (0, p - keep.shape[1]))              # post_c slots even where fewer were selected
@@ -2225,29 +2230,33 @@ class SecondDetector(nn.Module):
                 d = torch.gather(dirs, 1, top_idx.unsqueeze(-1).expand(-1, -1, cfg["num_direction_bins"]))
                 out_dl.append(torch.gather(torch.max(d, dim=-1)[1], 1, sel))
         boxes, scores, valid = torch.cat(out_boxes, 1), torch.cat(out_scores, 1), torch.cat(out_valid, 1)
-        if dirs is not None:
-            period = 2 * math.pi / cfg["num_direction_bins"]
-            rot = limit_period(boxes[..., 6] - cfg["direction_offset"], cfg["direction_limit_offset"], period)
-            boxes[..., 6] = rot + cfg["direction_offset"] + period * torch.cat(out_dl, 1).to(boxes.dtype)
-        r = self.post_center_range
-        valid = valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
+        valid = self._fix_direction_and_range(boxes, valid, None if dirs is None else out_dl)
         return {"boxes": boxes, "scores": scores, "labels": torch.cat(out_labels, 1), "valid": valid}
+
+    def _head_views(self, preds, batch_size, anchors=None):
+        """(cls, box, dir or None) of ``preds`` as [B, A, H, W, C] views -- a multi-head network's LISTS of such views (every view has
+        its own [A_s, H_s, W_s]: the *_segments kernels) pass through -- and ``anchors`` as the flat float32 [N, 7] list the decode
+        reads (None for heads that have none: the empty frame's maps behind lazy heads)."""
+        cfg = self.cfg
+        _, h, w = self.feature_map_size
+
+        def view5(t, code):
+            if isinstance(t, (list, tuple)):
+                assert all(v.dim() == 5 for v in t)
+                return list(t)
+            return t if t.dim() == 5 else t.reshape(batch_size, self.num_anchor_per_loc, h, w, code)
+        cls = view5(preds["cls_preds"], cfg["num_class"])
+        box = view5(preds["box_preds"], 7)
+        dirp = view5(preds["dir_cls_preds"], cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
+        if anchors is not None:
+            anchors = (anchors[0] if anchors.dim() == 3 else anchors).float().contiguous()
+        return cls, box, dirp, anchors
 
     def _predict_multiclass_fused(self, preds, batch_size, anchors):
         """:meth:`_predict_multiclass` on the device with (frame, class) items: select -> decode -> NMS (two launches) -> finalize from
         the head tensor in place, no host sync, no torch glue (capturable)."""
         cfg, mc = self.cfg, self.multiclass
-        a_per_loc = self.num_anchor_per_loc
-        _, h, w = self.feature_map_size
-
-        def view5(t, code):
-            return t if t.dim() == 5 else t.reshape(batch_size, a_per_loc, h, w, code)
-        cls = view5(preds["cls_preds"], cfg["num_class"])
-        box = view5(preds["box_preds"], 7)
-        dirp = view5(preds["dir_cls_preds"], cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
-        if anchors.dim() == 3:
-            anchors = anchors[0]
-        anchors = anchors.float().contiguous()
+        cls, box, dirp, anchors = self._head_views(preds, batch_size, anchors)
         dev = cls.device
         tab = mc["device"].get(dev)
         if tab is None:        # the per-class arrays the NMS and finalize kernels index (made once per device, outside any capture)
@@ -2257,8 +2266,7 @@ class SecondDetector(nn.Module):
         iou_t, post_t, off_t = tab
         top_idx, top_score, counts = ops.predict_select_classes(cls, mc["a_ranges"], mc["pre"], mc["thr"])
         dec, dets, dlab = ops.predict_decode_classes(box, dirp, anchors, top_idx, top_score, rotate=cfg["use_rotate_nms"])
-        kind, sem = ("rotate", "cpu") if cfg["use_rotate_nms"] else ("axis_aligned", "numba")
-        keep, num_keep = ops.nms_sorted_items(dets, counts, iou_t, post_t, kind, sem)
+        keep, num_keep = ops.nms_sorted_items(dets, counts, iou_t, post_t, *self._nms_kind())
         return ops.predict_finalize_classes(dec, top_score, dlab, keep, num_keep, off_t, mc["P"], dirp is not None,
                                             cfg["direction_offset"], cfg["direction_limit_offset"], cfg["num_direction_bins"],
                                             self.post_center_range)
@@ -2266,36 +2274,17 @@ class SecondDetector(nn.Module):
     def _predict_fused(self, preds, batch_size, anchors, anchors_mask=None):
         """select -> decode -> NMS -> finalize: five launches, no host sync, no torch glue."""
         cfg = self.cfg
-        a_per_loc = self.num_anchor_per_loc
-        _, h, w = self.feature_map_size
-
-        def view5(t, code):
-            if isinstance(t, (list, tuple)):      # several head tensors: every view has its own [A_s, H_s, W_s] (the *_segments kernels)
-                assert all(v.dim() == 5 for v in t)
-                return list(t)
-            if t.dim() == 5:
-                return t
-            return t.reshape(batch_size, a_per_loc, h, w, code)
-        cls = view5(preds["cls_preds"], cfg["num_class"])
-        box = view5(preds["box_preds"], 7)
-        dirp = view5(preds["dir_cls_preds"], cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
-        if anchors.dim() == 3:
-            anchors = anchors[0]
-        anchors = anchors.float().contiguous()
+        cls, box, dirp, anchors = self._head_views(preds, batch_size, anchors)
         lz = preds.get("lazy_heads")       # (tile_live, empty-frame heads): background tiles of the head tensor were never written
         lz_cls = lz_box = None
         if lz is not None:
-            bg = lz[1]
-            lz_cls = (lz[0], view5(bg["cls_preds"], cfg["num_class"]))
-            lz_box = (lz[0], (view5(bg["box_preds"], 7), view5(bg["dir_cls_preds"], cfg["num_direction_bins"]) if dirp is not None else None))
+            bg_cls, bg_box, bg_dir, _ = self._head_views(lz[1], batch_size)
+            lz_cls, lz_box = (lz[0], bg_cls), (lz[0], (bg_box, bg_dir if dirp is not None else None))
         top_idx, top_score, top_label, counts = ops.predict_select(cls, cfg["nms_pre_max_size"], cfg["nms_score_threshold"], lazy=lz_cls,
                                                                   anchor_mask=None if anchors_mask is None else anchors_mask.reshape(batch_size, -1))
         dec, dets, dlab = ops.predict_decode(box, dirp, anchors, top_idx, top_score, rotate=cfg["use_rotate_nms"], lazy=lz_box)
-        if cfg["use_rotate_nms"]:
-            keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], "rotate", "cpu", post_max=cfg["nms_post_max_size"])
-        else:
-            keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], "axis_aligned", "numba",
-                                            post_max=cfg["nms_post_max_size"])
+        kind, sem = self._nms_kind()
+        keep, num_keep = ops.nms_sorted(dets, counts, cfg["nms_iou_threshold"], kind, sem, post_max=cfg["nms_post_max_size"])
         return ops.predict_finalize(dec, top_score, top_label, dlab, keep, num_keep, cfg["nms_post_max_size"],
                                     dirp is not None, cfg["direction_offset"], cfg["direction_limit_offset"],
                                     cfg["num_direction_bins"], self.post_center_range)

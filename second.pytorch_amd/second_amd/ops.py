@@ -1836,18 +1836,53 @@ def _segment_args(views):
     return ptrs, strides, dims
 
 
+def predict_select_plan(anchors_per_frame, dtype):
+    """(name, first-stage chunks) of the form every select below takes for a head of ``dtype`` with that many anchors per frame
+    (sec_predict_select_plan_name: "radix32", "radix16", "direct", "chunk4+kpN", "chunk36+kpN"; chunks is 0 unless chunked).  Host only."""
+    chunks = ctypes.c_int(0)
+    name = rt.lib().sec_predict_select_plan_name(int(anchors_per_frame), rt.dtype_code(dtype), ctypes.byref(chunks))
+    return name.decode(), chunks.value
+
+
+def _select_outputs(b, n, k, dev):
+    """(top_idx [b, k], top_score, top_label, counts [b], key scratch of 4 bytes per anchor) of a select over n anchors per frame."""
+    return (torch.empty((b, k), dtype=torch.int32, device=dev), torch.empty((b, k), dtype=torch.float32, device=dev),
+            torch.empty((b, k), dtype=torch.int32, device=dev), torch.empty((b,), dtype=torch.int32, device=dev),
+            torch.empty((b * n,), dtype=torch.int32, device=dev))
+
+
+def _decode_outputs(rows, dev):
+    """(decoded [*rows, 7], dets [*rows, 6], dir_label [*rows]) of a decode; rows = (B, k) or (B, C, k)."""
+    return (torch.empty((*rows, 7), dtype=torch.float32, device=dev), torch.empty((*rows, 6), dtype=torch.float32, device=dev),
+            torch.empty(rows, dtype=torch.int32, device=dev))
+
+
+def _finalize_outputs(b, p, dev):
+    """(boxes [b, p, 7], scores, labels, valid as uint8) of a finalize."""
+    return (torch.empty((b, p, 7), dtype=torch.float32, device=dev), torch.empty((b, p), dtype=torch.float32, device=dev),
+            torch.empty((b, p), dtype=torch.int32, device=dev), torch.empty((b, p), dtype=torch.uint8, device=dev))
+
+
+def _finalize_result(boxes, scores, labels, valid):
+    # (the kernel writes 0 / 1 bytes: reinterpret, do not convert -- `.bool()` was the last torch kernel inside the captured step, 7.8 us)
+    return {"boxes": boxes, "scores": scores, "labels": labels, "valid": valid.view(torch.bool)}
+
+
+def _dir_args(dir_cls, box):
+    """(pointer, strides, bins) of the direction view of a decode; null / 0 without a direction head."""
+    if dir_cls is None:
+        return rt.ptr(None), None, 0
+    assert dir_cls.dtype == box.dtype
+    return rt.ptr(dir_cls), _strides5(dir_cls), dir_cls.shape[-1]
+
+
 def _predict_select_segments(views, k, score_thr):
     rt.require_gpu(*views)
     b, nc, dt = views[0].shape[0], views[0].shape[4], views[0].dtype
     assert all(v.dim() == 5 and v.shape[0] == b and v.shape[4] == nc and v.dtype == dt for v in views)
     n = sum(v.shape[1] * v.shape[2] * v.shape[3] for v in views)
     k = min(int(k), n, 1024)
-    dev = views[0].device
-    top_idx = torch.empty((b, k), dtype=torch.int32, device=dev)
-    top_score = torch.empty((b, k), dtype=torch.float32, device=dev)
-    top_label = torch.empty((b, k), dtype=torch.int32, device=dev)
-    counts = torch.empty((b,), dtype=torch.int32, device=dev)
-    keys = torch.empty((b * n,), dtype=torch.int32, device=dev)
+    top_idx, top_score, top_label, counts, keys = _select_outputs(b, n, k, views[0].device)
     ptrs, strides, dims = _segment_args(views)
     rc = rt.lib().sec_predict_select_segments(len(views), ptrs, strides, dims, b, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
                                               rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(dt), rt.stream())
@@ -1862,10 +1897,7 @@ def _predict_decode_segments(box, dir_cls, anchors, top_idx, top_score, rotate):
     n = sum(v.shape[1] * v.shape[2] * v.shape[3] for v in box)
     assert anchors.dtype == torch.float32 and anchors.is_contiguous() and tuple(anchors.shape) == (n, 7)
     k = top_idx.shape[1]
-    dev = box[0].device
-    dec = torch.empty((b, k, 7), dtype=torch.float32, device=dev)
-    dets = torch.empty((b, k, 6), dtype=torch.float32, device=dev)
-    dlab = torch.empty((b, k), dtype=torch.int32, device=dev)
+    dec, dets, dlab = _decode_outputs((b, k), box[0].device)
     ptrs, strides, dims = _segment_args(box)
     dptrs = dstrides = None
     bins = 0
@@ -1888,8 +1920,11 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     rows [0, counts[b]) of frame b (the reference masks by the threshold before its topk); rows behind them are unspecified.
     Order: descending logit (+0.0 before -0.0), ties by ascending anchor index; an anchor whose best logit is NaN is no candidate.
     ``lazy`` = (tile_live [B, tiles] int16 with bit 4 = "tile written", bg = the empty frame's view [1, A, H, W, num_class] with the
-    strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg`` (sec_predict_select_lazy).
-    ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry (sec_predict_select_masked).
+    strides of ``cls``): elements of unwritten 8 x 16 tiles are read from ``bg``; with an int32 coverage table in place of tile_live
+    (:func:`_lazy_cover`) the call goes to sec_predict_select_cover.
+    ``anchor_mask`` [B, A*H*W] bool / uint8: frame b keeps only the anchors with a non-zero entry.
+    Every form but the cover one is ONE call of sec_predict_select_masked, with a null table / background / mask where there is none
+    (exactly sec_predict_select / sec_predict_select_lazy then).
     A LIST of such views (1 to 4 head tensors of different map size, same dtype / batch / classes): the anchors of view s follow
     those of the views before it, ``top_idx`` are indices into that concatenation (sec_predict_select_segments; no lazy form, no mask)."""
     if isinstance(cls, (list, tuple)):
@@ -1898,39 +1933,15 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
     rt.require_gpu(cls)
     b, a, h, w, nc = cls.shape
     k = min(int(k), a * h * w, 1024)
-    dev = cls.device
-    top_idx = torch.empty((b, k), dtype=torch.int32, device=dev)
-    top_score = torch.empty((b, k), dtype=torch.float32, device=dev)
-    top_label = torch.empty((b, k), dtype=torch.int32, device=dev)
-    counts = torch.empty((b,), dtype=torch.int32, device=dev)
-    keys = torch.empty((b * a * h * w,), dtype=torch.int32, device=dev)
-    if _lazy_cover(lazy):
-        if anchor_mask is not None:
-            anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), dev, "anchor_mask")
-        cols, bgv = _lazy_args(cls, lazy, lambda t: t)
-        rc = rt.lib().sec_predict_select_cover(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
-                                               rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype), rt.ptr(cols),
-                                               rt.ptr(bgv), rt.ptr(anchor_mask) if anchor_mask is not None else None, rt.stream())
-        rt.check(rc, "sec_predict_select_cover")
-        return top_idx, top_score, top_label, counts
+    top_idx, top_score, top_label, counts, keys = _select_outputs(b, a * h * w, k, cls.device)
     if anchor_mask is not None:
-        anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), dev, "anchor_mask")
-        tile_live, bgv = _lazy_args(cls, lazy, lambda t: t) if lazy is not None else (None, None)
-        rc = rt.lib().sec_predict_select_masked(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
-                                                rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype),
-                                                rt.ptr(tile_live), rt.ptr(bgv), rt.ptr(anchor_mask), rt.stream())
-        rt.check(rc, "sec_predict_select_masked")
-        return top_idx, top_score, top_label, counts
-    if lazy is not None:
-        tile_live, bgv = _lazy_args(cls, lazy, lambda t: t)
-        rc = rt.lib().sec_predict_select_lazy(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
-                                              rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype),
-                                              rt.ptr(tile_live), rt.ptr(bgv), rt.stream())
-        rt.check(rc, "sec_predict_select_lazy")
-        return top_idx, top_score, top_label, counts
-    rc = rt.lib().sec_predict_select(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
-                                     rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype), rt.stream())
-    rt.check(rc, "sec_predict_select")
+        anchor_mask = _mask_u8(anchor_mask, (b, a * h * w), cls.device, "anchor_mask")
+    table, bgv = _lazy_args(cls, lazy, lambda t: t) if lazy is not None else (None, None)
+    entry = "sec_predict_select_cover" if _lazy_cover(lazy) else "sec_predict_select_masked"
+    rc = getattr(rt.lib(), entry)(rt.ptr(cls), _strides5(cls), b, a, h, w, nc, k, float(score_thr), rt.ptr(keys), rt.ptr(top_idx),
+                                  rt.ptr(top_score), rt.ptr(top_label), rt.ptr(counts), rt.dtype_code(cls.dtype), rt.ptr(table), rt.ptr(bgv),
+                                  rt.ptr(anchor_mask), rt.stream())
+    rt.check(rc, entry)
     return top_idx, top_score, top_label, counts
 
 
@@ -1938,7 +1949,7 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
 def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=None):
     """box: [B,A,H,W,7] view, dir_cls: [B,A,H,W,bins] view or None, anchors [A*H*W,7] fp32.
     -> (decoded [B,k,7] fp32, dets [B,k,6] fp32 NMS rows, dir_label [B,k] int32).
-    ``lazy`` = (tile_live, (bg_box, bg_dir)): as in :func:`predict_select` (sec_predict_decode_lazy).
+    ``lazy`` = (tile_live, (bg_box, bg_dir)): as in :func:`predict_select` (sec_predict_decode_lazy / sec_predict_decode_cover).
     ``box`` (and ``dir_cls``) LISTS of views: as in :func:`predict_select`, ``anchors`` is the flat list over all of them."""
     if isinstance(box, (list, tuple)):
         assert lazy is None, "the multi-tensor decode has no lazy form"
@@ -1947,28 +1958,18 @@ def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=
     b, a, h, w, code = box.shape
     assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
     k = top_idx.shape[1]
-    dev = box.device
-    dec = torch.empty((b, k, 7), dtype=torch.float32, device=dev)
-    dets = torch.empty((b, k, 6), dtype=torch.float32, device=dev)
-    dlab = torch.empty((b, k), dtype=torch.int32, device=dev)
-    if dir_cls is not None:
-        assert dir_cls.dtype == box.dtype
+    dec, dets, dlab = _decode_outputs((b, k), box.device)
+    dir_ptr, dir_strides, bins = _dir_args(dir_cls, box)
+    entry, lazy_tail = "sec_predict_decode", ()
     if lazy is not None:
-        tile_live, bgb = _lazy_args(box, lazy, lambda t: t[0])
+        table, bgb = _lazy_args(box, lazy, lambda t: t[0])
         bgd = _lazy_args(dir_cls, lazy, lambda t: t[1])[1] if dir_cls is not None else None
         entry = "sec_predict_decode_cover" if _lazy_cover(lazy) else "sec_predict_decode_lazy"
-        rc = getattr(rt.lib(), entry)(rt.ptr(box), _strides5(box), rt.ptr(dir_cls), _strides5(dir_cls) if dir_cls is not None else None,
-                                              dir_cls.shape[-1] if dir_cls is not None else 0, b, a, h, w, k, rt.ptr(anchors),
-                                              rt.ptr(top_idx), rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
-                                              rt.dtype_code(box.dtype), rt.ptr(tile_live), rt.ptr(bgb), rt.ptr(bgd), rt.stream())
-        rt.check(rc, entry)
-        return dec, dets, dlab
-    rc = rt.lib().sec_predict_decode(rt.ptr(box), _strides5(box), rt.ptr(dir_cls),
-                                     _strides5(dir_cls) if dir_cls is not None else None,
-                                     dir_cls.shape[-1] if dir_cls is not None else 0, b, a, h, w, k, rt.ptr(anchors),
-                                     rt.ptr(top_idx), rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets),
-                                     rt.ptr(dlab), rt.dtype_code(box.dtype), rt.stream())
-    rt.check(rc, "sec_predict_decode")
+        lazy_tail = (rt.ptr(table), rt.ptr(bgb), rt.ptr(bgd))
+    rc = getattr(rt.lib(), entry)(rt.ptr(box), _strides5(box), dir_ptr, dir_strides, bins, b, a, h, w, k, rt.ptr(anchors), rt.ptr(top_idx),
+                                  rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab), rt.dtype_code(box.dtype),
+                                  *lazy_tail, rt.stream())
+    rt.check(rc, entry)
     return dec, dets, dlab
 
 
@@ -1979,18 +1980,13 @@ def predict_finalize(dec, top_score, top_label, dir_label, keep, num_keep, post_
     rt.require_gpu(dec, keep, num_keep)
     b, k, _ = dec.shape
     p = min(int(post_max), k)
-    dev = dec.device
-    boxes = torch.empty((b, p, 7), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, p), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, p), dtype=torch.int32, device=dev)
-    valid = torch.empty((b, p), dtype=torch.uint8, device=dev)
+    boxes, scores, labels, valid = _finalize_outputs(b, p, dec.device)
     rc = rt.lib().sec_predict_finalize(rt.ptr(dec), rt.ptr(top_score), rt.ptr(top_label), rt.ptr(dir_label), rt.ptr(keep),
                                        rt.ptr(num_keep), b, k, p, int(bool(use_direction)), float(dir_offset),
                                        float(dir_limit_offset), int(num_dir_bins), rt.ptr(range6), rt.ptr(boxes),
                                        rt.ptr(scores), rt.ptr(labels), rt.ptr(valid), rt.stream())
     rt.check(rc, "sec_predict_finalize")
-    # (the kernel writes 0 / 1 bytes: reinterpret, do not convert -- `.bool()` was the last torch kernel inside the captured step, 7.8 us)
-    return {"boxes": boxes, "scores": scores, "labels": labels, "valid": valid.view(torch.bool)}
+    return _finalize_result(boxes, scores, labels, valid)
 
 
 # multi-class NMS (use_multi_class_nms, voxelnet.py:458-547): the same chain over (frame, class) items
@@ -2031,14 +2027,9 @@ def predict_decode_classes(box, dir_cls, anchors, top_idx, top_score, rotate=Tru
     assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
     assert top_idx.dim() == 3 and top_idx.is_contiguous() and top_score.is_contiguous() and top_score.shape == top_idx.shape
     _, nc, k = top_idx.shape
-    dev = box.device
-    dec = torch.empty((b, nc, k, 7), dtype=torch.float32, device=dev)
-    dets = torch.empty((b, nc, k, 6), dtype=torch.float32, device=dev)
-    dlab = torch.empty((b, nc, k), dtype=torch.int32, device=dev)
-    if dir_cls is not None:
-        assert dir_cls.dtype == box.dtype
-    rc = rt.lib().sec_predict_decode_classes(rt.ptr(box), _strides5(box), rt.ptr(dir_cls), _strides5(dir_cls) if dir_cls is not None else None,
-                                             dir_cls.shape[-1] if dir_cls is not None else 0, b, a, h, w, nc, k, rt.ptr(anchors),
+    dec, dets, dlab = _decode_outputs((b, nc, k), box.device)
+    dir_ptr, dir_strides, bins = _dir_args(dir_cls, box)
+    rc = rt.lib().sec_predict_decode_classes(rt.ptr(box), _strides5(box), dir_ptr, dir_strides, bins, b, a, h, w, nc, k, rt.ptr(anchors),
                                              rt.ptr(top_idx), rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
                                              rt.dtype_code(box.dtype), rt.stream())
     rt.check(rc, "sec_predict_decode_classes")
@@ -2076,17 +2067,13 @@ def predict_finalize_classes(dec, top_score, dir_label, keep, num_keep, post_off
     b, nc, k, _ = dec.shape
     assert post_offsets.dtype == torch.int32 and post_offsets.numel() == nc + 1
     p = int(post_total)
-    dev = dec.device
-    boxes = torch.empty((b, p, 7), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, p), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, p), dtype=torch.int32, device=dev)
-    valid = torch.empty((b, p), dtype=torch.uint8, device=dev)
+    boxes, scores, labels, valid = _finalize_outputs(b, p, dec.device)
     rc = rt.lib().sec_predict_finalize_classes(rt.ptr(dec), rt.ptr(top_score), rt.ptr(dir_label), rt.ptr(keep), rt.ptr(num_keep),
                                                rt.ptr(post_offsets), b, nc, k, p, int(bool(use_direction)), float(dir_offset),
                                                float(dir_limit_offset), int(num_dir_bins), rt.ptr(range6), rt.ptr(boxes), rt.ptr(scores),
                                                rt.ptr(labels), rt.ptr(valid), rt.stream())
     rt.check(rc, "sec_predict_finalize_classes")
-    return {"boxes": boxes, "scores": scores, "labels": labels, "valid": valid.view(torch.bool)}
+    return _finalize_result(boxes, scores, labels, valid)
 
 
 # ----------------------------------------------------------------------------- training: targets + loss

@@ -51,6 +51,7 @@ SYMBOLS = [
     "sec_pfn_kind_train_bwd",
     "sec_rpn_tile_cover_lds_bytes", "sec_rpn_tile_cover", "sec_conv2d_nhwc_gather_cover", "sec_conv2d_nhwc_tiles_cover",
     "sec_conv2d_nhwc_tiles_tail_cover", "sec_predict_select_cover", "sec_predict_decode_cover",
+    "sec_predict_select_plan_name",
 ]
 
 _lib = None
@@ -233,6 +234,8 @@ def lib():
         l.sec_predict_select_lazy.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, vp, ci, vp, vp, vp]
         l.sec_predict_decode_lazy.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
         l.sec_predict_finalize.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp]
+        l.sec_predict_select_plan_name.argtypes = [i64, ci, vp]
+        l.sec_predict_select_plan_name.restype = ctypes.c_char_p
         l.sec_assign_targets_workspace_bytes.argtypes = [ci, ci, ci]
         l.sec_assign_targets_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, cf, cf, vp, vp, vp, vp, sz, vp]
         l.sec_assign_targets_per_class_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]

@@ -29,7 +29,8 @@ REG_CAP = 72 * 1024          # keys one second-stage / direct workgroup holds; a
 
 # ---------------------------------------------------------------------------------------------------------------- the select
 def select_form(n, dtype):
-    """The form predict_select_launch takes for n anchors per frame (read from its code): a name and the number of first-stage chunks."""
+    """The form the select takes for n anchors per frame: a name and the number of first-stage chunks.  An independent restatement of
+    predict_select_decide (csrc/predict.hip); test_predict_ref_host.py holds it equal to ops.predict_select_plan."""
     if dtype == torch.float32:
         return "radix32", 0
     c4 = -(-n // SEL_CHUNK)

@@ -187,7 +187,8 @@ def test_masked_select(ops, dtype, shape):
 
 
 def _masked_entry_point_without_mask(ops, cls, k, thr, lazy=None):
-    """sec_predict_select_masked with a NULL mask (ops.predict_select routes a missing mask to the older entry points)."""
+    """sec_predict_select_masked with a NULL mask, called directly (ops.predict_select takes this route itself for every head form but the
+    cover one; tests/test_gpu_predict_edges.py drives the older sec_predict_select / sec_predict_select_lazy through ctypes)."""
     from second_amd import runtime as rt
     b, a, h, w, nc = cls.shape
     k = min(int(k), a * h * w, 1024)

@@ -89,6 +89,7 @@ def test_select_at_the_form_boundaries(ops, i, case):
     dtype, n, nc, b = case
     k, thr = 1000, 0.3
     form = R.select_form(n, dtype)
+    assert ops.predict_select_plan(n, dtype) == form
     seen = 0
     for p, pattern in enumerate(R.PATTERNS):
         x = R.make_logits(pattern, b, n, nc, thr, dtype, 100 * i + p)
@@ -250,6 +251,7 @@ def test_select_and_decode_over_three_and_four_segments(ops, maps, nc, dtype):
     border one anchor into a chunk and one anchor before its end; ties across every border rank by global index."""
     n = sum(a * h * w for a, h, w in maps)
     b, k, thr = 2, 1000, 0.3
+    assert ops.predict_select_plan(n, dtype) == R.select_form(n, dtype)          # the segments select decides on the summed anchor count
     starts = np.cumsum([a * h * w for a, h, w in maps])[:-1].tolist()
     box, dirs = _random_box_dir(b, n, dtype, 6)
     g = torch.Generator().manual_seed(8)
@@ -273,15 +275,12 @@ def test_select_and_decode_over_three_and_four_segments(ops, maps, nc, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. lazy / cover / mask
-@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[-1])
-@pytest.mark.parametrize("ahw", [(20, 13, 37), (2, 13, 37)])
-@pytest.mark.parametrize("form", ["tiles", "cover"])
-def test_lazy_cover_and_masked_addressing_on_ragged_maps(ops, form, ahw, dtype):
-    """Written-tile bits (8 x 16 grid) / cover words (8-row bands, 32-column words) on a map ragged against both, a background map with
-    scores above the threshold, an anchor mask on top: select and decode equal the plain entry points on where(written, head, background)
-    bit for bit, and the reference (with mask=) entry for entry.  (20, 13, 37) takes the chunk form, (2, 13, 37) the direct one."""
+def _ragged_lazy_inputs(form, ahw, dtype, b=2, nc=3, thr=0.3):
+    """A lazily written head on a map ragged against the tile grid / the cover words: the written-tile table (``form`` "tiles") or cover
+    words ("cover"), the pixel mask they stand for, and per head tensor ("cls", "box", "dir") the triple (the head with junk in its
+    unwritten elements, the background map, where(written, head, background)), all on the device; anchors; the generator, for more draws."""
     a, h, w = ahw
-    n, b, nc, k, thr = a * h * w, 2, 3, 1000, 0.3
+    n = a * h * w
     g = torch.Generator().manual_seed(21)
     x = R.make_logits("trained", b, n, nc, thr, dtype, 70).reshape(b, a, h, w, nc)
     bg = R.redraw_band((torch.randn(1, a, h, w, nc, generator=g) * 0.8 - 2.5).to(dtype), thr)       # a few percent of the background anchors pass 0.3
@@ -306,6 +305,19 @@ def test_lazy_cover_and_masked_addressing_on_ragged_maps(ops, form, ahw, dtype):
         t, back = t.reshape(b, a, h, w, code), back.reshape(1, a, h, w, code)
         heads[name] = (torch.where(wr, t, torch.full_like(t, junk)).contiguous().cuda(),         # unwritten elements hold junk
                        back.contiguous().cuda(), torch.where(wr, t, back.expand(b, -1, -1, -1, -1)).contiguous().cuda())
+    return table, written, heads, anchors, g
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: str(d).split(".")[-1])
+@pytest.mark.parametrize("ahw", [(20, 13, 37), (2, 13, 37)])
+@pytest.mark.parametrize("form", ["tiles", "cover"])
+def test_lazy_cover_and_masked_addressing_on_ragged_maps(ops, form, ahw, dtype):
+    """Written-tile bits (8 x 16 grid) / cover words (8-row bands, 32-column words) on a map ragged against both, a background map with
+    scores above the threshold, an anchor mask on top: select and decode equal the plain entry points on where(written, head, background)
+    bit for bit, and the reference (with mask=) entry for entry.  (20, 13, 37) takes the chunk form, (2, 13, 37) the direct one."""
+    a, h, w = ahw
+    n, b, nc, k, thr = a * h * w, 2, 3, 1000, 0.3
+    table, written, heads, anchors, g = _ragged_lazy_inputs(form, ahw, dtype, b, nc, thr)
     holes, bgc, full = heads["cls"]
     ref = R.select_reference(full, k, thr)
     got = _select_twice(ops, holes, k, thr, ref, lazy=(table, bgc))
@@ -328,6 +340,51 @@ def test_lazy_cover_and_masked_addressing_on_ragged_maps(ops, form, ahw, dtype):
     none = torch.zeros_like(mask)
     for cls_, kw in ((holes, {"lazy": (table, bgc)}), (full, {})):
         assert ops.predict_select(cls_, k, thr, anchor_mask=none, **kw)[3].tolist() == [0] * b
+
+
+def _select_through(entry, cls, k, thr, tail=()):
+    """sec_predict_select / sec_predict_select_lazy through ctypes (ops.predict_select itself calls sec_predict_select_masked), with the
+    allocations of ops.predict_select; ``tail`` = the tensors the entry point takes between the dtype and the stream."""
+    import ctypes
+    from second_amd import runtime as rt
+    b, a, h, w, nc = cls.shape
+    k = min(k, a * h * w, 1024)
+    out = (torch.empty((b, k), dtype=torch.int32, device=cls.device), torch.empty((b, k), dtype=torch.float32, device=cls.device),
+           torch.empty((b, k), dtype=torch.int32, device=cls.device), torch.empty((b,), dtype=torch.int32, device=cls.device))
+    keys = torch.empty((b * a * h * w,), dtype=torch.int32, device=cls.device)
+    rc = getattr(rt.lib(), entry)(rt.ptr(cls), (ctypes.c_int64 * 5)(*cls.stride()), b, a, h, w, nc, k, float(thr), rt.ptr(keys),
+                                  *[rt.ptr(t) for t in out], rt.dtype_code(cls.dtype), *[rt.ptr(t) for t in tail], rt.stream())
+    assert rc == 0, (entry, rc)
+    return out
+
+
+def _same_up_to_counts(got, want):
+    assert torch.equal(got[3], want[3]) and int(want[3].max()) > 0
+    for f in range(want[3].shape[0]):
+        c = int(want[3][f])
+        assert all(torch.equal(_bits(g[f, :c]), _bits(w[f, :c])) for g, w in zip(got[:3], want[:3])), f"frame {f}"
+
+
+@pytest.mark.parametrize("dtype,ahw,nc,form", [(torch.bfloat16, (2, 13, 37), 3, "direct"), (torch.float32, (2, 13, 37), 3, "radix32"),
+                                               (torch.bfloat16, (3, 1, 2731), 1, "chunk4+kp5")],
+                         ids=["bf16-direct", "fp32-radix32", "bf16-chunked"])
+def test_the_eager_and_lazy_entry_points_equal_the_masked_route(ops, dtype, ahw, nc, form):
+    """ops.predict_select reaches every head form but the cover one through sec_predict_select_masked; sec_predict_select and
+    sec_predict_select_lazy stay in the C API for callers without a mask.  Both, through ctypes, give ops.predict_select's four
+    outputs bit for bit up to counts: a [2, 2, 13, 37, 3] head (direct / radix32) and an 8193-anchor one (chunked); the lazy entry
+    point on the ragged tile table and background of test_lazy_cover_and_masked_addressing_on_ragged_maps."""
+    a, h, w = ahw
+    n, b, k, thr = a * h * w, 2, 1000, 0.3
+    assert ops.predict_select_plan(n, dtype) == R.select_form(n, dtype) and R.select_form(n, dtype)[0] == form
+    cls = R.make_logits("trained", b, n, nc, thr, dtype, 90).cuda().reshape(b, a, h, w, nc)
+    _same_up_to_counts(_select_through("sec_predict_select", cls, k, thr), ops.predict_select(cls, k, thr))
+    lazy_ahw = (20, 13, 37) if form.startswith("chunk") else (2, 13, 37)
+    assert ops.predict_select_plan(lazy_ahw[0] * 13 * 37, dtype)[0] == form
+    table, _, heads, _, _ = _ragged_lazy_inputs("tiles", lazy_ahw, dtype)
+    holes, bgc, full = heads["cls"]
+    want = ops.predict_select(holes, k, thr, lazy=(table, bgc))
+    _same_up_to_counts(_select_through("sec_predict_select_lazy", holes, k, thr, tail=(table, bgc)), want)
+    _same_up_to_counts(_select_through("sec_predict_select", full, k, thr), want)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 7. NaN and infinities

@@ -186,6 +186,22 @@ def test_every_listed_select_input_keeps_the_threshold_band():
                 assert (thr == 0.5 and bool((x[on] == 0).all()) and int(on.sum()) == 80) or not bool(on.any())
 
 
+def test_select_form_is_the_library_decision():
+    """select_form() (written from the documented table) against predict_select_decide through sec_predict_select_plan_name, a host-only
+    query: name and chunk count, all three dtypes, every listed boundary and its neighbours, and a seeded sample up to 6 M anchors."""
+    from second_amd import ops
+    ns = {m for n in R.BOUNDARY_N + R.BOUNDARY_N_HUGE + R.BOUNDARY_N_FP32 for m in (n - 1, n, n + 1)}
+    ns |= {int(n) for n in np.random.default_rng(5).integers(1, 6_000_001, 4000)}
+    seen = set()
+    for dtype in (torch.bfloat16, torch.float16, torch.float32):
+        for n in sorted(ns):
+            assert ops.predict_select_plan(n, dtype) == R.select_form(n, dtype), (n, dtype)
+            seen.add(R.select_form(n, dtype)[0])
+    assert seen == {"direct", "radix16", "radix32"} | {"chunk%d+kp%d" % (c, k) for c in (4, 36) for k in (5, 10, 20, 36)}
+    from second_amd import runtime as rt
+    assert rt.lib().sec_predict_select_plan_name(8193, 3, None) == b"" and rt.lib().sec_predict_select_plan_name(8193, -1, None) == b""
+
+
 def test_the_form_table_boundaries():
     """select_form() restates predict_select_launch's decision; the boundary list of the GPU test sits on every edge of it."""
     f = lambda n, dt=torch.bfloat16: R.select_form(n, dt)[0]
