@@ -36,6 +36,9 @@ extern "C" {
 #define SEC_BF16 2
 
 #define SEC_ABI_VERSION 9
+/* Widest box row the *_nd entry points take: 7 + custom_ndim values (GroundBox3dCoder.custom_ndim, second/core/box_coders.py:31-46;
+ * nuScenes velocity is custom_ndim 2).  The reference sets no limit and only ever uses two; four is a choice. */
+#define SEC_BOX_MAX_NDIM 11
 int sec_abi_version(void);
 /* Content checksum of `count` device tensors in one launch (+ one memset): sums [count][2] = (sum of the tensor's 32-bit words, sum of
  * word * (index + 1)), both mod 2^64.  h_ptrs / h_nbytes are HOST arrays (4-byte aligned pointers, byte counts that are multiples of
@@ -905,6 +908,32 @@ int sec_predict_finalize(const float *decoded, const float *top_score, const int
                          int post_max, int use_direction, float dir_offset, float dir_limit_offset,
                          int num_dir_bins, const float *range6, float *boxes, float *scores, int *labels,
                          unsigned char *valid, void *stream);
+/* Boxes with custom values: rows of box_ndim = 7 + custom_ndim values, 7 <= box_ndim <= SEC_BOX_MAX_NDIM (anchor generators'
+ * custom_values, GroundBox3dCoder.custom_ndim; second_box_decode, box_torch_ops.py:64-102).  `box` is a [B, A, H, W, box_ndim]
+ * view, `anchors` [N, box_ndim], `decoded` [B, k, box_ndim], `boxes` [B, post_max, box_ndim].  Columns 0-6 are those of the entry
+ * points above, expression by expression; column 7 + j is encoding + anchor (one rounded addition) in the decode and a copy in the
+ * finalize.  dets and dir_label are unchanged: NMS never sees the custom columns (boxes_for_nms = box[:, [0, 1, 3, 4, 6]]).
+ *   sec_predict_decode_nd          : sec_predict_decode plus the head's form -- all of tile_live / cover_cols / box_background /
+ *                                    dir_background NULL: eager; tile_live: sec_predict_decode_lazy; cover_cols: _cover.  Both
+ *                                    tables, a table without box_background or a background without a table: SEC_E_INVALID.
+ *   sec_predict_decode_segments_nd : sec_predict_decode_segments.
+ *   sec_predict_finalize_nd        : sec_predict_finalize; direction fix on column 6, range mask on columns 0-2.
+ * box_ndim 7 launches the kernels of the entry points above.  Checked on the host before anything is enqueued: what those entry
+ * points check (SEC_E_INVALID), then box_ndim outside the range: SEC_E_UNSUPPORTED.  The multi-class entry points below take 7 only. */
+int sec_predict_decode_nd(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                          int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
+                          const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets, int *dir_label,
+                          int dtype, int box_ndim, const unsigned short *tile_live, const unsigned *cover_cols,
+                          const void *box_background, const void *dir_background, void *stream);
+int sec_predict_decode_segments_nd(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+                                   const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
+                                   const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                   float *dets, int *dir_label, int dtype, int box_ndim, void *stream);
+int sec_predict_finalize_nd(const float *decoded, const float *top_score, const int *top_label,
+                            const int *dir_label, const int *keep, const int *num_keep, int batch, int k,
+                            int post_max, int use_direction, float dir_offset, float dir_limit_offset,
+                            int num_dir_bins, const float *range6, float *boxes, float *scores, int *labels,
+                            unsigned char *valid, int box_ndim, void *stream);
 /* Multi-class NMS (use_multi_class_nms, voxelnet.py:458-547): the same chain with (frame, class) ITEMS as the unit of work; item
  * i = frame * num_class + class everywhere below.  Class c selects among the anchors with h_a_begin[c] <= a < h_a_end[c] of the
  * [B, A, H, W, C] view (target_assigner.anchors_range(c); [0, A) for every class when nms_class_agnostic) by the sigmoid of column
@@ -1021,6 +1050,16 @@ int sec_assign_targets_sim_f32(const float *anchors, int n_anchor, const float *
                                const float *h_unmatched, const int *h_sim_kind, const double *h_sim_params, int *labels,
                                float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
                                const unsigned char *anchors_mask /* NULL = none */, void *stream);
+/* sec_assign_targets_sim_f32 on rows of box_ndim = 7 + custom_ndim values: the row pitch of anchors, gt_boxes and bbox_targets
+ * [batch, n_anchor, box_ndim].  The matching reads columns 0-6 and is unchanged; target column 7 + j is gt - anchor (one rounded
+ * subtraction, second_box_encode, box_np_ops.py:47-81) for positives and +0 otherwise.  Same workspace query.  box_ndim outside
+ * 7..SEC_BOX_MAX_NDIM: SEC_E_UNSUPPORTED before anything is enqueued; box_ndim 7 launches the kernels of sec_assign_targets_sim_f32. */
+int sec_assign_targets_nd_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                              const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                              const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                              const float *h_unmatched, const int *h_sim_kind, const double *h_sim_params, int *labels,
+                              float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
+                              const unsigned char *anchors_mask /* NULL = none */, int box_ndim, void *stream);
 /* ---------------------------------------------------------------------------------------------
  * Anchor-area mask (`anchor_area_threshold` of the KITTI PointPillars configs; second/data/preprocess.py:345-357,
  * box_np_ops.py:917-946): mask[b][n] = 1 when more than `threshold` voxels of frame b lie under anchor n's near box.
@@ -1044,6 +1083,15 @@ int sec_second_loss_f32(const float *cls_preds, const float *box_preds, const fl
                         const float *reg_targets, const float *anchors, const float *importance, int batch,
                         int n_anchor, int num_class, int num_dir_bins, const float *h_params17, float *d_cls, float *d_box,
                         float *d_dir, float *out6, void *workspace, size_t workspace_bytes, void *stream);
+/* sec_second_loss_f32 on rows of box_ndim = 7 + custom_ndim values: the row pitch of box_preds, reg_targets, anchors and d_box.
+ * h_params [10 + box_ndim]: the ten scalars of h_params17 followed by box_ndim code weights.  The sin-difference stays on column 6
+ * and the direction target on reg[6] + anchors[6]; columns 7.. get the plain weighted smooth L1 (add_sin_difference passes them
+ * through, voxelnet.py:704-714).  box_ndim outside 7..SEC_BOX_MAX_NDIM: SEC_E_UNSUPPORTED before anything is enqueued; box_ndim 7
+ * launches the kernels of sec_second_loss_f32.  The stacked-head loss below takes 7 only. */
+int sec_second_loss_nd_f32(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
+                           const float *reg_targets, const float *anchors, const float *importance, int batch,
+                           int n_anchor, int num_class, int num_dir_bins, const float *h_params, int box_ndim, float *d_cls,
+                           float *d_box, float *d_dir, float *out6, void *workspace, size_t workspace_bytes, void *stream);
 /* The same loss read straight from the STACKED heads of the training step: heads [batch, h, w, head_channels] channels last, 16 bit
  * = box [A*7] | cls [A*num_class] | dir [A*bins] | zero padding, the output of the three 1x1 head convolutions run as one
  * (second/pytorch/models/rpn.py:386-391; the reference views each as [B, A, H, W, code], anchor n = (a*H + y)*W + x, and hands three
@@ -1144,6 +1192,15 @@ int sec_augment_boxes_f32(const float *boxes, const int *box_offsets, int n_boxe
                           const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
                           const float *frame_params, const float *h_bev_range4, float *out_boxes, int *out_classes,
                           float *out_importance, int *out_offsets, void *stream);
+/* sec_augment_boxes_f32 on rows of box_ndim values in and out, box_ndim 7 or 9 (anything else: SEC_E_UNSUPPORTED -- the reference
+ * transforms a velocity only when shape[1] == 9, preprocess.py:749-799).  Columns 7, 8 = (vx, vy), in the kernel's stage order:
+ * y flip negates vy, x flip negates vx, the rotation makes (vx c + vy s, -vx s + vy c) with c, s of the frame's angle as for the
+ * centre (gt_boxes[:, 7:9] @ [[c, -s], [s, c]]), the scaling multiplies both.  Translation, per-object noise and the yaw wrap do
+ * not touch them.  Columns 0-6, the kept set, classes, importance and offsets are those of sec_augment_boxes_f32. */
+int sec_augment_boxes_nd_f32(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
+                             const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
+                             const float *frame_params, const float *h_bev_range4, int box_ndim, float *out_boxes, int *out_classes,
+                             float *out_importance, int *out_offsets, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Ground-truth database sampling: DataBaseSamplerV2.sample_all (second/core/sample_ops.py:95-216, 238-285) and the merge of

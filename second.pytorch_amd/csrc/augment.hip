@@ -253,14 +253,18 @@ __global__ __launch_bounds__(kBlock) void k_augment_points(float *__restrict__ p
 // ------------------------------------------------------------------------------------------------ boxes: transform, filter, compact
 // One workgroup walks the frames in order, 256 boxes at a time; a block scan of the keep flags places the survivors of a frame
 // behind those of the frames before it, in their original order.  Rows behind the last survivor are zeroed.
-__global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restrict__ boxes, const int *__restrict__ box_offsets, int n_boxes,
-                                                          int batch, const unsigned char *__restrict__ valid,
-                                                          const int *__restrict__ classes, const float *__restrict__ importance,
-                                                          const float *__restrict__ loc_transform,
-                                                          const float *__restrict__ rot_transform,
-                                                          const float *__restrict__ frame_params, float xmin, float ymin, float xmax,
-                                                          float ymax, float *__restrict__ out_boxes, int *__restrict__ out_classes,
-                                                          float *__restrict__ out_importance, int *__restrict__ out_offsets) {
+// VELO: rows of 9 values, columns 7 and 8 a velocity (vx, vy) that the flips, the rotation and the scaling transform as the reference
+// does for shape[1] == 9 (preprocess.py:749-799); translation, per-object noise and the yaw wrap leave it alone.
+template <bool VELO>
+__device__ __forceinline__ void augment_boxes_body(const float *__restrict__ boxes, const int *__restrict__ box_offsets, int n_boxes,
+                                                   int batch, const unsigned char *__restrict__ valid,
+                                                   const int *__restrict__ classes, const float *__restrict__ importance,
+                                                   const float *__restrict__ loc_transform,
+                                                   const float *__restrict__ rot_transform,
+                                                   const float *__restrict__ frame_params, float xmin, float ymin, float xmax,
+                                                   float ymax, float *__restrict__ out_boxes, int *__restrict__ out_classes,
+                                                   float *__restrict__ out_importance, int *__restrict__ out_offsets) {
+    constexpr int ND = VELO ? 9 : 7;
     __shared__ int s_scan[8];
     const int tid = threadIdx.x;
     int base = 0;
@@ -275,9 +279,11 @@ __global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restric
         for (int c0 = g0; c0 < g1; c0 += kBlock) {
             const int g = c0 + tid;
             float v[7] = {0, 0, 0, 0, 0, 0, 0};
+            float vx = 0.0f, vy = 0.0f;
             int keep = 0;
             if (g < g1) {
-                for (int k = 0; k < 7; ++k) v[k] = boxes[(size_t)g * 7 + k];
+                for (int k = 0; k < 7; ++k) v[k] = boxes[(size_t)g * ND + k];
+                if (VELO) { vx = boxes[(size_t)g * ND + 7]; vy = boxes[(size_t)g * ND + 8]; }
                 const bool ok = !valid || valid[g];
                 if (ok && loc_transform) {                          // box3d_transform_ (preprocess.py:469-475)
                     v[0] += loc_transform[3 * g]; v[1] += loc_transform[3 * g + 1]; v[2] += loc_transform[3 * g + 2];
@@ -288,6 +294,13 @@ __global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restric
                 float rx, ry;
                 rot_row(v[0], v[1], gc, gs, rx, ry);                // global_rotation_v2 (preprocess.py:781-799)
                 v[6] += angle;
+                if (VELO) {
+                    if (flip_y) vy = -vy;
+                    if (flip_x) vx = -vx;
+                    float wx, wy;
+                    rot_row(vx, vy, gc, gs, wx, wy);                // gt_boxes[:, 7:9] @ [[c, -s], [s, c]]
+                    vx = wx * scale; vy = wy * scale;
+                }
                 v[0] = rx * scale + fp[4]; v[1] = ry * scale + fp[5]; v[2] = v[2] * scale + fp[6];       // global_scaling_v2, global_translate_
                 v[3] *= scale; v[4] *= scale; v[5] *= scale;
                 keep = ok && v[0] > xmin && v[0] < xmax && v[1] > ymin && v[1] < ymax;   // filter_gt_box_outside_range_by_center: the edge is outside
@@ -296,7 +309,8 @@ __global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restric
             int total;
             const int pos = base + block_exclusive_scan(keep, s_scan, &total);
             if (keep) {
-                for (int k = 0; k < 7; ++k) out_boxes[(size_t)pos * 7 + k] = v[k];
+                for (int k = 0; k < 7; ++k) out_boxes[(size_t)pos * ND + k] = v[k];
+                if (VELO) { out_boxes[(size_t)pos * ND + 7] = vx; out_boxes[(size_t)pos * ND + 8] = vy; }
                 if (out_classes) out_classes[pos] = classes ? classes[g] : 1;
                 if (out_importance) out_importance[pos] = importance ? importance[g] : 1.0f;
             }
@@ -305,10 +319,32 @@ __global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restric
         if (tid == 0) out_offsets[b + 1] = base;
     }
     for (int g = base + tid; g < n_boxes; g += kBlock) {
-        for (int k = 0; k < 7; ++k) out_boxes[(size_t)g * 7 + k] = 0.0f;
+        for (int k = 0; k < ND; ++k) out_boxes[(size_t)g * ND + k] = 0.0f;
         if (out_classes) out_classes[g] = 0;
         if (out_importance) out_importance[g] = 0.0f;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_augment_boxes(const float *__restrict__ boxes, const int *__restrict__ box_offsets, int n_boxes,
+                                                          int batch, const unsigned char *__restrict__ valid,
+                                                          const int *__restrict__ classes, const float *__restrict__ importance,
+                                                          const float *__restrict__ loc_transform,
+                                                          const float *__restrict__ rot_transform,
+                                                          const float *__restrict__ frame_params, float xmin, float ymin, float xmax,
+                                                          float ymax, float *__restrict__ out_boxes, int *__restrict__ out_classes,
+                                                          float *__restrict__ out_importance, int *__restrict__ out_offsets) {
+    augment_boxes_body<false>(boxes, box_offsets, n_boxes, batch, valid, classes, importance, loc_transform, rot_transform, frame_params, xmin,
+                              ymin, xmax, ymax, out_boxes, out_classes, out_importance, out_offsets);
+}
+__global__ __launch_bounds__(kBlock) void k_augment_boxes_velo(const float *__restrict__ boxes, const int *__restrict__ box_offsets, int n_boxes,
+                                                               int batch, const unsigned char *__restrict__ valid,
+                                                               const int *__restrict__ classes, const float *__restrict__ importance,
+                                                               const float *__restrict__ loc_transform,
+                                                               const float *__restrict__ rot_transform,
+                                                               const float *__restrict__ frame_params, float xmin, float ymin, float xmax,
+                                                               float ymax, float *__restrict__ out_boxes, int *__restrict__ out_classes,
+                                                               float *__restrict__ out_importance, int *__restrict__ out_offsets) {
+    augment_boxes_body<true>(boxes, box_offsets, n_boxes, batch, valid, classes, importance, loc_transform, rot_transform, frame_params, xmin,
+                             ymin, xmax, ymax, out_boxes, out_classes, out_importance, out_offsets);
 }
 
 // blocks per frame for the two point kernels: the frames' sizes are device data, so the grid is sized for frames of the mean size
@@ -684,17 +720,32 @@ SEC_API int sec_augment_points_f32(float *points, int point_pitch, const int *po
     return check_launch();
 }
 
+static int augment_boxes_impl(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
+                              const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
+                              const float *frame_params, const float *h_bev_range4, float *out_boxes, int *out_classes,
+                              float *out_importance, int *out_offsets, int box_ndim, void *stream) {
+    if (batch <= 0 || n_boxes < 0 || !box_offsets || !frame_params || !h_bev_range4 || !out_offsets || (n_boxes > 0 && (!boxes || !out_boxes)) ||
+        (!loc_transform != !rot_transform))
+        return SEC_E_INVALID;
+    if (box_ndim != 7 && box_ndim != 9) return SEC_E_UNSUPPORTED;       // the reference transforms a velocity only when shape[1] == 9
+    hipLaunchKernelGGL(box_ndim == 9 ? k_augment_boxes_velo : k_augment_boxes, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, boxes, box_offsets,
+                       n_boxes, batch, valid, classes, importance, loc_transform, rot_transform, frame_params, h_bev_range4[0], h_bev_range4[1],
+                       h_bev_range4[2], h_bev_range4[3], out_boxes, out_classes, out_importance, out_offsets);
+    return check_launch();
+}
 SEC_API int sec_augment_boxes_f32(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
                                   const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
                                   const float *frame_params, const float *h_bev_range4, float *out_boxes, int *out_classes,
                                   float *out_importance, int *out_offsets, void *stream) {
-    if (batch <= 0 || n_boxes < 0 || !box_offsets || !frame_params || !h_bev_range4 || !out_offsets || (n_boxes > 0 && (!boxes || !out_boxes)) ||
-        (!loc_transform != !rot_transform))
-        return SEC_E_INVALID;
-    hipLaunchKernelGGL(k_augment_boxes, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, boxes, box_offsets, n_boxes, batch, valid, classes,
-                       importance, loc_transform, rot_transform, frame_params, h_bev_range4[0], h_bev_range4[1], h_bev_range4[2],
-                       h_bev_range4[3], out_boxes, out_classes, out_importance, out_offsets);
-    return check_launch();
+    return augment_boxes_impl(boxes, box_offsets, n_boxes, batch, valid, classes, importance, loc_transform, rot_transform, frame_params,
+                              h_bev_range4, out_boxes, out_classes, out_importance, out_offsets, 7, stream);
+}
+SEC_API int sec_augment_boxes_nd_f32(const float *boxes, const int *box_offsets, int n_boxes, int batch, const unsigned char *valid,
+                                     const int *classes, const float *importance, const float *loc_transform, const float *rot_transform,
+                                     const float *frame_params, const float *h_bev_range4, int box_ndim, float *out_boxes, int *out_classes,
+                                     float *out_importance, int *out_offsets, void *stream) {
+    return augment_boxes_impl(boxes, box_offsets, n_boxes, batch, valid, classes, importance, loc_transform, rot_transform, frame_params,
+                              h_bev_range4, out_boxes, out_classes, out_importance, out_offsets, box_ndim, stream);
 }
 
 SEC_API int sec_db_sample_select_f32(const float *gt_boxes, const int *gt_offsets, int n_gt, int batch, const int *gt_classes,

@@ -823,13 +823,17 @@ __global__ __launch_bounds__(kSelThreads) void k_predict_select_chunk(const T *_
     }
 }
 
-template <typename T, typename V = View5>
-__global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__ box, V vb, const T *__restrict__ dir,
-                                                          V vd, int ndir, PredGeom g, int K,
-                                                          const float *__restrict__ anchors, const int *__restrict__ top_idx,
-                                                          const float *__restrict__ top_score, int rotate,
-                                                          float *__restrict__ dec, float *__restrict__ dets,
-                                                          int *__restrict__ dir_label) {
+// The decode of one selected box.  WIDE = false: rows of 7 values (k_predict_decode).  WIDE = true: rows of nd = 7 + custom_ndim
+// values (k_predict_decode_nd; GroundBox3dCoder with custom_ndim > 0, box_torch_ops.py:15-102): columns 0-6 by the same expressions,
+// column 7 + j = encoding + anchor; dets and dir_label never see the custom columns.
+template <typename T, typename V, bool WIDE>
+__device__ __forceinline__ void predict_decode_row(const T *__restrict__ box, const V &vb, const T *__restrict__ dir,
+                                                   const V &vd, int ndir, const PredGeom &g, int K,
+                                                   const float *__restrict__ anchors, const int *__restrict__ top_idx,
+                                                   const float *__restrict__ top_score, int rotate,
+                                                   float *__restrict__ dec, float *__restrict__ dets,
+                                                   int *__restrict__ dir_label, int nd_arg) {
+    const int nd = WIDE ? nd_arg : 7;          // row pitch of anchors and dec
     int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= g.batch * K) return;
     int b = t / K;
@@ -851,7 +855,7 @@ __global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__
     float e[7];
 #pragma unroll
     for (int c = 0; c < 7; ++c) e[c] = ldf(pb + c * bsc);
-    const float *an = anchors + (size_t)n * 7;
+    const float *an = anchors + (size_t)n * nd;
     float xa = an[0], ya = an[1], za = an[2], wa = an[3], la = an[4], ha = an[5], ra = an[6];
     float diag = sqrtf(__fadd_rn(__fmul_rn(la, la), __fmul_rn(wa, wa)));
     float o[7];
@@ -863,7 +867,9 @@ __global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__
     o[5] = __fmul_rn(expf(e[5]), ha);
     o[6] = __fadd_rn(e[6], ra);
 #pragma unroll
-    for (int c = 0; c < 7; ++c) dec[(size_t)t * 7 + c] = o[c];
+    for (int c = 0; c < 7; ++c) dec[(size_t)t * nd + c] = o[c];
+    if constexpr (WIDE)
+        for (int c = 7; c < nd; ++c) dec[(size_t)t * nd + c] = __fadd_rn(ldf(pb + c * bsc), an[c]);
     float *d = dets + (size_t)t * 6;
     if (rotate) {        // boxes_for_nms = box[:, [0, 1, 3, 4, 6]] + score
         d[0] = o[0]; d[1] = o[1]; d[2] = o[3]; d[3] = o[4]; d[4] = o[6]; d[5] = top_score[t];
@@ -892,19 +898,41 @@ __global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__
     dir_label[t] = dl;
 }
 
-__global__ __launch_bounds__(kBlock) void k_predict_finalize(const float *__restrict__ dec, const float *__restrict__ top_score,
-                                                            const int *__restrict__ top_label, const int *__restrict__ dir_label,
-                                                            const int *__restrict__ keep, const int *__restrict__ num_keep,
-                                                            int batch, int K, int P, int use_dir, float dir_offset,
-                                                            float dir_limit_offset, float period, const float *__restrict__ range6,
-                                                            float *__restrict__ boxes, float *__restrict__ scores,
-                                                            int *__restrict__ labels, unsigned char *__restrict__ valid) {
+template <typename T, typename V = View5>
+__global__ __launch_bounds__(kBlock) void k_predict_decode(const T *__restrict__ box, V vb, const T *__restrict__ dir,
+                                                          V vd, int ndir, PredGeom g, int K,
+                                                          const float *__restrict__ anchors, const int *__restrict__ top_idx,
+                                                          const float *__restrict__ top_score, int rotate,
+                                                          float *__restrict__ dec, float *__restrict__ dets,
+                                                          int *__restrict__ dir_label) {
+    predict_decode_row<T, V, false>(box, vb, dir, vd, ndir, g, K, anchors, top_idx, top_score, rotate, dec, dets, dir_label, 7);
+}
+template <typename T, typename V = View5>
+__global__ __launch_bounds__(kBlock) void k_predict_decode_nd(const T *__restrict__ box, V vb, const T *__restrict__ dir,
+                                                             V vd, int ndir, PredGeom g, int K,
+                                                             const float *__restrict__ anchors, const int *__restrict__ top_idx,
+                                                             const float *__restrict__ top_score, int rotate,
+                                                             float *__restrict__ dec, float *__restrict__ dets,
+                                                             int *__restrict__ dir_label, int nd) {
+    predict_decode_row<T, V, true>(box, vb, dir, vd, ndir, g, K, anchors, top_idx, top_score, rotate, dec, dets, dir_label, nd);
+}
+
+// WIDE as in predict_decode_row: the direction fix on column 6, the range mask on columns 0-2, custom columns copied
+template <bool WIDE>
+__device__ __forceinline__ void predict_finalize_row(const float *__restrict__ dec, const float *__restrict__ top_score,
+                                                     const int *__restrict__ top_label, const int *__restrict__ dir_label,
+                                                     const int *__restrict__ keep, const int *__restrict__ num_keep,
+                                                     int batch, int K, int P, int use_dir, float dir_offset,
+                                                     float dir_limit_offset, float period, const float *__restrict__ range6,
+                                                     float *__restrict__ boxes, float *__restrict__ scores,
+                                                     int *__restrict__ labels, unsigned char *__restrict__ valid, int nd_arg) {
+    const int nd = WIDE ? nd_arg : 7;
     int t = blockIdx.x * kBlock + threadIdx.x;
     if (t >= batch * P) return;
     int b = t / P, j = t - b * P;
     bool ok = j < num_keep[b];
     int sel = ok ? keep[(size_t)b * K + j] : 0;
-    const float *s = dec + ((size_t)b * K + sel) * 7;
+    const float *s = dec + ((size_t)b * K + sel) * nd;
     float o[7];
 #pragma unroll
     for (int c = 0; c < 7; ++c) o[c] = s[c];
@@ -917,10 +945,32 @@ __global__ __launch_bounds__(kBlock) void k_predict_finalize(const float *__rest
         ok = ok && o[0] >= range6[0] && o[1] >= range6[1] && o[2] >= range6[2] && o[0] <= range6[3] && o[1] <= range6[4] &&
              o[2] <= range6[5];
 #pragma unroll
-    for (int c = 0; c < 7; ++c) boxes[(size_t)t * 7 + c] = o[c];
+    for (int c = 0; c < 7; ++c) boxes[(size_t)t * nd + c] = o[c];
+    if constexpr (WIDE)
+        for (int c = 7; c < nd; ++c) boxes[(size_t)t * nd + c] = s[c];
     scores[t] = top_score[(size_t)b * K + sel];
     labels[t] = top_label[(size_t)b * K + sel];
     valid[t] = ok ? 1 : 0;
+}
+__global__ __launch_bounds__(kBlock) void k_predict_finalize(const float *__restrict__ dec, const float *__restrict__ top_score,
+                                                            const int *__restrict__ top_label, const int *__restrict__ dir_label,
+                                                            const int *__restrict__ keep, const int *__restrict__ num_keep,
+                                                            int batch, int K, int P, int use_dir, float dir_offset,
+                                                            float dir_limit_offset, float period, const float *__restrict__ range6,
+                                                            float *__restrict__ boxes, float *__restrict__ scores,
+                                                            int *__restrict__ labels, unsigned char *__restrict__ valid) {
+    predict_finalize_row<false>(dec, top_score, top_label, dir_label, keep, num_keep, batch, K, P, use_dir, dir_offset, dir_limit_offset, period,
+                                range6, boxes, scores, labels, valid, 7);
+}
+__global__ __launch_bounds__(kBlock) void k_predict_finalize_nd(const float *__restrict__ dec, const float *__restrict__ top_score,
+                                                               const int *__restrict__ top_label, const int *__restrict__ dir_label,
+                                                               const int *__restrict__ keep, const int *__restrict__ num_keep,
+                                                               int batch, int K, int P, int use_dir, float dir_offset,
+                                                               float dir_limit_offset, float period, const float *__restrict__ range6,
+                                                               float *__restrict__ boxes, float *__restrict__ scores,
+                                                               int *__restrict__ labels, unsigned char *__restrict__ valid, int nd) {
+    predict_finalize_row<true>(dec, top_score, top_label, dir_label, keep, num_keep, batch, K, P, use_dir, dir_offset, dir_limit_offset, period,
+                               range6, boxes, scores, labels, valid, nd);
 }
 
 // ---- multi-class NMS (voxelnet.py:458-547): (frame, class) items ------------------------------------------------------------
@@ -1355,15 +1405,24 @@ SEC_API int sec_predict_select_cover(const void *cls, const int64_t *h_cls_strid
 struct DecodeArgs {                                  // what every decode entry point takes besides its head(s)
     int num_dir_bins, k; const float *anchors; const int *top_idx; const float *top_score; int rotate; float *decoded, *dets; int *dir_label;
     int dtype; hipStream_t st;
+    int box_ndim = 7;                                // values per box row: 7 + custom_ndim (the _nd entry points), else 7
 };
+constexpr int kBoxMaxNdim = SEC_BOX_MAX_NDIM;
+static bool box_ndim_ok(int nd) { return nd >= 7 && nd <= kBoxMaxNdim; }
 // the decode of a validated call; V as in predict_select_launch.  `dir` of the kernel says whether there is a direction head (with
 // a SegView that is all it says: the addresses come from vb / vd)
 template <typename V>
 static int predict_decode_launch(const void *box, const V &vb, const void *dir, const V &vd, const PredGeom &g, const DecodeArgs &a) {
     return by_dtype(a.dtype, [&](auto tag) {
         using T = typename decltype(tag)::type;
-        hipLaunchKernelGGL((k_predict_decode<T, V>), dim3(div_up((long long)g.batch * a.k, kBlock)), dim3(kBlock), 0, a.st, (const T *)box, vb,
-                           (const T *)dir, vd, a.num_dir_bins, g, a.k, a.anchors, a.top_idx, a.top_score, a.rotate, a.decoded, a.dets, a.dir_label);
+        const dim3 grid(div_up((long long)g.batch * a.k, kBlock));
+        if (a.box_ndim == 7)                         // seven values: the kernel of the entry points without a width
+            hipLaunchKernelGGL((k_predict_decode<T, V>), grid, dim3(kBlock), 0, a.st, (const T *)box, vb,
+                               (const T *)dir, vd, a.num_dir_bins, g, a.k, a.anchors, a.top_idx, a.top_score, a.rotate, a.decoded, a.dets, a.dir_label);
+        else
+            hipLaunchKernelGGL((k_predict_decode_nd<T, V>), grid, dim3(kBlock), 0, a.st, (const T *)box, vb,
+                               (const T *)dir, vd, a.num_dir_bins, g, a.k, a.anchors, a.top_idx, a.top_score, a.rotate, a.decoded, a.dets, a.dir_label,
+                               a.box_ndim);
         return check_launch();
     });
 }
@@ -1374,6 +1433,7 @@ static int predict_decode_head(const void *box, const int64_t *h_box_strides5, c
     if (!box || !h_box_strides5 || g.batch <= 0 || a.k <= 0 || !a.anchors || !a.top_idx || !a.top_score || !a.decoded || !a.dets || !a.dir_label ||
         !dtype_ok(a.dtype))
         return SEC_E_INVALID;
+    if (!box_ndim_ok(a.box_ndim)) return SEC_E_UNSUPPORTED;
     View5 vb, vd{};
     int rc = head_view(f, h_box_strides5, box, f.background, g.H, g.W, a.dtype, &vb);
     if (!rc && dir) rc = head_view(f, h_dir_strides5, dir, f.dir_background, g.H, g.W, a.dtype, &vd);
@@ -1408,18 +1468,50 @@ SEC_API int sec_predict_decode_cover(const void *box, const int64_t *h_box_strid
                                {nullptr, cover_cols, box_background, dir_background, nullptr});
 }
 
+// sec_predict_decode with rows of box_ndim values; the head's form is given by its tables (at most one of tile_live / cover_cols)
+SEC_API int sec_predict_decode_nd(const void *box, const int64_t *h_box_strides5, const void *dir, const int64_t *h_dir_strides5,
+                                  int num_dir_bins, int batch, int anchors_per_loc, int h, int w, int k, const float *anchors,
+                                  const int *top_idx, const float *top_score, int rotate, float *decoded, float *dets,
+                                  int *dir_label, int dtype, int box_ndim, const unsigned short *tile_live, const unsigned *cover_cols,
+                                  const void *box_background, const void *dir_background, void *stream) {
+    return predict_decode_head(box, h_box_strides5, dir, h_dir_strides5, {batch, anchors_per_loc, h, w, 1},
+                               {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream, box_ndim},
+                               {tile_live, cover_cols, box_background, dir_background, nullptr});
+}
+
+static int predict_finalize_impl(const float *decoded, const float *top_score, const int *top_label, const int *dir_label,
+                                 const int *keep, const int *num_keep, int batch, int k, int post_max, int use_direction,
+                                 float dir_offset, float dir_limit_offset, int num_dir_bins, const float *range6,
+                                 float *boxes, float *scores, int *labels, unsigned char *valid, int box_ndim, void *stream) {
+    if (!decoded || !top_score || !top_label || !keep || !num_keep || batch <= 0 || k <= 0 || post_max <= 0 || post_max > k ||
+        !boxes || !scores || !labels || !valid || (use_direction && (!dir_label || num_dir_bins <= 0)))
+        return SEC_E_INVALID;
+    if (!box_ndim_ok(box_ndim)) return SEC_E_UNSUPPORTED;
+    float period = use_direction ? 6.283185307179586f / (float)num_dir_bins : 0.0f;
+    const dim3 grid(div_up((long long)batch * post_max, kBlock));
+    if (box_ndim == 7)
+        hipLaunchKernelGGL(k_predict_finalize, grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
+                           dir_limit_offset, period, range6, boxes, scores, labels, valid);
+    else
+        hipLaunchKernelGGL(k_predict_finalize_nd, grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
+                           dir_limit_offset, period, range6, boxes, scores, labels, valid, box_ndim);
+    return check_launch();
+}
 SEC_API int sec_predict_finalize(const float *decoded, const float *top_score, const int *top_label, const int *dir_label,
                                  const int *keep, const int *num_keep, int batch, int k, int post_max, int use_direction,
                                  float dir_offset, float dir_limit_offset, int num_dir_bins, const float *range6,
                                  float *boxes, float *scores, int *labels, unsigned char *valid, void *stream) {
-    if (!decoded || !top_score || !top_label || !keep || !num_keep || batch <= 0 || k <= 0 || post_max <= 0 || post_max > k ||
-        !boxes || !scores || !labels || !valid || (use_direction && (!dir_label || num_dir_bins <= 0)))
-        return SEC_E_INVALID;
-    float period = use_direction ? 6.283185307179586f / (float)num_dir_bins : 0.0f;
-    hipLaunchKernelGGL(k_predict_finalize, dim3(div_up((long long)batch * post_max, kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
-                       dir_limit_offset, period, range6, boxes, scores, labels, valid);
-    return check_launch();
+    return predict_finalize_impl(decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
+                                 dir_limit_offset, num_dir_bins, range6, boxes, scores, labels, valid, 7, stream);
+}
+SEC_API int sec_predict_finalize_nd(const float *decoded, const float *top_score, const int *top_label, const int *dir_label,
+                                    const int *keep, const int *num_keep, int batch, int k, int post_max, int use_direction,
+                                    float dir_offset, float dir_limit_offset, int num_dir_bins, const float *range6,
+                                    float *boxes, float *scores, int *labels, unsigned char *valid, int box_ndim, void *stream) {
+    return predict_finalize_impl(decoded, top_score, top_label, dir_label, keep, num_keep, batch, k, post_max, use_direction, dir_offset,
+                                 dir_limit_offset, num_dir_bins, range6, boxes, scores, labels, valid, box_ndim, stream);
 }
 
 // ---- several head tensors ---------------------------------------------------------------------------------------------------
@@ -1457,10 +1549,10 @@ SEC_API int sec_predict_select_segments(int num_segments, const void *const *cls
                                  {k, score_thr, key_scratch, top_idx, top_score, top_label, counts, dtype, (hipStream_t)stream});
 }
 
-SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+static int predict_decode_segments_impl(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
                                         const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
                                         const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
-                                        float *dets, int *dir_label, int dtype, void *stream) {
+                                        float *dets, int *dir_label, int dtype, int box_ndim, void *stream) {
     SegView vb{}, vd{};
     long long n;
     if (int rc = mksegs(num_segments, box, h_box_strides5, h_dims3, &vb, &n)) return rc;
@@ -1470,8 +1562,23 @@ SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box
     if (batch <= 0 || k <= 0 || !anchors || !top_idx || !top_score || !decoded || !dets || !dir_label || !dtype_ok(dtype) ||
         (dir && num_dir_bins <= 0))
         return SEC_E_INVALID;
+    if (!box_ndim_ok(box_ndim)) return SEC_E_UNSUPPORTED;
     return predict_decode_launch((const void *)nullptr, vb, dir ? dir[0] : nullptr, vd, PredGeom{batch, 1, 1, (int)n, 1},
-                                 {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream});
+                                 {num_dir_bins, k, anchors, top_idx, top_score, rotate, decoded, dets, dir_label, dtype, (hipStream_t)stream, box_ndim});
+}
+SEC_API int sec_predict_decode_segments(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+                                        const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
+                                        const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                        float *dets, int *dir_label, int dtype, void *stream) {
+    return predict_decode_segments_impl(num_segments, box, h_box_strides5, dir, h_dir_strides5, h_dims3, num_dir_bins, batch, k, anchors, top_idx,
+                                        top_score, rotate, decoded, dets, dir_label, dtype, 7, stream);
+}
+SEC_API int sec_predict_decode_segments_nd(int num_segments, const void *const *box, const int64_t *h_box_strides5, const void *const *dir,
+                                           const int64_t *h_dir_strides5, const int *h_dims3, int num_dir_bins, int batch, int k,
+                                           const float *anchors, const int *top_idx, const float *top_score, int rotate, float *decoded,
+                                           float *dets, int *dir_label, int dtype, int box_ndim, void *stream) {
+    return predict_decode_segments_impl(num_segments, box, h_box_strides5, dir, h_dir_strides5, h_dims3, num_dir_bins, batch, k, anchors, top_idx,
+                                        top_score, rotate, decoded, dets, dir_label, dtype, box_ndim, stream);
 }
 
 // ---- multi-class NMS: (frame, class) items -----------------------------------------------------------------------------------

@@ -86,13 +86,16 @@ template <> struct Sim<SEC_SIM_DISTANCE> {
 // other classes are skipped, and a frame without a box of the class labels the whole range background (len(gt_boxes) == 0).
 struct AssignRange { int a_begin, a_end, filter; };
 
-template <int SIM>
-__global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__ anchors, int n_anchor,
-                                                      const float *__restrict__ gt, const int *__restrict__ gt_classes,
-                                                      const int *__restrict__ gt_offsets, AssignRange R,
-                                                      float *__restrict__ a_max, int *__restrict__ a_arg,
-                                                      int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask,
-                                                      SimParams P) {
+// WIDE (both passes): anchors, gt and targets are rows of nd = 7 + custom_ndim values (GroundBox3dCoder with custom_ndim > 0,
+// box_np_ops.py:47-81) instead of 7.  The matching reads columns 0-6 either way.
+template <int SIM, bool WIDE>
+__device__ __forceinline__ void assign_max_body(const float *__restrict__ anchors, int n_anchor,
+                                                const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                const int *__restrict__ gt_offsets, const AssignRange &R,
+                                                float *__restrict__ a_max, int *__restrict__ a_arg,
+                                                int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask,
+                                                const SimParams &P, int nd_arg) {
+    const int nd = WIDE ? nd_arg : 7;
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ unsigned char s_on[kMaxGtLds];
     const int b = blockIdx.y, a = R.a_begin + blockIdx.x * kBlock + threadIdx.x;
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
     if (a < n_anchor && amask && !amask[(size_t)b * n_total + a]) n_anchor = 0;
     float4 abv = make_float4(0, 0, 0, 0);
     if (a < n_anchor) {
-        abv = Sim<SIM>::stage(anchors + (size_t)a * 7);
+        abv = Sim<SIM>::stage(anchors + (size_t)a * nd);
     }
     float best = -1.0f;
     int arg = -1;
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
         const int cn = min(kMaxGtLds, g1 - c0);
         __syncthreads();
         for (int i = threadIdx.x; i < cn; i += kBlock) {
-            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * 7);
+            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * nd);
             s_on[i] = (R.filter == 0 || (gt_classes ? gt_classes[c0 + i] : 1) == R.filter) ? 1 : 0;
         }
         __syncthreads();
@@ -136,6 +139,24 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
         a_arg[(size_t)b * n_total + a] = arg;
     }
 }
+template <int SIM>
+__global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__ anchors, int n_anchor,
+                                                      const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                      const int *__restrict__ gt_offsets, AssignRange R,
+                                                      float *__restrict__ a_max, int *__restrict__ a_arg,
+                                                      int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask,
+                                                      SimParams P) {
+    assign_max_body<SIM, false>(anchors, n_anchor, gt, gt_classes, gt_offsets, R, a_max, a_arg, gt_max_bits, amask, P, 7);
+}
+template <int SIM>
+__global__ __launch_bounds__(kBlock) void k_assign_max_nd(const float *__restrict__ anchors, int n_anchor,
+                                                         const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                         const int *__restrict__ gt_offsets, AssignRange R,
+                                                         float *__restrict__ a_max, int *__restrict__ a_arg,
+                                                         int *__restrict__ gt_max_bits, const unsigned char *__restrict__ amask,
+                                                         SimParams P, int nd) {
+    assign_max_body<SIM, true>(anchors, n_anchor, gt, gt_classes, gt_offsets, R, a_max, a_arg, gt_max_bits, amask, P, nd);
+}
 
 // pass 2: labels / box targets / importance of create_target_np (positive_fraction = None, no anchor pruning)
 //
@@ -143,16 +164,18 @@ __global__ __launch_bounds__(kBlock) void k_assign_max(const float *__restrict__
 // maximum (negative when every anchor of the range lies inside the box's window), every anchor that ties with it is forced
 // positive, and the reference's -1 fill for a maximum of exactly 0 also matches a genuine similarity of exactly -1
 // (dist_norm = 2, dx = 2, dy = 0).  A box of another class gets NaN, which no similarity equals.
-template <int SIM>
-__global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict__ anchors, int n_anchor,
-                                                        const float *__restrict__ gt, const int *__restrict__ gt_classes,
-                                                        const float *__restrict__ gt_importance,
-                                                        const int *__restrict__ gt_offsets, AssignRange R,
-                                                        const float *__restrict__ a_max,
-                                                        const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
-                                                        float matched, float unmatched, int *__restrict__ labels,
-                                                        float *__restrict__ targets, float *__restrict__ importance,
-                                                        const unsigned char *__restrict__ amask, SimParams P) {
+// WIDE: target column 7 + j = gt - anchor for positives, 0 otherwise
+template <int SIM, bool WIDE>
+__device__ __forceinline__ void assign_write_body(const float *__restrict__ anchors, int n_anchor,
+                                                  const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                  const float *__restrict__ gt_importance,
+                                                  const int *__restrict__ gt_offsets, const AssignRange &R,
+                                                  const float *__restrict__ a_max,
+                                                  const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
+                                                  float matched, float unmatched, int *__restrict__ labels,
+                                                  float *__restrict__ targets, float *__restrict__ importance,
+                                                  const unsigned char *__restrict__ amask, const SimParams &P, int nd_arg) {
+    const int nd = WIDE ? nd_arg : 7;
     __shared__ float4 s_gt[kMaxGtLds];
     __shared__ float s_gmax[kMaxGtLds];
     __shared__ int s_any;
@@ -162,14 +185,14 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     n_anchor = min(n_anchor, R.a_end);
     if (threadIdx.x == 0) s_any = 0;
     float4 abv = make_float4(0, 0, 0, 0);
-    const float *p = anchors + (size_t)(a < n_anchor ? a : 0) * 7;
+    const float *p = anchors + (size_t)(a < n_anchor ? a : 0) * nd;
     if (a < n_anchor) abv = Sim<SIM>::stage(p);
     bool force = false;                       // "anchors_with_max_overlap": ties with some ground truth's best overlap
     for (int c0 = g0; c0 < g1; c0 += kMaxGtLds) {
         const int cn = min(kMaxGtLds, g1 - c0);
         __syncthreads();
         for (int i = threadIdx.x; i < cn; i += kBlock) {
-            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * 7);
+            s_gt[i] = Sim<SIM>::stage(gt + (size_t)(c0 + i) * nd);
             const bool on = R.filter == 0 || (gt_classes ? gt_classes[c0 + i] : 1) == R.filter;
             if (SIM == SEC_SIM_NEAREST_IOU) {
                 const float m = __int_as_float(gt_max_bits[c0 + i]);
@@ -193,6 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     int label = -1;
     float imp = 1.0f;
     float t[7] = {0, 0, 0, 0, 0, 0, 0};
+    const float *q_pos = nullptr;             // WIDE: the matched ground truth of a positive
     if (amask && !amask[o]) {                 // unmap() fills of a pruned anchor (target_ops.py:208-215): -1 / 0 / 0
         imp = 0.0f;
     } else if (s_any) {
@@ -212,7 +236,8 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
             imp = gt_importance[g0 + local];
         }
         if (label > 0) {   // second_box_encode(gt[arg], anchor)
-            const float *q = gt + (size_t)(g0 + arg) * 7;
+            const float *q = gt + (size_t)(g0 + arg) * nd;
+            q_pos = q;
             const float diag = sqrtf(__fadd_rn(__fmul_rn(p[4], p[4]), __fmul_rn(p[3], p[3])));
             t[0] = __fdiv_rn(__fsub_rn(q[0], p[0]), diag);
             t[1] = __fdiv_rn(__fsub_rn(q[1], p[1]), diag);
@@ -228,7 +253,35 @@ __global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict
     labels[o] = label;
     importance[o] = imp;
 #pragma unroll
-    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
+    for (int j = 0; j < 7; ++j) targets[o * nd + j] = t[j];
+    if constexpr (WIDE)
+        for (int j = 7; j < nd; ++j) targets[o * nd + j] = q_pos ? __fsub_rn(q_pos[j], p[j]) : 0.0f;
+}
+template <int SIM>
+__global__ __launch_bounds__(kBlock) void k_assign_write(const float *__restrict__ anchors, int n_anchor,
+                                                        const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                        const float *__restrict__ gt_importance,
+                                                        const int *__restrict__ gt_offsets, AssignRange R,
+                                                        const float *__restrict__ a_max,
+                                                        const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
+                                                        float matched, float unmatched, int *__restrict__ labels,
+                                                        float *__restrict__ targets, float *__restrict__ importance,
+                                                        const unsigned char *__restrict__ amask, SimParams P) {
+    assign_write_body<SIM, false>(anchors, n_anchor, gt, gt_classes, gt_importance, gt_offsets, R, a_max, a_arg, gt_max_bits, matched, unmatched,
+                                  labels, targets, importance, amask, P, 7);
+}
+template <int SIM>
+__global__ __launch_bounds__(kBlock) void k_assign_write_nd(const float *__restrict__ anchors, int n_anchor,
+                                                           const float *__restrict__ gt, const int *__restrict__ gt_classes,
+                                                           const float *__restrict__ gt_importance,
+                                                           const int *__restrict__ gt_offsets, AssignRange R,
+                                                           const float *__restrict__ a_max,
+                                                           const int *__restrict__ a_arg, const int *__restrict__ gt_max_bits,
+                                                           float matched, float unmatched, int *__restrict__ labels,
+                                                           float *__restrict__ targets, float *__restrict__ importance,
+                                                           const unsigned char *__restrict__ amask, SimParams P, int nd) {
+    assign_write_body<SIM, true>(anchors, n_anchor, gt, gt_classes, gt_importance, gt_offsets, R, a_max, a_arg, gt_max_bits, matched, unmatched,
+                                 labels, targets, importance, amask, P, nd);
 }
 
 // RegionSimilarityCalculator.compare: out[n, k] = similarity of anchor n with ground truth k; consecutive lanes walk k (the row)
@@ -247,6 +300,7 @@ struct LossParams {
     float alpha, gamma, sigma, pos_w, neg_w, cls_w, loc_w, dir_w, dir_offset, sin_factor;
     float code_w[7];
 };
+struct CodeWeightsNd { float w[SEC_BOX_MAX_NDIM]; };   // sec_second_loss_nd_f32: one weight per box value (code_w above is not read)
 
 constexpr int kCountChunks = 64;        // workgroups per frame of the positive count (deterministic: fixed chunks, fixed order)
 __global__ __launch_bounds__(kBlock) void k_loss_count(const int *__restrict__ labels, int n_anchor, float *__restrict__ part,
@@ -277,12 +331,17 @@ __global__ __launch_bounds__(kBlock) void k_loss_count(const int *__restrict__ l
 // per (frame, anchor): the three loss terms and their gradients; per-block partial sums [nblocks][6] =
 // (cls, loc, dir, cls_pos, cls_neg, -).  cls_preds [B, N, num_class] etc. contiguous; gradients of the TOTAL loss
 // loc_w * loc / B + cls_w * cls / B + dir_w * dir / B.
-__global__ __launch_bounds__(kBlock) void k_loss_main(const float *__restrict__ cls, const float *__restrict__ box,
-                                                     const float *__restrict__ dirp, const int *__restrict__ labels,
-                                                     const float *__restrict__ reg, const float *__restrict__ anchors,
-                                                     const float *__restrict__ importance, const float *__restrict__ cnt,
-                                                     LossParams P, float *__restrict__ d_cls, float *__restrict__ d_box,
-                                                     float *__restrict__ d_dir, float *__restrict__ partial) {
+// WIDE: box, reg, anchors and d_box are rows of nd = 7 + custom_ndim values with the weights W; the sin-difference stays on column 6
+// and the direction target on reg[6] + anchors[6], columns 7.. get the plain weighted smooth L1 (add_sin_difference passes them
+// through, voxelnet.py:704-714)
+template <bool WIDE>
+__device__ __forceinline__ void loss_main_body(const float *__restrict__ cls, const float *__restrict__ box,
+                                               const float *__restrict__ dirp, const int *__restrict__ labels,
+                                               const float *__restrict__ reg, const float *__restrict__ anchors,
+                                               const float *__restrict__ importance, const float *__restrict__ cnt,
+                                               const LossParams &P, float *__restrict__ d_cls, float *__restrict__ d_box,
+                                               float *__restrict__ d_dir, float *__restrict__ partial, const CodeWeightsNd &W, int nd_arg) {
+    const int nd = WIDE ? nd_arg : 7;
     const int b = blockIdx.y, a = blockIdx.x * kBlock + threadIdx.x;
     float s_cls = 0, s_loc = 0, s_dir = 0, s_pos = 0, s_neg = 0;
     __shared__ float s_norm[2];
@@ -323,27 +382,29 @@ __global__ __launch_bounds__(kBlock) void k_loss_main(const float *__restrict__ 
         // ---- localisation (smooth L1 on the sin-difference encoding), positives only
         const float wreg = (pos ? 1.0f : 0.0f) / norm * imp;
         const float s2 = P.sigma * P.sigma;
-        const float pr = box[o * 7 + 6] * P.sin_factor, tr = reg[o * 7 + 6] * P.sin_factor;
+        const float pr = box[o * nd + 6] * P.sin_factor, tr = reg[o * nd + 6] * P.sin_factor;
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            float pv = box[o * 7 + j], tv = reg[o * 7 + j], dscale = 1.0f;
+        for (int j = 0; j < (WIDE ? SEC_BOX_MAX_NDIM : 7); ++j) {
+            if (WIDE && j >= nd) break;
+            const float cw = WIDE ? W.w[j] : P.code_w[j];
+            float pv = box[o * nd + j], tv = reg[o * nd + j], dscale = 1.0f;
             if (j == 6) {
                 pv = sinf(pr) * cosf(tr);
                 tv = cosf(pr) * sinf(tr);
                 dscale = (cosf(pr) * cosf(tr) + sinf(pr) * sinf(tr)) * P.sin_factor;     // both encodings depend on the prediction
             }
-            const float diff = P.code_w[j] * (pv - tv);
+            const float diff = cw * (pv - tv);
             const float ad = fabsf(diff);
             const bool small = ad <= 1.0f / s2;
             const float l = small ? 0.5f * (ad * P.sigma) * (ad * P.sigma) : ad - 0.5f / s2;
             s_loc += l * wreg;
             const float dl = small ? s2 * diff : (diff > 0.0f ? 1.0f : (diff < 0.0f ? -1.0f : 0.0f));
-            d_box[o * 7 + j] = dl * P.code_w[j] * dscale * wreg * P.loc_w * inv_b;
+            d_box[o * nd + j] = dl * cw * dscale * wreg * P.loc_w * inv_b;
         }
         // ---- direction classifier (softmax cross-entropy on the heading bin of the ground truth)
         if (P.num_bins > 0) {
             const float kTwoPi = 6.28318548202514648f;
-            const float rot_gt = reg[o * 7 + 6] + anchors[(size_t)a * 7 + 6];
+            const float rot_gt = reg[o * nd + 6] + anchors[(size_t)a * nd + 6];
             const float off = limit_period_f(rot_gt - P.dir_offset, 0.0f, kTwoPi);
             int bin = (int)floorf(off / (kTwoPi / (float)P.num_bins));
             bin = bin < 0 ? 0 : (bin > P.num_bins - 1 ? P.num_bins - 1 : bin);
@@ -375,6 +436,22 @@ __global__ __launch_bounds__(kBlock) void k_loss_main(const float *__restrict__ 
         for (int w = 0; w < kBlock / 64; ++w) acc += red[threadIdx.x][w];
         partial[((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = acc;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_loss_main(const float *__restrict__ cls, const float *__restrict__ box,
+                                                     const float *__restrict__ dirp, const int *__restrict__ labels,
+                                                     const float *__restrict__ reg, const float *__restrict__ anchors,
+                                                     const float *__restrict__ importance, const float *__restrict__ cnt,
+                                                     LossParams P, float *__restrict__ d_cls, float *__restrict__ d_box,
+                                                     float *__restrict__ d_dir, float *__restrict__ partial) {
+    loss_main_body<false>(cls, box, dirp, labels, reg, anchors, importance, cnt, P, d_cls, d_box, d_dir, partial, CodeWeightsNd{}, 7);
+}
+__global__ __launch_bounds__(kBlock) void k_loss_main_nd(const float *__restrict__ cls, const float *__restrict__ box,
+                                                        const float *__restrict__ dirp, const int *__restrict__ labels,
+                                                        const float *__restrict__ reg, const float *__restrict__ anchors,
+                                                        const float *__restrict__ importance, const float *__restrict__ cnt,
+                                                        LossParams P, float *__restrict__ d_cls, float *__restrict__ d_box,
+                                                        float *__restrict__ d_dir, float *__restrict__ partial, CodeWeightsNd W, int nd) {
+    loss_main_body<true>(cls, box, dirp, labels, reg, anchors, importance, cnt, P, d_cls, d_box, d_dir, partial, W, nd);
 }
 
 // out[0..5] = loss, cls_loss_reduced, loc_loss_reduced, dir_loss_reduced, cls_pos_loss, cls_neg_loss (fixed summation order)
@@ -756,10 +833,11 @@ static int assign_targets_ranges(const float *anchors, int n_anchor, const float
                                  const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
                                  const float *h_unmatched, int *labels, float *bbox_targets, float *importance, void *workspace,
                                  size_t workspace_bytes, void *stream, const unsigned char *anchors_mask,
-                                 const int *h_sim_kind = nullptr, const double *h_sim_params = nullptr) {
+                                 const int *h_sim_kind = nullptr, const double *h_sim_params = nullptr, int box_ndim = 7) {
     if (n_anchor <= 0 || batch <= 0 || n_gt < 0 || n_class <= 0 || !anchors || !gt_offsets || !labels || !bbox_targets ||
         !importance || !h_class_anchor_begin || !h_class_ids || !h_matched || !h_unmatched || (n_gt > 0 && (!gt_boxes || !gt_classes)))
         return SEC_E_INVALID;
+    if (box_ndim < 7 || box_ndim > SEC_BOX_MAX_NDIM) return SEC_E_UNSUPPORTED;
     if (h_class_anchor_begin[0] != 0 || h_class_anchor_begin[n_class] != n_anchor) return SEC_E_INVALID;
     for (int c = 0; c < n_class; ++c)
         if (h_class_anchor_begin[c + 1] < h_class_anchor_begin[c] || h_class_ids[c] < 0) return SEC_E_INVALID;
@@ -807,7 +885,15 @@ static int assign_targets_ranges(const float *anchors, int n_anchor, const float
             dim3 grid(div_up(R.a_end - R.a_begin, kBlock), batch);
             SimParams P;
             const bool dist = sim_of(c, P) == SEC_SIM_DISTANCE;
-            if (pass == 0)
+            if (box_ndim != 7) {                 // rows of 7 + custom_ndim values (sec_assign_targets_nd_f32)
+                if (pass == 0)
+                    hipLaunchKernelGGL(dist ? k_assign_max_nd<SEC_SIM_DISTANCE> : k_assign_max_nd<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock), 0,
+                                       st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, R, a_max, a_arg, gt_max, anchors_mask, P, box_ndim);
+                else
+                    hipLaunchKernelGGL(dist ? k_assign_write_nd<SEC_SIM_DISTANCE> : k_assign_write_nd<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock),
+                                       0, st, anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, R, a_max, a_arg, gt_max,
+                                       h_matched[c], h_unmatched[c], labels, bbox_targets, importance, anchors_mask, P, box_ndim);
+            } else if (pass == 0)
                 hipLaunchKernelGGL(dist ? k_assign_max<SEC_SIM_DISTANCE> : k_assign_max<SEC_SIM_NEAREST_IOU>, grid, dim3(kBlock), 0,
                                    st, anchors, n_anchor, gt_boxes, gt_classes, gt_offsets, R, a_max, a_arg, gt_max, anchors_mask, P);
             else
@@ -857,6 +943,19 @@ SEC_API int sec_assign_targets_sim_f32(const float *anchors, int n_anchor, const
                                  workspace_bytes, stream, anchors_mask, h_sim_kind, h_sim_params);
 }
 
+// sec_assign_targets_sim_f32 on rows of box_ndim = 7 + custom_ndim values (anchors, gt_boxes, bbox_targets)
+SEC_API int sec_assign_targets_nd_f32(const float *anchors, int n_anchor, const float *gt_boxes, const int *gt_classes,
+                                      const float *gt_importance, const int *gt_offsets, int n_gt, int batch, int n_class,
+                                      const int *h_class_anchor_begin, const int *h_class_ids, const float *h_matched,
+                                      const float *h_unmatched, const int *h_sim_kind, const double *h_sim_params, int *labels,
+                                      float *bbox_targets, float *importance, void *workspace, size_t workspace_bytes,
+                                      const unsigned char *anchors_mask, int box_ndim, void *stream) {
+    if (!h_sim_kind || !h_sim_params) return SEC_E_INVALID;
+    return assign_targets_ranges(anchors, n_anchor, gt_boxes, gt_classes, gt_importance, gt_offsets, n_gt, batch, n_class,
+                                 h_class_anchor_begin, h_class_ids, h_matched, h_unmatched, labels, bbox_targets, importance, workspace,
+                                 workspace_bytes, stream, anchors_mask, h_sim_kind, h_sim_params, box_ndim);
+}
+
 SEC_API int sec_region_similarity_f32(const float *anchors, int n, const float *gt_boxes, int k, int kind, double dist_norm,
                                       int with_rotation, double rot_alpha, float *out, void *stream) {
     if (n < 0 || k < 0 || (kind != SEC_SIM_NEAREST_IOU && kind != SEC_SIM_DISTANCE)) return SEC_E_INVALID;
@@ -877,13 +976,15 @@ SEC_API size_t sec_second_loss_workspace_bytes(int batch, int n_anchor) {
     return align_up((size_t)2 * batch * kCountChunks * sizeof(float)) + align_up((size_t)batch * div_up(n_anchor, kBlock) * 6 * sizeof(float)) + 256;
 }
 
-SEC_API int sec_second_loss_f32(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
-                                const float *reg_targets, const float *anchors, const float *importance, int batch,
-                                int n_anchor, int num_class, int num_dir_bins, const float *h_params17, float *d_cls, float *d_box,
-                                float *d_dir, float *out6, void *workspace, size_t workspace_bytes, void *stream) {
+// h_params17 of sec_second_loss_f32; box_ndim != 7 (sec_second_loss_nd_f32): the ten scalars followed by box_ndim code weights
+static int second_loss_impl(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
+                            const float *reg_targets, const float *anchors, const float *importance, int batch,
+                            int n_anchor, int num_class, int num_dir_bins, const float *h_params17, float *d_cls, float *d_box,
+                            float *d_dir, float *out6, void *workspace, size_t workspace_bytes, int box_ndim, void *stream) {
     if (batch <= 0 || n_anchor <= 0 || num_class <= 0 || num_dir_bins < 0 || !cls_preds || !box_preds || !labels || !reg_targets ||
         !anchors || !importance || !h_params17 || !d_cls || !d_box || !out6 || (num_dir_bins > 0 && (!dir_preds || !d_dir)))
         return SEC_E_INVALID;
+    if (box_ndim < 7 || box_ndim > SEC_BOX_MAX_NDIM) return SEC_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < sec_second_loss_workspace_bytes(batch, n_anchor)) return SEC_E_WORKSPACE;
     LossParams P;
     P.batch = batch; P.n_anchor = n_anchor; P.num_class = num_class; P.num_bins = num_dir_bins;
@@ -899,10 +1000,31 @@ SEC_API int sec_second_loss_f32(const float *cls_preds, const float *box_preds, 
     float *partial = ar.take<float>((size_t)batch * nb * 6);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_loss_count, dim3(kCountChunks, batch), dim3(kBlock), 0, st, labels, n_anchor, cnt, importance);
-    hipLaunchKernelGGL(k_loss_main, dim3(nb, batch), dim3(kBlock), 0, st, cls_preds, box_preds, dir_preds, labels, reg_targets,
-                       anchors, importance, cnt, P, d_cls, d_box, d_dir, partial);
+    if (box_ndim == 7) {
+        hipLaunchKernelGGL(k_loss_main, dim3(nb, batch), dim3(kBlock), 0, st, cls_preds, box_preds, dir_preds, labels, reg_targets,
+                           anchors, importance, cnt, P, d_cls, d_box, d_dir, partial);
+    } else {
+        CodeWeightsNd W{};
+        for (int j = 0; j < box_ndim; ++j) W.w[j] = h_params17[10 + j];
+        hipLaunchKernelGGL(k_loss_main_nd, dim3(nb, batch), dim3(kBlock), 0, st, cls_preds, box_preds, dir_preds, labels, reg_targets,
+                           anchors, importance, cnt, P, d_cls, d_box, d_dir, partial, W, box_ndim);
+    }
     hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(kBlock), 0, st, partial, batch * nb, P, out6);
     return check_launch();
+}
+SEC_API int sec_second_loss_f32(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
+                                const float *reg_targets, const float *anchors, const float *importance, int batch,
+                                int n_anchor, int num_class, int num_dir_bins, const float *h_params17, float *d_cls, float *d_box,
+                                float *d_dir, float *out6, void *workspace, size_t workspace_bytes, void *stream) {
+    return second_loss_impl(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, importance, batch, n_anchor, num_class, num_dir_bins,
+                            h_params17, d_cls, d_box, d_dir, out6, workspace, workspace_bytes, 7, stream);
+}
+SEC_API int sec_second_loss_nd_f32(const float *cls_preds, const float *box_preds, const float *dir_preds, const int *labels,
+                                   const float *reg_targets, const float *anchors, const float *importance, int batch,
+                                   int n_anchor, int num_class, int num_dir_bins, const float *h_params, int box_ndim, float *d_cls,
+                                   float *d_box, float *d_dir, float *out6, void *workspace, size_t workspace_bytes, void *stream) {
+    return second_loss_impl(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, importance, batch, n_anchor, num_class, num_dir_bins,
+                            h_params, d_cls, d_box, d_dir, out6, workspace, workspace_bytes, box_ndim, stream);
 }
 
 // ---- the loss on the stacked heads (k_heads_loss): forward values, backward dY + bias gradient

@@ -166,13 +166,20 @@ class DeviceAugmenter:
     # ------------------------------------------------------------------------------------------------ the call
     def __call__(self, points, point_offsets, gt_boxes, gt_offsets, gt_classes=None, gt_mask=None, gt_importance=None, inplace=False,
                  out_point_capacity=None):
-        """points [N, 4 or 5] fp32 and gt_boxes [G, 7] fp32, frames concatenated with [B+1] int32 offsets; ``gt_mask`` [G] bool: the
+        """points [N, 4 or 5] fp32 and gt_boxes [G, 7] fp32 -- or [G, 9], columns 7 and 8 a velocity (NuScenesDatasetVelo) that the
+        flips, the rotation and the scaling transform (ops.augment_boxes); the stages that only read boxes take a contiguous copy of
+        columns 0-6 -- frames concatenated with [B+1] int32 offsets; ``gt_mask`` [G] bool: the
         reference's gt_boxes_mask (boxes of other classes: they block per-object moves, never move, and are dropped).
         -> (points, point_offsets, gt_boxes, gt_offsets, gt_classes[, gt_importance]): the arguments of DeviceTrainer.step.  The
         points are a copy unless ``inplace``; their count and offsets do not change.  The box tensors keep G rows: survivors first,
         in order, frame boundaries in the new gt_offsets, zero rows behind.  With a sampler the database sampling runs first: the
         boxes then have G + B*C*K rows, the points ``out_point_capacity`` rows (default: enough for every draw) with new offsets,
         and ``num_boxes`` of :meth:`draw` is that larger row count (``sampler.box_rows(G, B)``)."""
+        if gt_boxes.dim() != 2 or gt_boxes.shape[1] not in (7, 9):
+            raise ValueError(f"DeviceAugmenter: gt_boxes {tuple(gt_boxes.shape)}; rows of 7 values, or of 9 with a velocity in columns 7 and 8")
+        if self.sampler is not None and gt_boxes.shape[1] != 7:
+            raise ValueError("DeviceAugmenter: database sampling with 9-column gt_boxes (velocities) is not supported: the database "
+                             "holds 7-column boxes (the reference's concatenation fails on them too)")
         rt.require_gpu(points, point_offsets, gt_boxes, gt_offsets, gt_classes, gt_mask, gt_importance)
         if self.sampler is not None:
             want_importance = gt_importance is not None
@@ -187,13 +194,14 @@ class DeviceAugmenter:
         if not inplace:
             points = points.clone()
         first = loc_t = rot_t = None
+        boxes7 = gt_boxes if gt_boxes.shape[1] == 7 else gt_boxes[:, :7].contiguous()     # what the box-reading stages take
         if not self.per_object_skipped and g > 0:
             if self.loc_noises is None or self.loc_noises.shape[0] != g or tuple(self.rot_noises.shape) != tuple(self.loc_noises.shape[:2]):
                 raise ValueError(f"no per-object noise for {g} boxes: call draw(num_boxes={g}, batch_size={b}) or set_noise first")
-            first = ops.points_in_boxes(points, point_offsets, gt_boxes, gt_offsets, valid=gt_mask)
-            _, loc_t, rot_t = ops.noise_per_box(gt_boxes, gt_offsets, gt_mask, self.loc_noises, self.rot_noises,
+            first = ops.points_in_boxes(points, point_offsets, boxes7, gt_offsets, valid=gt_mask)
+            _, loc_t, rot_t = ops.noise_per_box(boxes7, gt_offsets, gt_mask, self.loc_noises, self.rot_noises,
                                                 max_boxes_per_frame=self.max_boxes_per_frame)
-        ops.augment_points_(points, point_offsets, self.frame_params, first, gt_boxes, gt_mask, loc_t, rot_t)
+        ops.augment_points_(points, point_offsets, self.frame_params, first, boxes7, gt_mask, loc_t, rot_t)
         boxes, offsets, classes, importance = ops.augment_boxes(gt_boxes, gt_offsets, self.frame_params, self.bev_range, valid=gt_mask,
                                                                 classes=gt_classes, importance=gt_importance, loc_transform=loc_t,
                                                                 rot_transform=rot_t)

@@ -17,7 +17,7 @@ strided layer, three modules per layer, the dense [B, 128, 200, 176] image and p
   * one call = copy the example into static-capacity buffers, ONE hipGraph replay (SimpleVoxel mean | SimpleVoxelRadius | PillarFeatureNet ->
     fused rulebook chain -> 14 sparse convs -> RPN on live tiles -> select / decode / NMS / finalize), ONE device -> host copy of
     the padded detections, and the reference's return value (voxelnet.py:616-643: a list of
-    ``{box3d_lidar [k, 7] float32, scores [k] float32, label_preds [k] int64, metadata}`` on the input's device);
+    ``{box3d_lidar [k, 7 + custom_ndim] float32, scores [k] float32, label_preds [k] int64, metadata}`` on the input's device);
   * precision follows the caller: ``net.half()`` (train.py:470) runs the fp16 pipeline, ``dtype=torch.bfloat16`` may be forced; fp32
     networks run the fp32-storage pipeline whose products are, by default, three bf16 MFMA passes on split operands ("bf16x3": 16
     significant bits per operand, fp32 accumulation -- inside the 1e-4 of the parity rule, NOT the reference's fp32 arithmetic);
@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .models import PILLAR_VFES, VFES, SecondDetector
+from .models import PILLAR_VFES, VFES, SecondDetector, box_ndim_of
 
 
 class NotAccelerable(NotImplementedError):
@@ -99,6 +99,28 @@ def _env_multiclass_nms():
     return os.environ.get("SEC_ACCELERATE_MULTICLASS_NMS", "0") == "1"
 
 
+def _custom_values(net, coder, why):
+    """The anchor generators' custom_values of a network whose box coder is the ground coder with ``custom_ndim`` extra values
+    (box_coders.py:31-46; code_size = 7 + custom_ndim), one list per generator; [] for the plain 7-value coder.  Any other coder is
+    named in ``why``."""
+    custom_ndim = int(getattr(coder, "custom_ndim", 0) or 0)
+    if (type(coder).__name__ == "BevBoxCoder" or getattr(coder, "vec_encode", False) or getattr(coder, "linear_dim", False)
+            or int(coder.code_size) != 7 + custom_ndim):
+        why.append("box coder other than the ground coder of 7 + custom_ndim values (vec_encode, linear_dim and the BEV coder are not served)")
+        return []
+    if custom_ndim == 0:
+        return []
+    if custom_ndim > ops.BOX_MAX_NDIM - 7:
+        why.append(f"box coder with {custom_ndim} custom values (at most {ops.BOX_MAX_NDIM - 7})")
+        return []
+    gens = list(getattr(net.target_assigner, "_anchor_generators", []))
+    values = [[float(v) for v in getattr(g, "custom_values", getattr(g, "_custom_values", ()))] for g in gens]
+    if not values or any(len(v) != custom_ndim for v in values):
+        why.append(f"anchor generators whose custom_values do not match the box coder's custom_ndim {custom_ndim}")
+        return []
+    return values
+
+
 def model_config(net, multiclass_nms=False):
     """The ``SecondDetector`` configuration of a reference-built VoxelNet (attribute names of voxelnet.py:100-171, rpn.py:202-300,
     spconv.utils.VoxelGeneratorV2).  Raises :class:`NotAccelerable` for networks outside the fused path.
@@ -132,8 +154,9 @@ def model_config(net, multiclass_nms=False):
     if not getattr(net, "_use_sigmoid_score", True) or not getattr(net, "_encode_background_as_zeros", True):
         why.append("softmax scores / background class")
     coder = getattr(net, "_box_coder", None) or net.target_assigner.box_coder
-    if int(coder.code_size) != 7 or getattr(coder, "vec_encode", False) or getattr(coder, "linear_dim", False):
-        why.append("box coder other than the 7-value ground coder")
+    custom = _custom_values(net, coder, why)
+    if multiclass and multiclass_nms and custom:
+        why.append("multiclass_nms with custom box values")
     if why:
         raise NotAccelerable("accelerate_model: not reproducible by the fused pipeline: " + "; ".join(why))
     vg = net.voxel_generator
@@ -169,6 +192,8 @@ def model_config(net, multiclass_nms=False):
         use_rotate_nms=bool(net._use_rotate_nms),
         post_center_range=_seq(net._post_center_range) if len(net._post_center_range) else [-1e30] * 3 + [1e30] * 3,
     )
+    if custom:                                   # GroundBox3dCoder.custom_ndim > 0 (nuScenes velocity): box rows of 7 + custom_ndim values
+        cfg.update(anchor_custom_values=custom)
     if multiclass:
         nc = int(net._num_class)
         lists = {k: list(getattr(net, a)) for k, a in (("nms_score_thresholds", "_nms_score_thresholds"), ("nms_pre_max_sizes", "_nms_pre_max_sizes"),
@@ -236,8 +261,9 @@ class _Pending:
             cur = torch.cuda.current_stream()
             self.packed.record_stream(cur)                # produced on the lane's stream, consumed wherever the caller is
             p = sess.outs["post"]
-            valid = slot["host_packed"].numpy()[:, 9 * p:10 * p] > 0.5
-            res = eng._results(self.packed, valid, p, self.batch, self.meta)
+            nd = eng.box_ndim
+            valid = slot["host_packed"].numpy()[:, (nd + 2) * p:(nd + 3) * p] > 0.5
+            res = eng._results(self.packed, valid, p, self.batch, self.meta, nd)
             eng.stats["fused_calls"] += 1
         self.results = res
         slot["busy"] = None
@@ -394,6 +420,7 @@ class _Session:
         # (the anchors: compared by content, every call -- a freed-and-reallocated tensor can reuse an address and a version counter)
         flags = torch.cat([counters.reshape(-1), self.anchor_flag, stale])      # [overflow counters..., anchors differ, weights changed]
         self.anchor_flag.zero_()                                                # ready for the next call's compare
+        # packed [B, (box_ndim + 3) * post]: the boxes' rows, then scores, labels and validity
         return {"packed": packed, "counters": counters, "limits": [int(c) for _, c in checks], "post": int(out["scores"].shape[1]), "flags": flags}
 
     def build(self, graph):
@@ -438,6 +465,7 @@ class FusedVoxelNet:
     def __init__(self, net, dtype=None, graph=True, static=None, margin=1.25, row_bucket=16384, train_dtype=None, fp32_exact=False,
                  deferred=False, lanes=3, multiclass_nms=False):
         self.net, self.cfg = net, model_config(net, multiclass_nms=multiclass_nms)
+        self.box_ndim = box_ndim_of(self.cfg)        # values per anchor / box row: 7 + the coder's custom_ndim
         # deferred: eval-mode calls return at once with self-filling dicts (DeferredDetection); consecutive calls alternate between
         # `lanes` sessions on their own streams, so call k + 1's copies and graph overlap call k's tail (see _static_deferred)
         import os
@@ -570,7 +598,7 @@ class FusedVoxelNet:
         if not isinstance(m, torch.Tensor) or m.dtype not in (torch.bool, torch.uint8) or not m.is_cuda or m.device != anc.device or anc.dim() < 2:
             return False
         batch = anc.shape[0]
-        n_anchor = anc.numel() // (batch * 7) if batch else 0
+        n_anchor = anc.numel() // (batch * self.box_ndim) if batch else 0
         return m.dim() >= 2 and m.shape[0] == batch and m.numel() == batch * n_anchor and self.cfg["nms_score_threshold"] > 0
 
     def _accepts_training(self, example):
@@ -619,7 +647,7 @@ class FusedVoxelNet:
         if bool(self.weights_changed_flag().item()):     # (this mode syncs per layer anyway)
             det = self.refresh(force=True)
         batch = example["anchors"].shape[0]
-        anchors = example["anchors"].reshape(batch, -1, 7).float()
+        anchors = example["anchors"].reshape(batch, -1, self.box_ndim).float()
         with torch.no_grad():
             voxels = example["voxels"]
             pitch = None
@@ -641,7 +669,7 @@ class FusedVoxelNet:
     def _session(self, det, example, batch, lane=0):
         voxels = example["voxels"]
         n = voxels.shape[0]
-        anchors0 = example["anchors"].reshape(batch, -1, 7)[0]
+        anchors0 = example["anchors"].reshape(batch, -1, self.box_ndim)[0]
         has_mask = "anchors_mask" in example
         key = (batch, tuple(voxels.shape[1:]), voxels.dtype, voxels.device, int(anchors0.shape[0]), lane, has_mask)
         sess = self._sessions.get(key)
@@ -695,7 +723,7 @@ class FusedVoxelNet:
 
     def _static(self, det, example):
         batch = example["anchors"].shape[0]
-        anchors = example["anchors"].reshape(batch, -1, 7)
+        anchors = example["anchors"].reshape(batch, -1, self.box_ndim)
         lane = -1 if self.deferred else 0           # beside asynchronous lanes the synchronous path owns a session of its own
         for attempt in range(4):
             sess = self._session(det, example, batch, lane)
@@ -732,8 +760,9 @@ class FusedVoxelNet:
         self.stats["fused_calls"] += 1
         p = sess.outs["post"]
         hp = sess.host_packed.numpy()
-        valid = hp[:, 9 * p:10 * p] > 0.5
-        return self._results(packed, valid, p, batch, self._meta(example, batch))
+        nd = self.box_ndim
+        valid = hp[:, (nd + 2) * p:(nd + 3) * p] > 0.5
+        return self._results(packed, valid, p, batch, self._meta(example, batch), nd)
 
     def _static_deferred(self, det, example):
         """The asynchronous form of :meth:`_static`: nothing waits.  Lane ``k % lanes`` (its own session: buffers, graph, stream) takes
@@ -742,7 +771,7 @@ class FusedVoxelNet:
         the synchronous path checks after its sync (overflow counters, anchor equality, weight content) is checked when the call is
         resolved; a call that fails a check is redone synchronously from the example it still holds."""
         batch = example["anchors"].shape[0]
-        anchors = example["anchors"].reshape(batch, -1, 7)
+        anchors = example["anchors"].reshape(batch, -1, self.box_ndim)
         lane = self._lane
         self._lane = (lane + 1) % self.lanes
         sess = self._session(det, example, batch, lane)          # (first call of a lane: calibrates and captures, synchronously)
@@ -773,10 +802,10 @@ class FusedVoxelNet:
         return [DeferredDetection(pend, b) for b in range(batch)]
 
     @staticmethod
-    def _results(packed, valid, p, batch, metas):
-        boxes = packed[:, :7 * p].view(batch, p, 7)
-        scores = packed[:, 7 * p:8 * p]
-        labels = packed[:, 8 * p:9 * p].long()          # (the packed copy carries them as floats: exact for class indices)
+    def _results(packed, valid, p, batch, metas, nd=7):
+        boxes = packed[:, :nd * p].view(batch, p, nd)
+        scores = packed[:, nd * p:(nd + 1) * p]
+        labels = packed[:, (nd + 1) * p:(nd + 2) * p].long()          # (the packed copy carries them as floats: exact for class indices)
         res = []
         for b, meta in zip(range(batch), metas):
             idx = np.flatnonzero(valid[b])

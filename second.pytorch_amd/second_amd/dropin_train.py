@@ -268,6 +268,9 @@ class FusedTrainStep:
         the parameters stay the reference's fp32 tensors."""
         if dtype not in (torch.bfloat16, torch.float16):
             raise NotTrainable("accelerate_model(training): 16-bit features only (train_dtype=torch.bfloat16 / torch.float16)")
+        if cfg.get("anchor_custom_values"):
+            raise NotTrainable("accelerate_model(training): custom box values (box coder with custom_ndim > 0) have no captured training "
+                               "step: the fused head loss serves the 7-value box code only (train through second_amd.training.DeviceTrainer)")
         if cfg.get("heads"):
             raise NotTrainable("accelerate_model(training): multi-head network (VoxelNetNuscenesMultiHead: RPNNoHead + small_head / large_head) "
                                "has no captured training step")

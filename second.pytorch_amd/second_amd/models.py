@@ -316,11 +316,40 @@ def grid_size_of(cfg):
     return np.round((r[3:] - r[:3]) / v).astype(np.int64)  # (x, y, z)
 
 
+def anchor_custom_values(cfg, num_groups=None):
+    """``cfg["anchor_custom_values"]`` -- the anchor generators' custom_values (second/core/anchor_generator.py:30-70; nuScenes:
+    ``[0, 0]``, the velocity's base value) -- as one float32 array per anchor group.  The key holds a list of floats (every group's) or
+    one such list per group, all of one length (the reference asserts equal ndim across generators, target_assigner.py:22-23); absent
+    or empty: no custom values, [] * groups.  More than ops.BOX_MAX_NDIM - 7 values are refused."""
+    v = cfg.get("anchor_custom_values")
+    nested = v is not None and len(v) > 0 and isinstance(v[0], (list, tuple, np.ndarray))
+    if num_groups is None:      # (a config adopted from a reference-built network has no anchor table: one list per generator it had)
+        num_groups = len(cfg.get("anchor_groups") or cfg.get("anchor_sizes") or (v if nested else [0]))
+    if v is None or len(v) == 0:
+        return [np.zeros((0,), np.float32)] * num_groups
+    per_group = [list(g) for g in v] if nested else [list(v)] * num_groups
+    if len(per_group) != num_groups:
+        raise ValueError(f"anchor_custom_values: {len(per_group)} lists for {num_groups} anchor groups")
+    if len({len(g) for g in per_group}) != 1:
+        raise ValueError(f"anchor_custom_values: every anchor group needs the same number of values, got {[len(g) for g in per_group]}")
+    if len(per_group[0]) > ops.BOX_MAX_NDIM - 7:
+        raise ValueError(f"anchor_custom_values: {len(per_group[0])} custom values; at most {ops.BOX_MAX_NDIM - 7} are supported "
+                         f"(box rows of up to {ops.BOX_MAX_NDIM} values)")
+    return [np.asarray(g, np.float64).astype(np.float32) for g in per_group]
+
+
+def box_ndim_of(cfg):
+    """Values per box row of a config: 7 + the number of custom values (GroundBox3dCoder.code_size, box_coders.py:31-46)."""
+    return 7 + len(anchor_custom_values(cfg)[0])
+
+
 def generate_anchors(cfg, feature_map_size):
-    """[A*D*H*W, 7] anchors ordered (anchor, z, y, x) like target_assigner.generate_anchors
-    (second/core/target_assigner.py:169-207 over box_np_ops.create_anchors_3d_range :606-638)."""
+    """[A*D*H*W, 7 + c] anchors ordered (anchor, z, y, x) like target_assigner.generate_anchors
+    (second/core/target_assigner.py:169-207 over box_np_ops.create_anchors_3d_range :606-638); the c values of
+    :func:`anchor_custom_values` are appended to every anchor of their group."""
     out = []
     groups = cfg.get("anchor_groups") or [[i] for i in range(len(cfg["anchor_sizes"]))]
+    custom = anchor_custom_values(cfg, len(groups))
     for gi, grp in enumerate(groups):   # one anchor generator: (size, rotation) major, then z, y, x
         d, h, w = group_feature_map_size(cfg, gi, feature_map_size)
         rots = np.array(cfg.get("group_rotations", {}).get(gi, cfg["rotations"]), np.float32)
@@ -335,14 +364,16 @@ def generate_anchors(cfg, feature_map_size):
             zc = np.linspace(rng[2], rng[5], d, dtype=np.float32)
             yc = np.linspace(rng[1], rng[4], h, dtype=np.float32)
             xc = np.linspace(rng[0], rng[3], w, dtype=np.float32)
-        a = np.zeros((len(grp), len(rots), d, h, w, 7), np.float32)
+        nd = 7 + len(custom[gi])
+        a = np.zeros((len(grp), len(rots), d, h, w, nd), np.float32)
+        a[..., 7:] = custom[gi]
         a[..., 0] = xc[None, None, None, None, :]
         a[..., 1] = yc[None, None, None, :, None]
         a[..., 2] = zc[None, None, :, None, None]
         for si, sz in enumerate(grp):
             a[si, ..., 3:6] = np.array(cfg["anchor_sizes"][sz], np.float32)
         a[..., 6] = rots[None, :, None, None, None]
-        out.append(a.reshape(-1, 7))
+        out.append(a.reshape(-1, nd))
     return np.concatenate(out, 0)
 
 
@@ -1696,6 +1727,8 @@ class SecondDetector(nn.Module):
     prediction dicts; ``forward_points`` is the device-resident fast path (raw clouds in, detections out,
     no host sync until the caller reads the result)."""
 
+    box_ndim = 7        # values per box row; __init__ sets 7 + the config's custom values
+
     def __init__(self, cfg=CAR_FHD):
         super().__init__()
         self.cfg = cfg
@@ -1721,18 +1754,23 @@ class SecondDetector(nn.Module):
         self.num_anchor_per_loc = a_per_loc
         fm = [1, int(gs[1]) // cfg["downsample_factor"], int(gs[0]) // cfg["downsample_factor"]]
         self.feature_map_size = fm
+        self.box_ndim = box_ndim_of(cfg)       # 7 + custom values (nuScenes velocity: 9): the heads' box_code_size, every box row's width
+        if self.box_ndim != 7 and cfg.get("multiclass_nms"):
+            raise ValueError(f"{cfg['name']}: multiclass_nms with anchor_custom_values is not supported (the multi-class NMS chain "
+                             f"serves box rows of 7 values)")
         self.heads = cfg.get("heads")          # multi-head networks (VoxelNetNuscenesMultiHead): [large_head on "out", small_head on "stage0"]
         if self.heads:
             self._check_heads(cfg, fm)
-            self.rpn = RPNNoHead(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"], **cfg["rpn"])
-            kw = dict(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"],
+            self.rpn = RPNNoHead(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"], box_code_size=self.box_ndim,
+                                 **cfg["rpn"])
+            kw = dict(num_class=cfg["num_class"], num_direction_bins=cfg["num_direction_bins"], box_code_size=self.box_ndim,
                       use_direction_classifier=cfg["rpn"].get("use_direction_classifier", True))
             # at top level, as the reference has them (net_multi_head.py:131-148)
             self.small_head = SmallObjectHead(cfg["rpn"]["num_filters"][0], num_anchor_per_loc=self.heads[1]["num_anchor_per_loc"], **kw)
             self.large_head = DefaultHead(sum(cfg["rpn"]["num_upsample_filters"]), num_anchor_per_loc=self.heads[0]["num_anchor_per_loc"], **kw)
         else:
             self.rpn = RPNV2(num_class=cfg["num_class"], num_anchor_per_loc=a_per_loc, num_direction_bins=cfg["num_direction_bins"],
-                             **cfg["rpn"])
+                             box_code_size=self.box_ndim, **cfg["rpn"])
         self.register_buffer("global_step", torch.LongTensor(1).zero_())
         if cfg.get("anchor_sizes"):
             self.register_buffer("anchors", torch.from_numpy(generate_anchors(cfg, fm)), persistent=False)
@@ -1875,7 +1913,7 @@ class SecondDetector(nn.Module):
                 feats = self.voxel_feature_extractor(voxels, num_points, coors)
         preds = self.network_forward(feats, coors, batch_size, in_pitch=pitch)
         with torch.no_grad():
-            return self.predict(preds, example["anchors"].view(batch_size, -1, 7), example.get("anchors_mask"))
+            return self.predict(preds, example["anchors"].view(batch_size, -1, self.box_ndim), example.get("anchors_mask"))
 
     def forward_points(self, points, point_offsets, static=False):
         """points [N,4] cuda float32 (clouds concatenated), point_offsets [B+1] cuda int32.
@@ -2103,7 +2141,8 @@ class SecondDetector(nn.Module):
         entry are dropped before the score threshold (voxelnet.py:429-439)."""
         cfg = self.cfg
         nc = cfg["num_class"]
-        box = preds["box_preds"].reshape(batch_size, -1, 7)
+        nd = self.box_ndim
+        box = preds["box_preds"].reshape(batch_size, -1, nd)
         if nc == 1:
             scores = torch.sigmoid(preds["cls_preds"].reshape(batch_size, -1).float())
             labels = None
@@ -2116,8 +2155,8 @@ class SecondDetector(nn.Module):
         masked = torch.where(passing, scores, torch.full_like(scores, -1.0))
         top_scores, top_idx = torch.topk(masked, k, dim=1)
         counts = (top_scores >= cfg["nms_score_threshold"]).sum(1).to(torch.int32)
-        enc = torch.gather(box, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7)).float()
-        anc = anchors[top_idx] if anchors.dim() == 2 else torch.gather(anchors, 1, top_idx.unsqueeze(-1).expand(-1, -1, 7))
+        enc = torch.gather(box, 1, top_idx.unsqueeze(-1).expand(-1, -1, nd)).float()
+        anc = anchors[top_idx] if anchors.dim() == 2 else torch.gather(anchors, 1, top_idx.unsqueeze(-1).expand(-1, -1, nd))
         dec = decode_boxes(enc, anc)
         if "dir_cls_preds" in preds:
             d = preds["dir_cls_preds"].reshape(batch_size, -1, cfg["num_direction_bins"])
@@ -2160,7 +2199,7 @@ class SecondDetector(nn.Module):
         return valid & (boxes[..., :3] >= r[:3]).all(-1) & (boxes[..., :3] <= r[3:]).all(-1)
 
     def predict_device(self, preds, batch_size, anchors=None, anchors_mask=None):
-        """-> dict of padded device tensors: boxes [B,P,7], scores [B,P], labels [B,P], valid [B,P] (bool).
+        """-> dict of padded device tensors: boxes [B,P,box_ndim], scores [B,P], labels [B,P], valid [B,P] (bool).
         ``anchors_mask`` [B, A] bool / uint8 (the example's, or :meth:`anchor_area_mask`): frame b keeps the anchors with a non-zero entry."""
         cfg = self.cfg
         anchors = self.anchors if anchors is None else anchors
@@ -2187,7 +2226,7 @@ class SecondDetector(nn.Module):
         p = min(cfg["nms_post_max_size"], keep.shape[1])
         valid = self._arange_p[:p].unsqueeze(0) < num_keep.unsqueeze(1)
         sel = torch.where(valid, keep[:, :p], torch.zeros_like(keep[:, :p])).long()   # slots past num_keep are undefined
-        boxes = torch.gather(dec, 1, sel.unsqueeze(-1).expand(-1, -1, 7))
+        boxes = torch.gather(dec, 1, sel.unsqueeze(-1).expand(-1, -1, dec.shape[-1]))
         scores = torch.gather(top_scores, 1, sel)
         valid = self._fix_direction_and_range(boxes, valid, None if dir_labels is None else torch.gather(dir_labels, 1, sel))
         return {"boxes": boxes, "scores": scores, "labels": torch.gather(top_labels, 1, sel), "valid": valid}
@@ -2246,7 +2285,7 @@ class SecondDetector(nn.Module):
                 return list(t)
             return t if t.dim() == 5 else t.reshape(batch_size, self.num_anchor_per_loc, h, w, code)
         cls = view5(preds["cls_preds"], cfg["num_class"])
-        box = view5(preds["box_preds"], 7)
+        box = view5(preds["box_preds"], self.box_ndim)
         dirp = view5(preds["dir_cls_preds"], cfg["num_direction_bins"]) if "dir_cls_preds" in preds else None
         if anchors is not None:
             anchors = (anchors[0] if anchors.dim() == 3 else anchors).float().contiguous()
@@ -2461,9 +2500,9 @@ class InFlightRunner:
 
 
 def decode_boxes(enc, anc):
-    """GroundBox3dCoder.decode (second_box_decode, second/pytorch/core/box_torch_ops.py:56-101)."""
-    xa, ya, za, wa, la, ha, ra = anc.unbind(-1)
-    xt, yt, zt, wt, lt, ht, rt = enc.unbind(-1)
+    """GroundBox3dCoder.decode (second_box_decode, second/pytorch/core/box_torch_ops.py:56-101); columns 7.. (custom values): t + a."""
+    xa, ya, za, wa, la, ha, ra = anc[..., :7].unbind(-1)
+    xt, yt, zt, wt, lt, ht, rt = enc[..., :7].unbind(-1)
     diag = torch.sqrt(la * la + wa * wa)
     return torch.stack([xt * diag + xa, yt * diag + ya, zt * ha + za, torch.exp(wt) * wa, torch.exp(lt) * la,
-                        torch.exp(ht) * ha, rt + ra], -1)
+                        torch.exp(ht) * ha, rt + ra, *(enc[..., 7:] + anc[..., 7:]).unbind(-1)], -1)

@@ -1851,15 +1851,26 @@ def _select_outputs(b, n, k, dev):
             torch.empty((b * n,), dtype=torch.int32, device=dev))
 
 
-def _decode_outputs(rows, dev):
-    """(decoded [*rows, 7], dets [*rows, 6], dir_label [*rows]) of a decode; rows = (B, k) or (B, C, k)."""
-    return (torch.empty((*rows, 7), dtype=torch.float32, device=dev), torch.empty((*rows, 6), dtype=torch.float32, device=dev),
+BOX_MAX_NDIM = 11                            # include/second_hip.h SEC_BOX_MAX_NDIM: widest box row of the *_nd entry points
+
+
+def _box_ndim(nd, what):
+    """The row width 7 + custom_ndim of ``what``, checked against the range the *_nd entry points serve."""
+    nd = int(nd)
+    if not 7 <= nd <= BOX_MAX_NDIM:
+        raise ValueError(f"{what}: box rows of {nd} values; supported are 7 to {BOX_MAX_NDIM} (7 + up to {BOX_MAX_NDIM - 7} custom values)")
+    return nd
+
+
+def _decode_outputs(rows, dev, nd=7):
+    """(decoded [*rows, nd], dets [*rows, 6], dir_label [*rows]) of a decode; rows = (B, k) or (B, C, k)."""
+    return (torch.empty((*rows, nd), dtype=torch.float32, device=dev), torch.empty((*rows, 6), dtype=torch.float32, device=dev),
             torch.empty(rows, dtype=torch.int32, device=dev))
 
 
-def _finalize_outputs(b, p, dev):
-    """(boxes [b, p, 7], scores, labels, valid as uint8) of a finalize."""
-    return (torch.empty((b, p, 7), dtype=torch.float32, device=dev), torch.empty((b, p), dtype=torch.float32, device=dev),
+def _finalize_outputs(b, p, dev, nd=7):
+    """(boxes [b, p, nd], scores, labels, valid as uint8) of a finalize."""
+    return (torch.empty((b, p, nd), dtype=torch.float32, device=dev), torch.empty((b, p), dtype=torch.float32, device=dev),
             torch.empty((b, p), dtype=torch.int32, device=dev), torch.empty((b, p), dtype=torch.uint8, device=dev))
 
 
@@ -1893,11 +1904,12 @@ def _predict_select_segments(views, k, score_thr):
 def _predict_decode_segments(box, dir_cls, anchors, top_idx, top_score, rotate):
     rt.require_gpu(*box, anchors, top_idx, top_score)
     b, dt = box[0].shape[0], box[0].dtype
-    assert all(v.dim() == 5 and v.shape[0] == b and v.shape[4] == 7 and v.dtype == dt for v in box)
+    nd = _box_ndim(box[0].shape[4], "predict_decode")
+    assert all(v.dim() == 5 and v.shape[0] == b and v.shape[4] == nd and v.dtype == dt for v in box)
     n = sum(v.shape[1] * v.shape[2] * v.shape[3] for v in box)
-    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and tuple(anchors.shape) == (n, 7)
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and tuple(anchors.shape) == (n, nd)
     k = top_idx.shape[1]
-    dec, dets, dlab = _decode_outputs((b, k), box[0].device)
+    dec, dets, dlab = _decode_outputs((b, k), box[0].device, nd)
     ptrs, strides, dims = _segment_args(box)
     dptrs = dstrides = None
     bins = 0
@@ -1906,10 +1918,11 @@ def _predict_decode_segments(box, dir_cls, anchors, top_idx, top_score, rotate):
         assert len(dir_cls) == len(box) and all(d.dtype == dt and tuple(d.shape[:4]) == tuple(v.shape[:4]) and d.shape[4] == bins
                                                 for d, v in zip(dir_cls, box))
         dptrs, dstrides, _ = _segment_args(dir_cls)
-    rc = rt.lib().sec_predict_decode_segments(len(box), ptrs, strides, dptrs, dstrides, dims, bins, b, k, rt.ptr(anchors), rt.ptr(top_idx),
-                                              rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
-                                              rt.dtype_code(dt), rt.stream())
-    rt.check(rc, "sec_predict_decode_segments")
+    entry, nd_tail = ("sec_predict_decode_segments", ()) if nd == 7 else ("sec_predict_decode_segments_nd", (nd,))
+    rc = getattr(rt.lib(), entry)(len(box), ptrs, strides, dptrs, dstrides, dims, bins, b, k, rt.ptr(anchors), rt.ptr(top_idx),
+                                  rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab),
+                                  rt.dtype_code(dt), *nd_tail, rt.stream())
+    rt.check(rc, entry)
     return dec, dets, dlab
 
 
@@ -1947,25 +1960,33 @@ def predict_select(cls, k, score_thr, lazy=None, anchor_mask=None):
 
 @_traced("predict_decode")
 def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=None):
-    """box: [B,A,H,W,7] view, dir_cls: [B,A,H,W,bins] view or None, anchors [A*H*W,7] fp32.
-    -> (decoded [B,k,7] fp32, dets [B,k,6] fp32 NMS rows, dir_label [B,k] int32).
+    """box: [B,A,H,W,nd] view, dir_cls: [B,A,H,W,bins] view or None, anchors [A*H*W,nd] fp32; nd = 7 + custom_ndim, taken from ``box``.
+    -> (decoded [B,k,nd] fp32, dets [B,k,6] fp32 NMS rows, dir_label [B,k] int32).
     ``lazy`` = (tile_live, (bg_box, bg_dir)): as in :func:`predict_select` (sec_predict_decode_lazy / sec_predict_decode_cover).
+    nd > 7: every form is one call of sec_predict_decode_nd, which takes the table of either lazy form (custom column 7 + j =
+    encoding + anchor).
     ``box`` (and ``dir_cls``) LISTS of views: as in :func:`predict_select`, ``anchors`` is the flat list over all of them."""
     if isinstance(box, (list, tuple)):
         assert lazy is None, "the multi-tensor decode has no lazy form"
         return _predict_decode_segments(list(box), None if dir_cls is None else list(dir_cls), anchors, top_idx, top_score, rotate)
     rt.require_gpu(box, anchors, top_idx, top_score)
     b, a, h, w, code = box.shape
-    assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
+    nd = _box_ndim(code, "predict_decode")
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, nd)
     k = top_idx.shape[1]
-    dec, dets, dlab = _decode_outputs((b, k), box.device)
+    dec, dets, dlab = _decode_outputs((b, k), box.device, nd)
     dir_ptr, dir_strides, bins = _dir_args(dir_cls, box)
     entry, lazy_tail = "sec_predict_decode", ()
+    table = bgb = bgd = None
     if lazy is not None:
         table, bgb = _lazy_args(box, lazy, lambda t: t[0])
         bgd = _lazy_args(dir_cls, lazy, lambda t: t[1])[1] if dir_cls is not None else None
         entry = "sec_predict_decode_cover" if _lazy_cover(lazy) else "sec_predict_decode_lazy"
         lazy_tail = (rt.ptr(table), rt.ptr(bgb), rt.ptr(bgd))
+    if nd != 7:
+        cover = _lazy_cover(lazy)
+        entry = "sec_predict_decode_nd"
+        lazy_tail = (nd, rt.ptr(None if cover else table), rt.ptr(table if cover else None), rt.ptr(bgb), rt.ptr(bgd))
     rc = getattr(rt.lib(), entry)(rt.ptr(box), _strides5(box), dir_ptr, dir_strides, bins, b, a, h, w, k, rt.ptr(anchors), rt.ptr(top_idx),
                                   rt.ptr(top_score), int(bool(rotate)), rt.ptr(dec), rt.ptr(dets), rt.ptr(dlab), rt.dtype_code(box.dtype),
                                   *lazy_tail, rt.stream())
@@ -1976,16 +1997,19 @@ def predict_decode(box, dir_cls, anchors, top_idx, top_score, rotate=True, lazy=
 @_traced("predict_finalize")
 def predict_finalize(dec, top_score, top_label, dir_label, keep, num_keep, post_max, use_direction, dir_offset,
                      dir_limit_offset, num_dir_bins, range6):
-    """-> dict(boxes [B,P,7], scores [B,P], labels [B,P] int32, valid [B,P] bool)."""
+    """dec [B,k,nd] -> dict(boxes [B,P,nd], scores [B,P], labels [B,P] int32, valid [B,P] bool); nd > 7 (custom columns, copied):
+    sec_predict_finalize_nd."""
     rt.require_gpu(dec, keep, num_keep)
-    b, k, _ = dec.shape
+    b, k, nd = dec.shape
+    nd = _box_ndim(nd, "predict_finalize")
     p = min(int(post_max), k)
-    boxes, scores, labels, valid = _finalize_outputs(b, p, dec.device)
-    rc = rt.lib().sec_predict_finalize(rt.ptr(dec), rt.ptr(top_score), rt.ptr(top_label), rt.ptr(dir_label), rt.ptr(keep),
-                                       rt.ptr(num_keep), b, k, p, int(bool(use_direction)), float(dir_offset),
-                                       float(dir_limit_offset), int(num_dir_bins), rt.ptr(range6), rt.ptr(boxes),
-                                       rt.ptr(scores), rt.ptr(labels), rt.ptr(valid), rt.stream())
-    rt.check(rc, "sec_predict_finalize")
+    boxes, scores, labels, valid = _finalize_outputs(b, p, dec.device, nd)
+    entry, nd_tail = ("sec_predict_finalize", ()) if nd == 7 else ("sec_predict_finalize_nd", (nd,))
+    rc = getattr(rt.lib(), entry)(rt.ptr(dec), rt.ptr(top_score), rt.ptr(top_label), rt.ptr(dir_label), rt.ptr(keep),
+                                  rt.ptr(num_keep), b, k, p, int(bool(use_direction)), float(dir_offset),
+                                  float(dir_limit_offset), int(num_dir_bins), rt.ptr(range6), rt.ptr(boxes),
+                                  rt.ptr(scores), rt.ptr(labels), rt.ptr(valid), *nd_tail, rt.stream())
+    rt.check(rc, entry)
     return _finalize_result(boxes, scores, labels, valid)
 
 
@@ -2024,7 +2048,9 @@ def predict_decode_classes(box, dir_cls, anchors, top_idx, top_score, rotate=Tru
     dir_label [B, C, K])."""
     rt.require_gpu(box, anchors, top_idx, top_score)
     b, a, h, w, code = box.shape
-    assert code == 7 and anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
+    if code != 7:
+        raise ValueError(f"predict_decode_classes: box rows of {code} values; the multi-class NMS chain serves 7 only (no custom values)")
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape == (a * h * w, 7)
     assert top_idx.dim() == 3 and top_idx.is_contiguous() and top_score.is_contiguous() and top_score.shape == top_idx.shape
     _, nc, k = top_idx.shape
     dec, dets, dlab = _decode_outputs((b, nc, k), box.device)
@@ -2064,7 +2090,9 @@ def predict_finalize_classes(dec, top_score, dir_label, keep, num_keep, post_off
     post_total its last entry.  -> dict(boxes [B, P, 7], scores [B, P], labels [B, P] int32, valid [B, P] bool), P = post_total; the
     valid rows in row order are the reference's order."""
     rt.require_gpu(dec, keep, num_keep, post_offsets)
-    b, nc, k, _ = dec.shape
+    b, nc, k, code = dec.shape
+    if code != 7:
+        raise ValueError(f"predict_finalize_classes: box rows of {code} values; the multi-class NMS chain serves 7 only (no custom values)")
     assert post_offsets.dtype == torch.int32 and post_offsets.numel() == nc + 1
     p = int(post_total)
     boxes, scores, labels, valid = _finalize_outputs(b, p, dec.device)
@@ -2108,12 +2136,14 @@ def similarity_spec(sim):
 def region_similarity(anchors, gt, kind="nearest_iou", distance_norm=None, with_rotation=False, rotation_alpha=0.5):
     """RegionSimilarityCalculator.compare on the device: [N, K] fp32 similarities of anchors [N,7] with boxes [K,7].
     kind "nearest_iou": NearestIouSimilarity; "distance": DistanceSimilarity(distance_norm, with_rotation, rotation_alpha) in the
-    arithmetic numba compiles (float32 differences and squared distance, float64 from the division on, one rounding)."""
+    arithmetic numba compiles (float32 differences and squared distance, float64 from the division on, one rounding).
+    Rows wider than 7 (custom values) are compared on a contiguous copy of their first seven columns."""
     rt.require_gpu(anchors, gt)
     if kind not in ("nearest_iou", "distance"):
         raise ValueError(f"region similarity kind {kind!r}: expected 'nearest_iou' or 'distance'")
     spec = similarity_spec(None if kind == "nearest_iou" else dict(kind="distance", distance_norm=distance_norm,
                                                                    with_rotation=with_rotation, rotation_alpha=rotation_alpha))
+    anchors, gt = (t[:, :7] if t.dim() == 2 and t.shape[1] > 7 else t for t in (anchors, gt))
     anchors, gt = anchors.float().contiguous(), gt.float().contiguous()
     assert anchors.dim() == 2 and anchors.shape[1] == 7 and gt.dim() == 2 and gt.shape[1] == 7 and gt.device == anchors.device
     n, k = anchors.shape[0], gt.shape[0]
@@ -2125,13 +2155,22 @@ def region_similarity(anchors, gt, kind="nearest_iou", distance_norm=None, with_
 
 
 def _assign_sim(l, specs, anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, n, begin, ids, mt, ut, labels, targets,
-                importance, ws, anchors_mask):
+                importance, ws, anchors_mask, nd=7):
+    """sec_assign_targets_sim_f32, the superset entry point; rows of nd > 7 values: sec_assign_targets_nd_f32."""
     kinds = (ctypes.c_int * n)(*[s[0] for s in specs])
     params = (ctypes.c_double * (3 * n))(*[v for s in specs for v in (s[1], 1.0 if s[2] else 0.0, s[3])])
-    rc = l.sec_assign_targets_sim_f32(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes), rt.ptr(gt_importance),
-                                      rt.ptr(gt_offsets), g, b, n, begin, ids, mt, ut, kinds, params, rt.ptr(labels), rt.ptr(targets),
-                                      rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.ptr(anchors_mask), rt.stream())
-    rt.check(rc, "sec_assign_targets_sim_f32")
+    entry, nd_tail = ("sec_assign_targets_sim_f32", ()) if nd == 7 else ("sec_assign_targets_nd_f32", (nd,))
+    rc = getattr(l, entry)(rt.ptr(anchors), a, rt.ptr(gt_boxes) if g else None, rt.ptr(gt_classes), rt.ptr(gt_importance),
+                           rt.ptr(gt_offsets), g, b, n, begin, ids, mt, ut, kinds, params, rt.ptr(labels), rt.ptr(targets),
+                           rt.ptr(importance), rt.ptr(ws), ws.numel(), rt.ptr(anchors_mask), *nd_tail, rt.stream())
+    rt.check(rc, entry)
+
+
+def _assign_box_ndim(anchors, gt_boxes, what):
+    """The row width shared by anchors [A, nd] and gt_boxes [G, nd] of an assignment."""
+    nd = _box_ndim(anchors.shape[1], what)
+    assert gt_boxes.dim() == 2 and gt_boxes.shape[1] == nd, f"{what}: gt_boxes [G, {nd}] for anchors of {nd} values, got {tuple(gt_boxes.shape)}"
+    return nd
 
 
 @_traced("assign_targets")
@@ -2140,12 +2179,15 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
     """TargetAssigner.assign -> create_target_np (second/core/target_ops.py:29-229) with NearestIouSimilarity and
     GroundBox3dCoder.encode, for a whole batch on the device.  anchors [A,7] fp32; gt_boxes [G,7] fp32 (frames concatenated),
     gt_offsets [B+1] int32.  -> labels [B,A] int32, bbox_targets [B,A,7] fp32, importance [B,A] fp32.
+    Rows of nd = 7 + custom_ndim values (anchors [A,nd], gt_boxes [G,nd] -> bbox_targets [B,A,nd]) go to sec_assign_targets_nd_f32:
+    the same matching on columns 0-6, target column 7 + j = gt - anchor on positives.
     ``anchors_mask`` [B, A] bool / uint8 = create_target_np's prune_anchor_fn (where(mask)): anchors with a zero entry are left out of
     the matching and come back as label -1, targets 0, importance 0.
     ``similarity``: None = NearestIouSimilarity through the entry points that know nothing else; otherwise what
     :func:`similarity_spec` takes, through sec_assign_targets_sim_f32."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
-    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.dim() == 2
+    nd = _assign_box_ndim(anchors, gt_boxes, "assign_targets")
     assert gt_offsets.dtype == torch.int32
     gt_boxes = gt_boxes.float().contiguous()
     a, b, g = anchors.shape[0], gt_offsets.numel() - 1, gt_boxes.shape[0]
@@ -2160,18 +2202,18 @@ def assign_targets(anchors, gt_boxes, gt_offsets, matched_threshold, unmatched_t
         assert gt_importance.numel() == g and gt_importance.device == dev, "gt_importance: one weight per ground-truth box, on the anchors' device"
         gt_importance = gt_importance.to(torch.float32).contiguous()
     labels = torch.empty((b, a), dtype=torch.int32, device=dev)
-    targets = torch.empty((b, a, 7), dtype=torch.float32, device=dev)
+    targets = torch.empty((b, a, nd), dtype=torch.float32, device=dev)
     importance = torch.empty((b, a), dtype=torch.float32, device=dev)
     l = rt.lib()
     ws = rt.workspace(l.sec_assign_targets_workspace_bytes(b, a, g), dev)
-    if similarity is not None:              # one range, class id 0 = every ground truth, with the similarity asked for
+    if similarity is not None or nd != 7:   # one range, class id 0 = every ground truth, with the similarity asked for
         if anchors_mask is not None:
             anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
         if gt_classes is None:
             gt_classes = torch.ones((g,), dtype=torch.int32, device=dev)
         _assign_sim(l, [similarity_spec(similarity)], anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, 1,
                     (ctypes.c_int * 2)(0, a), (ctypes.c_int * 1)(0), (ctypes.c_float * 1)(float(matched_threshold)),
-                    (ctypes.c_float * 1)(float(unmatched_threshold)), labels, targets, importance, ws, anchors_mask)
+                    (ctypes.c_float * 1)(float(unmatched_threshold)), labels, targets, importance, ws, anchors_mask, nd)
         return labels, targets, importance
     if anchors_mask is not None:            # one range, class id 0 = every ground truth: sec_assign_targets_f32 with the mask
         anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
@@ -2199,9 +2241,11 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     (target_assigner.py:90-160, only ground truth of class k); class_ids[c] = 0: assign_all with per-anchor thresholds
     (target_assigner.py:53-88).  Same outputs as assign_targets; ``anchors_mask`` [B, A] as there (each range sees its slice).
     ``similarities``: None = NearestIouSimilarity for every range, through the entry points that know nothing else; otherwise one
-    :func:`similarity_spec` entry per range (the reference's region_similarity_calculators), through sec_assign_targets_sim_f32."""
+    :func:`similarity_spec` entry per range (the reference's region_similarity_calculators), through sec_assign_targets_sim_f32.
+    Rows of 7 + custom_ndim values: as in :func:`assign_targets`."""
     rt.require_gpu(anchors, gt_boxes, gt_offsets)
-    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.shape[1] == 7
+    assert anchors.dtype == torch.float32 and anchors.is_contiguous() and anchors.dim() == 2
+    nd = _assign_box_ndim(anchors, gt_boxes, "assign_targets_per_class")
     assert gt_offsets.dtype == torch.int32
     gt_boxes = gt_boxes.float().contiguous()
     a, b, g = anchors.shape[0], gt_offsets.numel() - 1, gt_boxes.shape[0]
@@ -2210,7 +2254,7 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     assert gt_classes is not None and gt_classes.dtype == torch.int32 and gt_classes.numel() == g
     dev = anchors.device
     labels = torch.empty((b, a), dtype=torch.int32, device=dev)
-    targets = torch.empty((b, a, 7), dtype=torch.float32, device=dev)
+    targets = torch.empty((b, a, nd), dtype=torch.float32, device=dev)
     importance = torch.empty((b, a), dtype=torch.float32, device=dev)
     l = rt.lib()
     ws = rt.workspace(l.sec_assign_targets_workspace_bytes(b, a, g), dev)
@@ -2218,6 +2262,8 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
     ids = (ctypes.c_int * n)(*[int(v) for v in class_ids])
     mt = (ctypes.c_float * n)(*[float(v) for v in matched_thresholds])
     ut = (ctypes.c_float * n)(*[float(v) for v in unmatched_thresholds])
+    if similarities is None and nd != 7:
+        similarities = [None] * n
     if similarities is not None:
         assert len(similarities) == n, "similarities: one entry per anchor range"
         if gt_importance is not None:
@@ -2226,7 +2272,7 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
         if anchors_mask is not None:
             anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
         _assign_sim(l, [similarity_spec(s) for s in similarities], anchors, a, gt_boxes, g, gt_classes, gt_importance, gt_offsets, b, n,
-                    begin, ids, mt, ut, labels, targets, importance, ws, anchors_mask)
+                    begin, ids, mt, ut, labels, targets, importance, ws, anchors_mask, nd)
         return labels, targets, importance
     if anchors_mask is not None:
         anchors_mask = _mask_u8(anchors_mask, (b, a), dev, "anchors_mask")
@@ -2246,13 +2292,15 @@ def assign_targets_per_class(anchors, gt_boxes, gt_offsets, gt_classes, class_an
 AUG_MAX_TRY, AUG_MAX_BOXES_PER_FRAME = 128, 512      # limits of sec_noise_per_box_f32 (include/second_hip.h)
 
 
-def _aug_frames(points, point_offsets, boxes, box_offsets, valid):
+def _aug_frames(points, point_offsets, boxes, box_offsets, valid, widths=(7,)):
     """Argument checks the augmentation wrappers share; returns (valid as uint8 or None, batch)."""
     rt.require_gpu(points, point_offsets, boxes, box_offsets, valid)
     if points is not None:
         assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous(), "points: contiguous fp32 [N, pitch]"
         assert point_offsets.dtype == torch.int32 and point_offsets.numel() == box_offsets.numel()
-    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 7 and boxes.is_contiguous(), "boxes: contiguous fp32 [G, 7]"
+    if boxes.dim() == 2 and boxes.shape[1] not in widths:
+        raise ValueError(f"boxes of {boxes.shape[1]} values; this stage takes rows of {' or '.join(str(w) for w in widths)}")
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.is_contiguous(), "boxes: contiguous fp32 [G, 7]"
     assert box_offsets.dtype == torch.int32 and box_offsets.numel() >= 2
     if valid is not None:
         assert valid.numel() == boxes.shape[0] and valid.dtype in (torch.bool, torch.uint8), "valid: one bool per box"
@@ -2324,8 +2372,11 @@ def augment_boxes(boxes, box_offsets, frame_params, bev_range, valid=None, class
                   rot_transform=None):
     """The boxes' side of the same stages, the range filter of filter_gt_box_outside_range_by_center on (xmin, ymin, xmax, ymax) =
     ``bev_range`` and the compaction: -> (out_boxes [G, 7], out_offsets [B+1] int32, out_classes [G] int32, out_importance [G]),
-    survivors first in their original order, zero rows behind out_offsets[-1]."""
-    valid, b = _aug_frames(None, None, boxes, box_offsets, valid)
+    survivors first in their original order, zero rows behind out_offsets[-1].
+    boxes [G, 9] (columns 7, 8 a velocity, NuScenesDatasetVelo) -> out_boxes [G, 9] through sec_augment_boxes_nd_f32: the flips, the
+    rotation and the scaling act on the velocity as in the reference's shape[1] == 9 branches; no other width is served."""
+    valid, b = _aug_frames(None, None, boxes, box_offsets, valid, widths=(7, 9))
+    nd = boxes.shape[1]
     rt.require_gpu(frame_params, classes, importance, loc_transform, rot_transform)
     g, dev = boxes.shape[0], boxes.device
     assert frame_params.dtype == torch.float32 and tuple(frame_params.shape) == (b, 8) and frame_params.is_contiguous()
@@ -2335,15 +2386,16 @@ def augment_boxes(boxes, box_offsets, frame_params, bev_range, valid=None, class
     if importance is not None:
         assert importance.numel() == g
         importance = importance.to(torch.float32).contiguous()
-    out_boxes = torch.empty((g, 7), dtype=torch.float32, device=dev)
+    out_boxes = torch.empty((g, nd), dtype=torch.float32, device=dev)
     out_classes = torch.empty((g,), dtype=torch.int32, device=dev)
     out_importance = torch.empty((g,), dtype=torch.float32, device=dev)
     out_offsets = torch.empty((b + 1,), dtype=torch.int32, device=dev)
-    rc = rt.lib().sec_augment_boxes_f32(rt.ptr(boxes), rt.ptr(box_offsets), g, b, rt.ptr(valid), rt.ptr(classes), rt.ptr(importance),
-                                        rt.ptr(loc_transform), rt.ptr(rot_transform), rt.ptr(frame_params), rt.f_arr(bev_range),
-                                        rt.ptr(out_boxes), rt.ptr(out_classes), rt.ptr(out_importance), rt.ptr(out_offsets),
-                                        rt.stream())
-    rt.check(rc, "sec_augment_boxes_f32")
+    entry, nd_tail = ("sec_augment_boxes_f32", ()) if nd == 7 else ("sec_augment_boxes_nd_f32", (nd,))
+    rc = getattr(rt.lib(), entry)(rt.ptr(boxes), rt.ptr(box_offsets), g, b, rt.ptr(valid), rt.ptr(classes), rt.ptr(importance),
+                                  rt.ptr(loc_transform), rt.ptr(rot_transform), rt.ptr(frame_params), rt.f_arr(bev_range), *nd_tail,
+                                  rt.ptr(out_boxes), rt.ptr(out_classes), rt.ptr(out_importance), rt.ptr(out_offsets),
+                                  rt.stream())
+    rt.check(rc, entry)
     return out_boxes, out_offsets, out_classes, out_importance
 
 
@@ -2434,13 +2486,20 @@ LOSS_DEFAULTS = dict(alpha=0.25, gamma=2.0, sigma=3.0, pos_cls_weight=1.0, neg_c
 def second_loss_raw(cls_preds, box_preds, dir_preds, labels, reg_targets, anchors, importance, **cfg):
     """VoxelNet.loss (second/pytorch/models/voxelnet.py:239-312) values and head gradients in one fused pass.
     cls_preds [B,N,C], box_preds [B,N,7], dir_preds [B,N,bins] or None: contiguous fp32.  -> (out6, d_cls, d_box, d_dir) with
-    out6 = (loss, cls_loss_reduced, loc_loss_reduced, dir_loss_reduced, cls_pos_loss, cls_neg_loss)."""
+    out6 = (loss, cls_loss_reduced, loc_loss_reduced, dir_loss_reduced, cls_pos_loss, cls_neg_loss).
+    box_preds / reg_targets [B,N,nd] and anchors [N,nd] with nd = 7 + custom_ndim: sec_second_loss_nd_f32, which needs ``code_weights``
+    of nd values (the default holds 7); columns 7.. get the plain weighted smooth L1."""
     rt.require_gpu(cls_preds, box_preds, labels, reg_targets, anchors, importance)
     p = dict(LOSS_DEFAULTS, **cfg)
     for t in (cls_preds, box_preds, reg_targets, anchors, importance) + ((dir_preds,) if dir_preds is not None else ()):
         assert t.dtype == torch.float32 and t.is_contiguous(), "second_loss takes contiguous fp32 tensors"
     assert labels.dtype == torch.int32 and labels.is_contiguous()
     b, n, nc = cls_preds.shape
+    nd = _box_ndim(box_preds.shape[-1], "second_loss")
+    assert reg_targets.shape[-1] == nd and anchors.shape[-1] == nd, f"second_loss: reg_targets and anchors rows of {nd} values, as box_preds"
+    if len(p["code_weights"]) != nd:
+        raise ValueError(f"second_loss: code_weights has {len(p['code_weights'])} entries, box rows have {nd} values (box_ndim): "
+                         f"pass code_weights of {nd}")
     bins = dir_preds.shape[-1] if dir_preds is not None else 0
     dev = cls_preds.device
     d_cls, d_box = torch.empty_like(cls_preds), torch.empty_like(box_preds)
@@ -2451,10 +2510,11 @@ def second_loss_raw(cls_preds, box_preds, dir_preds, labels, reg_targets, anchor
                        *p["code_weights"]])
     l = rt.lib()
     ws = rt.workspace(l.sec_second_loss_workspace_bytes(b, n), dev)
-    rc = l.sec_second_loss_f32(rt.ptr(cls_preds), rt.ptr(box_preds), rt.ptr(dir_preds), rt.ptr(labels), rt.ptr(reg_targets),
-                               rt.ptr(anchors), rt.ptr(importance), b, n, nc, bins, params, rt.ptr(d_cls), rt.ptr(d_box),
-                               rt.ptr(d_dir), rt.ptr(out6), rt.ptr(ws), ws.numel(), rt.stream())
-    rt.check(rc, "sec_second_loss_f32")
+    entry, nd_tail = ("sec_second_loss_f32", ()) if nd == 7 else ("sec_second_loss_nd_f32", (nd,))
+    rc = getattr(l, entry)(rt.ptr(cls_preds), rt.ptr(box_preds), rt.ptr(dir_preds), rt.ptr(labels), rt.ptr(reg_targets),
+                           rt.ptr(anchors), rt.ptr(importance), b, n, nc, bins, params, *nd_tail, rt.ptr(d_cls), rt.ptr(d_box),
+                           rt.ptr(d_dir), rt.ptr(out6), rt.ptr(ws), ws.numel(), rt.stream())
+    rt.check(rc, entry)
     return out6, d_cls, d_box, d_dir
 
 
@@ -2469,7 +2529,7 @@ class SecondLossFunction(torch.autograd.Function):
         dts = (cls_preds.dtype, box_preds.dtype, None if dir_preds is None else dir_preds.dtype)
         f = lambda t, k: t.reshape(b, -1, k).float().contiguous()
         nc = cfg.get("num_class", 1)
-        out6, d_cls, d_box, d_dir = second_loss_raw(f(cls_preds, nc), f(box_preds, 7),
+        out6, d_cls, d_box, d_dir = second_loss_raw(f(cls_preds, nc), f(box_preds, reg_targets.shape[-1]),
                                                     None if dir_preds is None else f(dir_preds, cfg.get("num_direction_bins", 2)),
                                                     labels, reg_targets, anchors, importance,
                                                     **{k: v for k, v in cfg.items() if k in LOSS_DEFAULTS})

@@ -51,6 +51,8 @@ SYMBOLS = [
     "sec_pfn_kind_train_bwd",
     "sec_rpn_tile_cover_lds_bytes", "sec_rpn_tile_cover", "sec_conv2d_nhwc_gather_cover", "sec_conv2d_nhwc_tiles_cover",
     "sec_conv2d_nhwc_tiles_tail_cover", "sec_predict_select_cover", "sec_predict_decode_cover",
+    "sec_predict_decode_nd", "sec_predict_decode_segments_nd", "sec_predict_finalize_nd", "sec_assign_targets_nd_f32",
+    "sec_second_loss_nd_f32", "sec_augment_boxes_nd_f32",
     "sec_predict_select_plan_name",
 ]
 
@@ -278,6 +280,13 @@ def lib():
         l.sec_assign_targets_masked_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
         l.sec_region_similarity_f32.argtypes = [vp, ci, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp]
         l.sec_assign_targets_sim_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+        # rows of 7 + custom_ndim values: the argument lists above with box_ndim added
+        l.sec_predict_decode_nd.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
+        l.sec_predict_decode_segments_nd.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp]
+        l.sec_predict_finalize_nd.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, ci, vp]
+        l.sec_assign_targets_nd_f32.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, ci, vp]
+        l.sec_second_loss_nd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, sz, vp]
+        l.sec_augment_boxes_nd_f32.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp]
         l.sec_db_sample_merge_points_f32.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, sz, vp]
         cd = ctypes.c_double
         l.sec_kitti_eval_overlaps.argtypes = [ci, ci, vp, vp, vp, vp, vp, ci, ci, ll, ci, ci, ci, cd, vp, vp]

@@ -167,6 +167,14 @@ class DeviceTrainer:
         self.similarities = group_similarities(self.cfg, len(mts))
         self.loss_cfg = dict(ops.LOSS_DEFAULTS, direction_offset=self.cfg["direction_offset"], num_class=self.cfg["num_class"],
                              num_direction_bins=self.cfg["num_direction_bins"], **(loss_cfg or {}))
+        # custom box values (anchor_custom_values; nuScenes velocity): gt_boxes [G, box_ndim], reg_targets [B, A, box_ndim] and one code
+        # weight per value -- the config's ``code_weights`` or loss_cfg's, else 1 for every value
+        nd = getattr(det, "box_ndim", 7)
+        if nd != 7 and not (loss_cfg or {}).get("code_weights"):
+            self.loss_cfg["code_weights"] = tuple(float(v) for v in self.cfg.get("code_weights") or (1.0,) * nd)
+        if len(self.loss_cfg["code_weights"]) != nd:
+            raise ValueError(f"DeviceTrainer: code_weights has {len(self.loss_cfg['code_weights'])} entries, {self.cfg['name']} has box rows "
+                             f"of {nd} values (box_ndim)")
         self.amp_dtype = amp_dtype
         D.broadcast_parameters(det, 0)
         # the reference's adam_optimizer + fixed weight decay (car.fhd.config:180-188) -> AdamW
@@ -564,6 +572,9 @@ class MultiHeadDeviceTrainer(DeviceTrainer):
                                       "use training.DeviceTrainer")
         if not det.pillars:
             raise NotImplementedError(f"MultiHeadDeviceTrainer: {det.cfg['name']}: the multi-head step is built for the PointPillars front end")
+        if getattr(det, "box_ndim", 7) != 7:
+            raise NotImplementedError(f"MultiHeadDeviceTrainer: {det.cfg['name']}: custom box values (anchor_custom_values) are not trained "
+                                      "on the multi-head step (box rows of 7 values only)")
 
     def _dense_module(self):
         return self._dense
